@@ -2,9 +2,18 @@
 """bench.py — env-steps/sec of the batched RLToyEnv.step() hot path on MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full        (every leg and extra described below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python bench.py --gpus N ...            (starts its N ranks itself, as a child torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up (--warmup launches), times exactly --steps launches of the leg `value` is (launch + the
+path's all-gather) once, and prints the line: `value`, `ms_per_step` and the contract keys, with `roofline` and
+`cpu_baseline` null.  `--full` adds everything else below -- the `none` / `replayed` / `full` / `peer_copy` legs, five
+repeats per leg (the median is reported), the roofline with measured HBM ceilings and live PMC traffic, the CPU baselines,
+the single-step legs and the other workloads.  `--dump-outputs DIR` writes what the last timed launch returned as
+DIR/<name>.npy (bench.output_sample); the inputs are seeded, so two builds given the same arguments can be compared.
 
 Workload (BASELINE.json configs[1]): discrete 8 states x 8 actions, reward_delay 4,
 sequence_length 3, 65 536 env instances per GPU sharing one MDP, uniform random actions
@@ -361,6 +370,33 @@ def action_rotation(wl, F, N, device, seed, min_total=512 << 20, min_n=4, max_n=
     return [first] + [make_actions(wl, F, N, device, seed + 1000 * j) for j in range(1, n)]
 
 
+def output_sample(out, gathered, seed=0, budget=48 << 20, budget_gathered=8 << 20):
+    """--dump-outputs: what a caller of the timed path receives from one launch -- the rollout's (obs, reward, terminated,
+    truncated), [K, N, ...] each, and the gathered observation tensor ([world, N, ...] -> [world * N, ...]) -- as host arrays,
+    float32 (float64 where the output is).  An output larger than its budget is a fixed seeded sample: the same env
+    instances (and, when one env's rollout alone exceeds the budget, the same steps) in every run."""
+    obs, rew, term, trunc = out
+    K, N = rew.shape
+    per = sum(t[0, 0].numel() * (8 if t.dtype == torch.float64 else 4) for t in out)      # bytes per env step, over the four arrays
+    rng = np.random.default_rng(seed)
+    nk = min(K, max(1, budget // per))
+    ne = min(N, max(1, budget // (per * nk)))
+    ks = torch.as_tensor(np.sort(rng.choice(K, nk, replace=False)) if nk < K else np.arange(K), device=rew.device)
+    es = torch.as_tensor(np.sort(rng.choice(N, ne, replace=False)) if ne < N else np.arange(N), device=rew.device)
+
+    def host(t):
+        return (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    res = {name: host(t.index_select(0, ks).index_select(1, es))
+           for name, t in (("obs", obs), ("reward", rew), ("terminated", term), ("truncated", trunc))}
+    if gathered is not None:
+        g = gathered.flatten(0, 1)
+        G = g.shape[0]
+        ng = min(G, max(1, budget_gathered // (g[0].numel() * (8 if g.dtype == torch.float64 else 4))))
+        gs = torch.as_tensor(np.sort(rng.choice(G, ng, replace=False)) if ng < G else np.arange(G), device=g.device)
+        res["gathered_obs"] = host(g.index_select(0, gs))
+    return res
+
+
 # the other BASELINE.json configs (and cfg2 on the RNG north_star names), timed in the same run after the cfg2 leg
 EXTRA_LEGS = (("cfg2", "philox"), ("cfg3", "numpy"), ("cfg4", "numpy"), ("cfg5", "numpy"), ("cfg5", "philox"),
               ("cfg2_noise", "numpy"), ("cfg2_noise", "philox"),   # (+ cfg2 with both noises, reference-exact streams and the north_star RNG)
@@ -533,8 +569,9 @@ def main():
     ap.add_argument("--workload-steps", type=int, default=10, help="timed launches of each `workloads` leg")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo only for tests that run several ranks on one GPU (RCCL is the product path)")
-    ap.add_argument("--repeats", type=int, default=5, help="every timed leg is repeated this many times; the MEDIAN repeat is "
-                    "reported (`value`, `ms_per_step`, `roofline.launch_us`), all repeats in `*_runs`")
+    ap.add_argument("--repeats", type=int, default=None, help="every timed leg is repeated this many times; the MEDIAN repeat is "
+                    "reported (`value`, `ms_per_step`, `roofline.launch_us`), all repeats in `*_runs` (default: 5 with --full or "
+                    "--only-leg, 1 in a plain run, whose timed launches are then exactly --steps)")
     ap.add_argument("--only-leg", default=None, choices=["rotating", "replayed"],
                     help="profiling: time only this form of the main workload's launches (no collective, no other legs), so that a "
                     "rocprofv3 --kernel-trace --stats of the run holds ONE leg per kernel (profiles/r04_kernel_stats_<leg>.csv)")
@@ -543,7 +580,17 @@ def main():
     ap.add_argument("--print-detail", action="store_true", help="also print the full record, prefixed BENCH_DETAIL, before the contract line")
     ap.add_argument("--full-gather-steps", type=int, default=4,
                     help="bench steps of the [K, N_local, ...] all-gather leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline leg: the `none` / `replayed` / `full` legs, repeats, roofline and measured "
+                    "HBM ceilings, live PMC traffic, CPU baselines, single-step legs and the other workloads.  Without it a run "
+                    "sets up, warms up, times --steps launches of the leg `value` is, and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed launches, write what the last timed launch returned (observations, rewards, terminated, "
+                    "truncated, the gathered observation tensor) as DIR/<name>.npy, float32; a fixed seeded sample of env "
+                    "instances when the whole is larger than 56 MB")
     args = ap.parse_args()
+    if not args.full and (args.peer_copy or args.cpu_all_cores):
+        raise SystemExit("bench.py: --peer-copy and --cpu-all-cores are legs of a --full run")
 
     if args.cpu_baselines_only:       # a child of rank 0 of a multi-rank run (fresh process, never touches the GPU)
         cpu_py, cpu_py_all, cpu_all = cpu_baselines_forked(args.cpu_baselines_only, args.cpu_all_cores)
@@ -574,6 +621,10 @@ def main():
     extra = []
     if args.only_leg is not None:       # a profiling run of one leg of the main kernel: nothing else on the device
         args.no_workloads = args.no_cpu_baseline = args.no_pmc = args.no_single_step = args.no_collective = True
+    # a plain run (no --full): only what the line's `value` and `ms_per_step` need -- the leg `value` is, timed once
+    lean = not args.full and args.only_leg is None
+    if lean:
+        args.no_workloads = args.no_cpu_baseline = args.no_pmc = args.no_single_step = True
     if world == 1 and args.workload == "cfg2" and args.rng == "numpy" and not args.no_workloads and not args.disable \
             and args.envs is None:
         extra = list(EXTRA_LEGS)
@@ -593,7 +644,7 @@ def main():
     # (the GPU is idle while the host cores are timed; BENCH_r05: 89 s of driver time for a 2.4 ms timed region).
     pmc, pmc_proc, pmc_out = None, None, None
     per_env_cached = []
-    for w, r in ([(args.workload, args.rng)] + extra) if rank == 0 else []:        # N different MDPs per env: built by forked workers, now
+    for w, r in ([(args.workload, args.rng)] + extra) if rank == 0 and not lean else []:  # N different MDPs per env: built by forked workers, now
         if WORKLOADS[w].get("per_env_mdps") and "_mdps" not in WORKLOADS[w]:
             n_ = N if w == args.workload else WORKLOADS[w]["envs"]
             prebuild_per_env(WORKLOADS[w], n_, os.getpid())
@@ -706,7 +757,7 @@ def main():
     # round 3 and taken out again: the candidates measured the same with the collective, and a picked stream that happened to
     # share a hardware queue with an image handle's side stream serialised cfg4's prepare and render stages -- 7.4 or 8.4 ms per
     # launch from run to run.)
-    R = max(1, args.repeats)
+    R = max(1, args.repeats if args.repeats is not None else (1 if lean else 5))
 
     def timed_reps(steps, gathers, events=False, rotate=True):
         """R back-to-back repeats of timed(): [(elapsed_s, kernel_ms)]; the MEDIAN repeat is what a leg reports
@@ -724,20 +775,31 @@ def main():
     legs = {}
     kernel_us_runs = replay_us_runs = None
     el_none = None
-    if args.only_leg in (None, "rotating"):
+    dumped = None
+
+    def snapshot(steps, gatherers):
+        """What the last of `steps` launches of the leg just timed returned (run() fills outs[it % NB])."""
+        j = (steps - 1) % NB
+        return output_sample(outs[j], gatherers[j].out if gatherers is not None else None)
+
+    if args.only_leg in (None, "rotating") and not (lean and dist is not None):
         run(max(args.warmup, 1), None)
         reps = timed_reps(args.steps, None, events=True)
         el_none, legs["none"] = leg_record(reps, args.steps)
         legs["none"]["host_enqueue_s"] = host_enqueue[0]
         kernel_us_runs = [k * 1e3 / args.steps for _, k in reps]
+        if args.dump_outputs and rank == 0:
+            dumped = snapshot(args.steps, None)
     # the same launches replaying ONE action tensor (what rounds 1-2 timed): its reads may be cache hits
-    if args.only_leg in (None, "replayed"):
+    if args.only_leg in (None, "replayed") and not lean:
         run(2, None, rotate=False)
         reps = timed_reps(args.steps, None, events=True, rotate=False)
         replay_us_runs = [k * 1e3 / args.steps for _, k in reps]
         if el_none is None:
             el_none, legs["none"] = leg_record(reps, args.steps)
             kernel_us_runs = replay_us_runs
+            if args.dump_outputs and rank == 0:
+                dumped = snapshot(args.steps, None)
     elapsed, collective = el_none, "none" + (f" ({no_coll_why})" if no_coll_why else "")
     diag = None
     if dist is not None and args.only_leg is None:
@@ -751,9 +813,12 @@ def main():
         legs["last_row"]["host_enqueue_s"] = host_enqueue[0]
         legs["last_row"]["bytes_per_rank_per_launch"] = g_last[0].local.numel() * g_last[0].local.element_size()
         elapsed = el_last
+        if args.dump_outputs and rank == 0:
+            dumped = snapshot(args.steps, g_last)
         collective = ("all_gather_into_tensor (%s, %d rank%s, async_op) of the current observation shard after every "
                       "launch, on the backend's high-priority stream beside the next launch"
                       % ("RCCL" if args.backend == "nccl" else args.backend, dist.get_world_size(), "" if world == 1 else "s"))
+    if dist is not None and args.only_leg is None and not lean:
         # ---- what a scaling line needs to explain itself: per rank, the launch alone (HIP events on
         # the launch stream, from the `none` leg), the collective alone (G back-to-back gathers between events, nothing
         # else on the device) and what the collective adds per launch when it runs beside the rollouts; min / max over ranks
@@ -889,37 +954,39 @@ def main():
     value = total_steps / elapsed
     mark("main_legs")
 
-    # ---- roofline of the dominant kernel (fused rollout), per launch: the median repeat
-    launch_us = statistics.median(kernel_us_runs)
-    per_launch_s = launch_us * 1e-6
-    alg_bytes = wl["alg_bytes_fused"] * N * F
-    achieved = alg_bytes / per_launch_s / 1e9
-    kname = env.rollout_kernel_name(F)          # what the library's dispatch launches (mdpp_kernel_name)
-    traffic, traffic_src = committed_traffic(args.workload, args.rng, N, F, kname)
-    main_pmc = (pmc or {}).get(leg_name(args.workload, args.rng))
-    main_valu = None
-    if main_pmc is not None and kname.split("<")[0] in main_pmc["kernels"]:   # measured in this run, on the kernel that was timed
-        traffic, traffic_src = main_pmc["bytes_per_launch"], main_pmc["note"]
-        main_valu = main_pmc.get("valu_insts_per_launch")
-    vr = valu_roofline(main_valu, launch_us, achieved / HBM_PEAK_GBS)
-    roofline = {"bound": "hbm", "bound_measured": vr["bound"], "valu_frac": vr["valu_frac"], "valu": vr, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "kernel": kname,
-                "alg_bytes_per_env_step": wl["alg_bytes_fused"], "alg_bytes_per_launch": alg_bytes,
-                "launch_us": launch_us, "env_steps_per_launch": N * F,
-                "launch_us_runs": {"min": min(kernel_us_runs), "median": launch_us, "max": max(kernel_us_runs), "repeats": R},
-                "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
-                "achievable": f"{HBM_ACHIEVABLE_GBS:.0f} GB/s: the float4 copy of MI355X_MICROARCH.md; `peak_measured` is this device's own",
-                "action_tensors": NA, "action_bytes_rotated": NA * acts[0].numel() * acts[0].element_size(),
-                "reads": f"`frac`: the launches cycle through {NA} distinct action tensors "
-                         f"({NA * acts[0].numel() * acts[0].element_size() >> 20} MiB together, above the 256 MiB "
-                         "Infinity Cache); `frac_replayed`: the same launches replaying one tensor"}
-    if replay_us_runs is not None:
-        rus = statistics.median(replay_us_runs)
-        roofline["frac_replayed"] = alg_bytes / (rus * 1e-6) / 1e9 / HBM_PEAK_GBS
-        roofline["launch_us_replayed"] = rus
-        roofline["launch_us_replayed_runs"] = {"min": min(replay_us_runs), "median": rus, "max": max(replay_us_runs)}
-    if args.only_leg is not None:
-        roofline["only_leg"] = args.only_leg
+    roofline = None
+    if not lean:
+        # ---- roofline of the dominant kernel (fused rollout), per launch: the median repeat
+        launch_us = statistics.median(kernel_us_runs)
+        per_launch_s = launch_us * 1e-6
+        alg_bytes = wl["alg_bytes_fused"] * N * F
+        achieved = alg_bytes / per_launch_s / 1e9
+        kname = env.rollout_kernel_name(F)          # what the library's dispatch launches (mdpp_kernel_name)
+        traffic, traffic_src = committed_traffic(args.workload, args.rng, N, F, kname)
+        main_pmc = (pmc or {}).get(leg_name(args.workload, args.rng))
+        main_valu = None
+        if main_pmc is not None and kname.split("<")[0] in main_pmc["kernels"]:   # measured in this run, on the kernel that was timed
+            traffic, traffic_src = main_pmc["bytes_per_launch"], main_pmc["note"]
+            main_valu = main_pmc.get("valu_insts_per_launch")
+        vr = valu_roofline(main_valu, launch_us, achieved / HBM_PEAK_GBS)
+        roofline = {"bound": "hbm", "bound_measured": vr["bound"], "valu_frac": vr["valu_frac"], "valu": vr, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "kernel": kname,
+                    "alg_bytes_per_env_step": wl["alg_bytes_fused"], "alg_bytes_per_launch": alg_bytes,
+                    "launch_us": launch_us, "env_steps_per_launch": N * F,
+                    "launch_us_runs": {"min": min(kernel_us_runs), "median": launch_us, "max": max(kernel_us_runs), "repeats": R},
+                    "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
+                    "achievable": f"{HBM_ACHIEVABLE_GBS:.0f} GB/s: a float4 copy kernel on MI355X; `peak_measured` is this device's own",
+                    "action_tensors": NA, "action_bytes_rotated": NA * acts[0].numel() * acts[0].element_size(),
+                    "reads": f"`frac`: the launches cycle through {NA} distinct action tensors "
+                             f"({NA * acts[0].numel() * acts[0].element_size() >> 20} MiB together, above the 256 MiB "
+                             "Infinity Cache); `frac_replayed`: the same launches replaying one tensor"}
+        if replay_us_runs is not None:
+            rus = statistics.median(replay_us_runs)
+            roofline["frac_replayed"] = alg_bytes / (rus * 1e-6) / 1e9 / HBM_PEAK_GBS
+            roofline["launch_us_replayed"] = rus
+            roofline["launch_us_replayed_runs"] = {"min": min(replay_us_runs), "median": rus, "max": max(replay_us_runs)}
+        if args.only_leg is not None:
+            roofline["only_leg"] = args.only_leg
 
     single = None
     if not args.no_single_step:
@@ -947,7 +1014,7 @@ def main():
                 workloads[key] = {"error": repr(e)}
             torch.cuda.empty_cache()
     mark("workloads")
-    if rank == 0:
+    if rank == 0 and roofline is not None:
         peaks = hbm_ceilings(device)
         roofline["peak_measured"] = peaks
         # the fraction that belongs to `value` (the leg WITH the path's all-gather; `frac` is the kernel alone)
@@ -996,7 +1063,7 @@ def main():
     mark("cpu_port_and_ceilings")
 
     if rank == 0:
-        v_none = legs["none"]["env_steps_per_s"]
+        v_none = legs["none"]["env_steps_per_s"] if "none" in legs else None
         v_last = legs["last_row"]["env_steps_per_s"] if "last_row" in legs else None
         line = {
             "metric": "env-steps/sec", "value": value, "unit": "env-steps/s", "n_gpus": world,
@@ -1035,6 +1102,10 @@ def main():
         line["config"]["collective_short"] = ("none" if v_last is None else
                                               f"all_gather_into_tensor({backend_used}, {world} rank{'s' if world != 1 else ''}) after every launch")
         line["timing_s"] = phases
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         emit(line, args.detail_out, args.print_detail)
     if dist is not None and not dist_done:
         dist.destroy_process_group()
@@ -1079,7 +1150,7 @@ def compact_line(full):
                       "envs_per_gpu": cfg.get("envs_per_gpu"), "fuse": cfg.get("fuse"),
                       "env_steps_per_bench_step": cfg.get("env_steps_per_bench_step"), "rng": cfg.get("rng"),
                       "collective": cfg.get("collective_short") or str(cfg.get("collective"))[:80]}
-    line["roofline"] = {"bound": roof.get("bound"), "achieved": _r(roof.get("achieved"), 5), "peak": roof.get("peak"),
+    line["roofline"] = None if not roof else {"bound": roof.get("bound"), "achieved": _r(roof.get("achieved"), 5), "peak": roof.get("peak"),
                         "unit": roof.get("unit"), "frac": _r(roof.get("frac")), "traffic": roof.get("traffic"),
                         "frac_value": _r(roof.get("frac_value")), "frac_replayed": _r(roof.get("frac_replayed")),
                         "valu_frac": _r(roof.get("valu_frac")), "bound_measured": roof.get("bound_measured"),

@@ -202,3 +202,43 @@ def test_contract_line_is_the_last_line_of_stdout(capfd, tmp_path):
     assert sum(1 for ln in lines if ln.startswith("{")) == 1              # ONE JSON line
     detail = json.loads(out.read_text())
     assert detail["workloads"]["cfg4"]["launch_us_runs"] and last["detail"] == str(out)
+
+
+def test_dump_sample_is_fixed_bounded_and_float():
+    """--dump-outputs: the arrays of one launch as float32, a seeded sample of env instances (the same in every run) when the
+    whole is over budget, the gathered observation tensor flattened to [world * N, ...]."""
+    import numpy as np
+    import torch
+    K, N = 64, 8192
+    g = torch.Generator().manual_seed(1)
+    out = (torch.randint(0, 8, (K, N), generator=g, dtype=torch.int64), torch.rand((K, N), generator=g),
+           torch.randint(0, 2, (K, N), generator=g, dtype=torch.uint8), torch.zeros((K, N), dtype=torch.uint8))
+    gathered = out[0][-1].view(1, N)
+    a = bench.output_sample(out, gathered, budget=1 << 20, budget_gathered=1 << 20)
+    b = bench.output_sample(out, gathered, budget=1 << 20, budget_gathered=1 << 20)
+    assert set(a) == {"obs", "reward", "terminated", "truncated", "gathered_obs"}
+    assert sum(x.nbytes for x in a.values()) <= 2 << 20
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    assert a["obs"].shape[0] == K and 0 < a["obs"].shape[1] < N and a["reward"].shape == a["obs"].shape
+    assert np.array_equal(a["gathered_obs"], out[0][-1].float().numpy())          # small enough to be whole
+    cols = np.nonzero((out[1].numpy() == a["reward"][:, :1]).all(axis=0))[0]        # the first sampled env is one of the batch
+    assert len(cols) == 1 and np.array_equal(a["obs"][:, 0], out[0][:, cols[0]].float().numpy())
+    small = tuple(t[:8, :100] for t in out)
+    s = bench.output_sample(small, None)
+    assert "gathered_obs" not in s and np.array_equal(s["reward"], small[1].numpy())    # under budget: every value
+
+
+def test_plain_run_line_has_the_contract_keys_without_the_extras():
+    """A plain run (no --full) has no roofline, CPU baselines or other workloads: the line says so with nulls and keeps
+    every contract key."""
+    import json
+    full = _canned_full_record()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                  "scaling", "vs_baseline", "dtype", "data", "config", "collective_ok", "launches", "elapsed_s")}
+    plain.update(roofline=None, cpu_baseline=None, cpu_baseline_port=None, single_step=None, workloads=None)
+    line = json.loads(bench.compact_line(plain))
+    assert line["metric"] == "env-steps/sec" and line["unit"] == "env-steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == full["dtype"] and line["steps"] == full["steps"]
+    assert abs(line["value"] / full["value"] - 1) < 1e-4 and abs(line["ms_per_step"] / full["ms_per_step"] - 1) < 1e-4
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "workloads" not in line

@@ -51,7 +51,7 @@ def test_bench_multi_rank_path_with_two_ranks_on_one_gpu(spawn_fresh, tmp_path):
     root = os.path.dirname(HERE)
     argv = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
             "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-            "--envs", "4096", "--fuse", "64", "--backend", "gloo", "--no-single-step", "--full-gather-steps", "2", "--peer-copy",
+            "--envs", "4096", "--fuse", "64", "--backend", "gloo", "--no-single-step", "--full-gather-steps", "2", "--peer-copy", "--full",
             "--detail-out", str(tmp_path / "detail.json")]
     r = spawn_fresh(argv, env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=800)
     assert r["returncode"] == 0, r["stdout"][-2000:] + "\n" + r["stderr"][-6000:]
@@ -110,7 +110,7 @@ def test_bench_world_8_rehearsal_on_one_gpu(spawn_fresh, tmp_path):
     root = os.path.dirname(HERE)
     argv = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
             "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "2",
-            "--envs", "8192", "--fuse", "64", "--backend", "gloo", "--no-single-step", "--full-gather-steps", "2", "--peer-copy",
+            "--envs", "8192", "--fuse", "64", "--backend", "gloo", "--no-single-step", "--full-gather-steps", "2", "--peer-copy", "--full",
             "--detail-out", str(tmp_path / "detail.json")]
     r = spawn_fresh(argv, env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=1400)
     assert r["returncode"] == 0, r["stdout"][-2000:] + "\n" + r["stderr"][-6000:]
@@ -151,3 +151,48 @@ def test_bench_preflight_refuses_rccl_with_fewer_devices_than_ranks(spawn_fresh)
     r = spawn_fresh([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1"], env={}, timeout=250)
     assert r["returncode"] != 0
     assert "needs 8 visible devices" in (r["stdout"] + r["stderr"])
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_exactly_steps_and_dumps_the_last_launch(spawn_fresh, tmp_path):
+    """A plain run (no --full): one RCCL rank, --warmup launches, then exactly --steps timed launches, timed once; the line
+    carries the contract keys and none of the extras.  --dump-outputs writes what the LAST timed launch returned: the same
+    env and action tensors replayed here (warmup + steps launches) give the same arrays, and the gathered observation tensor
+    is that launch's last observation row."""
+    import json
+    import numpy as np
+    import torch
+    import bench
+    from mdp_playground_amd import RLToyVectorEnv
+    root = os.path.dirname(HERE)
+    dump = tmp_path / "dump"
+    r = spawn_fresh([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--envs", "4096",
+                     "--fuse", "64", "--dump-outputs", str(dump), "--detail-out", str(tmp_path / "detail.json")],
+                    env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=500)
+    assert r["returncode"] == 0, r["stdout"][-2000:] + "\n" + r["stderr"][-6000:]
+    lines = [ln for ln in r["stdout"].splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, r["stdout"][-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "env-steps/sec" and line["unit"] == "env-steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "u8" and line["n_gpus"] == 1 and line["steps"] == line["launches"] == 3 and line["warmup"] == 1
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "workloads" not in line
+    assert line["collective_ok"] is True and line["value_none"] is None
+    assert abs(line["value"] - 4096 * 64 * 3 / line["elapsed_s"]) <= 1e-3 * line["value"]
+    assert abs(line["ms_per_step"] * 3e-3 - line["elapsed_s"]) <= 1e-3 * line["elapsed_s"]
+    detail = json.loads((tmp_path / "detail.json").read_text())
+    assert detail["repeats"] == 1 and set(detail["collective_legs"]) == {"last_row"}
+    assert len(detail["collective_legs"]["last_row"]["elapsed_s_runs"]) == 1
+    got = {k: np.load(dump / f"{k}.npy") for k in ("obs", "reward", "terminated", "truncated", "gathered_obs")}
+    assert all(x.dtype == np.float32 for x in got.values())
+    assert got["obs"].shape == got["reward"].shape == (64, 4096)          # under the size budget: every value
+    assert np.array_equal(got["gathered_obs"], got["obs"][-1])
+    wl = bench.WORKLOADS["cfg2"]
+    dev = torch.device("cuda", 0)
+    env = RLToyVectorEnv(num_envs=4096, device=dev, env_id_offset=0, rng="numpy", autoreset="same_step", **wl["config"])
+    acts = bench.action_rotation(wl, 64, 4096, dev, 12345)
+    for i in range(1 + 3):
+        out = env.rollout(acts[i % len(acts)])
+    want = [x.float().cpu().numpy() for x in out]
+    env.close()
+    for name, w in zip(("obs", "reward", "terminated", "truncated"), want):
+        assert np.array_equal(got[name], w), name

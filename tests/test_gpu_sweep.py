@@ -23,6 +23,19 @@ SWEEP = sorted(k for k in gu.CASES if "_x" in k and k.rsplit("_x", 1)[-1].isdigi
 KERNELS = {}
 
 
+def _refused_like_the_reference(cfg, e, seeds=None):
+    """A configuration refused at construction: the host restatement of the reference's generator (the MDP and, with pictures,
+    the picture templates) refuses it with the same exception -- the library declines nothing the reference accepts."""
+    from mdp_playground_amd import image_obs, mdp
+    import warnings
+    with warnings.catch_warnings(), pytest.raises(type(e)):
+        warnings.simplefilter("ignore")
+        for c in ([dict(cfg, seed=x) for x in seeds] if seeds is not None else [cfg]):
+            m = mdp.build_mdp(c)
+            if m.kind == "discrete" and m.image is not None:
+                image_obs.build_templates(max(m.S, m.S_irr) if m.irrelevant else m.S, m.image)
+
+
 def _same(x, y):
     return torch.equal(x.view(torch.int32) if x.dtype.is_floating_point else x, y.view(torch.int32) if y.dtype.is_floating_point else y)
 
@@ -31,9 +44,6 @@ def _same(x, y):
 @pytest.mark.parametrize("name", SWEEP)
 def test_sweep_config_at_scale_specialised_equals_general(name, rng):
     from mdp_playground_amd import _capi as capi
-    idx = int(name.rsplit("_x", 1)[-1])
-    if rng.startswith("numpy-") and idx % 5 != (1 if "next" in rng else 3 if "disabled" in rng else 4):
-        pytest.skip("the other autoreset modes / a ragged batch: every fifth configuration each")
     cfg = gu.case_config(name)
     image = bool(cfg.get("image_representations"))
     N, F = (256, 24) if image else (1024, 48)
@@ -215,6 +225,32 @@ def _fuzz_configs(n, seed):
     return out
 
 
+def _same_calls_as_general_kernels(env, cfg, kw, seed, scale=1.0):
+    """_check_vs_oracle's calls (a rollout of 72, three single steps, a rollout of 40) on `env` and on a twin handle with every
+    specialisation switched off (the general kernels the goldens pin): every output of every env and the status words equal."""
+    from mdp_playground_amd import _capi as capi
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        twin = _venv(num_envs=env.num_envs, env_id_offset=env.env_id_offset, **kw, **cfg)
+    twin.set_kernel_options(*capi.OPTIONS)
+    assert _same(env._obs, twin._obs)
+    g = np.random.default_rng(seed)
+    for K in (72, 1, 1, 1, 40):
+        acts = _rand_actions(env, K, g)
+        if scale != 1.0:
+            acts = (acts * np.float32(scale)).astype(np.float32)
+        at = torch.as_tensor(acts, device=env.device)
+        if K == 1:
+            ra, rb = env.step(at[0])[:4], twin.step(at[0])[:4]
+        else:
+            ra, rb = env.rollout(at), twin.rollout(at)
+        torch.cuda.synchronize()
+        assert all(_same(x, y) for x, y in zip(ra, rb)), (cfg, kw, K, env.rollout_kernel_name(K), twin.rollout_kernel_name(K))
+    assert np.array_equal(env.status(), twin.status())
+    twin.close()
+
+
 def _check_vs_oracle(env, k, cfg, mode, kw, seed, scale=1.0, stride=37):
     """A fused rollout of 72 steps, three single steps, a rollout of 40 on `env`; every `stride`-th env stepped through its own oracle."""
     from mdp_playground_amd import _capi as capi
@@ -225,7 +261,7 @@ def _check_vs_oracle(env, k, cfg, mode, kw, seed, scale=1.0, stride=37):
     nextm = kw["autoreset"] == "next_step"        # gymnasium >= 1.0: the call after an episode's last step IS that env's reset()
     philox = env.rng == "philox"
     if philox and nextm:     # (Philox streams are keyed by the BATCH's tick, which also advances on an env's reset call: this per-env loop does not model that)
-        pytest.skip("next-step autoreset on Philox streams: test_gpu_boundary.py / the specialised-equals-general comparison")
+        return _same_calls_as_general_kernels(env, cfg, kw, seed, scale)
     horizon = kw.get("max_episode_steps", 0)
     disc = env.kind == "discrete"
     init = env._obs.cpu().numpy().copy()
@@ -326,7 +362,7 @@ def test_random_configurations_specialised_equals_general(k):
         try:
             a = _venv(**nkw, **kw, **cfg)
         except (NotImplementedError, ValueError, AssertionError, IndexError, KeyError) as e:      # (a combination the host generator refuses, like the reference: e.g. reward_dist + make_denser, IndexError in both)
-            pytest.skip(f"refused at construction: {type(e).__name__}")
+            return _refused_like_the_reference(cfg, e, nkw.get("seeds"))
         b = _venv(**nkw, **kw, **cfg)
     b.set_kernel_options(*capi.OPTIONS)
     g = np.random.default_rng(100 + k)
@@ -374,7 +410,7 @@ def test_random_configurations_default_dispatch_vs_oracle(k):
         try:
             env = _venv(**nkw, **kw, **cfg)
         except (NotImplementedError, ValueError, AssertionError, IndexError, KeyError) as e:
-            pytest.skip(f"refused at construction: {type(e).__name__}")
+            return _refused_like_the_reference(cfg, e, nkw.get("seeds"))
     _check_vs_oracle(env, k, cfg, mode, kw, 500 + k)
     assert not (env.status() & 0x80000000).any()
     env.close()
@@ -583,7 +619,7 @@ def test_random_widened_configurations_specialised_equals_general(k):
         try:
             a = _venv(num_envs=N, **kw, **cfg)
         except (NotImplementedError, ValueError, AssertionError, IndexError, KeyError, TypeError) as e:
-            pytest.skip(f"refused at construction: {type(e).__name__}: {str(e)[:80]}")
+            return _refused_like_the_reference(cfg, e)
         b = _venv(num_envs=N, **kw, **cfg)
     b.set_kernel_options(*capi.OPTIONS)
     names = (a.rollout_kernel_name(F), a.rollout_kernel_name(1), b.rollout_kernel_name(F))
@@ -635,7 +671,7 @@ def test_random_widened_configurations_default_dispatch_vs_oracle(k):
         try:
             env = _venv(num_envs=N, **kw, **cfg)
         except (NotImplementedError, ValueError, AssertionError, IndexError, KeyError, TypeError) as e:
-            pytest.skip(f"refused at construction: {type(e).__name__}: {str(e)[:80]}")
+            return _refused_like_the_reference(cfg, e)
     _check_vs_oracle(env, k, cfg, mode, kw, 1500 + k, scale=1.05 if env.kind == "continuous" else 1.0, stride=29)
     assert not (env.status() & 0x80000000).any()
     env.close()
@@ -681,7 +717,7 @@ def test_random_operation_sequences_specialised_equals_general(fam, k):
         try:
             a = _venv(**nkw, **kw, **cfg)
         except (NotImplementedError, ValueError, AssertionError, IndexError, KeyError, TypeError) as e:
-            pytest.skip(f"refused at construction: {type(e).__name__}")
+            return _refused_like_the_reference(cfg, e, nkw.get("seeds"))
         b = _venv(**nkw, **kw, **cfg)
     b.set_kernel_options(*capi.OPTIONS)
     g = np.random.default_rng(4000 + k)
@@ -792,7 +828,7 @@ def test_pictures_of_fused_rollouts_vs_oracle(src, key):
         try:
             env = _venv(num_envs=N, autoreset="disabled", **cfg)
         except (NotImplementedError, ValueError, AssertionError, IndexError, KeyError, TypeError) as e:
-            pytest.skip(f"refused at construction: {type(e).__name__}")
+            return _refused_like_the_reference(cfg, e)
         twin = _venv(num_envs=N, autoreset="disabled", **{k: v for k, v in cfg.items() if not k.startswith("image_")})
         m = mdp.build_mdp(cfg)
     tpl = image_obs.build_templates(m.S, m.image)
@@ -853,7 +889,7 @@ def test_random_configurations_two_unequal_shards_equal_one_batch(fam, k):
         try:
             whole = make(0, N)
         except (NotImplementedError, ValueError, AssertionError, IndexError, KeyError, TypeError) as e:
-            pytest.skip(f"refused at construction: {type(e).__name__}")
+            return _refused_like_the_reference(cfg, e, seeds if per_env else None)
         parts = [(0, cut, make(0, cut)), (cut, N, make(cut, N))]
     g = np.random.default_rng(7000 + k)
     assert all(_same(whole._obs[lo:hi], p._obs) for lo, hi, p in parts), (fam, k, "initial observations")
