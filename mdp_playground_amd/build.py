@@ -27,7 +27,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=o
 # With the compiler's default, SGPRs are spilled into the lanes of a VGPR, and where that VGPR is itself spilled inside divergent control
 # flow the values parked in the inactive lanes are lost: k_continuous_step<32, 4, PHILOX> ended episodes that had not ended (lanes 43-60
 # of a wave, whenever another lane of the wave ran the in-step reset; round 6, found by the random configurations against the oracle,
-# tools/repro_c14.py).  These translation units spill SGPRs to memory instead; the hand-tuned rollout kernels do not spill and keep
+# pinned by tests/test_gpu_sweep.py::test_general_continuous_kernel_beyond_12_dimensions_on_philox_streams_vs_oracle).  These translation units spill SGPRs to memory instead; the hand-tuned rollout kernels do not spill and keep
 # the default.
 SPILL_SAFE = ["-mllvm", "-amdgpu-spill-sgpr-to-vgpr=0"]
 # (+ the quiet kernel's two units: their Philox instantiations have 32 B of VGPR scratch and the flag costs them 0.4-1.5 %)

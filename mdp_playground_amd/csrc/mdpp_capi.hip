@@ -99,8 +99,6 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     memset(&h->cfg, 0, sizeof(h->cfg));
     h->cfg = *cfg;
     h->device = device;
-    h->num_cus = 256;
-    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0) h->num_cus = v; }
     h->tick = 0; h->reset_tick = 0;
     h->opts = 0; h->kname[0] = 0;
     h->d_P = h->d_rtable = h->d_rbits = h->d_is_term = h->d_init_cdf = h->d_noise_cdf = nullptr;
@@ -127,9 +125,6 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
         const size_t imgs = (size_t)cfg->num_envs * (cfg->irrelevant ? 2 : 1);
         h->img_chunk = imgs <= 32768 ? 64 : imgs <= 65536 ? 32 : 16;
     }
-#ifdef MDPP_ABL_IMG_CHUNK
-    h->img_chunk = MDPP_ABL_IMG_CHUNK;
-#endif
     h->img_ready = false; h->img_fast_ok = false; h->img_lines_ready = false; h->img_colb = 64;
     for (int r = 0; r < 32; r++) h->imgc_disc_rows[r] = 0;
     h->img_n_radii = h->img_n_cls_x = h->img_n_cls_y = 0;
@@ -192,9 +187,6 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
         {
             int lo = 0, hi = 0;
             TRYHIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-#ifdef MDPP_ABL_SIDE_NORMAL
-            hi = 0;
-#endif
             TRYHIP(hipStreamCreateWithPriority(&h->side_stream, hipStreamNonBlocking, hi));
         }
         for (hipEvent_t *e : {&h->ev_entry, &h->ev_side[0], &h->ev_side[1], &h->ev_render[0], &h->ev_render[1]})

@@ -32,12 +32,6 @@ namespace mdpp {
 #ifndef MDPP_CAHEAD_SMALL_D
 #define MDPP_CAHEAD_SMALL_D 4      // noisy rollouts at D <= 4: action rows in flight (Philox streams; numpy streams twice as many)
 #endif
-#ifndef MDPP_CONT_ROWS
-#define MDPP_CONT_ROWS 1           // rewards and flags leave as whole rows of the workgroup (see "whole-row stores" in the kernel)
-#endif
-#ifndef MDPP_CBUFS
-#define MDPP_CBUFS 1               // noise-free rollouts: action rows in flight = MDPP_CBUFS x MDPP_CAHEAD (buffers rotated by NAME: a
-#endif                             // single loop over 8 or more rows is past the compiler's unroll budget and lands in scratch)
 constexpr int kCAheadQuiet = MDPP_CAHEAD, kCAheadNoise = 1; // noisy steps take microseconds: one row ahead hides the load, and a
                                                             // deeper ring would not unroll (step body too large) -> scratch
 constexpr int kCRsrc = 0x00020000;
@@ -55,9 +49,6 @@ __device__ __forceinline__ float c_fdiv_or_mul(float x, float div, float inv, bo
 // count the same K * (D + 1) draws, so nothing is drawn ahead of what the reference would draw.
 // The producer lanes of a wave are not in lockstep: see "park" below.
 constexpr int kNRing = 4;                      // steps of normals buffered per env
-#ifndef MDPP_NP_BATCH
-#define MDPP_NP_BATCH 1
-#endif
 #ifndef MDPP_NP_PARK
 #define MDPP_NP_PARK 3             // (3-6 measure within 1 %, 8 and 12 stall the leading lanes at the ring limit)
 #endif
@@ -178,7 +169,7 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
     // counters (groups staged / groups stored), no barrier (a barrier per group took back most of the gain: 662 -> 641 us).
     // (whole-row stores pay where a step is long: cfg3, D = 12, 610 -> 595 us; at D = 2 the row hand-over between the workgroup's
     //  waves costs more than the stores it saves -- 320 against 281 us per launch, profiles/r05_ablation_d2.txt)
-    constexpr bool CROWS = MDPP_CONT_ROWS && !HELPER && !K1 && D >= 8;
+    constexpr bool CROWS = !HELPER && !K1 && D >= 8;
     static_assert(!K1 || !HELPER, "one step: no helper waves");
     static_assert(!PAR || (K1 && NOISE && !PHILOX), "parallel draws: one step, numpy streams");
     constexpr int kPP = 16;                     // PAR: stream positions evaluated side by side (4 per wave)
@@ -214,13 +205,9 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
     const ZigLds zig{s_ki, s_wi, s_fi};
     // (PAR: one env wave per workgroup -- "lane" and "wave" of the consumer code below are those of that wave, whichever it is)
     const int ln = PAR ? (tid & 63) : (tid & (kBlock - 1)), wv = PAR ? 0 : (ln >> 6);
-    // Workgroup b runs on XCD b % 8 (round-robin dispatch): in a rollout every XCD steps one contiguous eighth of the envs, so that what
-    // its L2 writes back per output row is one contiguous range (MDPP_C_XCD; as in k_discrete_rollout_lean)
-#ifndef MDPP_C_XCD
-#define MDPP_C_XCD 0             /* (measured: cfg3 0.659-0.663 -> 0.649-0.661, cfg5 and c_d2_n0 unchanged: off) */
-#endif
-    const uint32_t bxc = (MDPP_C_XCD && !K1 && (gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-    const uint32_t i = PAR ? blockIdx.x * 64u + (uint32_t)(tid & 63) : bxc * WG + ln;
+    // Blocks go in launch order: the XCD-contiguous order of k_discrete_rollout_lean measured cfg3 0.659-0.663 -> 0.649-0.661 here,
+    // cfg5 and c_d2_n0 unchanged.
+    const uint32_t i = PAR ? blockIdx.x * 64u + (uint32_t)(tid & 63) : blockIdx.x * WG + ln;
     if (i >= (uint32_t)a.N) return;             // HELPER launches require N % kBlock == 0
     const uint32_t N = (uint32_t)a.N;
     const uint64_t genv = (uint64_t)(a.env_id_offset + (int64_t)i);     // global env id (Philox key)
@@ -256,9 +243,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
     if (HELPER && PHILOX && tid >= kBlock) {
         // ---------------- producer lane, Philox: no stream state, every lane of the wave does the same work
         uint32_t hstatus = 0;
-#ifdef MDPP_ABL_NOPROD
-        return;
-#endif
         const int me = tid / kBlock - 1;        // producer index: this wave makes the steps k = me (mod NPROD)
         if (NPROD > 1) __builtin_amdgcn_s_setprio(MDPP_PRODUCER_PRIO);
         uint32_t made = 0;
@@ -319,9 +303,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             // ---------------- generator lane: the words of the env's noise stream, in order, by position -----------------
             // Word p of the launch goes to s_raw[p & 31][lane]; a batch is made when it fits the lane's window (the walker
             // has taken s_rp[lane] words: positions below s_rp + kWRing are free).  No data-dependent control flow.
-#ifdef MDPP_ABL_WK_NOGEN
-            return;
-#endif
             Pcg64 hg;
             hg.load(a.env_s, a.env_inc, i);
             Pcg64Limbs lg;
@@ -363,9 +344,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             return;
         }
         if (tid >= kBlock) {
-#ifdef MDPP_ABL_WK_NOWALK
-            return;
-#endif
             // ---------------- walker lane: numpy's ziggurat over the words of the ring, in numpy's order -----------------
             // One round = up to NB fast attempts on the next NB words (98.8 % of attempts succeed: one table lookup, one
             // compare).  The accepted prefix goes to the normals ring; the first rejected word parks the lane with that
@@ -388,11 +366,7 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             auto z_put = [&](uint32_t c11, double v) __attribute__((always_inline)) { *(lds_f64p)(uintptr_t)((c11 & SM) | z0) = v; };
             for (;;) {
                 const uint32_t cons = __hip_atomic_load(&s_cons[wv], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef MDPP_ABL_WK_NOCONS
-                const uint32_t nlim = total + (cons & 1u);
-#else
                 const uint32_t nlim = kZ0 ? total : min(total, cons * nd + (uint32_t)kWRing);       // (Z0: no normals ring to respect)
-#endif
                 const uint32_t gp = __hip_atomic_load(&s_gp[ln], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 bool progress = false;
                 const bool can = !parked && n < nlim && rp < gp;
@@ -442,11 +416,7 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
                         // sign = bit 8 of the word -> bit 63 (x >= +0: numpy's `if (sign & 0x1) x = -x`)
                         const uint64_t xb = (uint64_t)__double_as_longlong(x);
                         xs[u] = __longlong_as_double((long long)(((uint64_t)(((uint32_t)(xb >> 32) & 0x7FFFFFFFu) | ((wlo << 23) & 0x80000000u)) << 32) | (uint32_t)xb));   // (v_bfi_b32)
-#ifndef MDPP_ABL_WK_NOSLOW
                         bad |= (rabs < kw[u].x) ? 0u : (1u << u);
-#else
-                        bad |= (rabs < kw[u].x + 0x7fffffffffffffffULL) ? 0u : (1u << u);
-#endif
                     }
                     const uint32_t m = (uint32_t)__builtin_ctz(bad);        // accepted prefix (<= allowed)
                     const bool rej = m < allowed;
@@ -502,13 +472,8 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
                             const double u1 = (double)(raw_at(rp << 11) >> 11) * (1.0 / 9007199254740992.0);
                             const double u2 = (double)(raw_at((rp + 1u) << 11) >> 11) * (1.0 / 9007199254740992.0);
                             rp += 2u;
-#ifdef MDPP_ABL_WK_CHEAPTAIL        /* timing only: what the two log1p of a tail try cost the launch */
-                            const double xx = u1 * nor_inv_r;
-                            const double yy = u2 + 8.0;
-#else
                             const double xx = -nor_inv_r * log1p(-u1);
                             const double yy = -log1p(-u2);
-#endif
                             if (yy + yy > xx * xx) {
                                 if (!kZ0) z_put(n << 11, ((pr >> 17) & 0x1) ? -(nor_r + xx) : nor_r + xx);
                                 n += 1u;
@@ -574,7 +539,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
                 cons = __hip_atomic_load(&s_cons[wv], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const uint32_t lim = min((uint32_t)K, cons + (uint32_t)kNRing);
                 const uint64_t bcan = __builtin_amdgcn_ballot_w64(!parked && kl < lim);
-#if MDPP_NP_BATCH
                 // One round = up to MDPP_NP_ATTEMPTS fast attempts per lane, made as a batch: the words of the next states first
                 // (they do not depend on what the attempts decide), then all table lookups at once (one LDS round trip instead of
                 // one per attempt), then the accepted prefix is stored; the stream stops behind the first rejected word, which
@@ -613,23 +577,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
                     }
                     parked = parked || rej;
                 }
-#else
-#pragma unroll
-                for (int u = 0; u < MDPP_NP_ATTEMPTS; u++) {   // fast attempts per round of bookkeeping
-                    if (!parked && kl < lim) {
-                        uint64_t r = hg.next64();
-                        const uint64_t r0 = r;
-                        const int idx = (int)(r & 0xff);
-                        r >>= 8;
-                        const int sign = (int)(r & 0x1);
-                        const uint64_t rabs = (r >> 1) & 0x000fffffffffffffULL;
-                        double x = (double)rabs * zig.wi[idx];
-                        x = sign ? -x : x;
-                        if (rabs < zig.ki[idx]) put(x);
-                        else { parked = true; pr = r0; }
-                    }
-                }
-#endif
                 const uint64_t bpark = __builtin_amdgcn_ballot_w64(parked);
                 if (bpark != 0) {
                     // (no "urgent" rule for a parked lane that holds the next step back: the producer is the
@@ -691,9 +638,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
         if (hstatus) atomicOr(&a.status[i], hstatus);
         return;
     }
-#ifdef MDPP_ABL_WK_NOCONS
-    if (WALK) return;
-#endif
     // (round 5: a noisy step at D <= 4 takes 0.8 us, less than a load's round trip -- one row ahead left the consumer waiting for its
     //  action every step; its step body is small enough to unroll four times)
     //  (c_d2_n0, us per launch at 1 / 2 / 4 / 8 rows ahead: numpy streams 458 / 426 / 402 / 382, Philox 399 / 365 / 342 / 355)
@@ -774,9 +718,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
         }
         s_ki[tid] = k1_ki; s_wi[tid] = k1_wi; s_fi[tid] = k1_fi;
         __syncthreads();
-#ifdef MDPP_ABL_PAR_RET1
-        return;
-#endif
         // ---- every position as the start of a draw: kind 0 accepted at once, 1 wedge accepted, 2 wedge rejected (two words
         // either way), 3 anything else (tail; a wedge whose uniform lies behind the last position) ----
         uint32_t kind[4], idxs[4];
@@ -798,9 +739,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             pend = pend || kind[q] == 4u;
             p_v[p * 64 + l] = x;
         }
-#ifdef MDPP_ABL_PAR_NOWEDGE
-        pend = false;
-#endif
         for (int pass = 0; pass < 4 && __builtin_amdgcn_ballot_w64(pend) != 0; pass++) {       // (one pass serves a lane's first open wedge point)
             int q = 0;
             double x = 0.0;
@@ -832,12 +770,9 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
         }
         ((uint8_t *)p_k)[l * 4 + w4] = (uint8_t)(kind[0] | (kind[1] << 2) | (kind[2] << 4) | (kind[3] << 6));
         __syncthreads();
-#ifdef MDPP_ABL_PAR_RET2
-        return;
-#endif
         // ---- ONE wave walks the stream like numpy: draw d starts at position `pos`.  Not the integrating wave: that one holds the
         // env's state in registers since the top of the launch, and numpy's loop (exp, log1p) inlined into its path spilled
-        // them to scratch (the walk alone then took 4.6 us of a 13.5 us launch, tools/ablate_step1.py); a wave that only made
+        // them to scratch (the walk alone then took 4.6 us of a 13.5 us launch, in an ablation build); a wave that only made
         // words has nothing live here.  It also stores the generator state behind the last word consumed. ----
         if (env_wave) __syncthreads();              // (the walker's normals: every wave of the block passes ONE more barrier)
         else if ((tid >> 6) != ((env_w + 1) & 3)) { __syncthreads(); return; }
@@ -863,7 +798,7 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
         const uint32_t kinds = p_k[l];
         const int nd = D + (a.has_r_noise ? 1 : 0);
         // A ROLLED loop over the draws (unrolled, its D + 1 copies of numpy's loop -- exp, log1p -- are tens of KB of code that
-        // every wave walks past).  Measured (tools/ablate_step1.py, cfg5 at 65 536 envs, replayed graph): words + kinds 4.1 us of
+        // every wave walks past).  Measured (ablation builds, cfg5 at 65 536 envs, replayed graph): words + kinds 4.1 us of
         // the launch, this walk 2.4, the integrator and its stores 4.9 -- and 2.9 for numpy's loop below: a TAIL draw (layer 0
         // beyond |x| = 3.65: two float64 log1p, 2.6 in 10 000 draws) costs about 2 us, a launch of 852 000 draws holds some 220
         // of them, and the launch ends with its slowest wave.  A variant that settled all draws in registers first and sent
@@ -882,11 +817,9 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
                 const bool slow = k >= 2u;
                 double z = p_v[(pos < (uint32_t)kPP ? pos : 0u) * 64 + l];
                 pg.pos = slow ? pos : pos + (k == 0u ? 1u : 2u);
-#ifndef MDPP_ABL_PAR_NOGEN
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64(slow) != 0, 0)) {
                     if (slow) z = np_standard_normal_lds(pg, zig);      // numpy's own loop on the words from `pos` on
                 }
-#endif
                 s_z[d * 64 + l] = z;            // (read back by the integrating wave where the step uses the normal)
             }
         }
@@ -901,9 +834,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
         __syncthreads();
         return;
         }
-#ifdef MDPP_ABL_PAR_RET3
-        return;
-#endif
     } else if constexpr (K1 && ZIG) {           // (launched with N % 256 == 0: every wave of the block reaches the barrier)
         s_ki[tid] = k1_ki; s_wi[tid] = k1_wi; s_fi[tid] = k1_fi;
         __syncthreads();
@@ -999,11 +929,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
 
     auto load_row = [&](int k, float (&dst)[D]) {
         const uint32_t kk = (uint32_t)min(k, K - 1);
-#ifdef MDPP_ABL_NOLOAD
-#pragma unroll
-        for (int d = 0; d < D; d++) dst[d] = 0.001f * (float)((kk + d + i) & 1023u) - 0.5f;
-        return;
-#endif
         if (D == 2) {
             typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
             u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r_act, vrow, kk * row_bytes, 0);
@@ -1020,9 +945,9 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
 
     // (round 6: at D <= 4 a step takes 0.45 us -- four rows ahead were less than a loaded HBM round trip: two buffers of four rows,
     //  c_d2 0.338 -> 0.391 of HBM; three: 0.393; at D = 12 two buffers measure the same as one and eight rows in ONE buffer go to scratch)
-    constexpr int kCBufs = NOISE ? 1 : (D <= 4 && MDPP_CBUFS < 2) ? 2 : MDPP_CBUFS;
-    static_assert(kCBufs >= 1 && kCBufs <= 3, "one to three named buffers");
-    float pre[kCAhead][D], pre1[kCBufs > 1 ? kCAhead : 1][D], pre2[kCBufs > 2 ? kCAhead : 1][D];
+    //  (the buffers are rotated by name: a single loop over 8 or more rows is past the compiler's unroll budget and lands in scratch)
+    constexpr int kCBufs = NOISE ? 1 : D <= 4 ? 2 : 1;
+    float pre[kCAhead][D], pre1[kCBufs > 1 ? kCAhead : 1][D];
     if constexpr (!K1) {
 #pragma unroll
     for (int u = 0; u < kCAhead; u++) load_row(u, pre[u]);
@@ -1030,10 +955,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
     if constexpr (kCBufs > 1 && !K1) {
 #pragma unroll
         for (int u = 0; u < kCAhead; u++) load_row(kCAhead + u, pre1[u]);
-    }
-    if constexpr (kCBufs > 2 && !K1) {
-#pragma unroll
-        for (int u = 0; u < kCAhead; u++) load_row(2 * kCAhead + u, pre2[u]);
     }
 
     auto rmin4 = [&](const uint32_t *p) -> uint32_t {
@@ -1065,9 +986,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             uint32_t spins = 0;
             // (producer k % NPROD has made k / NPROD + 1 steps once step k is in the ring)
             // (WALK: the walker publishes whole steps in s_prod[0])
-#ifdef MDPP_ABL_WK_NOWAIT
-            if (!WALK)
-#endif
             if (!kZ0)                    // (Z0: nothing of the walker's is read)
             while (__hip_atomic_load(&s_prod[WALK ? 0 : k % NPROD][wv], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <
                    (uint32_t)(WALK ? k + 1 : k / NPROD + 1)) {
@@ -1285,10 +1203,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             dist_prev = norm_rel(cur);
         }
         // ---- outputs
-#ifdef MDPP_ABL_NOSTORE
-        status ^= (__float_as_uint(cur[0]) + __float_as_uint(r) + (done ? 1 : 0) + (tr ? 1 : 0)) & 0x100u;
-        return;
-#endif
         if (D == 2) {
             typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
             __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(cur[0]), __float_as_uint(cur[1])},
@@ -1297,7 +1211,7 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             if (V > 1 && full_wave) {
             // rows of D floats -> the wave's 64 rows as one contiguous block, through a wave-private
             // LDS tile: every store instruction then writes 1 KiB of consecutive bytes instead of 64
-            // pieces of 16 B at a stride of 4 D bytes (+15 % on cfg3, tools/ablate_cont.py)
+            // pieces of 16 B at a stride of 4 D bytes (+15 % on cfg3, measured)
             u32x4 *tile = (u32x4 *)(s_tr + (size_t)wv * 64 * D);
             const int l = ln & 63;
 #pragma unroll
@@ -1321,10 +1235,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
                         r_obs, vrow + 16u * q + so * (uint32_t)(D * 4), 0, MDPP_ST_NT);
             }
         }
-#ifdef MDPP_ABL_NORF
-        status ^= (__float_as_uint(r) + (done ? 1 : 0) + (tr ? 1 : 0)) & 0x100u;
-        return;
-#endif
         if constexpr (CROWS) {
             if (crows && k < k_rows) {                  // (wave-uniform)
                 const int grp = k / kRS, slot = k & (kRS - 1);
@@ -1370,7 +1280,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
     for (int gq = 0; gq < ngrp; gq++) {
         chunk(pre, gq * kCBufs);
         if constexpr (kCBufs > 1) chunk(pre1, gq * kCBufs + 1);
-        if constexpr (kCBufs > 2) chunk(pre2, gq * kCBufs + 2);
     }
     // the last full chunks and the ragged tail: rows already in the buffers (loads past the end were clamped)
     for (int k = ngrp * kCBufs * kCAhead; k < (K1 ? 0 : K); k++) {
@@ -1381,7 +1290,7 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
             if (uu == u) {
 #pragma unroll
                 for (int d = 0; d < D; d++)
-                    act[d] = (kCBufs > 2 && b == 2) ? pre2[kCBufs > 2 ? uu : 0][d] : (kCBufs > 1 && b == 1) ? pre1[kCBufs > 1 ? uu : 0][d] : pre[uu][d];
+                    act[d] = (kCBufs > 1 && b == 1) ? pre1[kCBufs > 1 ? uu : 0][d] : pre[uu][d];
             }
         step(act, k);
     }
@@ -1393,12 +1302,7 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
         // One step leaves 150-250 B of state per env: as plain stores they sit dirty in the L2s until the launch ends and are
         // written back THEN, all at once, before the next launch may start (MI355X_MICROARCH.md, "boundary": + B / 6 TB/s for B
         // dirty bytes: 10 MB = 1.7 us per step); as non-temporal stores they leave while the other waves still compute.
-#ifndef MDPP_K1_PLAIN_STORES
-#ifdef MDPP_K1_ABL_NOSTATE          /* timing only: no state stores at all */
-        if (steps == 0x7fffffffu) a.meta[i].x = __float_as_uint(sd[0][0] + cur[0]);
-        return;
-#endif
-        // (where a cfg3 launch's 5.42 us go, tools/ablate_step1.py: without these state stores 3.78, without the observation /
+        // (where a cfg3 launch's 5.42 us go, measured by ablation builds: without these state stores 3.78, without the observation /
         //  reward / flag stores 5.21, without both 2.71 -- the stores drain at about 7 TB/s, 13.5 MB of them.  Storing the rows as 16
         //  bytes per lane through an LDS tile, 9 instructions instead of 37, changed nothing: 5.40 against 5.48 -- bytes, not requests.)
 #pragma unroll
@@ -1412,7 +1316,6 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
         if (ZIG && !PAR) g.store(a.env_s, i);       // (PAR: the walking wave stored it)
         if (status) atomicOr(&a.status[i], status);
         return;
-#endif
     }
 #pragma unroll
     for (int k = 0; k <= ORDER; k++)
@@ -1483,12 +1386,10 @@ bool launch_continuous_step1(const ContinuousArgs &a, const float *actions, floa
         }                                                                                                                     \
     }
     MDPP_K1(12, 1, 4) MDPP_K1(12, 2, 4)
-#ifndef MDPP_CF_SHAPES_MIN
     MDPP_K1(2, 1, 2) MDPP_K1(2, 2, 2) MDPP_K1(4, 1, 4) MDPP_K1(4, 2, 4)
     MDPP_K1(8, 1, 8) MDPP_K1(8, 2, 8) MDPP_K1(12, 1, 12) MDPP_K1(12, 2, 12)
     MDPP_K1(4, 1, 2) MDPP_K1(4, 2, 2) MDPP_K1(8, 1, 4) MDPP_K1(8, 2, 4)
     MDPP_K1(2, 3, 2)                // (the reference's *_move_to_a_point_p_order_3 sweeps)
-#endif
 #undef MDPP_K1
     return false;
 }
@@ -1562,17 +1463,11 @@ bool launch_continuous_fast(const ContinuousArgs &a, int K, const float *actions
                             hipStream_t s, char *name_out) {
     if (!a.fast_ok || (a.opts & MDPP_OPT_NO_CFAST) || (a.philox && (a.opts & MDPP_OPT_NO_PHILOX_FAST))) return false;
 #define MDPP_CF(DD, OO, RR) if (a.D == DD && a.order == OO && a.n_rel == RR) { launch_t<DD, OO, RR>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out); return true; }
-#ifdef MDPP_CF_SHAPES_D2             // (disassembly builds: the reference's sweep shape alone)
-    MDPP_CF(2, 1, 2)
-    return false;
-#endif
     MDPP_CF(12, 1, 4) MDPP_CF(12, 2, 4)
-#ifndef MDPP_CF_SHAPES_MIN          // (resource-usage / ablation builds compile the BASELINE shapes only)
     MDPP_CF(2, 1, 2) MDPP_CF(2, 2, 2) MDPP_CF(4, 1, 4) MDPP_CF(4, 2, 4)
     MDPP_CF(8, 1, 8) MDPP_CF(8, 2, 8) MDPP_CF(12, 1, 12) MDPP_CF(12, 2, 12)
     MDPP_CF(4, 1, 2) MDPP_CF(4, 2, 2) MDPP_CF(8, 1, 4) MDPP_CF(8, 2, 4)
     MDPP_CF(2, 3, 2)                // (the reference's *_move_to_a_point_p_order_3 sweeps)
-#endif
 #undef MDPP_CF
     return false;
 }

@@ -98,12 +98,7 @@ __global__ __launch_bounds__(HELPER ? 2 * kBlock : kBlock) void k_discrete_rollo
         lds_R[k] = w;
     }
     __syncthreads();
-#ifdef MDPP_ABL_HALFWAVE
-    if (tid & 32) return;   // experiment: 32 active lanes per wave, twice the waves
-    const uint32_t i = blockIdx.x * (kBlock / 2) + (tid >> 6) * 32 + (tid & 31);
-#else
     const uint32_t i = blockIdx.x * kBlock + (HELPER ? (tid & (kBlock - 1)) : tid);
-#endif
     if (i >= (uint32_t)a.N) return;
     const uint32_t N = (uint32_t)a.N;
     const uint32_t A = (uint32_t)a.A, S = (uint32_t)a.S, L = (uint32_t)a.L;
@@ -242,12 +237,8 @@ __global__ __launch_bounds__(HELPER ? 2 * kBlock : kBlock) void k_discrete_rollo
 
     // ---- phase A of a step: everything that does not need the reward bit -------------------
     auto stepA = [&](uint64_t col, uint32_t so) -> Pending {
-#ifdef MDPP_ABL_NOLDSP
-        const uint32_t nxt = (e.cur + (uint32_t)col) & 7u;
-#else
         const uint32_t nxt = S8 ? (((uint32_t)col >> (e.cur << 2)) & 0xFu)            // D1
                                 : (uint32_t)((col >> (e.cur << 2)) & 0xFu);
-#endif
         if (POW2) {                                                                   // D3 / D4 key
             e.key = ((e.key << a.s_shift) | nxt) & a.key_mask;
         } else {
@@ -259,22 +250,14 @@ __global__ __launch_bounds__(HELPER ? 2 * kBlock : kBlock) void k_discrete_rollo
         e.steps += 1;
         e.phase = (e.phase + 1 == every_n) ? 0u : e.phase + 1;
         Pending p;
-#ifdef MDPP_ABL_NOLDSR
-        p.word = e.key;
-#else
         p.word = lds_R[e.key >> 5];                                                    // in flight
-#endif
         p.sh = e.key & 31u;
         p.so = so;
         const bool full = (e.hist & nan_mask) != nan_mask;   // L transitions since reset (:1822)
         const bool pay = e.phase == 0;                       // steps % every_n == 0 (:1975)
         const uint32_t done = (term32 >> nxt) & 1u;                                   // D7
         const uint32_t tr = (has_max && e.steps >= max_steps) ? 1u : 0u;
-#ifdef MDPP_ABL_NORESET
-        const bool need = false;
-#else
         const bool need = autoreset && ((done | tr) != 0);
-#endif
         p.flags = (full ? 1u : 0u) | (done << 1) | (need ? 4u : 0u) | (pay ? 8u : 0u);
         // queue ran dry (rare): draw in place
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(need && e.qc == 0) != 0, 0)) {
@@ -302,14 +285,10 @@ __global__ __launch_bounds__(HELPER ? 2 * kBlock : kBlock) void k_discrete_rollo
             e.qv = need ? (e.qv >> 4) : e.qv;
             e.qc = e.qc - (need ? 1u : 0u);
         }
-#ifndef MDPP_ABL_NOSTORE
         if (OBS64) __builtin_amdgcn_raw_buffer_store_b64(u32x2{e.cur, 0u}, r_obs, v8, so * 8u, MDPP_ST_NT);
         else __builtin_amdgcn_raw_buffer_store_b32(e.cur, r_obs, v4, so * 4u, MDPP_ST_NT);
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)done, r_term, v1, so, MDPP_ST_NT);
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)tr, r_trunc, v1, so, MDPP_ST_NT);
-#else
-        e.status ^= (e.cur + done + tr) & 0x100u;
-#endif
         return p;
     };
     // ---- phase B: reward bit -> delay line -> reward.  The reference applies, in this order,
@@ -329,11 +308,7 @@ __global__ __launch_bounds__(HELPER ? 2 * kBlock : kBlock) void k_discrete_rollo
         const float r_t = bit ? rs3 : rs1;
         const float rout = done ? r_t : r_nt;
         if (DELAY) e.ring = (p.flags & 4u) ? 0u : e.ring;
-#ifndef MDPP_ABL_NOSTORE
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rout), r_rew, v4, p.so * 4u, MDPP_ST_NT);
-#else
-        e.status ^= __float_as_uint(rout) & 0x100u;
-#endif
     };
 
     // Software pipeline: at the top of chunk c the action loads of chunk c+2 are issued, the
@@ -364,9 +339,7 @@ __global__ __launch_bounds__(HELPER ? 2 * kBlock : kBlock) void k_discrete_rollo
         uint64_t col1[kAhead];
 #pragma unroll
         for (int u = 0; u < kAhead; u++) col1[u] = column(act1[u]);
-#ifndef MDPP_ABL_NOREFILL
         if (HELPER) pull(); else refill();
-#endif
         if (c > 0) { // peeled so that the chunk body has no per-step branch
             Pending p = stepA(col0[0], (uint32_t)kbase * N);
             stepB(pend);
@@ -405,11 +378,7 @@ bool launch_discrete_fast(const DiscreteArgs &a, int K, const int32_t *actions, 
                           float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
                           hipStream_t s, char *name_out) {
     if (!a.fast_ok) return false;
-#ifdef MDPP_ABL_HALFWAVE
-    const int grid = (a.N + kBlock / 2 - 1) / (kBlock / 2);
-#else
     const int grid = (a.N + kBlock - 1) / kBlock;
-#endif
     const bool pow2 = a.s_shift != 0xFFFFFFFFu, dl = a.delay > 0, s8 = a.S <= 8;
     // helper waves pay off on long rollouts of full 256-env blocks
     const bool helper = K >= 32 && (a.N % kBlock) == 0 && a.autoreset && !(a.opts & MDPP_OPT_NO_HELPER);

@@ -33,14 +33,14 @@
 //   * "reset happened" = the history words before and after it differ
 // NZ (Philox streams only; bit 0 transition noise, bit 1 reward noise; mdpp_discrete_lean_noise.hip): everything random
 // about tick t is one word / one float32 normal of a block that serves four ticks (mdpp_rng.hpp philox_pnoise_*,
-// PhiloxTickNormals).  H makes the chunk's eight transition-noise nibbles (noisy << 3 | index of the re-drawn state among
-// the others) beside its start states; the E lane applies one with seven instructions and re-encodes the column byte
+// PhiloxTickNormals).  The O2 lane makes the chunk's eight transition-noise nibbles (noisy << 3 | index of the re-drawn
+// state among the others), H its start states; the E lane applies one with seven instructions and re-encodes the column byte
 // with a v_perm_b32 of a constant; the O1 lane makes its own eight normals per chunk (two blocks, two packed Box-Muller
 // pairs) and forms the reward in float64 in the reference's order (:1980-1990, :2107).
 // NZ on NUMPY streams (round 4; mdpp_discrete_lean_npnoise.hip): the reference's own draws, bit for bit, without putting a
 // generator on the E lane (k_discrete_rollout_quiet<PN, RN> runs both PCG64 streams, the categorical search and the
-// ziggurat inside the recurrence: 607 us per cfg2 launch).  The H wave owns both streams:
-//   * transition noise (:1604-1622) takes exactly one word of the state space's stream per step, so H makes the chunk's
+// ziggurat inside the recurrence: 607 us per cfg2 launch).  The O2 wave owns the state space's stream, the H wave the env's:
+//   * transition noise (:1604-1622) takes exactly one word of the state space's stream per step, so O2 makes the chunk's
 //     eight words ahead like the Philox form; the categorical around table entry n is searched ONCE for all n -- with
 //     a = #{j : TL[j] <= r}, b = #{j : TU[j] <= r} the re-drawn state is min(a, n) + max(b - n, 0) (DiscreteArgs::pn_TL:
 //     exact whenever the rows' thresholds agree, which the host checks) -- and E applies the byte (a | b << 4);
@@ -113,23 +113,8 @@ namespace mdpp {
 #ifndef MDPP_LEAN_HMIN
 #define MDPP_LEAN_HMIN 16
 #endif
-#ifndef MDPP_LEAN_PHILOX_PN_O2
-#define MDPP_LEAN_PHILOX_PN_O2 1   // Philox transition noise: the chunk's noise nibbles are made by the O2 wave (1) / the H wave (0)
-#endif
-#ifndef MDPP_LEAN_H_LIMBS
-#define MDPP_LEAN_H_LIMBS 0        // (the limb form of PCG64 on the numpy H wave: 137 us per cfg2 launch either way -- H is not what bounds it)
-#endif
-#ifndef MDPP_LEAN_H_SSTAB
-#define MDPP_LEAN_H_SSTAB 0        // numpy H wave without noise: start state by the word's top 11 bits from lds_sstab (1) / eight compares (0)
-#endif
 #ifndef MDPP_LEAN_HSLEEP
 #define MDPP_LEAN_HSLEEP 8
-#endif
-#ifndef MDPP_LEAN_XCD_CONTIG
-#define MDPP_LEAN_XCD_CONTIG 1     // every XCD steps one contiguous eighth of the envs (0: blocks in launch order, round-robin over the XCDs)
-#endif
-#ifndef MDPP_LEAN_ROWS
-#define MDPP_LEAN_ROWS 3           // whole-row stores (header): bit 0 obs and flags, bit 1 the rewards too, bit 2 also in the noise instantiations
 #endif
 namespace lean {
 constexpr int kChunk = MDPP_LEAN_CHUNK;   // steps between hand-off polls; also the action prefetch distance
@@ -215,13 +200,9 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     constexpr bool Z0 = (NZ & 4) != 0;
     static_assert(!Z0 || NRN, "sigma-0 draws: numpy streams with the reward_noise key");
     constexpr bool NRX = NRN && !Z0;                                  // ... whose values are used
-    // (Z0 without transition noise: the records carry no normal and the O waves are the noise-free kernel's -- the deep ring and the
-    //  whole-row stores of the noise-free form, MDPP_LEAN_Z0_ROWS)
-#ifndef MDPP_LEAN_Z0_ROWS
-#define MDPP_LEAN_Z0_ROWS 0        /* measured: d_s8_rn0 236 -> 233-238 us, nothing -- the H / E position pipeline bounds this form, not its stores */
-#endif
-    constexpr bool ZROWS = MDPP_LEAN_Z0_ROWS && Z0 && !PN;
-    constexpr int KD = (NRN && !ZROWS) ? kDepthNp : kDepth;           // E->O ring depth in steps
+    // (Z0 keeps the numpy-noise ring and per-lane stores: the noise-free form's deep ring and whole-row stores measured d_s8_rn0
+    //  236 -> 233-238 us, nothing -- the H / E position pipeline bounds this form, not its stores)
+    constexpr int KD = NRN ? kDepthNp : kDepth;                       // E->O ring depth in steps
     __shared__ __align__(16) uint32_t lds_rec[3][KD][kBlock];
     __shared__ __align__(16) uint32_t lds_V[2048];            // reward bit & NaN gate, by the 4 low nibbles
     __shared__ __align__(16) uint2 lds_col[16];               // action a, byte s: P[s][a] | 8 | is_term[P[s][a]] << 7
@@ -233,18 +214,18 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     __shared__ uint32_t lds_prod[kBlock / 64];                // steps published by E wave w
     __shared__ __align__(8) uint32_t lds_cons[kBlock / 64][2]; // steps consumed by the O1 / O2 wave w
     __shared__ uint32_t lds_done;                             // E waves that have finished
-    // Whole-row stores (MDPP_LEAN_ROWS; tools/bench_store.hip: the same bytes leave 10 % faster when one wave writes the
+    // Whole-row stores (tools/bench_store.hip: the same bytes leave 10 % faster when one wave writes the
     // workgroup's whole piece of an output row -- obs 2 KiB, reward 1 KiB, flags 256 B -- than when every wave writes its
     // own 64 envs of every row): of a chunk's 8 rows the O waves w take rows w and w + 4, for all 256 envs of the block.
     // The O2 wave reads the other E waves' records (E waits for ALL four O2 waves before it reuses a ring slot); the O1
     // wave -- its reward path carries state from step to step -- computes its own envs' 8 rewards as before and hands
     // them to the O2 waves through lds_rw (kRB chunks deep), which store them too.  Blocks with spare lanes (N % 256)
     // keep the per-lane stores.
-    constexpr bool ROWS2 = (MDPP_LEAN_ROWS & 1) != 0 && !IRR && (NZ == 0 || ZROWS || (MDPP_LEAN_ROWS & 4) != 0);   // (noise: the O waves are long stages there -- no gain, measured)
+    constexpr bool ROWS2 = !IRR && NZ == 0;   // (noise: the O waves are long stages there -- no gain, measured)
     // (rewards through the O2 waves: numpy streams only -- with Philox streams, where E runs at the lowest priority, 124-128 us per cfg2
     //  launch became 132-133; numpy streams 115-120 -> 112-118; without whole-row stores 129-137, all on one lease)
-    constexpr bool ROWS1 = (MDPP_LEAN_ROWS & 2) != 0 && ROWS2 && !PHILOX && (!NRN || ZROWS);
-    constexpr int kRB = ZROWS ? 2 : 4;                        // chunks of staged rewards (the O1 waves run this far ahead of the stores; Z0: LDS)
+    constexpr bool ROWS1 = ROWS2 && !PHILOX;
+    constexpr int kRB = 4;                                    // chunks of staged rewards (the O1 waves run this far ahead of the stores)
     __shared__ __align__(16) float lds_rw[ROWS1 ? kRB : 1][kChunk][ROWS1 ? kBlock : 4];
     __shared__ __align__(16) uint32_t lds_rprod[kBlock / 64], lds_rcons[kBlock / 64];   // chunks staged by O1 wave w / stored by O2 wave w
     typedef typename std::conditional<IRR, uint64_t, uint32_t>::type S0Word;   // a nibble per tick; with an irrelevant sub-space two
@@ -264,12 +245,12 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     // Philox streams with noise (round 4, the transition-noise nibbles made by the O2 wave): E last, the three waves that make
     // Philox blocks level -- E 1, O1 2, H 2, O2 2 (3 without reward noise): 191 -> 168 us both noises, 143 -> 138 transition
     // noise alone (24 combinations: profiles/r04_ablation_lean_philox_noise.txt)
-    constexpr bool kPhNoise = PHILOX && NZ != 0 && MDPP_LEAN_PHILOX_PN_O2;
+    constexpr bool kPhNoise = PHILOX && NZ != 0;
     constexpr int kPrioE = MDPP_LEAN_PRIO_FORCED ? MDPP_LEAN_PRIO_E : kNpNoise ? 2 : !PHILOX ? MDPP_LEAN_PRIO_E : 1;
     constexpr int kPrioO = MDPP_LEAN_PRIO_FORCED ? MDPP_LEAN_PRIO_O : kNpNoise ? 1 : !PHILOX ? MDPP_LEAN_PRIO_O : kPhNoise ? 2 : (PN ? 2 : 3);
     constexpr int kPrioH = MDPP_LEAN_PRIO_FORCED ? MDPP_LEAN_PRIO_H : kNpNoise ? 3 : !PHILOX ? MDPP_LEAN_PRIO_H : kPhNoise ? 2 : (PN ? 3 : 2);
     static_assert(NZ == 0 || (!IRR && !NEXT), "noise on the lean kernel: one sub-space, same-step autoreset");
-    __shared__ __align__(16) uint32_t lds_pn[(PN && PHILOX) ? kHChunks : 1][kBlock];       // H -> E: the chunk's 8 transition-noise nibbles
+    __shared__ __align__(16) uint32_t lds_pn[(PN && PHILOX) ? kHChunks : 1][kBlock];       // O2 -> E: the chunk's 8 transition-noise nibbles
     // numpy streams (header): transition-noise bytes of a chunk; per stream position the draw's value and {start state, kind, words}
     __shared__ __align__(16) uint32_t lds_pn2[NPN ? kHChunksNp : 1][2][kBlock];
     __shared__ __align__(16) double lds_x[NRX ? kXR : 1][kBlock];
@@ -278,8 +259,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     __shared__ uint32_t lds_hhead[NRN ? kBlock : 1], lds_epos[NRN ? kBlock : 1];   // positions made by H / reached by E
     // the two categorical searches of H by the word's top bits: byte = the answer where the bucket holds no threshold, 0xFF
     // where it does (then the thresholds are counted: a few lanes per thousand)
-    constexpr bool HSS = MDPP_LEAN_H_SSTAB && !PHILOX && NZ == 0 && !IRR;
-    __shared__ uint8_t lds_sstab[(NRN || NPN || HSS) ? 2048 : 1];     // start state by r >> 53
+    __shared__ uint8_t lds_sstab[(NRN || NPN) ? 2048 : 1];     // start state by r >> 53
     __shared__ uint8_t lds_pntab[NPN ? 4096 : 1];                     // a | b << 4 by r >> 52
     __shared__ ulonglong2 lds_kw[NRN ? 256 : 1];                       // ziggurat {ki, wi * 2^52}
     __shared__ double lds_fi[NRN ? 256 : 1];
@@ -324,7 +304,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
         lds_R[k] = wd;
     }
     if (tid < kBlock) { lds_ring[tid] = 0; lds_head[tid] = 0; if (NRN) { lds_hhead[tid] = 0; lds_epos[tid] = 0; } }
-    if (NRN || NPN || HSS) {
+    if (NRN || NPN) {
         for (uint32_t k = tid; k < 2048u; k += kRoles * kBlock) {
             const uint64_t lo = (uint64_t)k << 53, hi = lo + ((1ULL << 53) - 1ULL);       // the bucket's words
             uint32_t c0 = 0, c1 = 0;
@@ -371,7 +351,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     //  writes the word back at the end of the launch, and with K <= kDepth it could get there before O1 starts)
     uint32_t steps_at_launch = 0;
     {
-        const uint32_t eb0 = (MDPP_LEAN_XCD_CONTIG && (gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+        const uint32_t eb0 = ((gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
         const uint32_t i0 = eb0 * kBlock + l;
         if (EVN && role == 1 && i0 < (uint32_t)a.N) steps_at_launch = ((const uint32_t *)&a.state[i0])[2] & 0x7FFFFFFFu;
     }
@@ -380,7 +360,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     // Workgroup b runs on XCD b % 8 (round-robin dispatch).  Give every XCD one contiguous eighth of the
     // envs, so that what its L2 writes back per output row is one contiguous range, not every eighth
     // 256-env piece of it.
-    const uint32_t eblk = (MDPP_LEAN_XCD_CONTIG && (gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const uint32_t eblk = ((gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
     const uint32_t i = eblk * kBlock + l;
     const uint32_t N = (uint32_t)a.N;
     const bool rows = ROWS2 && (N % (uint32_t)kBlock) == 0u;       // (every wave of every block is there)
@@ -403,9 +383,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
 
     // =============================================================== H: start-state producer
     if (role == 3) {
-#if defined(MDPP_ABL_NOH) && defined(MDPP_ABL_NORESET)
-        return;         // (only together with NORESET: without the H waves every reset spins to its bound -- minutes per launch)
-#endif
         if (!ar && !PN && !NRN) return;
         __builtin_amdgcn_s_setprio(kPrioH);
         if constexpr (PHILOX) {
@@ -456,16 +433,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
                     pk |= (S0Word)(s0 | 8u) << (kEN * 4 * u);
                 }
                 lds_s0[c % kHChunks][l] = pk;
-                if constexpr (PN && !MDPP_LEAN_PHILOX_PN_O2) {   // noisy << 3 | j (S <= 8: j <= 6), mdpp_rng.hpp philox_pnoise_index
-                    uint32_t wp[kChunk], pn = 0;
-                    words(kPhiloxPNoiseStream, wp);
-#pragma unroll
-                    for (int u = 0; u < kChunk; u++) {
-                        const uint32_t e = philox_pnoise_index(wp[u], a.pn_T, a.pn_M);
-                        pn |= ((e & 7u) | ((e >> 5) & 8u)) << (4 * u);
-                    }
-                    lds_pn[c % kHChunks][l] = pn;
-                }
                 if ((l & 63) == 0) wg_store_rel(&lds_hprod[w], (uint32_t)(c + 1));
             }
             if (status) atomicOr(&a.status[i], status);
@@ -485,9 +452,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             uint32_t vals = 0, tail = 0, spins = 0; // !RN: the start-state queue (as on quiet handles)
             // start state of a reset whose word is r: #{j : ceil(cdf[j] 2^53) <= r >> 11}
             auto start_of = [&](uint64_t r) __attribute__((always_inline)) -> uint32_t {
-#ifdef MDPP_ABL_NP_NOSS
-                return (uint32_t)(r >> 61) % 6u;
-#endif
                 uint32_t s0 = lds_sstab[(uint32_t)(r >> 53)];
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64(s0 == 0xFFu) != 0, 0)) {
                     if (s0 == 0xFFu) {
@@ -532,11 +496,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
                                 const uint64_t xb = (uint64_t)__double_as_longlong(x);
                                 const double xs = __longlong_as_double((long long)(((uint64_t)(((uint32_t)(xb >> 32) & 0x7FFFFFFFu) |
                                                                                    (((uint32_t)wd << 23) & 0x80000000u)) << 32) | (uint32_t)xb));
-#ifdef MDPP_ABL_NP_NOSLOW
-                                const bool ok = rabs < kw.x + 0x7fffffffffffffffULL;
-#else
                                 const bool ok = rabs < kw.x;
-#endif
                                 rej |= ok ? 0u : (1u << u);
                                 const uint32_t slot = (hq + (uint32_t)u) & (uint32_t)(kXR - 1);
                                 lds_x[slot][l] = xs;
@@ -653,32 +613,14 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             if (status) atomicOr(&a.status[i], status);
             return;
         }
-        Pcg64 g;
+        Pcg64 g;                // (the limb form of PCG64 here: 137 us per cfg2 launch either way -- H is not what bounds it)
         g.load(a.env_s, a.env_inc, i);
-#if MDPP_LEAN_H_LIMBS
-        // (the hand-scheduled limb form of the generator: 31 instead of 46 vector instructions per word on the filler wave)
-        Pcg64LimbsLo gl;
-        gl.from(g);
-        auto draw = [&](Pcg64LimbsLo &gg) -> uint32_t {
-#else
         auto draw = [&](Pcg64 &gg) -> uint32_t {
-#endif
             const uint64_t r0 = gg.next64();
             const uint64_t m = r0 >> 11;
             uint32_t s0 = 0;
-            if constexpr (HSS) {                                 // (the bucket's answer; 0xFF = a threshold inside it: count)
-                s0 = lds_sstab[(uint32_t)(r0 >> 53)];
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(s0 == 0xFFu) != 0, 0)) {
-                    if (s0 == 0xFFu) {
-                        s0 = 0;
 #pragma unroll
-                        for (int j = 0; j < 8; j++) s0 += (lds_T[j] <= m) ? 1u : 0u;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; j++) s0 += (lds_T[j] <= m) ? 1u : 0u;
-            }
+            for (int j = 0; j < 8; j++) s0 += (lds_T[j] <= m) ? 1u : 0u;
             if (IRR) {                                           // relevant, then irrelevant, like reset() (:2255-2264)
                 const uint64_t m1 = gg.next64() >> 11;
                 uint32_t s1 = 0;
@@ -697,19 +639,11 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             const uint64_t bw = __builtin_amdgcn_ballot_w64(want);
             const bool urgent = __builtin_amdgcn_ballot_w64(want && cnt <= 2) != 0;
             if (__builtin_popcountll(bw) >= kMinLanes || urgent) {
-#if MDPP_LEAN_H_LIMBS
-                Pcg64LimbsLo n = gl;
-#else
                 Pcg64 n = g;
-#endif
                 const uint32_t s0 = draw(n) | 8u;
                 if (want) {
                     const uint32_t sh = (tail & 7u) * 4u;
-#if MDPP_LEAN_H_LIMBS
-                    gl = n;
-#else
                     g = n;
-#endif
                     vals = (vals & ~((IRR ? 0xFFu : 0xFu) << sh)) | (s0 << sh);
                     tail += (uint32_t)kEN;                       // (in nibbles = in draws of the stream)
                 }
@@ -720,9 +654,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             }
         }
         // un-draw what the env lane did not take: s_prev = (s - inc) * M^-1 (mod 2^128)
-#if MDPP_LEAN_H_LIMBS
-        gl.to(g);
-#endif
         const uint32_t head = wg_load_acq(&lds_head[l]);
         for (uint32_t q = tail - head; q > 0; q--) {
             uint64_t lo = g.s_lo - g.inc_lo;
@@ -739,9 +670,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
 
     // =============================================================== O1: reward path
     if (role == 1) {
-#ifdef MDPP_ABL_NOO1
-        return;
-#endif
         __builtin_amdgcn_s_setprio(kPrioO);
         auto r_rew = __builtin_amdgcn_make_buffer_rsrc((void *)reward, 0, total * 4u, kPRsrc);
         const uint32_t v4 = i * 4u;
@@ -789,11 +717,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             }
             if (nextmode) rout = (ra != rb) ? 0.0f : rout;                           // the reset call returns reward 0
             if (stage) { *stage = rout; return; }
-#if defined(MDPP_ABL_NOSTORE) || defined(MDPP_ABL_NOREW)
-            status ^= __float_as_uint(rout) & 0x100u;
-#else
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rout), r_rew, v4, so * 4u, MDPP_LEAN_ST_AUX);
-#endif
         };
         for (int c = 0; c < nchunks; c++) {
             const int kbase = c * kChunk;
@@ -801,11 +725,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             if constexpr (RN && PHILOX)       // (before the wait: independent of E)
                 chunk_normals(a.philox_seed, genv, (ptick0 + (uint64_t)kbase) >> 2, r4, kPhiloxRNoiseStream, zc);
             uint32_t spins = 0;
-#ifdef MDPP_ABL_FREEO
-            while (false) {
-#else
             while (wg_load_acq(&lds_prod[w]) < upto) {
-#endif
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
             }
@@ -851,14 +771,11 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
 
     // =============================================================== O2: observation, terminated, truncated
     if (role == 2) {
-#ifdef MDPP_ABL_NOO2
-        return;
-#endif
         // (numpy transition noise: this wave runs the state space's generator -- a long stage like H)
         // (3 beside an H wave that only keeps the start-state queue, 2 beside one that evaluates the env stream: 159 / 306 us per
         //  cfg2 launch with transition noise / both noises, against 202 / 313 at the O waves' priority)
         __builtin_amdgcn_s_setprio(MDPP_LEAN_PRIO_O2 >= 0 ? MDPP_LEAN_PRIO_O2 : (NPN && !MDPP_LEAN_PRIO_FORCED) ? (NRN ? 2 : 3)
-                                   : (PN && PHILOX && MDPP_LEAN_PHILOX_PN_O2 && !MDPP_LEAN_PRIO_FORCED) ? (RN ? 2 : 3) : kPrioO);
+                                   : (PN && PHILOX && !MDPP_LEAN_PRIO_FORCED) ? (RN ? 2 : 3) : kPrioO);
         auto r_obs = __builtin_amdgcn_make_buffer_rsrc(obs, 0, total * (OBS64 ? 8u : 4u) * (uint32_t)kEN, kPRsrc);
         auto r_term = __builtin_amdgcn_make_buffer_rsrc((void *)term, 0, total, kPRsrc);
         auto r_rew2 = __builtin_amdgcn_make_buffer_rsrc((void *)reward, 0, total * 4u, kPRsrc);
@@ -866,13 +783,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
         const uint32_t v1 = i, v4 = i * 4u, v8 = i * 8u, v16 = i * 16u;
         auto emit = [&](uint32_t rb, uint32_t rc, uint32_t so) {
             const uint32_t o = rb & 7u;
-#ifdef MDPP_ABL_NOSTORE
-            status ^= (o + rc) & 0x100u;
-            return;
-#endif
-#ifdef MDPP_ABL_NOOBS
-            status ^= o & 0x100u;
-#else
             if (IRR) {
                 const uint32_t o1 = (rc >> 8) & 7u;
                 // (128-bit stores: the whole offset in the VGPR, see the store-data hazard note in mdpp_discrete_quiet.hip)
@@ -880,13 +790,8 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
                 else __builtin_amdgcn_raw_buffer_store_b64(u32x2{o, o1}, r_obs, v8, so * 8u, MDPP_LEAN_ST_AUX);
             } else if (OBS64) __builtin_amdgcn_raw_buffer_store_b64(u32x2{o, 0u}, r_obs, v8, so * 8u, MDPP_LEAN_ST_AUX);
             else __builtin_amdgcn_raw_buffer_store_b32(o, r_obs, v4, so * 4u, MDPP_LEAN_ST_AUX);
-#endif
-#ifdef MDPP_ABL_NOBYTES
-            status ^= rc & 0x100u;
-#else
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((rc >> 7) & 1u), r_term, v1, so, MDPP_LEAN_ST_AUX_BYTES);
             __builtin_amdgcn_raw_buffer_store_b8(HASMAX ? (uint8_t)(rc >> 16) : (uint8_t)0, r_trunc, v1, so, MDPP_LEAN_ST_AUX_BYTES);
-#endif
         };
         // numpy transition noise (header): this wave owns the state space's stream and makes the noise bytes of chunk pc --
         // one word per step -- up to kHChunksNp chunks ahead of the chunk E has finished (slot pc % kHChunksNp is free then)
@@ -901,9 +806,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
                 for (int u = 0; u < kChunk; u++) {
                     const uint64_t r = gs.next64();
                     uint32_t by = lds_pntab[(uint32_t)(r >> 52)];
-#ifdef MDPP_ABL_NP_NOPNC
-                    by = 7u | ((uint32_t)(r >> 63) << 4);
-#endif
                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(by == 0xFFu) != 0, 0)) {
                         if (by == 0xFFu) {
                             uint32_t na = 0, nb = 0;
@@ -924,7 +826,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
         // Philox transition noise: the chunk's eight nibbles (noisy << 3 | index among the other states) are a function of
         // (seed, env, tick) alone -- made here, up to kHChunks chunks ahead of the chunk E has finished, instead of on the
         // H wave, whose chain (start states AND noise words: four Philox blocks per chunk) set the pace
-        constexpr bool PPN = PN && PHILOX && MDPP_LEAN_PHILOX_PN_O2;
+        constexpr bool PPN = PN && PHILOX;
         const uint64_t genv2 = (uint64_t)(a.env_id_offset + (int64_t)i);
         int ppc = 0;
         auto make_ppn = [&](int upto_chunk) __attribute__((always_inline)) {
@@ -946,11 +848,7 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             const int kbase = c * kChunk;
             const uint32_t upto = (uint32_t)min(kbase + kChunk, K);
             uint32_t spins = 0;
-#ifdef MDPP_ABL_FREEO
-            while (false) {
-#else
             while (wg_load_acq(&lds_prod[w]) < upto) {
-#endif
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
             }
@@ -972,17 +870,10 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
 #pragma unroll
                 for (int h = 0; h < kChunk / 4; h++) {
                     const uint32_t kk = (uint32_t)kbase + ws + 4u * (uint32_t)h, slot = kk % (uint32_t)KD;
-#if !defined(MDPP_ABL_NOSTORE) && !defined(MDPP_ABL_NOREW)
                     if constexpr (ROWS1) {          // (whole offset in the VGPR: mdpp_discrete_quiet.hip's hazard note)
                         const u32x4 v = *(const u32x4 *)&lds_rw[c % kRB][ws + 4u * (uint32_t)h][4u * ln];
                         __builtin_amdgcn_raw_buffer_store_b128(v, r_rew2, (blk0 + 4u * ln) * 4u + kk * N * 4u, 0, MDPP_LEAN_ST_AUX);
                     }
-#endif
-#ifdef MDPP_ABL_NOSTORE
-                    status ^= lds_rec[1][slot][l] & 0x100u;
-                    continue;
-#endif
-#ifndef MDPP_ABL_NOOBS
                     if (OBS64) {                    // lane ln: envs 2 ln, 2 ln + 1 and 128 + 2 ln, 129 + 2 ln -- each store 1 KiB in one piece
                         const u32x2 b0 = *(const u32x2 *)&lds_rec[1][slot][2u * ln];
                         const u32x2 b1 = *(const u32x2 *)&lds_rec[1][slot][128u + 2u * ln];
@@ -992,8 +883,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
                         const u32x4 b = *(const u32x4 *)&lds_rec[1][slot][4u * ln];
                         __builtin_amdgcn_raw_buffer_store_b128(u32x4{b.x & 7u, b.y & 7u, b.z & 7u, b.w & 7u}, r_obs, (blk0 + 4u * ln) * 4u + kk * N * 4u, 0, MDPP_LEAN_ST_AUX);
                     }
-#endif
-#ifndef MDPP_ABL_NOBYTES
                     const u32x4 c4 = *(const u32x4 *)&lds_rec[2][slot][4u * ln];
                     // byte j of the flag words = the flag of env 4 ln + j: bit 7 of byte 0 / byte 2 of its record
                     const uint32_t t01 = __builtin_amdgcn_perm(c4.y, c4.x, 0x0c0c0400u), t23 = __builtin_amdgcn_perm(c4.w, c4.z, 0x04000c0cu);
@@ -1002,7 +891,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
                     uint32_t uw = 0u;
                     if (HASMAX) uw = __builtin_amdgcn_perm(c4.y, c4.x, 0x0c0c0602u) | __builtin_amdgcn_perm(c4.w, c4.z, 0x06020c0cu);
                     __builtin_amdgcn_raw_buffer_store_b32(uw, r_trunc, blk0 + 4u * ln, kk * N, MDPP_LEAN_ST_AUX_BYTES);
-#endif
                 }
             } else if (kbase + kChunk <= K) {
                 uint32_t rb[kChunk], rc[kChunk];
@@ -1117,12 +1005,10 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             }
             s0c = lds_s0[c % kHChunks][l];
             if constexpr (PN) {
-                if (MDPP_LEAN_PHILOX_PN_O2) {
-                    spins = 0;
-                    while (wg_load_acq(&lds_pprod[w]) < (uint32_t)(c + 1)) {
-                        __builtin_amdgcn_s_sleep(1);
-                        if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
-                    }
+                spins = 0;
+                while (wg_load_acq(&lds_pprod[w]) < (uint32_t)(c + 1)) {
+                    __builtin_amdgcn_s_sleep(1);
+                    if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
                 }
                 pnc = lds_pn[c % kHChunks][l];
             }
@@ -1187,9 +1073,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             need = need || cnt >= 0x10000u;
             rc = __builtin_amdgcn_perm(cnt, entry, 0x0c060c00u);                       // byte 0 the entry, byte 2 truncated
         }
-#ifdef MDPP_ABL_NORESET
-        need = false;
-#endif
         need = need && ar;
         uint32_t rec_a = k2n;
         if (nextmode) {
@@ -1257,9 +1140,6 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
             const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r_act, v4, kk * N * 8u, MDPP_LEAN_LD_AUX);
             return make_uint2(v.x, v.y);
         } else {
-#ifdef MDPP_ABL_NOLOAD
-            return (int)((kk * 7u + i) & 7u);
-#endif
             return __builtin_amdgcn_raw_buffer_load_b32(r_act, v4, kk * N * 4u, MDPP_LEAN_LD_AUX);
         }
     };
@@ -1286,20 +1166,10 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
                 const uint64_t cc = __hip_atomic_load((const uint64_t *)&lds_cons[w][0], __ATOMIC_ACQUIRE,
                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
                 uint32_t have = min((uint32_t)cc, (uint32_t)(cc >> 32));
-#ifdef MDPP_ABL_NOO1
-                have = (uint32_t)(cc >> 32);
-#endif
-#ifdef MDPP_ABL_NOO2
-                have = (uint32_t)cc;
-#ifdef MDPP_ABL_NOO1
-                have = must;
-#endif
-#else
                 if (rows) {                         // whole-row stores: every O2 wave reads this wave's records
 #pragma unroll
                     for (int j = 0; j < kBlock / 64; j++) have = min(have, wg_load_acq(&lds_cons[j][1]));
                 }
-#endif
                 if (have >= must) break;
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
@@ -1478,13 +1348,8 @@ bool launch_discrete_lean(const DiscreteArgs &a, int K, const int32_t *actions, 
 #endif
 #define MDPP_LEAN_L3(O64, DL, HM) do { if (evn) MDPP_LEAN_LAUNCH(O64, DL, HM, true); else MDPP_LEAN_LAUNCH(O64, DL, HM, false); } while (0)
 #define MDPP_LEAN_L2(O64, DL) do { if (hm) MDPP_LEAN_L3(O64, DL, true); else MDPP_LEAN_L3(O64, DL, false); } while (0)
-#ifdef MDPP_LEAN_SHAPES_MIN       // (ablation builds: the bench shape only)
-    if (a.obs_i32 || !dl || hm || !evn) return false;
-    MDPP_LEAN_LAUNCH(true, true, false, true);
-#else
     if (a.obs_i32) { if (dl) MDPP_LEAN_L2(false, true); else MDPP_LEAN_L2(false, false); }
     else { if (dl) MDPP_LEAN_L2(true, true); else MDPP_LEAN_L2(true, false); }
-#endif
 #undef MDPP_LEAN_GO
 #undef MDPP_LEAN_L2
 #undef MDPP_LEAN_L3

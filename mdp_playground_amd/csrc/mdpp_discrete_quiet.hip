@@ -135,24 +135,14 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
     extern __shared__ __align__(16) unsigned char lds[];
     __shared__ float s_rsel[4];
     __shared__ __align__(16) uint32_t s_prod[kBlock / 64], s_cons[kBlock / 64];   // steps published by E wave w / consumed by O wave w
-    // Whole-row stores (round 6; k_discrete_rollout_lean's since round 4).  Every store INSTRUCTION of the O wave cost the launch
-    // about the same whatever it carried (build without the two 64-byte flag stores: 183 -> 162 us at S = 50, without any store
-    // 134): four per step and wave, 64 to 512 bytes each.  Of a chunk's 8 rows O wave w now takes rows w and w + 4 for all 256
-    // envs of the block: observations and flags straight from the other E waves' records in the ring (2 x 1 KiB / 256 B per
-    // instruction), the rewards -- the reward path carries a delay line per lane, so every O wave still computes its own envs'
-    // -- through two staging buffers in LDS (1 KiB per instruction): 10 store instructions per chunk and wave instead of 32.
-    // E waits for ALL four O waves before it reuses a ring slot.  Rollouts of full chunks; a ragged last chunk, final
-    // observations (mdpp_step) and the forms short of LDS keep the per-lane stores.
-    // MEASURED (tools/ablate.py, rows against per-lane stores on one lease): S = 50 unit rewards 0.435 -> 0.435-0.453 of HBM, S = 24
-    // with reward_dist 0.447 -> 0.417-0.421, S = 50 with the noise key 0.221 -> 0.216 -- the hand-over between the workgroup's
-    // waves costs what the fewer stores save wherever the O wave is a long stage.  Built, verified (the sweep and oracle tests ran
-    // green on it), and left OFF: -DMDPP_Q_ROWS=1 turns it on.
-#ifndef MDPP_Q_ROWS
-#define MDPP_Q_ROWS 0
-#endif
-    constexpr bool QROWS = MDPP_Q_ROWS && ROLES >= 2 && !IRR && NPH == 0 && !(PE && RN);
-    __shared__ __align__(16) float s_rw[QROWS ? 2 : 1][QROWS ? 8 : 1][QROWS ? kBlock : 4];
-    __shared__ __align__(16) uint32_t s_rprod[kBlock / 64], s_rcons[kBlock / 64];   // chunks staged / stored by O wave w
+    // Per-lane stores.  Every store INSTRUCTION of the O wave costs the launch about the same whatever it carries (build without
+    // the two 64-byte flag stores: 183 -> 162 us at S = 50, without any store 134), but whole-row stores as in
+    // k_discrete_rollout_lean (O wave w takes rows w and w + 4 of a chunk for all 256 envs of the block, the rewards through LDS
+    // staging buffers: 10 store instructions per chunk and wave instead of 32) measured no better (round 6, on one lease): S = 50
+    // unit rewards 0.435 -> 0.435-0.453 of HBM, S = 24 with reward_dist 0.447 -> 0.417-0.421, S = 50 with the noise key 0.221 ->
+    // 0.216 -- the hand-over between the workgroup's waves costs what the fewer stores save wherever the O wave is a long stage.
+    // (s_rprod / s_rcons were that form's counters: nothing reads them, but they stay, zeroed, as they fix the kernels' LDS layout)
+    __shared__ __align__(16) uint32_t s_rprod[kBlock / 64], s_rcons[kBlock / 64];
     __shared__ __align__(8) uint64_t s_start[ROLES == 3 ? kBlock : 1];   // H -> E
     __shared__ uint32_t s_head[ROLES == 3 ? kBlock : 1];                 // E -> H
     __shared__ uint32_t s_done;                                         // E waves that have finished
@@ -188,11 +178,8 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
     constexpr int kThreads = (ROLES + NPH) * kBlock;
     const int tid = threadIdx.x;
     // Workgroup b runs on XCD b % 8 (round-robin dispatch): with full blocks every XCD steps one contiguous eighth of the envs, so
-    // that what its L2 writes back per output row is one contiguous range (as in k_discrete_rollout_lean; MDPP_Q_XCD_CONTIG)
-#ifndef MDPP_Q_XCD_CONTIG
-#define MDPP_Q_XCD_CONTIG 1
-#endif
-    const uint32_t eblk = (MDPP_Q_XCD_CONTIG && DUO && (gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    // that what its L2 writes back per output row is one contiguous range (as in k_discrete_rollout_lean)
+    const uint32_t eblk = (DUO && (gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
     const int role = DUO ? tid / kBlock : 0;        // 0 = E, 1 = O, 2 = H
     const int l = DUO ? (tid & (kBlock - 1)) : tid, w = l >> 6;
     // shared MDP -> LDS (same carve as k_discrete_step) + the irrelevant sub-space's table and cdf
@@ -465,13 +452,6 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
     const bool autoreset = SF ? true : a.autoreset != 0, has_max = SF ? false : a.max_steps > 0;
     const uint32_t max_steps = (uint32_t)a.max_steps, every_n = SF ? 1u : (uint32_t)a.every_n, delay = (uint32_t)a.delay;
     const bool isE = !DUO || role == 0;
-    const bool rows_ok = QROWS && final_obs == nullptr;         // whole-row stores (QROWS above): full blocks are a condition of ROLES >= 2
-    // min over the four waves' counters (two 64-bit LDS reads)
-    auto qmin4 = [&](const uint32_t *p) __attribute__((always_inline)) -> uint32_t {
-        const uint64_t x = __hip_atomic_load((const uint64_t *)p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const uint64_t y = __hip_atomic_load((const uint64_t *)p + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return min(min((uint32_t)x, (uint32_t)(x >> 32)), min((uint32_t)y, (uint32_t)(y >> 32)));
-    };
     // =============================================================== X: the env stream by position (header, XR)
     if constexpr (XR) if (role == 2) {
         __builtin_amdgcn_s_setprio(kPrioH);
@@ -870,7 +850,7 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
         return ((uint64_t)hi << 32) | lo;
     };
     // ---- O: record -> reward, delay line, all global stores of step `so`
-    auto emitO = [&](const uint64_t rec, const double z, const uint32_t so, float *stage = nullptr) __attribute__((always_inline)) {
+    auto emitO = [&](const uint64_t rec, const double z, const uint32_t so) __attribute__((always_inline)) {
         const uint32_t lo = (uint32_t)rec, hi = (uint32_t)(rec >> 32);
         const uint32_t k2 = hi >> 5;
         const uint32_t done = hi & 1u;
@@ -920,17 +900,10 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
                 if (need) for (uint32_t dd = 0; dd < delay; dd++) a.ring_keys[(size_t)dd * N + i] = kNoKey;
             }
         }
-        if (stage) { *stage = rout; return; }           // (whole-row stores: the rows leave later, see QROWS)
-#ifdef MDPP_ABL_Q_NOSTORE       /* timing only: what the O wave's global stores cost the launch */
-        status ^= (lo ^ __float_as_uint(rout) ^ hi) & 0x100u;
-#else
         put_obs(r_obs, so, lo & 0xFFu, (lo >> 16) & 0xFFu);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rout), r_rew, v4, so * N * 4u, MDPP_ST_NT);
-#ifndef MDPP_ABL_Q_NOBYTES
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)done, r_term, v1, so * N, MDPP_ST_NT);
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)((hi >> 1) & 1u), r_trunc, v1, so * N, MDPP_ST_NT);
-#endif
-#endif
     };
 
     if (!DUO) {
@@ -983,8 +956,7 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
             if (kbase + kPre > kDepth) {                // stay within the ring: at most kDepth - 8 steps ahead of O
                 const uint32_t must = (uint32_t)(kbase + kPre - kDepth);
                 uint32_t spins = 0;
-                // (whole-row stores: every O wave reads this wave's records)
-                while ((rows_ok ? qmin4(s_cons) : __hip_atomic_load(&s_cons[w], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < must) {
+                while (__hip_atomic_load(&s_cons[w], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < must) {
                     __builtin_amdgcn_s_sleep(1);
                     if (++spins > kQSpinLimit) { status |= kQStatusInternal; break; }
                 }
@@ -1042,7 +1014,6 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > kQSpinLimit) { status |= kQStatusInternal; break; }
             }
-            const bool rowc = rows_ok && kbase + kPre <= K;             // (wave-uniform)
             if (kbase + kPre <= K) {
                 uint64_t rec[kPre];
                 double zz[kPre];
@@ -1051,45 +1022,8 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
                     rec[u] = ring[((kbase + u) % kDepth) * kBlock + l];
                     zz[u] = (RN && !rn_z0) ? ringz[((kbase + u) % kDepth) * kBlock + l] : 0.0;
                 }
-                if (rowc && c >= 2) {                       // the staging buffer of chunk c - 2: stored by all four O waves
-                    uint32_t sp2 = 0;
-                    while (qmin4(s_rcons) < (uint32_t)(c - 1)) {
-                        __builtin_amdgcn_s_sleep(1);
-                        if (++sp2 > kQSpinLimit) { status |= kQStatusInternal; break; }
-                    }
-                }
 #pragma unroll
-                for (int u = 0; u < kPre; u++) emitO(rec[u], zz[u], (uint32_t)(kbase + u), rowc ? &s_rw[QROWS ? (c & 1) : 0][QROWS ? u : 0][QROWS ? l : 0] : nullptr);
-                if constexpr (QROWS) if (rowc) {
-                    if ((l & 63) == 0) __hip_atomic_store(&s_rprod[w], (uint32_t)(c + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    uint32_t sp2 = 0;       // all four E waves are through the chunk, all four O waves have staged its rewards
-                    while (qmin4(s_prod) < upto || qmin4(s_rprod) < (uint32_t)(c + 1)) {
-                        __builtin_amdgcn_s_sleep(1);
-                        if (++sp2 > kQSpinLimit) { status |= kQStatusInternal; break; }
-                    }
-                    const uint32_t blk0 = eblk * kBlock, ln = (uint32_t)l & 63u, ws = (uint32_t)__builtin_amdgcn_readfirstlane(w);
-#pragma unroll
-                    for (int h = 0; h < kPre / 4; h++) {
-                        const uint32_t ru = ws + 4u * (uint32_t)h, kk = (uint32_t)kbase + ru;
-                        const uint32_t *recs = (const uint32_t *)(ring + (kk % (uint32_t)kDepth) * kBlock);     // [env]{lo, hi}
-                        // (128-bit stores: the whole offset in the VGPR, see kQRsrc)
-                        const u32x4 rw4 = *(const u32x4 *)&s_rw[QROWS ? (c & 1) : 0][QROWS ? ru : 0][QROWS ? 4u * ln : 0];
-                        __builtin_amdgcn_raw_buffer_store_b128(rw4, r_rew, (blk0 + 4u * ln) * 4u + kk * N * 4u, 0, MDPP_ST_NT);
-                        const u32x4 ra = *(const u32x4 *)(recs + 8u * ln), rb = *(const u32x4 *)(recs + 8u * ln + 4u);      // envs 4 ln .. 4 ln + 3
-                        if (OBS64) {                    // lane ln: envs 2 ln, 2 ln + 1 and 128 + 2 ln, 129 + 2 ln -- 1 KiB per instruction
-                            const u32x4 r0 = *(const u32x4 *)(recs + 4u * ln), r1 = *(const u32x4 *)(recs + 256u + 4u * ln);
-                            __builtin_amdgcn_raw_buffer_store_b128(u32x4{r0.x & 0xFFu, 0u, r0.z & 0xFFu, 0u}, r_obs, (blk0 + 2u * ln) * 8u + kk * N * 8u, 0, MDPP_ST_NT);
-                            __builtin_amdgcn_raw_buffer_store_b128(u32x4{r1.x & 0xFFu, 0u, r1.z & 0xFFu, 0u}, r_obs, (blk0 + 128u + 2u * ln) * 8u + kk * N * 8u, 0, MDPP_ST_NT);
-                        } else {
-                            __builtin_amdgcn_raw_buffer_store_b128(u32x4{ra.x & 0xFFu, ra.z & 0xFFu, rb.x & 0xFFu, rb.z & 0xFFu}, r_obs, (blk0 + 4u * ln) * 4u + kk * N * 4u, 0, MDPP_ST_NT);
-                        }
-                        // byte j of the flag words = the flag of env 4 ln + j: bits 0 / 1 of its record's high word
-                        const uint32_t hw = (ra.y & 3u) | ((ra.w & 3u) << 8) | ((rb.y & 3u) << 16) | ((rb.w & 3u) << 24);
-                        __builtin_amdgcn_raw_buffer_store_b32(hw & 0x01010101u, r_term, blk0 + 4u * ln, kk * N, MDPP_ST_NT);
-                        __builtin_amdgcn_raw_buffer_store_b32((hw >> 1) & 0x01010101u, r_trunc, blk0 + 4u * ln, kk * N, MDPP_ST_NT);
-                    }
-                    if ((l & 63) == 0) __hip_atomic_store(&s_rcons[w], (uint32_t)(c + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
+                for (int u = 0; u < kPre; u++) emitO(rec[u], zz[u], (uint32_t)(kbase + u));
             } else {
                 for (int k = kbase; k < K; k++)
                     emitO(ring[(k % kDepth) * kBlock + l], (RN && !rn_z0) ? ringz[(k % kDepth) * kBlock + l] : 0.0, (uint32_t)k);

@@ -36,14 +36,11 @@ namespace mdpp {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
-// Workgroup b runs on XCD b % 8 (round-robin dispatch).  With MDPP_IMG_XCD every XCD renders one contiguous eighth of a launch's
+// Workgroup b runs on XCD b % 8 (round-robin dispatch).  Here every XCD renders one contiguous eighth of a launch's
 // pictures -- its L2 then writes back ONE sequential range instead of every eighth 28 KiB piece of the output: cfg4 5 970-6 210 ->
 // 5 600 us per launch (0.60-0.62 -> 0.66 of HBM; round 6, tools/ablate.py x0 / x1 on one lease).
-#ifndef MDPP_IMG_XCD
-#define MDPP_IMG_XCD 1
-#endif
 __device__ __forceinline__ uint32_t img_xcd_block() {
-    return (MDPP_IMG_XCD && (gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    return ((gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
 }
 constexpr int kImgPad = 8;               // zero border of the fast renderer's templates, pixels
 constexpr int kImgColDw = 1536;          // dwords of LDS image columns per wave (6 KiB)
@@ -400,9 +397,6 @@ struct TplRegs { u32x4 v[4]; };          // a padded template (<= 64 rows x 64 B
 // four per evaluated dword here; an address-space-3 pointer made from an integer is used as it is
 typedef __attribute__((address_space(3))) const uint8_t *lds_u8p;
 typedef __attribute__((address_space(3))) uint32_t *lds_u32p;
-#ifndef MDPP_IMG_LEAN_LOOP
-#define MDPP_IMG_LEAN_LOOP 1       // the trimmed evaluation loop (integer LDS addresses, integer near test in half pixels, byte-address columns)
-#endif
 
 __device__ __forceinline__ TplRegs load_tpl(const ImageArgs &a, uint32_t tix, int lane) {
     const u32x4 *gt = (const u32x4 *)(a.tplp_data + (size_t)tix * ((size_t)a.tplp * 64));
@@ -428,13 +422,11 @@ __device__ __forceinline__ u32x4 load_near(const ImageArgs &a, const RecRegs &r,
 }
 
 __device__ __forceinline__ void stage_tpl(const ImageArgs &a, const TplRegs &tp, uint8_t *lds, int wave, int lane) {
-#ifndef MDPP_IMG_ABL_NOTPL
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int c = lane + 64 * j;
         if (c < a.tplp * 4) *(u32x4 *)(lds + (c >> 2) * 256 + wave * 64 + (c & 3) * 16) = tp.v[j];
     }
-#endif
 }
 
 // Evaluation half: the template of this image is already in the wave's LDS columns (stage_tpl);
@@ -449,10 +441,8 @@ __device__ __forceinline__ ColRange render_fast_eval(const ImageArgs &a, const R
     const float fcx = __uint_as_float(r.hi[0]), fcy = __uint_as_float(r.hi[1]);
     const int X0 = (int)(r.hi[2] & 0xFFFFu), X1 = (int)(r.hi[2] >> 16);
     const int Q0 = (int)(r.hi[3] & 0xFFFFu), Q1 = (int)(r.hi[3] >> 16);
-    const float rr = (float)R + 4.5f, rr2 = rr * rr;          // near radius of the general renderer
-    (void)rr2;
-    // ... in integers (MDPP_IMG_LEAN_LOOP): doubled coordinates against the centre rounded to half pixels (off by <= 0.36 px), radius
-    // R + 5 -- a superset of the float test's dwords inside the same bounding box, and every pixel of a dword it lets through
+    // The near test in integers: doubled coordinates against the centre rounded to half pixels (off by <= 0.36 px), radius
+    // R + 5 -- a superset of the dwords of the general renderer's float test (radius R + 4.5) inside the same bounding box, and every pixel of a dword it lets through
     // still lies within R + 5.36 + 1.5 of the centre: inside the zero border (R + 8) after the map's rounding
     int ncx2, ncy2;                              // (scalar registers; through asm: the compiler folds a readfirstlane of a uniform value away
     {                                            //  and keeps the value in a vector register, which costs the loop two instructions per test)
@@ -476,12 +466,10 @@ __device__ __forceinline__ ColRange render_fast_eval(const ImageArgs &a, const R
         // (integer LDS addresses: the template rows start at LDS offset lbase -- 0 for this kernel, which has no static LDS; a
         //  multiple of 256 folds into the row accumulator)
         const uint32_t lbase = (uint32_t)(uintptr_t)(lds_u8p)lds;
-        if (MDPP_IMG_LEAN_LOOP) {
-            if (__builtin_expect((lbase & 255u) != 0u || lbase > 0xC000u, 0)) __builtin_trap();
-            A5 += (int)(lbase >> 8) << 16;
-        }
+        if (__builtin_expect((lbase & 255u) != 0u || lbase > 0xC000u, 0)) __builtin_trap();
+        A5 += (int)(lbase >> 8) << 16;
         const uint32_t cbase = (uint32_t)(uintptr_t)(lds_u32p)lds_col - 4u * (uint32_t)B0, HQ4 = 4u * (uint32_t)HQ;
-        if (MDPP_IMG_LEAN_LOOP && a.near_tab) {
+        if (a.near_tab) {
             // Table-driven enumeration (round 4): the lane's eight (dx, dq) entries, relative to the centre rounded to whole
             // pixels; an entry outside the record's box (or the padding entry) fails two unsigned compares.  No idle lanes
             // inside a bounding box, no near test, no walk: 8 rounds of 64 dwords for R = 20 where the box took 10.
@@ -521,10 +509,7 @@ __device__ __forceinline__ ColRange render_fast_eval(const ImageArgs &a, const R
         // images with angles {0, 180} against 11.3 with {90, 270}); near 90 / 270 the same happens to lanes that walk ALONG an
         // image row.  So the walk follows the map: x fastest where |d xs / d x| >= |d xs / d y|, y fastest otherwise -- the
         // lanes of an iteration then read along template rows either way (wave-uniform choice, no per-pixel cost).
-#ifndef MDPP_IMG_WALK
-#define MDPP_IMG_WALK 1
-#endif
-        const bool xfast = MDPP_IMG_WALK && (a0 < 0 ? -a0 : a0) >= (a1 < 0 ? -a1 : a1);
+        const bool xfast = (a0 < 0 ? -a0 : a0) >= (a1 < 0 ? -a1 : a1);
         const int span = xfast ? bw : bhq;                          // lanes per line of the walk
         const uint32_t inv = 65536u / (uint32_t)span + 1u;         // k / span == (k * inv) >> 16 here (k < 2^16 / span)
         const int kq = (int)(((uint32_t)lane * inv) >> 16), kr = lane - kq * span;
@@ -532,8 +517,6 @@ __device__ __forceinline__ ColRange render_fast_eval(const ImageArgs &a, const R
         const int d64 = 64 / span, r64 = 64 - d64 * span;
         const int yend = 4 * Q1, ywrap = 4 * bhq;
         for (int k = lane; k < nb; k += 64) {
-#ifndef MDPP_IMG_ABL_ZERO
-#if MDPP_IMG_LEAN_LOOP
             const int dx2 = 2 * x + ncx2, dy2 = 2 * y + ncy2;        // (v_lshl_add_u32 with a scalar)
             if (dx2 * dx2 + dy2 * dy2 <= rr2i) {          // (plain multiplies: __mul24 sign-extends its operands from 24 bits first, two shifts each)
                 const int bx = A2 + __mul24(a0, x) + __mul24(a1, y);      // |a_i| <= 2^16, x, y < 2^23
@@ -549,22 +532,6 @@ __device__ __forceinline__ ColRange render_fast_eval(const ImageArgs &a, const R
                 // (y is a multiple of 4: the dword's byte address in the columns is x * 4 HQ + y)
                 *(lds_u32p)(uintptr_t)(__umul24((uint32_t)x, HQ4) + (uint32_t)y + cbase) = word;
             }
-#else
-            const float ddx = (float)x - fcx, ddy = (float)y + 1.5f - fcy;
-            if (ddx * ddx + ddy * ddy <= rr2) {
-                const int bx = A2 + __mul24(a0, x) + __mul24(a1, y);      // |a_i| <= 2^16, x, y < 2^23
-                const int by = A5 + __mul24(a3, x) + __mul24(a4, y);
-                uint32_t word = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    // byte 2 of each accumulator = its integer part (< 256): address = uy * 256 + ux
-                    const uint32_t addr = __builtin_amdgcn_perm((uint32_t)(by + b * a4), (uint32_t)(bx + b * a1), 0x0c0c0602u);
-                    word |= (uint32_t)lds[addr] << (8 * b);
-                }
-                lds_col[__mul24(x, HQ) + (y >> 2) - B0] = word;
-            }
-#endif
-#endif
             if (xfast) {
                 y += 4 * d64; x += r64;
                 if (x >= X1) { x -= bw; y += 4; }
@@ -585,7 +552,6 @@ __device__ __forceinline__ void render_fast_store(const ImageArgs &a, const ColR
                                                   uint8_t *__restrict__ out, int lane) {
     const auto r_out = __builtin_amdgcn_make_buffer_rsrc((void *)out, 0, a.W * a.H, 0x00020000);
     const int nchunk = (a.W * a.H) >> 4;
-#if MDPP_IMG_LEAN_LOOP
     // (round 4) every lane reads unconditionally: chunks outside the box come from the wave's ZERO CHUNK (the last 16 bytes of its
     // column buffer, cleared once per kernel) -- one v_cndmask_b32 on the address instead of an exec-mask branch around each read,
     // so the seven LDS reads of an image are in flight together instead of one wait per store
@@ -595,21 +561,8 @@ __device__ __forceinline__ void render_fast_store(const ImageArgs &a, const ColR
     auto put = [&](int c) {
         const uint32_t rel = (uint32_t)(c - cr.C0);
         const u32x4 v = *(lds_cu128p)(uintptr_t)(rel < nin ? cb + 16u * rel : zaddr);
-#ifdef MDPP_IMG_ABL_NOSTORE
-        if (v.x == 0x12345678u)
-#endif
         __builtin_amdgcn_raw_buffer_store_b128(v, r_out, c * 16, 0, MDPP_IMG_ST_AUX);   // beyond the descriptor: dropped
     };
-#else
-    auto put = [&](int c) {
-        u32x4 v = u32x4{0u, 0u, 0u, 0u};
-        if ((uint32_t)(c - cr.C0) < (uint32_t)(cr.C1 - cr.C0)) v = *(const u32x4 *)(lds_col + 4 * (c - cr.C0));
-#ifdef MDPP_IMG_ABL_NOSTORE
-        if (v.x == 0x12345678u)
-#endif
-        __builtin_amdgcn_raw_buffer_store_b128(v, r_out, c * 16, 0, MDPP_IMG_ST_AUX);   // beyond the descriptor: dropped
-    };
-#endif
     if (NST > 0) {
 #pragma unroll
         for (int u = 0; u < NST; u++) put(lane + 64 * u);
@@ -631,70 +584,14 @@ __global__ __launch_bounds__(kBlock) void k_image_obs_fast(ImageArgs a, long M, 
     extern __shared__ __align__(16) uint8_t lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     uint32_t *const lds_col = (uint32_t *)(lds + (size_t)a.tplp * 256) + (size_t)wave * a.coldw;
-    if (MDPP_IMG_LEAN_LOOP && lane < 4) lds_col[a.coldw - 4 + lane] = 0u;      // the wave's zero chunk (render_fast_store)
-    // Work distribution (round 3): a wave CLAIMS its next image from a counter instead of walking j, j + (waves in the grid),
-    // ...: the next batch's state / draw / record kernels run beside this kernel on a few CUs, images differ in cost, and with
-    // a static split the slowest wave sets the kernel's duration (a 32-step render: 427 us alone, 465-475 us beside them).
-    // cfg4 on one box: static 7 770 us per launch; claims of 1 / 2 / 4 / 8 images 6 960 / 7 380 / 7 620 / 7 720 (consecutive
-    // images in one wave cost more than the coarser balance saves); 8 / 16 / 32 / 64 counters 7 110 / 6 930 / 6 910 / 6 950.
-    // Round 5: ONE picture per wave, then the workgroup ENDS (MDPP_IMG_DYNAMIC = 0 with a grid of one wave per picture): the
-    // hardware's dispatcher hands out the pictures in address order, so the chip's write front is the dispatch order -- the
-    // form in which plain fills run 20 % faster than on a persistent grid (mdpp_probe_hbm, tools/bench_store.hip).  It gives
-    // up the next picture's prefetch under the current one's evaluation (20 waves per CU hide the two round trips instead) and
-    // needs no claim counters: cfg4 6 530-6 550 -> 6 300 us per launch on one lease (0.568 -> 0.589); two / four pictures per
-    // wave 6 460 / 6 640; non-temporal stores 6 384.  The claiming loop stays below for MDPP_IMG_DYNAMIC = 1.
-#ifndef MDPP_IMG_DYNAMIC
-#define MDPP_IMG_DYNAMIC 0
-#endif
-#ifndef MDPP_IMG_CLAIM
-#define MDPP_IMG_CLAIM 1
-#endif
-    constexpr long kImgClaim = MDPP_IMG_CLAIM;
+    if (lane < 4) lds_col[a.coldw - 4 + lane] = 0u;      // the wave's zero chunk (render_fast_store)
+    // Round 5: ONE picture per wave, then the workgroup ENDS (a grid of one wave per picture): the hardware's dispatcher hands
+    // out the pictures in address order, so the chip's write front is the dispatch order -- the form in which plain fills run
+    // 20 % faster than on a persistent grid (mdpp_probe_hbm, tools/bench_store.hip).  It gives up the next picture's prefetch
+    // under the current one's evaluation (20 waves per CU hide the two round trips instead) and needs no claim counters (`ctr`
+    // is not read): cfg4 6 530-6 550 -> 6 300 us per launch on one lease (0.568 -> 0.589) against the persistent grid whose waves
+    // claimed their pictures from counters (rounds 3-4); two / four pictures per wave 6 460 / 6 640; non-temporal stores 6 384.
     const size_t isz = (size_t)a.W * a.H;
-#if MDPP_IMG_DYNAMIC
-    // One counter per group of waves (wave id mod kImgCtrs: its waves sit on CUs all over the chip), each over its own
-    // contiguous slice of the images: a single counter saturates -- 65 536 same-address atomics per batch took as long as the
-    // rendering itself.  The claim's result stays in a vector register until it is needed, a whole chunk later.
-    const long wid = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kBlock / 64) + wave));
-    const long grp = wid % kImgCtrs;
-    const long per = (M + kImgCtrs - 1) / kImgCtrs;
-    const long g0 = grp * per;
-    M = g0 + per < M ? g0 + per : M;             // (from here on: the end of this group's slice)
-    uint32_t *const gctr = ctr + grp * 32;
-    uint32_t pend = 0;
-    auto claim_issue = [&]() __attribute__((always_inline)) { if (lane == 0) pend = atomicAdd(gctr, (uint32_t)kImgClaim); };
-    auto claim_take = [&]() __attribute__((always_inline)) -> long {
-        return g0 + (long)(uint32_t)__builtin_amdgcn_readfirstlane((int)pend);
-    };
-    claim_issue();
-    long base = claim_take();
-    if (base >= M) return;
-    claim_issue();                               // (one chunk ahead)
-    long j = base;
-    RecRegs cur = load_rec(rec + j);
-    u32x4 near_cur = load_near(a, cur, lane);
-    stage_tpl(a, load_tpl(a, cur.lo[7] >> 12, lane), lds, wave, lane);
-    for (;;) {
-        const bool last_of_chunk = j + 1 >= base + kImgClaim || j + 1 >= M;
-        long jn = j + 1;
-        if (last_of_chunk) {                     // (wave-uniform)
-            jn = claim_take();
-            base = jn;
-            if (jn < M) claim_issue();
-        }
-        const bool more = jn < M;
-        const bool skip = cur.lo[7] & (1u << 11);
-        const RecRegs nxt = load_rec(rec + (more ? jn : j));
-        const TplRegs tp = load_tpl(a, nxt.lo[7] >> 12, lane);
-        const u32x4 near_nxt = load_near(a, nxt, lane);
-        ColRange cr{0, 0};
-        if (!skip) cr = render_fast_eval(a, cur, lds, lds_col, wave, lane, near_cur);
-        stage_tpl(a, tp, lds, wave, lane);
-        if (!skip) render_fast_store<NST>(a, cr, lds_col, img + (size_t)j * isz, lane);
-        if (!more) break;
-        j = jn; cur = nxt; near_cur = near_nxt;
-    }
-#else
     const int nw = (int)gridDim.x * (kBlock / 64);
     const uint32_t bx = img_xcd_block();
     long j = __builtin_amdgcn_readfirstlane((int)(bx * (kBlock / 64) + wave));
@@ -718,7 +615,6 @@ __global__ __launch_bounds__(kBlock) void k_image_obs_fast(ImageArgs a, long M, 
         if (!more) break;
         j = jn; cur = nxt; near_cur = near_nxt;
     }
-#endif
 }
 
 // ---- wide templates (round 5) --------------------------------------------------------------------
@@ -822,20 +718,13 @@ __global__ __launch_bounds__(kWideBlock) void k_image_obs_wide(ImageArgs a, long
                                                                uint8_t *__restrict__ img) {
     extern __shared__ __align__(16) uint8_t lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-#ifndef MDPP_IMG_XCD_WIDE
-#define MDPP_IMG_XCD_WIDE MDPP_IMG_XCD
-#endif
-    // MDPP_IMG_WIDE_PAIR (round 6): a wave renders TWO consecutive pictures.  A picture starts with two dependent round trips -- its
+    // Round 6: a wave renders TWO consecutive pictures.  A picture starts with two dependent round trips -- its
     // record, then the template rows the record names -- which three waves per SIMD (LDS: 12.6 KiB of template per wave) do not hide;
     // both records are loaded up front, and the second picture's template rows are in flight (in registers) while the first
     // picture is evaluated and stored: img100_all 1 835 -> 1 567-1 590 us per 64-step launch (0.358 -> 0.415-0.419 of HBM; a rolling
     // form with three / four / eight pictures per wave: 0.399 / 0.400-0.408 / 0.390 -- tools/ablate.py p0 / p1 / p2 / p4, one lease).
-#ifndef MDPP_IMG_WIDE_PAIR
-#define MDPP_IMG_WIDE_PAIR 1
-#endif
-    const long wid = __builtin_amdgcn_readfirstlane((int)((MDPP_IMG_XCD_WIDE ? img_xcd_block() : blockIdx.x) * (kWideBlock / 64) + wave));
+    const long wid = __builtin_amdgcn_readfirstlane((int)(img_xcd_block() * (kWideBlock / 64) + wave));
     const size_t isz = (size_t)a.W * a.H;
-#if MDPP_IMG_WIDE_PAIR == 1
     const long j0 = 2 * wid, j1 = j0 + 1;
     if (j0 >= M) return;
     const bool has1 = j1 < M;
@@ -849,13 +738,6 @@ __global__ __launch_bounds__(kWideBlock) void k_image_obs_wide(ImageArgs a, long
         wide_tpl_stage(a, r1, lds, wave, lane, t);
         render_wide<false>(a, r1, lds, wave, lane, img + (size_t)j1 * isz);
     }
-#else
-    const long j = wid;
-    if (j >= M) return;
-    const RecRegs r = load_rec(rec + j);
-    if (r.lo[7] & (1u << 11)) return;
-    render_wide(a, r, lds, wave, lane, img + (size_t)j * isz);
-#endif
 }
 
 // The launch arguments every image kernel of a batch of K steps shares (buf: the scratch set of a pipelined rollout).
@@ -919,11 +801,8 @@ __global__ __launch_bounds__(kBlock) void k_image_step1(ImageArgs a, const int32
     extern __shared__ __align__(16) uint8_t lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     uint32_t *const lds_col = (uint32_t *)(lds + (size_t)a.tplp * 256) + (size_t)wave * a.coldw;     // (WIDE: no image columns in LDS)
-    if (!WIDE && MDPP_IMG_LEAN_LOOP && lane < 4) lds_col[a.coldw - 4 + lane] = 0u;      // the wave's zero chunk (render_fast_store)
-#ifndef MDPP_IMG_XCD_STEP1
-#define MDPP_IMG_XCD_STEP1 MDPP_IMG_XCD
-#endif
-    const long i = __builtin_amdgcn_readfirstlane((int)((MDPP_IMG_XCD_STEP1 ? img_xcd_block() : blockIdx.x) * ((WIDE ? kWideBlock : kBlock) / 64) + wave));
+    if (!WIDE && lane < 4) lds_col[a.coldw - 4 + lane] = 0u;      // the wave's zero chunk (render_fast_store)
+    const long i = __builtin_amdgcn_readfirstlane((int)(img_xcd_block() * ((WIDE ? kWideBlock : kBlock) / 64) + wave));
     if (i >= a.N) return;
     // Everything the wave needs from memory before it can draw, in ONE batch of scalar loads: the generator, the state, and the
     // step's two flag bytes as the dwords they sit in (there is no scalar byte load, and a vector load -- or a load behind a
@@ -946,11 +825,6 @@ __global__ __launch_bounds__(kBlock) void k_image_step1(ImageArgs a, const int32
     const bool two = (a.autoreset != 0) & (flags != 0);
     const int s_fin0 = state_final[i * SUB], s_fin1 = state_final[i * SUB + SUB - 1];   // (read only where two: scratch the state kernel fills for every env)
     const ShiftBounds sb = shift_bounds(a, a.r0);
-#ifdef MDPP_S1I_ABL_NODRAW                       // (timing only, tools/ablate_step1.py: a made-up transform, no generator)
-    Xform x00{a.r0, a.W / 2 + (int)(i % 7) - 3, a.H / 2 + (int)(i % 5) - 2, (int)(i % 360), 0};
-    Xform x01 = x00, x10 = x00, x11 = x00;
-    (void)sb;
-#else
     // the reference's order: the step's observation (one picture per sub-space, relevant then irrelevant), then reset()'s
     const Xform x00 = draw_xform(a, sb, g, h);
     Xform x01 = x00;
@@ -960,7 +834,6 @@ __global__ __launch_bounds__(kBlock) void k_image_step1(ImageArgs a, const int32
         x10 = draw_xform(a, sb, g, h);
         if (SUB == 2) x11 = draw_xform(a, sb, g, h);
     }
-#endif
     if constexpr (!PHILOX) {
         if (lane == 0) {
             g.store(a.rng_s, i);
@@ -984,10 +857,6 @@ __global__ __launch_bounds__(kBlock) void k_image_step1(ImageArgs a, const int32
             render_fast_store<NST>(a, cr, lds_col, out, lane);
         }
     };
-#ifdef MDPP_S1I_ABL_NOPIC                        // (timing only: the serial head of the wave alone)
-    if (x00.cx == 12345 && lane == 1) img_out[i] = (uint8_t)(x10.cy + x11.cy + x01.cy + s_out0 + s_fin0 + s_out1 + s_fin1);
-    return;
-#endif
 #pragma unroll 1
     for (int q = 0; q < SUB; q++) {
         const size_t j = (size_t)i * SUB + q;
@@ -1065,38 +934,13 @@ int launch_image_obs(mdpp_env *h, int K, const int32_t *state_out, const int32_t
         const unsigned nblk = (unsigned)((M + per_block - 1) / per_block);
         if (h->img_fast_ok && !(h->opts & MDPP_OPT_NO_IMGFAST) && h->img_colb == 128) {
             const size_t lds_bytes = image_fast_lds(h, a);                  // (host-checked: <= 64 KiB)
-            const long per_wg = (long)(kWideBlock / 64) * (MDPP_IMG_WIDE_PAIR ? 2 : 1);            // pictures per workgroup
+            const long per_wg = (long)(kWideBlock / 64) * 2;            // pictures per workgroup: two per wave
             const dim3 grid((unsigned)((M + per_wg - 1) / per_wg));
             hipLaunchKernelGGL(k_image_obs_wide, grid, dim3(kWideBlock), lds_bytes, s, a, M, a.rec0, img_out);
             if (img_final) hipLaunchKernelGGL(k_image_obs_wide, grid, dim3(kWideBlock), lds_bytes, s, a, M, a.rec1, img_final);
         } else if (h->img_fast_ok && !(h->opts & MDPP_OPT_NO_IMGFAST)) {
             const size_t lds_bytes = image_fast_lds(h, a);
-            unsigned per_cu = (unsigned)((160u * 1024u) / ((lds_bytes + 511) & ~(size_t)511));
-            per_cu = per_cu < 1u ? 1u : (per_cu > 8u ? 8u : per_cu);
-#ifdef MDPP_IMG_WG_PER_CU
-            per_cu = MDPP_IMG_WG_PER_CU;
-#endif
-            // (the comment below: rounds 1-2 had 40 KiB per workgroup, 4 resident workgroups per CU)
-            // (phase 2 = the pipelined rollout: a few CUs keep a slot free, so that the next batch's state
-            // kernel, which needs a little LDS, can run beside this one)
-            // a few slots (rounds 1-2, 40 KiB of LDS per workgroup, four per CU: as many as the state kernel has workgroups --
-            // 16 gave no overlap at all, 32 and 64 the same +13 %; round 3, LDS sized by the launch, five per CU for cfg4 and
-            // batches of 32 steps: 7 385 / 7 672 us per launch with 32 reserved slots, 7 227 / 7 551 with 8, 7 289 / 7 660
-            // with none, on two boxes)
-            unsigned reserve = 8u;
-#ifdef MDPP_IMG_RESERVE
-            reserve = MDPP_IMG_RESERVE;
-#endif
-            const unsigned resident = per_cu * (unsigned)h->num_cus - (phase == 2 ? reserve : 0u);
-#ifndef MDPP_IMG_ONESHOT
-#define MDPP_IMG_ONESHOT 1         /* pictures per wave of the one-shot grid (0: the persistent grid of rounds 1-4, with MDPP_IMG_DYNAMIC = 1) */
-#endif
-#if MDPP_IMG_ONESHOT
-            const dim3 grid((nblk + MDPP_IMG_ONESHOT - 1) / MDPP_IMG_ONESHOT);
-            (void)resident;
-#else
-            const dim3 grid(nblk < resident ? nblk : resident);
-#endif
+            const dim3 grid(nblk);                                          // one wave per picture (k_image_obs_fast)
             const int nst = (int)(((size_t)a.W * a.H / 16 + 63) / 64);
             for (int pass = 0; pass < (img_final ? 2 : 1); pass++) {
                 const ImgRec *rec = pass ? a.rec1 : a.rec0;

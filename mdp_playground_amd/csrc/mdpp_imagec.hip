@@ -60,10 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_imagec_obs(ImageCArgs a, long M, con
     extern __shared__ __align__(16) uint32_t lds_codes[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // (workgroup b runs on XCD b % 8: every XCD renders one contiguous eighth of the launch's pictures, as in mdpp_image.hip)
-#ifndef MDPP_IMGC_XCD
-#define MDPP_IMGC_XCD 1
-#endif
-    const uint32_t bx = (MDPP_IMGC_XCD && (gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const uint32_t bx = ((gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
     const long j = __builtin_amdgcn_readfirstlane((int)((long)bx * (kBlock / 64) + wave));
     if (j >= M) return;
     if (mask && !mask[j % a.N]) return;
@@ -136,12 +133,8 @@ __global__ __launch_bounds__(kBlock) void k_imagec_obs(ImageCArgs a, long M, con
         return;
     }
     const auto r_out = __builtin_amdgcn_make_buffer_rsrc((void *)(img + (size_t)j * isz), 0, (int)isz, 0x00020000);
-#ifdef MDPP_IMGC_DIRECT
-    for (int g = lane; g < ngroup; g += 64) {
-#else
     for (int g0 = 0; g0 < ngroup; g0 += 64) {                      // (every lane takes part in every round's stores)
         const int g = min(g0 + lane, ngroup - 1);
-#endif
         const uint32_t c = codes[g];
         const uint32_t ln = GRID ? (uint32_t)a.lines[g] : 0u;       // white where no shape covers the line
         u32x4 o0, o1, o2;
@@ -167,11 +160,6 @@ __global__ __launch_bounds__(kBlock) void k_imagec_obs(ImageCArgs a, long M, con
             o1 = u32x4{d[4], d[5], d[6], d[7]};
             o2 = u32x4{d[8], d[9], d[10], d[11]};
         }
-#ifdef MDPP_IMGC_DIRECT
-        __builtin_amdgcn_raw_buffer_store_b128(o0, r_out, g * 48, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(o1, r_out, g * 48 + 16, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(o2, r_out, g * 48 + 32, 0, 0);
-#else
         // The lane's 48 bytes go through a 3 KiB LDS slab of the wave, so that every store instruction writes 1 KiB
         // CONTIGUOUS (lane l: bytes 16 l ..) instead of 16 bytes out of every 48
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        // (the slab's previous round has been read)
@@ -185,7 +173,6 @@ __global__ __launch_bounds__(kBlock) void k_imagec_obs(ImageCArgs a, long M, con
             const int off = k * 1024 + lane * 16;
             if (off < nb) __builtin_amdgcn_raw_buffer_store_b128(sl[k * 64 + lane], r_out, base + off, 0, 0);
         }
-#endif
     }
 }
 

@@ -272,7 +272,6 @@ struct GridArgs {
 struct mdpp_env {
     mdpp_config cfg;
     int device;
-    int num_cus;                // compute units of `device` (persistent-kernel grids)
     std::string err;
     uint64_t tick;              // env steps taken so far (ring head = tick mod delay; Philox counter)
     uint64_t reset_tick;        // reset() calls so far (Philox counter)

@@ -1,12 +1,11 @@
 """One launch = one step (mdpp_step): the step1 kernels against the rollout kernels with K = 1.
 
-    python tools/bench_step1.py [cfg2 cfg3 cfg5 ...] [--check] [--variants]
+    python tools/bench_step1.py [cfg2 cfg3 cfg5 ...] [--check]
 
 Per workload of bench.py's WORKLOADS: (a) --check: a handle on the default dispatch against a handle with NO_STEP1 on
 the same actions, every output of every step and the end state / stream states bit for bit, single steps interleaved with
 fused rollouts (the start-state queue is shared); (b) timing: HIP events over 500 eager steps, the host's enqueue time per
-call, a replayed graph of 64 steps.  --variants: the tuning knobs of mdpp_discrete_step1.hip (environment variables read at
-table upload).  Writes one JSON line per measurement.
+call, a replayed graph of 64 steps.  Writes one JSON line per measurement.
 """
 import json
 import os
@@ -119,7 +118,7 @@ def timing(name, wl, N, rng, opts=(), label=""):
 
 def main():
     args = [x for x in sys.argv[1:] if not x.startswith("--")] or ["cfg2"]
-    do_check, variants = "--check" in sys.argv, "--variants" in sys.argv
+    do_check = "--check" in sys.argv
     rngs = ["numpy", "philox"] if "--philox" in sys.argv else ["numpy"]
     bad = 0
     for name in args:
@@ -131,13 +130,6 @@ def main():
                 bad += check(name, wl, 1000, rng)          # a ragged last block
             timing(name, wl, N, rng, ("NO_STEP1",), "rollout kernel, K = 1")
             timing(name, wl, N, rng, (), "default")
-            if variants and wl["kind"] == "discrete":
-                for wg in ("64", "256"):
-                    for rounds, fill in (("1", "6"), ("1", "1"), ("6", "6"), ("0", "6")):
-                        os.environ.update(MDPP_STEP1_WG=wg, MDPP_STEP1_ROUNDS=rounds, MDPP_STEP1_FILL=fill)
-                        timing(name, wl, N, rng, (), f"WG={wg} rounds={rounds} fill={fill}")
-                for k in ("MDPP_STEP1_WG", "MDPP_STEP1_ROUNDS", "MDPP_STEP1_FILL"):
-                    os.environ.pop(k, None)
     sys.exit(1 if bad else 0)
 
 
