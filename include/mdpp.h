@@ -17,7 +17,8 @@
  * What each entry point replaces in the reference (/root/reference):
  *   mdpp_create + mdpp_upload_*   RLToyEnv.__init__            mdp_playground/envs/rl_toy_env.py:216-853
  *                                 (the tables themselves are generated on the host by
- *                                  mdp_playground_amd/mdp.py, restating :855-1575)
+ *                                  mdp_playground_amd/mdp.py, restating :855-1575, or for
+ *                                  per-env discrete MDPs by mdpp_generate_discrete)
  *   mdpp_seed_streams             RLToyEnv.seed / Space.seed   rl_toy_env.py:2379-2406,
  *                                                              spaces/discrete_extended.py:7-9
  *   mdpp_reset                    RLToyEnv.reset               rl_toy_env.py:2217-2377
@@ -207,6 +208,34 @@ int mdpp_upload_discrete_tables(mdpp_env *h, const uint8_t *P_host, const double
                                 const uint8_t *rbits_host, const uint8_t *is_term_host,
                                 const double *init_cdf_host, const double *noise_cdf_host);
 
+/* Per-env discrete MDPs generated on the device (mdpp_generate.hip): table i is what mdp.build_mdp({**config,
+ * "seed": seeds_host[i]}) builds, bit for bit -- P, and the rewardable sequences into rbits or rtable -- drawn from numpy's
+ * PCG64(SeedSequence) streams in the host's order.  For a handle with cfg.num_tables == cfg.num_envs, S <= 255, no
+ * irrelevant sub-space and MDPP_REWARD_SEQUENCES; which configs qualify is decided by mdp.device_coverage (the sequence
+ * draw must take Generator.choice's Floyd branch).  Numpy-stream handles also get every env's streams: ENV fresh from
+ * the seed, SPACE as P's generation left it (its buffered half-word is not kept, as with mdpp_seed_streams), and with
+ * cfg.image IMAGE fresh from seed_dict["image_representations"].  The kernels are then selected exactly as after
+ * mdpp_upload_discrete_tables.  Synchronous.  What the config alone decides travels in mdpp_gen_params; is_term,
+ * init_cdf and noise_cdf are the host tables of mdpp_upload_discrete_tables for ONE env (every env shares them). */
+typedef struct {
+    int32_t diameter, n_term, maximally_connected, repeats;   /* repeats = repeats_in_sequences */
+    uint64_t total;             /* sequence numbers picked from: (A - n_term)^L with repeats, else prod(radices) per set */
+    uint32_t n_sel;             /* picks per choice() call: int(reward_density * total), at least 1 */
+    int32_t n_radices;          /* without repeats: L radices (A - n_term) - pos // diameter; with repeats 0 */
+    uint32_t radices[16];
+    const double *rews;         /* host: the unshuffled np.linspace(reward_dist[0], reward_dist[1], n_rews), n_rews > 1,
+                                   or NULL: every value is 1.0 */
+    uint32_t n_rews;
+    int32_t image;              /* cfg.image (image_representations) */
+    uint64_t *seed_dicts;       /* host out: uint64 [N][8] = the env seed, then the 7 entries of _SEED_KEYS; NULL: none */
+} mdpp_gen_params;
+int mdpp_generate_discrete(mdpp_env *h, const uint64_t *seeds_host, const mdpp_gen_params *params,
+                           const uint8_t *is_term_host, const double *init_cdf_host, const double *noise_cdf_host);
+/* The discrete tables as the kernels read them, in mdpp_upload_discrete_tables' layout (any pointer may be NULL;
+ * asking for the reward table the handle does not keep is an error).  Synchronises the device. */
+int mdpp_get_discrete_tables(mdpp_env *h, uint8_t *P_host, double *rtable_host, uint8_t *rbits_host,
+                             uint8_t *is_term_host, double *init_cdf_host);
+
 /* Irrelevant sub-space tables (host; shared by all envs or one set per env like the others):
  *   P_irr uint8 [T][S_irr][A_irr]   transition_function_irrelevant            rl_toy_env.py:1153-1228
  *   init_cdf_irr double[T][S_irr]   cumsum(irrelevant_init_state_dist) normalised  :1025-1037, :2260
@@ -235,6 +264,9 @@ int mdpp_upload_image_lines(mdpp_env *h, const uint8_t *lines_host);
  * has_uint32, uinteger} exactly as numpy's bit_generator.state reports them. */
 int mdpp_seed_streams(mdpp_env *h, int stream, const uint64_t *words_host);
 int mdpp_get_streams(mdpp_env *h, int stream, uint64_t *words_host);
+/* The same for fresh generators, computed on the device: stream i = PCG64(SeedSequence(seeds_host[i])), seeds below 2^64
+ * (what mdp.new_generator(seed) starts from; no buffered half-word). */
+int mdpp_seed_streams_seedseq(mdpp_env *h, int stream, const uint64_t *seeds_host);
 
 /* reset(): mask_dev == NULL resets every env, else only envs with mask_dev[i] != 0.
  * obs_dev receives the new first observation of the reset envs (others untouched). */

@@ -39,6 +39,7 @@ EXPORTS = [
     "mdpp_episode_stats", "mdpp_probe_hbm", "mdpp_probe_launch",
     "mdpp_peer_create", "mdpp_peer_handle", "mdpp_peer_open", "mdpp_peer_push", "mdpp_peer_fence", "mdpp_peer_wait", "mdpp_peer_buffer",
     "mdpp_peer_status", "mdpp_peer_last_error", "mdpp_peer_destroy",
+    "mdpp_generate_discrete", "mdpp_get_discrete_tables", "mdpp_seed_streams_seedseq",
 ]
 
 
@@ -68,6 +69,14 @@ class MdppConfig(C.Structure):
         ("img_r0", C.c_int32), ("img_r_min", C.c_int32), ("img_r_max", C.c_int32),
         ("img_log_min_r", C.c_double), ("img_log_max_r", C.c_double), ("img_tpl_size", C.c_int32),
         ("episode_stats", C.c_int32), ("target_f64", C.c_int32),
+    ]
+
+
+class MdppGenParams(C.Structure):
+    _fields_ = [
+        ("diameter", C.c_int32), ("n_term", C.c_int32), ("maximally_connected", C.c_int32), ("repeats", C.c_int32),
+        ("total", C.c_uint64), ("n_sel", C.c_uint32), ("n_radices", C.c_int32), ("radices", C.c_uint32 * 16),
+        ("rews", C.c_void_p), ("n_rews", C.c_uint32), ("image", C.c_int32), ("seed_dicts", C.c_void_p),
     ]
 
 
@@ -117,6 +126,9 @@ def load():
     L.mdpp_upload_image_templates.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.mdpp_seed_streams.argtypes = [vp, i32, vp]
     L.mdpp_get_streams.argtypes = [vp, i32, vp]
+    L.mdpp_seed_streams_seedseq.argtypes = [vp, i32, vp]
+    L.mdpp_generate_discrete.argtypes = [vp, vp, C.POINTER(MdppGenParams), vp, vp, vp]
+    L.mdpp_get_discrete_tables.argtypes = [vp] * 6
     L.mdpp_reset.argtypes = [vp, vp, vp, vp]
     L.mdpp_step.argtypes = [vp] * 8
     L.mdpp_step_n.argtypes = [vp, i32] + [vp] * 6

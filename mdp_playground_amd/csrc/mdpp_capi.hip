@@ -463,29 +463,14 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
 
 static inline bool t_fits53(uint64_t t) { return t <= (1ULL << 53) - 1; }
 
-extern "C" int mdpp_upload_discrete_tables(mdpp_env *h, const uint8_t *P, const double *rtable,
-                                           const uint8_t *rbits, const uint8_t *is_term,
-                                           const double *init_cdf, const double *noise_cdf) {
-    if (!h) return MDPP_EINVAL;
-    if (h->cfg.kind != MDPP_KIND_DISCRETE) return fail(h, MDPP_EINVAL, "upload_discrete_tables: not a discrete handle");
-    if (!P || !is_term || !init_cdf) return fail(h, MDPP_EINVAL, "upload_discrete_tables: null table");
-    if (h->cfg.unit_rewards ? !rbits : !rtable) return fail(h, MDPP_EINVAL, "upload_discrete_tables: reward table missing");
-    if (h->cfg.has_transition_noise && !noise_cdf) return fail(h, MDPP_EINVAL, "upload_discrete_tables: noise_cdf missing");
-    HIPCHK(h, hipSetDevice(h->device));
+// What the kernels' dispatch derives from a discrete handle's tables: DiscreteArgs' fast-path constants and the one-launch
+// step's blob.  Shared by the host upload and the device generator (mdpp_generate_discrete), so that a handle selects the
+// same kernels whichever built its tables.  P / rtable / rbits are read for single-table handles only (every specialised
+// path needs T == 1); is_term / init_cdf / noise_cdf are table 0's rows.
+static int discrete_derived(mdpp_env *h, const uint8_t *P, const double *rtable, const uint8_t *rbits,
+                            const uint8_t *is_term, const double *init_cdf, const double *noise_cdf) {
     const size_t T = (size_t)h->cfg.num_tables, S = (size_t)h->cfg.S, A = (size_t)h->cfg.A;
-    const bool wide = S > 255;          // (P is then uint16[T][S][A] behind the same pointer)
-    // every P entry must be a valid state id: the kernels index tables with it unchecked
-    for (size_t k = 0; k < T * S * A; k++)
-        if ((wide ? (size_t)((const uint16_t *)P)[k] : (size_t)P[k]) >= S) return fail(h, MDPP_EINVAL, "upload_discrete_tables: P entry out of range");
-    HIPCHK(h, hipMemcpy(h->d_P, P, T * S * A * (wide ? 2 : 1), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_is_term, is_term, T * S, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->d_init_cdf, init_cdf, T * S * sizeof(double), hipMemcpyHostToDevice));
-    if (h->cfg.unit_rewards)
-        HIPCHK(h, hipMemcpy(h->d_rbits, rbits, T * h->rbits_stride, hipMemcpyHostToDevice));
-    else
-        HIPCHK(h, hipMemcpy(h->d_rtable, rtable, T * (size_t)h->nkeys * sizeof(double), hipMemcpyHostToDevice));
-    if (h->cfg.has_transition_noise)
-        HIPCHK(h, hipMemcpy(h->d_noise_cdf, noise_cdf, S * S * sizeof(double), hipMemcpyHostToDevice));
+    const bool wide = S > 255;
     if (wide || h->cfg.L > 7) {     // no specialised kernel serves such a handle (launch_discrete_step: mdpp_discrete_wide.hip / _long.hip)
         DiscreteArgs &a = h->dargs;
         a.shape_ok = a.fast_ok = a.shape_ok_irr = a.lean_next_ok = a.shape_ok_noise = a.shape_ok_noise_np = 0u;
@@ -670,6 +655,196 @@ extern "C" int mdpp_upload_discrete_tables(mdpp_env *h, const uint8_t *P, const 
         }
     }
     h->tables_ready = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_upload_discrete_tables(mdpp_env *h, const uint8_t *P, const double *rtable,
+                                           const uint8_t *rbits, const uint8_t *is_term,
+                                           const double *init_cdf, const double *noise_cdf) {
+    if (!h) return MDPP_EINVAL;
+    if (h->cfg.kind != MDPP_KIND_DISCRETE) return fail(h, MDPP_EINVAL, "upload_discrete_tables: not a discrete handle");
+    if (!P || !is_term || !init_cdf) return fail(h, MDPP_EINVAL, "upload_discrete_tables: null table");
+    if (h->cfg.unit_rewards ? !rbits : !rtable) return fail(h, MDPP_EINVAL, "upload_discrete_tables: reward table missing");
+    if (h->cfg.has_transition_noise && !noise_cdf) return fail(h, MDPP_EINVAL, "upload_discrete_tables: noise_cdf missing");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t T = (size_t)h->cfg.num_tables, S = (size_t)h->cfg.S, A = (size_t)h->cfg.A;
+    const bool wide = S > 255;          // (P is then uint16[T][S][A] behind the same pointer)
+    // every P entry must be a valid state id: the kernels index tables with it unchecked
+    for (size_t k = 0; k < T * S * A; k++)
+        if ((wide ? (size_t)((const uint16_t *)P)[k] : (size_t)P[k]) >= S) return fail(h, MDPP_EINVAL, "upload_discrete_tables: P entry out of range");
+    HIPCHK(h, hipMemcpy(h->d_P, P, T * S * A * (wide ? 2 : 1), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_is_term, is_term, T * S, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->d_init_cdf, init_cdf, T * S * sizeof(double), hipMemcpyHostToDevice));
+    if (h->cfg.unit_rewards)
+        HIPCHK(h, hipMemcpy(h->d_rbits, rbits, T * h->rbits_stride, hipMemcpyHostToDevice));
+    else
+        HIPCHK(h, hipMemcpy(h->d_rtable, rtable, T * (size_t)h->nkeys * sizeof(double), hipMemcpyHostToDevice));
+    if (h->cfg.has_transition_noise)
+        HIPCHK(h, hipMemcpy(h->d_noise_cdf, noise_cdf, S * S * sizeof(double), hipMemcpyHostToDevice));
+    return discrete_derived(h, P, rtable, rbits, is_term, init_cdf, noise_cdf);
+}
+
+// device buffers of one call, freed on every way out
+struct DevTemp {
+    std::vector<void *> ptrs;
+    ~DevTemp() { for (void *p : ptrs) (void)hipFree(p); }
+    hipError_t alloc(void **p, size_t bytes) {
+        hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+        if (e == hipSuccess) ptrs.push_back(*p);
+        return e;
+    }
+};
+
+// generator scratch per launch (sequence bitsets, picks, value permutations): envs go in chunks below this
+static const size_t kGenScratchCap = (size_t)256 << 20;
+
+extern "C" int mdpp_generate_discrete(mdpp_env *h, const uint64_t *seeds, const mdpp_gen_params *p,
+                                      const uint8_t *is_term, const double *init_cdf, const double *noise_cdf) {
+    if (!h) return MDPP_EINVAL;
+    const mdpp_config &c = h->cfg;
+    if (c.kind != MDPP_KIND_DISCRETE) return fail(h, MDPP_EINVAL, "generate_discrete: not a discrete handle");
+    if (!seeds || !p || !is_term || !init_cdf) return fail(h, MDPP_EINVAL, "generate_discrete: null argument");
+    if (c.has_transition_noise && !noise_cdf) return fail(h, MDPP_EINVAL, "generate_discrete: noise_cdf missing");
+    if (c.num_tables != c.num_envs || c.irrelevant || c.S > 255 || c.reward_kind != MDPP_REWARD_SEQUENCES)
+        return fail(h, MDPP_EUNSUPPORTED, "generate_discrete: needs one table per env, no irrelevant sub-space, S <= 255 and "
+                                          "rewardable sequences");
+    // the parameters must describe this handle's shape: every key and P entry the kernel writes is then in range
+    const int d = p->diameter, n_term = p->n_term, L = c.L;
+    const uint32_t nn = (uint32_t)(c.A - n_term);
+    bool ok = d >= 1 && c.S == c.A * d && n_term >= 0 && n_term < c.A && p->n_sel >= 1 && p->n_sel <= p->total &&
+              (p->image != 0) == (c.image != 0);
+    if (ok && p->repeats) {
+        uint64_t t = 1;
+        for (int i = 0; i < L; i++) t *= nn;
+        ok = p->total == t;
+    } else if (ok) {
+        uint64_t t = 1;
+        ok = p->n_radices == L;
+        for (int i = 0; ok && i < L; i++) {
+            ok = p->radices[i] == nn - (uint32_t)(i / d) && p->radices[i] >= 1;
+            t *= p->radices[i];
+        }
+        ok = ok && p->total == t;
+    }
+    const uint64_t n_seqs = (uint64_t)d * p->n_sel;
+    if (ok && p->rews) ok = p->n_rews >= n_seqs && p->n_rews > 1;
+    if (!ok) return fail(h, MDPP_EINVAL, "generate_discrete: parameters do not match the handle");
+    GenArgs a;
+    memset(&a, 0, sizeof(a));
+    a.set_words = (p->total + 63u) / 64u;
+    a.perm_off = a.set_words + (uint64_t)(p->repeats ? 1 : d) * p->n_sel;
+    a.scratch_words = a.perm_off + (p->rews ? ((uint64_t)p->n_rews + 1u) / 2u : 0u);
+    const size_t per_env = (size_t)a.scratch_words * 8u;
+    if (per_env > kGenScratchCap) return fail(h, MDPP_EUNSUPPORTED, "generate_discrete: scratch per env above the cap");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t N = (size_t)c.num_envs, S = (size_t)c.S, A = (size_t)c.A;
+    const int chunk = (int)std::min(N, std::max<size_t>(1, kGenScratchCap / std::max<size_t>(per_env, 8)));
+    DevTemp tmp;
+    uint64_t *d_seeds = nullptr, *d_sd = nullptr, *d_scr = nullptr;
+    double *d_rews = nullptr;
+    HIPCHK(h, tmp.alloc((void **)&d_seeds, N * 8));
+    HIPCHK(h, hipMemcpy(d_seeds, seeds, N * 8, hipMemcpyHostToDevice));
+    if (p->rews) {
+        HIPCHK(h, tmp.alloc((void **)&d_rews, (size_t)p->n_rews * 8));
+        HIPCHK(h, hipMemcpy(d_rews, p->rews, (size_t)p->n_rews * 8, hipMemcpyHostToDevice));
+    }
+    if (p->seed_dicts) HIPCHK(h, tmp.alloc((void **)&d_sd, N * 64));
+    HIPCHK(h, tmp.alloc((void **)&d_scr, (size_t)chunk * per_env));
+    HIPCHK(h, hipMemset(h->d_P, 0, N * S * A));
+    if (c.unit_rewards) HIPCHK(h, hipMemset(h->d_rbits, 0, N * h->rbits_stride));
+    else HIPCHK(h, hipMemset(h->d_rtable, 0, N * (size_t)h->nkeys * sizeof(double)));
+    a.S = c.S; a.A = c.A; a.L = L; a.diameter = d; a.n_term = n_term; a.maxc = p->maximally_connected ? 1 : 0;
+    a.repeats = p->repeats ? 1 : 0; a.unit = c.unit_rewards ? 1 : 0;
+    a.total = p->total; a.n_sel = p->n_sel;
+    for (int i = 0; i < 16; i++) a.radix[i] = p->repeats ? 0u : p->radices[i];
+    a.rews = d_rews; a.n_rews = p->rews ? p->n_rews : 0u;
+    a.nkeys = h->nkeys; a.rbits_stride = h->rbits_stride;
+    a.seeds = d_seeds; a.P = (uint8_t *)h->d_P; a.rbits = (uint8_t *)h->d_rbits; a.rtable = (double *)h->d_rtable;
+    a.sd = d_sd;
+    if (c.rng_mode == MDPP_RNG_NUMPY_PCG64) {          // (Philox handles keep no stream state)
+        a.env_s = (ulonglong2 *)h->d_rng_s[MDPP_STREAM_ENV]; a.env_inc = (ulonglong2 *)h->d_rng_inc[MDPP_STREAM_ENV];
+        a.sp_s = (ulonglong2 *)h->d_rng_s[MDPP_STREAM_SPACE]; a.sp_inc = (ulonglong2 *)h->d_rng_inc[MDPP_STREAM_SPACE];
+        if (c.image) {
+            a.im_s = (ulonglong2 *)h->d_rng_s[MDPP_STREAM_IMAGE]; a.im_inc = (ulonglong2 *)h->d_rng_inc[MDPP_STREAM_IMAGE];
+            a.im_half = (uint2 *)h->d_rng_half;
+        }
+    }
+    a.scratch = d_scr;
+    for (size_t first = 0; first < N; first += (size_t)chunk)
+        HIPCHK(h, launch_generate_discrete(a, (int)first, (int)std::min((size_t)chunk, N - first)));
+    HIPCHK(h, hipDeviceSynchronize());
+    if (p->seed_dicts) HIPCHK(h, hipMemcpy(p->seed_dicts, d_sd, N * 64, hipMemcpyDeviceToHost));
+    // the tables every env shares, one row per table as the kernels index them
+    {
+        std::vector<uint8_t> term(N * S);
+        std::vector<double> cdf(N * S);
+        for (size_t i = 0; i < N; i++) {
+            memcpy(term.data() + i * S, is_term, S);
+            memcpy(cdf.data() + i * S, init_cdf, S * sizeof(double));
+        }
+        HIPCHK(h, hipMemcpy(h->d_is_term, term.data(), N * S, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->d_init_cdf, cdf.data(), N * S * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (c.has_transition_noise)
+        HIPCHK(h, hipMemcpy(h->d_noise_cdf, noise_cdf, S * S * sizeof(double), hipMemcpyHostToDevice));
+    int rc;
+    if (N == 1) {          // a single table: the specialised paths read it on the host
+        std::vector<uint8_t> P(S * A), rbits(c.unit_rewards ? h->rbits_stride : 0);
+        std::vector<double> rtable(c.unit_rewards ? 0 : h->nkeys);
+        HIPCHK(h, hipMemcpy(P.data(), h->d_P, S * A, hipMemcpyDeviceToHost));
+        if (c.unit_rewards) HIPCHK(h, hipMemcpy(rbits.data(), h->d_rbits, h->rbits_stride, hipMemcpyDeviceToHost));
+        else HIPCHK(h, hipMemcpy(rtable.data(), h->d_rtable, (size_t)h->nkeys * sizeof(double), hipMemcpyDeviceToHost));
+        rc = discrete_derived(h, P.data(), c.unit_rewards ? nullptr : rtable.data(), c.unit_rewards ? rbits.data() : nullptr,
+                              is_term, init_cdf, noise_cdf);
+    } else {
+        rc = discrete_derived(h, nullptr, nullptr, nullptr, is_term, init_cdf, noise_cdf);
+    }
+    if (rc != MDPP_OK) return rc;
+    if (c.rng_mode == MDPP_RNG_NUMPY_PCG64) {
+        if (h->dargs.fast_ok)     // (as mdpp_seed_streams: no start state drawn ahead from an older env stream survives)
+            HIPCHK(h, hipMemset2D((char *)h->d_state + 4, 16, 0, 4, N));
+        h->streams_ready[MDPP_STREAM_ENV] = h->streams_ready[MDPP_STREAM_SPACE] = true;
+        if (c.image) h->streams_ready[MDPP_STREAM_IMAGE] = true;
+    }
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_get_discrete_tables(mdpp_env *h, uint8_t *P, double *rtable, uint8_t *rbits, uint8_t *is_term,
+                                        double *init_cdf) {
+    if (!h) return MDPP_EINVAL;
+    if (h->cfg.kind != MDPP_KIND_DISCRETE) return fail(h, MDPP_EINVAL, "get_discrete_tables: not a discrete handle");
+    if (!h->tables_ready) return fail(h, MDPP_ESTATE, "get_discrete_tables: tables not uploaded");
+    if ((rtable && !h->d_rtable) || (rbits && !h->d_rbits))
+        return fail(h, MDPP_EINVAL, "get_discrete_tables: this handle keeps the other reward table (unit_rewards)");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());
+    const size_t T = (size_t)h->cfg.num_tables, S = (size_t)h->cfg.S, A = (size_t)h->cfg.A;
+    if (P) HIPCHK(h, hipMemcpy(P, h->d_P, T * S * A * (S > 255 ? 2 : 1), hipMemcpyDeviceToHost));
+    if (rtable) HIPCHK(h, hipMemcpy(rtable, h->d_rtable, T * (size_t)h->nkeys * sizeof(double), hipMemcpyDeviceToHost));
+    if (rbits) HIPCHK(h, hipMemcpy(rbits, h->d_rbits, T * h->rbits_stride, hipMemcpyDeviceToHost));
+    if (is_term) HIPCHK(h, hipMemcpy(is_term, h->d_is_term, T * S, hipMemcpyDeviceToHost));
+    if (init_cdf) HIPCHK(h, hipMemcpy(init_cdf, h->d_init_cdf, T * S * sizeof(double), hipMemcpyDeviceToHost));
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_seed_streams_seedseq(mdpp_env *h, int stream, const uint64_t *seeds) {
+    if (!h || !seeds) return MDPP_EINVAL;
+    if (h->cfg.rng_mode != MDPP_RNG_NUMPY_PCG64) return fail(h, MDPP_ESTATE, "seed_streams_seedseq: handle is in Philox mode");
+    if (stream < 0 || stream >= MDPP_NUM_STREAMS || !h->d_rng_s[stream]) return fail(h, MDPP_EINVAL, "seed_streams_seedseq: bad stream");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t N = (size_t)h->cfg.num_envs;
+    DevTemp tmp;
+    uint64_t *d_seeds = nullptr;
+    HIPCHK(h, tmp.alloc((void **)&d_seeds, N * 8));
+    HIPCHK(h, hipMemcpy(d_seeds, seeds, N * 8, hipMemcpyHostToDevice));
+    const bool half = (stream == MDPP_STREAM_IMAGE || stream == MDPP_STREAM_ACTION) && h->d_rng_half;
+    // (behind whatever the caller's streams still run on the old state, as mdpp_seed_streams' copies are)
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, launch_seed_streams_seedseq(d_seeds, (int)N, h->d_rng_s[stream], h->d_rng_inc[stream], half ? h->d_rng_half : nullptr));
+    if (stream == MDPP_STREAM_ENV && h->cfg.kind == MDPP_KIND_DISCRETE && h->dargs.fast_ok)
+        HIPCHK(h, hipMemset2D((char *)h->d_state + 4, 16, 0, 4, N));
+    HIPCHK(h, hipDeviceSynchronize());
+    h->streams_ready[stream] = true;
     return MDPP_OK;
 }
 

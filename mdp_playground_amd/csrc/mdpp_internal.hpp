@@ -316,6 +316,26 @@ struct mdpp_env {
 };
 
 namespace mdpp {
+// Per-env discrete MDP generation (mdpp_generate.hip, mdpp_generate_discrete): what one lane needs for env e
+struct GenArgs {
+    int32_t S, A, L, diameter, n_term, maxc, repeats, unit;
+    uint64_t total;             // sequence numbers picked from (per independent set without repeats)
+    uint32_t n_sel;             // picks per draw
+    uint32_t radix[16];         // without repeats: the digit radices, position 0 first
+    const double *rews;         // device: the unshuffled reward_dist values (n_rews > 1), or null (every value 1.0)
+    uint32_t n_rews;
+    uint32_t nkeys, rbits_stride;
+    const uint64_t *seeds;      // device [N]
+    uint8_t *P;                 // [N][S][A]
+    uint8_t *rbits;             // [N][rbits_stride] (unit) ...
+    double *rtable;             // ... or [N][nkeys]
+    uint64_t *sd;               // [N][8] seed dicts, or null
+    ulonglong2 *env_s, *env_inc, *sp_s, *sp_inc, *im_s, *im_inc;   // PCG64 streams (null: not written)
+    uint2 *im_half;
+    uint64_t *scratch;          // [count][scratch_words]: bitset of `total` bits, picks, permutation of the values
+    uint64_t scratch_words, set_words, perm_off;
+};
+
 // implemented in the kernel translation units
 // name_out != nullptr: a dry run -- the launcher writes the name of the kernel it would launch (at most
 // kNameLen bytes) and launches nothing
@@ -366,3 +386,6 @@ int launch_image_step1(mdpp_env *h, const int32_t *state_out, const int32_t *sta
                        const uint8_t *trunc, uint8_t *img_out, uint8_t *img_final, hipStream_t s);
 const char *image_obs_kernel_name(const mdpp_env *h, int K);    // the renderer launch_image_obs() uses
 } // namespace mdpp
+// mdpp_generate.hip: envs [first, first + count) of a GenArgs block; PCG64(SeedSequence(seeds[i])) into a stream's buffers
+hipError_t launch_generate_discrete(const mdpp::GenArgs &a, int first, int count);
+hipError_t launch_seed_streams_seedseq(const uint64_t *seeds, int N, void *st, void *inc, void *half);

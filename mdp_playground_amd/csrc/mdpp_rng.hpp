@@ -22,6 +22,15 @@ static __device__ const uint64_t d_zig_ki[256] = NPZ_KI_INIT;
 static __device__ const double d_zig_wi[256] = NPZ_WI_INIT;
 static __device__ const double d_zig_fi[256] = NPZ_FI_INIT;
 
+// high 64 bits of a 64 x 64-bit product
+__host__ __device__ __forceinline__ uint64_t mulhi64(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
 struct Pcg64 {
     uint64_t s_lo, s_hi, inc_lo, inc_hi;
 
@@ -33,10 +42,11 @@ struct Pcg64 {
         st[i] = make_ulonglong2(s_lo, s_hi);
     }
     // state = state * 0x2360ED051FC65DA44385DF649FCCF645 + inc (mod 2^128); output XSL-RR of the new state
-    __device__ __forceinline__ uint64_t next64() {
+    // (host-callable too: the MDP generator of mdpp_generate.hip is a __host__ __device__ template)
+    __host__ __device__ __forceinline__ uint64_t next64() {
         const uint64_t M_HI = 0x2360ED051FC65DA4ULL, M_LO = 0x4385DF649FCCF645ULL;
         uint64_t lo = s_lo * M_LO;
-        uint64_t hi = __umul64hi(s_lo, M_LO) + s_lo * M_HI + s_hi * M_LO;
+        uint64_t hi = mulhi64(s_lo, M_LO) + s_lo * M_HI + s_hi * M_LO;
         uint64_t nlo = lo + inc_lo;
         uint64_t carry = nlo < lo ? 1ULL : 0ULL;
         s_lo = nlo;
@@ -98,7 +108,7 @@ struct Half32 {
     uint32_t has32, u32;
 };
 template <class G>
-__device__ __forceinline__ uint32_t next32(G &g, Half32 &h) {
+__host__ __device__ __forceinline__ uint32_t next32(G &g, Half32 &h) {
     if (h.has32) { h.has32 = 0; return h.u32; }
     uint64_t n = g.next64();
     h.has32 = 1; h.u32 = (uint32_t)(n >> 32);
@@ -549,6 +559,104 @@ __device__ __forceinline__ int searchsorted_right(const double *cdf, int n, doub
     int c = 0;
     for (int i = 0; i < n; i++) c += (cdf[i] <= u) ? 1 : 0;
     return c;
+}
+
+// ---- numpy's seeding and the draws of MDP generation (mdpp_generate.hip) ---------------------------------------------
+// Host-callable as well as device code: the generator is one template for both.
+
+// PCG64(SeedSequence(seed)) for an integer seed below 2^64 (numpy/random/bit_generator.pyx): the seed as 1 or 2 uint32
+// entropy words, hashmix / mix into a pool of 4 words, generate_state(4 uint64) -> initstate = v0 << 64 | v1,
+// initseq = v2 << 64 | v3; then pcg_setseq_128_srandom_r: inc = initseq << 1 | 1, state = step(0) + initstate, step.
+__host__ __device__ inline void pcg64_seedseq(uint64_t seed, Pcg64 &g) {
+    const uint32_t INIT_A = 0x43b0d7e5u, MULT_A = 0x931e8875u, INIT_B = 0x8b51f9ddu, MULT_B = 0x58f38dedu;
+    const uint32_t MIX_MULT_L = 0xca01f9ddu, MIX_MULT_R = 0x4973f715u;
+    const uint32_t ent[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const int n_ent = (seed >> 32) ? 2 : 1;
+    uint32_t hc = INIT_A;
+    auto hashmix = [&hc](uint32_t v) -> uint32_t {
+        v ^= hc; hc *= MULT_A; v *= hc; v ^= v >> 16; return v;
+    };
+    auto mix = [](uint32_t x, uint32_t y) -> uint32_t {
+        uint32_t r = MIX_MULT_L * x - MIX_MULT_R * y; r ^= r >> 16; return r;
+    };
+    uint32_t pool[4];
+    for (int i = 0; i < 4; i++) pool[i] = hashmix(i < n_ent ? ent[i] : 0u);
+    for (int src = 0; src < 4; src++)
+        for (int dst = 0; dst < 4; dst++)
+            if (src != dst) pool[dst] = mix(pool[dst], hashmix(pool[src]));
+    uint32_t w[8];
+    uint32_t hb = INIT_B;
+    for (int i = 0; i < 8; i++) {
+        uint32_t v = pool[i & 3];
+        v ^= hb; hb *= MULT_B; v *= hb; v ^= v >> 16;
+        w[i] = v;
+    }
+    const uint64_t v0 = w[0] | (uint64_t)w[1] << 32, v1 = w[2] | (uint64_t)w[3] << 32;
+    const uint64_t v2 = w[4] | (uint64_t)w[5] << 32, v3 = w[6] | (uint64_t)w[7] << 32;
+    // inc = (v2 << 64 | v3) << 1 | 1
+    g.inc_hi = v2 << 1 | v3 >> 63;
+    g.inc_lo = v3 << 1 | 1u;
+    g.s_lo = g.s_hi = 0;
+    (void)g.next64();
+    const uint64_t lo = g.s_lo + v1;
+    g.s_hi += v0 + (lo < v1 ? 1u : 0u);
+    g.s_lo = lo;
+    (void)g.next64();
+}
+
+// random_bounded_uint64(off = 0, rng, use_masked = false): a value in [0, rng], Lemire's method -- on the generator's
+// buffered 32-bit half-words for rng < 2^32 (buffered_bounded_lemire_uint32 without a local buffer), on 64-bit draws
+// beyond (bounded_lemire_uint64: 128-bit product, threshold (2^64 - (rng + 1)) mod (rng + 1)).  rng = 0 draws nothing.
+template <class G>
+__host__ __device__ inline uint64_t np_bounded_u64(G &g, Half32 &h, uint64_t rng) {
+    if (rng == 0) return 0;
+    if (rng <= 0xFFFFFFFFull) {
+        if (rng == 0xFFFFFFFFull) return next32(g, h);
+        const uint32_t r = (uint32_t)rng, r_excl = r + 1u;
+        uint64_t m = (uint64_t)next32(g, h) * r_excl;
+        uint32_t leftover = (uint32_t)m;
+        if (leftover < r_excl) {
+            const uint32_t threshold = (0xFFFFFFFFu - r) % r_excl;
+            while (leftover < threshold) {
+                m = (uint64_t)next32(g, h) * r_excl;
+                leftover = (uint32_t)m;
+            }
+        }
+        return m >> 32;
+    }
+    if (rng == ~0ull) return g.next64();
+    const uint64_t r_excl = rng + 1;
+    uint64_t x = g.next64();
+    uint64_t leftover = x * r_excl;
+    if (leftover < r_excl) {
+        const uint64_t threshold = (~0ull - rng) % r_excl;
+        while (leftover < threshold) {
+            x = g.next64();
+            leftover = x * r_excl;
+        }
+    }
+    return mulhi64(x, r_excl);
+}
+
+// random_interval(max): a value in [0, max] by masked rejection (what Generator.shuffle draws)
+template <class G>
+__host__ __device__ inline uint64_t np_interval(G &g, Half32 &h, uint64_t max) {
+    if (max == 0) return 0;
+    uint64_t mask = max;
+    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16; mask |= mask >> 32;
+    uint64_t v;
+    if (max <= 0xFFFFFFFFull) {
+        do { v = next32(g, h) & mask; } while (v > max);
+    } else {
+        do { v = g.next64() & mask; } while (v > max);
+    }
+    return v;
+}
+
+// Generator.random(): a double in [0, 1) from the top 53 bits of one 64-bit draw
+template <class G>
+__host__ __device__ inline double np_random_f64(G &g) {
+    return (double)(g.next64() >> 11) * (1.0 / 9007199254740992.0);
 }
 
 } // namespace mdpp

@@ -232,6 +232,17 @@ def _next_set_prob(S, A, s):
     return prob
 
 
+def _terminal_and_init(A, diameter, n_term):
+    """:868-881 terminal states = the last n_term states of every independent set; :1003-1018 rho_0 uniform over the
+    non-terminal states."""
+    terminal = np.array([j * A - 1 - i for j in range(1, diameter + 1) for i in range(n_term)],
+                        dtype=np.int64)
+    n_nonterm = A - n_term
+    init_dist = np.array(([1 / (n_nonterm * diameter) for _ in range(n_nonterm)]
+                          + [0 for _ in range(n_term)]) * diameter)
+    return terminal, init_dist
+
+
 def _rewardable_sequences(env_rng, n_nonterm, A, L, fraction, repeats, diameter):
     """get_sequences, rl_toy_env.py:1273-1473: pick sequence numbers without replacement from
     the env generator and decode them (base-n digits with repeats, a Lehmer-style mixed-radix
@@ -301,14 +312,9 @@ def build_discrete(config) -> DiscreteMDP:
     S = A * diameter                                      # :589-591
     S_irr = A_irr * diameter
     tn = config.get("transition_noise", None)
-    # :868-881 terminal states = the last int(density * A) states of every independent set
     n_term = int(config.get("terminal_state_density", 0.25) * A)
-    terminal = np.array([j * A - 1 - i for j in range(1, diameter + 1) for i in range(n_term)],
-                        dtype=np.int64)
+    terminal, init_dist = _terminal_and_init(A, diameter, n_term)
     n_nonterm = A - n_term
-    # :1003-1018 rho_0 uniform over non-terminal states
-    init_dist = np.array(([1 / (n_nonterm * diameter) for _ in range(n_nonterm)]
-                          + [0 for _ in range(n_term)]) * diameter)
     # :1050-1151 P, drawn from the relevant state space's own generator.  With an irrelevant
     # sub-space the two state spaces are wrapped in a TupleExtended seeded with
     # seed_dict["state_space"] (:725-728), and gymnasium's Tuple.seed(int) (third-party, 0.29 / 1.x)
@@ -632,3 +638,107 @@ def build_many(config, seeds, workers=None):
     with mp.get_context("fork").Pool(n) as pool, contextlib.redirect_stdout(io.StringIO()):
         parts = pool.map(_build_chunk, chunks)
     return [m for part in parts for m in part]
+
+
+# ---- per-env discrete MDPs generated on the device (mdpp_generate.hip) ----------------------------------------------------
+# RLToyVectorEnv(seeds=[...]) builds env i's tables from {**config, "seed": seeds[i]} in one launch when the config is
+# covered below; everything else keeps build_discrete on the host.  The device restates build_discrete draw for draw.
+
+DEVICE_SCRATCH_CAP = 256 << 20      # bytes of generator scratch (sequence bitset, picks, value permutation) per launch
+
+
+def _floyd(total, n_sel):
+    """Generator.choice(total, size=n_sel, replace=False) takes Floyd's branch (the device's); otherwise a partial
+    Fisher-Yates over arange(total), which stays on the host."""
+    return total <= 10000 or n_sel <= total // 50
+
+
+def device_gen_params(config):
+    """What build_discrete derives from the config alone for a covered discrete config: the dict the device generator
+    needs (mdpp_gen_params in include/mdpp.h) plus the tables that are the same for every seed."""
+    L = config.get("sequence_length", 1)
+    diameter = config.get("diameter", 1)
+    A = config["action_space_size"]
+    S = A * diameter
+    n_term = int(config.get("terminal_state_density", 0.25) * A)
+    n_nonterm = A - n_term
+    fraction = config.get("reward_density", 0.25)
+    repeats = bool(config.get("repeats_in_sequences", False))
+    if repeats:
+        radices = []
+        total = n_nonterm ** L
+    else:
+        radices = [n_nonterm - (i // diameter) for i in range(L)]
+        total = int(np.prod(radices))
+    n_sel = int(fraction * total) or 1
+    n_seqs = diameter * n_sel
+    rews = None
+    unit = True
+    reward_dist = config.get("reward_dist", None)
+    if isinstance(reward_dist, list):                     # rl_toy_env.py:1528-1544
+        n_rews = diameter * n_seqs
+        if n_rews > 1:
+            rews = np.ascontiguousarray(np.linspace(reward_dist[0], reward_dist[1], num=n_rews), dtype=np.float64)
+            unit = bool(np.all(rews == 1.0))
+    terminal, init_dist = _terminal_and_init(A, diameter, n_term)
+    is_term = np.zeros(S, dtype=np.uint8)
+    is_term[terminal] = 1
+    cdf = np.cumsum(np.asarray(init_dist, dtype=np.float64))
+    set_words = -(-total // 64)
+    pick_words = (1 if repeats else diameter) * n_sel
+    perm_words = 0 if rews is None else -(-len(rews) // 2)
+    return dict(S=S, A=A, L=L, diameter=diameter, n_term=n_term,
+                maximally_connected=bool(config.get("maximally_connected", True)), repeats=repeats,
+                total=total, n_sel=n_sel, radices=radices, rews=rews, unit_rewards=unit,
+                image=bool(config.get("image_representations", False)),
+                is_term=is_term, init_cdf=cdf / cdf[-1],
+                scratch_words=set_words + pick_words + perm_words, set_words=set_words,
+                perm_off=set_words + pick_words)
+
+
+def device_coverage(config, seeds):
+    """(True, "") when the per-env MDPs of {**config, "seed": s} for every s in seeds can be generated on the device, else
+    (False, reason).  Decided by the config and the seeds, not by a user option."""
+    if config == {} or str(config.get("state_space_type", "")).lower() != "discrete":
+        return False, "not a discrete env"
+    if config.get("use_custom_mdp", False):
+        return False, "use_custom_mdp"
+    if config.get("irrelevant_features", False):
+        return False, "irrelevant_features"
+    A = config.get("action_space_size")
+    if type(A) is not int or A < 1:
+        return False, "action_space_size is not an int"
+    diameter = config.get("diameter", 1)
+    if type(diameter) is not int or diameter < 1:
+        return False, "diameter is not a positive int"
+    if A * diameter > 255:
+        return False, "S > 255"
+    L = config.get("sequence_length", 1)
+    if type(L) is not int or not 1 <= L <= 15:
+        return False, "sequence_length outside 1..15"
+    for s in seeds:
+        if type(s) is not int or not 0 <= s < 2 ** 64:
+            return False, "a seed is not an int in [0, 2^64)"
+    rd = config.get("reward_dist", None)
+    if rd is not None and not (isinstance(rd, list) and len(rd) == 2):
+        return False, "reward_dist is neither None nor a 2-element list"
+    if isinstance(rd, list) and config.get("make_denser", False) and L > 1:
+        return False, "reward_dist list with make_denser and sequence_length > 1"
+    n_term = int(config.get("terminal_state_density", 0.25) * A)
+    n_nonterm = A - n_term
+    if n_nonterm < 1 or n_term < 0:
+        return False, "no non-terminal states"
+    fraction = config.get("reward_density", 0.25)
+    if not isinstance(fraction, (int, float)) or not 0 <= fraction <= 1:
+        return False, "reward_density outside [0, 1]"
+    repeats = bool(config.get("repeats_in_sequences", False))
+    if not repeats and L > diameter * n_nonterm:
+        return False, "sequence_length > diameter * non-terminal states without repeats"
+    if float(A * diameter) ** L > 4.0e9:                  # mdpp_create: S^L keys at most
+        return False, "S^L too large"
+    p = device_gen_params(config)
+    if not _floyd(p["total"], p["n_sel"]):
+        return False, "the sequence draw takes choice's tail-shuffle branch"
+    if 8 * p["scratch_words"] > DEVICE_SCRATCH_CAP:
+        return False, "generator scratch per env above the cap"
+    return True, ""

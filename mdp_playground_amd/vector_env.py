@@ -9,7 +9,9 @@ Each env instance i of the batch behaves exactly like one reference object:
   gymnasium SyncVectorEnv does); its space generator (discrete P-noise, continuous reset
   sampling) is the reference's own for i = 0 and ``Space.seed(space_seed + i)`` for i > 0.
 * ``RLToyVectorEnv(seeds=[s0, s1, ...], **config)`` — N *different* MDPs: instance i is the
-  reference ``RLToyEnv(**{**config, "seed": seeds[i]})`` verbatim (tables per env in HBM).
+  reference ``RLToyEnv(**{**config, "seed": seeds[i]})`` verbatim (tables per env in HBM).  Discrete
+  configs that ``mdp.device_coverage`` accepts are generated on the device in one launch
+  (mdpp_generate.hip, bit-identical to the host builder); ``tables_built_on`` says which path ran.
 
 ``rng="numpy"`` (default) keeps numpy ``Generator(PCG64)`` streams per env on the device, so
 noise and resets are bit-identical to the reference under identical seeds; ``rng="philox"`` is a
@@ -19,6 +21,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+from collections.abc import Sequence
 
 import numpy as np
 import torch
@@ -33,6 +36,32 @@ _AUTORESET = {"disabled": capi.AUTORESET_DISABLED, "same_step": capi.AUTORESET_S
 
 def _stack(arrs, dtype):
     return np.ascontiguousarray(np.stack([np.asarray(a) for a in arrs]), dtype=dtype)
+
+
+class _LazyMDPs(Sequence):
+    """env.mdps of a handle whose tables were generated on the device: MDP i is built on the host (mdp.build_mdp) the
+    first time it is read, and kept."""
+
+    def __init__(self, config, seeds, first):
+        self._config, self._seeds = config, list(seeds)
+        self._built = {0: first}
+
+    def __len__(self):
+        return len(self._seeds)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        n = len(self._seeds)
+        i = int(i)
+        if i < 0:
+            i += n
+        if not 0 <= i < n:
+            raise IndexError("mdps index out of range")
+        m = self._built.get(i)
+        if m is None:
+            m = self._built[i] = mdp_mod.build_mdp({**self._config, "seed": self._seeds[i]})
+        return m
 
 
 class RLToyVectorEnv:
@@ -56,6 +85,7 @@ class RLToyVectorEnv:
         if self.device.index is None:          # 'cuda' -> 'cuda:<current>': step() compares tensors' devices with it
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.config = copy.deepcopy(config)   # the reference mutates its config (:339,...); we do not
+        self._gen = None                      # mdp.device_gen_params when the per-env tables are generated on the device
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
                 raise ValueError("num_envs != len(seeds)")
@@ -65,7 +95,14 @@ class RLToyVectorEnv:
                     raise ValueError("len(mdps) != len(seeds)")
                 self.mdps = list(mdps)
             else:
-                self.mdps = [mdp_mod.build_mdp({**config, "seed": s}) for s in seeds]
+                # env 0 on the host always: shapes, flags, spaces and the reference's config errors come from it
+                first = mdp_mod.build_mdp({**config, "seed": seeds[0]})
+                if mdp_mod.device_coverage(self.config, seeds)[0]:
+                    self._gen = mdp_mod.device_gen_params(self.config)
+                    self._seeds = list(seeds)
+                    self.mdps = _LazyMDPs(self.config, seeds, first)
+                else:
+                    self.mdps = [first] + [mdp_mod.build_mdp({**config, "seed": s}) for s in seeds[1:]]
         else:
             if num_envs is None:
                 num_envs = 1
@@ -132,18 +169,27 @@ class RLToyVectorEnv:
         # the reference constructor ends with reset(seed=seed_dict["env"]) (:831-833)
         self._reset_all()
 
+    @property
+    def tables_built_on(self):
+        """"device" when the per-env discrete tables were generated on the GPU (mdpp_generate_discrete), else "host"."""
+        return "host" if self._gen is None else "device"
+
     # ------------------------------------------------------------------ construction helpers
     def _init_discrete(self, cfg):
         m = self.mdps[0]
-        for o in self.mdps[1:]:
+        for o in ([] if self._gen is not None else self.mdps[1:]):
             if (o.S, o.A, o.sequence_length, o.delay, o.S_irr, o.A_irr) != \
                     (m.S, m.A, m.sequence_length, m.delay, m.S_irr, m.A_irr):
                 raise ValueError("per-env MDPs must share S, A, sequence_length and delay")
         cfg.S, cfg.A, cfg.L = m.S, m.A, m.sequence_length
         cfg.num_tables = self.num_envs if self._per_env else 1
-        unit = all(v == 1.0 for mm in self.mdps for k, v in mm.rewardable_sequences.items()
-                   if len(k) == mm.sequence_length)
-        custom_r = [mm.reward_matrix is not None for mm in self.mdps]
+        if self._gen is not None:
+            unit = self._gen["unit_rewards"]
+            custom_r = [False]
+        else:
+            unit = all(v == 1.0 for mm in self.mdps for k, v in mm.rewardable_sequences.items()
+                       if len(k) == mm.sequence_length)
+            custom_r = [mm.reward_matrix is not None for mm in self.mdps]
         if any(custom_r) and not all(custom_r):
             raise ValueError("per-env MDPs must all use a reward matrix or all use rewardable sequences")
         cfg.reward_kind = capi.REWARD_STATE_ACTION if custom_r[0] else capi.REWARD_SEQUENCES
@@ -192,6 +238,43 @@ class RLToyVectorEnv:
         self.reward_matrix = m.reward_matrix               # use_custom_mdp with matrices (:1259-1267)
 
     def _upload_discrete(self):
+        if self._gen is not None:
+            self._generate_discrete()
+        else:
+            self._upload_discrete_host()
+        if self._image is not None:
+            t = self._image
+            tpl = np.ascontiguousarray(t["tpl"], dtype=np.uint8)
+            cx = np.ascontiguousarray(t["cls_x"], dtype=np.int16)
+            cy = np.ascontiguousarray(t["cls_y"], dtype=np.int16)
+            rc = self._lib.mdpp_upload_image_templates(self._h, capi.nptr(tpl), tpl.shape[1],
+                                                       t["n_cls_x"], t["n_cls_y"], capi.nptr(cx),
+                                                       capi.nptr(cy))
+            capi.check(self._lib, self._h, rc, "mdpp_upload_image_templates")
+
+    def _generate_discrete(self):
+        """Every env's tables and streams in one launch (mdpp_generate_discrete); the seed dicts come back to the host."""
+        g = self._gen
+        p = capi.MdppGenParams()
+        p.diameter, p.n_term = g["diameter"], g["n_term"]
+        p.maximally_connected, p.repeats = int(g["maximally_connected"]), int(g["repeats"])
+        p.total, p.n_sel, p.n_radices = g["total"], g["n_sel"], len(g["radices"])
+        for j, r in enumerate(g["radices"]):
+            p.radices[j] = r
+        rews = g["rews"]
+        p.rews, p.n_rews = (None, 0) if rews is None else (rews.ctypes.data, len(rews))
+        p.image = int(g["image"])
+        sd = np.zeros((self.num_envs, 8), np.uint64)
+        p.seed_dicts = sd.ctypes.data
+        seeds = np.array(self._seeds, dtype=np.uint64)
+        noise = self.mdps[0].noise_cdf()
+        noise = None if noise is None else np.ascontiguousarray(noise, dtype=np.float64)
+        rc = self._lib.mdpp_generate_discrete(self._h, capi.nptr(seeds), C.byref(p), capi.nptr(g["is_term"]),
+                                              capi.nptr(g["init_cdf"]), capi.nptr(noise))
+        capi.check(self._lib, self._h, rc, "mdpp_generate_discrete")
+        self._seed_dicts = sd
+
+    def _upload_discrete_host(self):
         ms = self.mdps
         unit = bool(self._cfg.unit_rewards)
         P = _stack([m.P for m in ms], np.uint8 if ms[0].S <= 255 else np.uint16)      # (S > 255: 16-bit entries, mdpp_discrete_wide.hip)
@@ -217,15 +300,6 @@ class RLToyVectorEnv:
             rc = self._lib.mdpp_upload_discrete_irrelevant(self._h, capi.nptr(P1), capi.nptr(cdf1),
                                                            capi.nptr(noise1))
             capi.check(self._lib, self._h, rc, "mdpp_upload_discrete_irrelevant")
-        if self._image is not None:
-            t = self._image
-            tpl = np.ascontiguousarray(t["tpl"], dtype=np.uint8)
-            cx = np.ascontiguousarray(t["cls_x"], dtype=np.int16)
-            cy = np.ascontiguousarray(t["cls_y"], dtype=np.int16)
-            rc = self._lib.mdpp_upload_image_templates(self._h, capi.nptr(tpl), tpl.shape[1],
-                                                       t["n_cls_x"], t["n_cls_y"], capi.nptr(cx),
-                                                       capi.nptr(cy))
-            capi.check(self._lib, self._h, rc, "mdpp_upload_image_templates")
 
     def _init_grid(self, cfg):
         """Grid envs (rl_toy_env.py:539-541, :780-811): int64 cell vectors, one-hot +-1 actions."""
@@ -362,6 +436,21 @@ class RLToyVectorEnv:
         (gymnasium Env.reset -> seeding.np_random; rl_toy_env.py:2225).  Space streams are only
         (re)built at construction."""
         N, off = self.num_envs, self.env_id_offset
+        if self._gen is not None:
+            # device-generated handle: the generator seeded every stream; a re-seed runs SeedSequence on the device
+            if initial:
+                for st in (capi.STREAM_ENV, capi.STREAM_SPACE) + ((capi.STREAM_IMAGE,) if self._image is not None else ()):
+                    self.seeded_streams[st] = self.get_rng_streams(st)
+                return
+            if env_seed + off + N - 1 < 2 ** 64:
+                seeds = np.uint64(env_seed + off) + np.arange(N, dtype=np.uint64)
+                rc = self._lib.mdpp_seed_streams_seedseq(self._h, capi.STREAM_ENV, capi.nptr(seeds))
+                capi.check(self._lib, self._h, rc, "mdpp_seed_streams_seedseq")
+                self.seeded_streams[capi.STREAM_ENV] = self.get_rng_streams(capi.STREAM_ENV)
+            else:
+                self._put_stream(capi.STREAM_ENV, np.stack([mdp_mod.pcg64_words(mdp_mod.new_generator(env_seed + off + i))
+                                                            for i in range(N)]))
+            return
         if self._per_env:
             env_words = np.stack([mdp_mod.pcg64_words(mdp_mod.new_generator(
                 m.seed_dict["env"] if env_seed is None or initial else env_seed + off + i))
@@ -507,7 +596,10 @@ class RLToyVectorEnv:
         try:
             if by_offset:
                 capi.check(self._lib, h, self._lib.mdpp_graph_capture(h, 1), "mdpp_graph_capture")
-            with torch.cuda.graph(g, stream=side):
+            # (thread-local capture: the captured launches make no call that is unsafe during a capture, and in the default
+            #  global mode a HIP call from ANY other thread of the process -- a process group's watchdog querying its events,
+            #  RCCL's own threads -- invalidates the capture; the failed graph's destructor then aborts the process)
+            with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
                 launches(side.cuda_stream)
         finally:
             if by_offset:
@@ -748,6 +840,40 @@ class RLToyVectorEnv:
             return d
         out = rows(cur, np.asarray(self._get_augmented_state()["total_transitions_episode"], dtype=np.int64))
         out["last_episode"] = rows(last, last[nk].astype(np.int64))
+        return out
+
+    def get_mdp_tables(self):
+        """The discrete tables the kernels read, as host numpy arrays: P uint8 [T, S, A] (uint16 beyond 255 states), the
+        reward table -- rbits uint8 [T, ceil(S^L / 8)] with unit rewards, else rtable float64 [T, S^L] (S * A with a
+        reward matrix) -- is_term uint8 [T, S] and init_cdf float64 [T, S]; T = num_envs for per-env MDPs, else 1."""
+        if self.kind != "discrete":
+            raise capi.MdppError("get_mdp_tables: discrete envs only")
+        c = self._cfg
+        T, S, A = c.num_tables, c.S, c.A
+        nkeys = S * A if c.reward_kind == capi.REWARD_STATE_ACTION else S ** c.L
+        P = np.zeros((T, S, A), np.uint8 if S <= 255 else np.uint16)
+        is_term = np.zeros((T, S), np.uint8)
+        init_cdf = np.zeros((T, S), np.float64)
+        out = {"P": P, "is_term": is_term, "init_cdf": init_cdf}
+        if c.unit_rewards:
+            out["rbits"] = rbits = np.zeros((T, (nkeys + 7) // 8), np.uint8)
+            rtable = None
+        else:
+            out["rtable"] = rtable = np.zeros((T, nkeys), np.float64)
+            rbits = None
+        rc = self._lib.mdpp_get_discrete_tables(self._h, capi.nptr(P), capi.nptr(rtable), capi.nptr(rbits),
+                                                capi.nptr(is_term), capi.nptr(init_cdf))
+        capi.check(self._lib, self._h, rc, "mdpp_get_discrete_tables")
+        return out
+
+    def get_seed_dicts(self):
+        """uint64 [N, 8]: per env the seed dict of its MDP -- "env", then mdp._SEED_KEYS in order (rl_toy_env.py:285-333)."""
+        if self._gen is not None:
+            return self._seed_dicts.copy()
+        out = np.zeros((self.num_envs, 8), np.uint64)
+        for i in range(self.num_envs):
+            m = self.mdps[i if self._per_env else 0]
+            out[i] = [m.seed_dict.get("env") or 0] + [m.seed_dict.get(k) or 0 for k in mdp_mod._SEED_KEYS]
         return out
 
     def get_rng_streams(self, stream=capi.STREAM_ENV):
