@@ -43,11 +43,33 @@ def _hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def _stale(target, deps):
+def _stale(target, deps, cmd=None):
+    """True if target is missing, older than a dep, or (cmd given) was not built by exactly cmd: the command is kept
+    beside the object in target + ".cmd", so a change of flags (EXTRA_FLAGS: SPILL_SAFE is a correctness flag)
+    rebuilds the object without --force."""
     if not os.path.exists(target):
         return True
     t = os.path.getmtime(target)
-    return any(os.path.getmtime(d) > t for d in deps)
+    if any(os.path.getmtime(d) > t for d in deps):
+        return True
+    return cmd is not None and _stamp(target) != _cmd_text(cmd)
+
+
+def _cmd_text(cmd):
+    return " ".join(cmd) + "\n"
+
+
+def _stamp(target):
+    try:
+        with open(target + ".cmd") as f:
+            return f.read()
+    except OSError:
+        return None
+
+
+def _write_stamp(target, cmd):
+    with open(target + ".cmd", "w") as f:
+        f.write(_cmd_text(cmd))
 
 
 def build(force=False, verbose=False):
@@ -60,15 +82,20 @@ def build(force=False, verbose=False):
         obj = os.path.join(CSRC, s.replace(".hip", ".o"))
         objs.append(obj)
         extra = [os.path.join(CSRC, d) for d in INCLUDED_SOURCES.get(s, [])]
-        if force or _stale(obj, [src] + extra + hdrs):
-            jobs.append([hipcc] + FLAGS + EXTRA_FLAGS.get(s, []) + ["-c", src, "-o", obj])
+        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(s, []) + ["-c", src, "-o", obj]
+        if force or _stale(obj, [src] + extra + hdrs, cmd):
+            jobs.append(cmd)
 
     def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
+        out = cmd[cmd.index("-o") + 1]
+        if os.path.exists(out + ".cmd"):
+            os.remove(out + ".cmd")    # a failed or interrupted compile leaves no stamp behind
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + r.stdout)
+        _write_stamp(out, cmd)
         return r.stdout
 
     if jobs:
@@ -79,8 +106,9 @@ def build(force=False, verbose=False):
             for out in ex.map(run, jobs):
                 if verbose and out.strip():
                     print(out)
-    if jobs or force or _stale(OUT, objs):
-        run([hipcc, "--offload-arch=gfx950", "-shared", "-o", OUT] + objs)
+    link = [hipcc, "--offload-arch=gfx950", "-shared", "-o", OUT] + objs
+    if jobs or force or _stale(OUT, objs, link):
+        run(link)
     return OUT
 
 

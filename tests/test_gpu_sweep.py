@@ -251,8 +251,10 @@ def _same_calls_as_general_kernels(env, cfg, kw, seed, scale=1.0):
     twin.close()
 
 
-def _check_vs_oracle(env, k, cfg, mode, kw, seed, scale=1.0, stride=37):
-    """A fused rollout of 72 steps, three single steps, a rollout of 40 on `env`; every `stride`-th env stepped through its own oracle."""
+def _check_vs_oracle(env, k, cfg, mode, kw, seed, scale=1.0, stride=37, calls=(72, 1, 1, 1, 40), flags=None):
+    """A fused rollout of 72 steps, three single steps, a rollout of 40 on `env` (or the rollout lengths `calls`: 1 = a single
+    step); every `stride`-th env stepped through its own oracle (stride 1: every env).  `flags`, a list, receives (K, the
+    [K, N] terminated | truncated flags of every env) per call."""
     from mdp_playground_amd import _capi as capi
     from test_gpu_parity import _oracle_for
     N = env.num_envs
@@ -265,7 +267,7 @@ def _check_vs_oracle(env, k, cfg, mode, kw, seed, scale=1.0, stride=37):
     horizon = kw.get("max_episode_steps", 0)
     disc = env.kind == "discrete"
     init = env._obs.cpu().numpy().copy()
-    sample = list(range(3, N, stride))
+    sample = list(range(3 if stride > 1 else 0, N, stride))
     oracles = []
     for i in sample:
         o = _oracle_for(env, i)
@@ -278,7 +280,7 @@ def _check_vs_oracle(env, k, cfg, mode, kw, seed, scale=1.0, stride=37):
         assert np.array_equal(np.asarray(o.reset()), init[i]), (k, i)
         oracles.append([o, 0, False])
     g = np.random.default_rng(seed)
-    for K in (72, 1, 1, 1, 40):
+    for K in calls:
         acts = _rand_actions(env, K, g)
         if scale != 1.0:
             acts = (acts * np.float32(scale)).astype(np.float32)
@@ -288,6 +290,8 @@ def _check_vs_oracle(env, k, cfg, mode, kw, seed, scale=1.0, stride=37):
             obs, rew, term, trunc = (x[None].cpu().numpy() for x in (o1, r1, t1, tr1))
         else:
             obs, rew, term, trunc = (x.cpu().numpy() for x in env.rollout(at))
+        if flags is not None:
+            flags.append((K, term.astype(bool) | trunc.astype(bool)))
         ends = None if philox else (env.get_rng_streams(capi.STREAM_ENV), env.get_rng_streams(capi.STREAM_SPACE))
         for (o, i), rec in zip(zip([x[0] for x in oracles], sample), oracles):
             for t in range(K):
@@ -1118,8 +1122,8 @@ _EVERY_LANE = {
     "quiet_philox_noise": (dict(state_space_type="discrete", action_space_type="discrete", state_space_size=20, action_space_size=20, delay=3, sequence_length=2,
                                 transition_noise=0.1, reward_noise=0.2, seed=8), dict(autoreset="same_step", rng="philox", philox_seed=9), "k_discrete_rollout_quiet<"),
     "cfast_philox_noise": (dict(state_space_type="continuous", action_space_type="continuous", state_space_dim=12, action_space_dim=12, relevant_indices=[0, 1, 2, 3],
-                                irrelevant_features=True, target_point=[0, 0, 0, 0], target_radius=0.05, state_space_max=10, action_space_max=1,
-                                transition_dynamics_order=2, inertia=1, time_unit=0.1, make_denser=True, reward_function="move_to_a_point",
+                                irrelevant_features=True, target_point=[0, 0, 0, 0], target_radius=1.0, state_space_max=1, action_space_max=1,
+                                transition_dynamics_order=2, inertia=1, time_unit=1.0, make_denser=True, reward_function="move_to_a_point",
                                 transition_noise=0.05, reward_noise=0.05, seed=0), dict(autoreset="same_step", rng="philox", philox_seed=9, max_episode_steps=11), "k_continuous_rollout_fast<"),
     "cfast_d2_sigma0": (dict(state_space_type="continuous", action_space_type="continuous", state_space_dim=2, action_space_dim=2, target_point=[0, 0], target_radius=0.5,
                              state_space_max=10, action_space_max=1, transition_dynamics_order=1, inertia=1, time_unit=1.0, make_denser=True,
@@ -1131,7 +1135,7 @@ _EVERY_LANE = {
                                 target_point=[0, 0, 0, 0], target_radius=1.0, state_space_max=4, action_space_max=1, transition_dynamics_order=3, inertia=1, time_unit=0.5,
                                 make_denser=True, reward_function="move_to_a_point", transition_noise=0.02, seed=2), dict(autoreset="same_step"), "k_continuous_step<DMAX=12,OMAX=4"),   # (general kernel, 36 B of scratch)
     "cfast_numpy_noise_limit": (dict(state_space_type="continuous", action_space_type="continuous", state_space_dim=12, action_space_dim=12, relevant_indices=[0, 1, 2, 3],
-                                     irrelevant_features=True, target_point=[0, 0, 0, 0], target_radius=0.05, state_space_max=10, action_space_max=1,
+                                     irrelevant_features=True, target_point=[0, 0, 0, 0], target_radius=1.0, state_space_max=1, action_space_max=1,
                                      transition_dynamics_order=1, inertia=1, time_unit=1.0, make_denser=True, reward_function="move_to_a_point",
                                      transition_noise=0.05, seed=0), dict(autoreset="same_step", max_episode_steps=9), "k_continuous_rollout_fast<"),
 }
@@ -1143,14 +1147,20 @@ def test_rollout_kernels_with_register_spills_every_lane_vs_oracle(name):
     """docs/round6.md section 10: the compiler parks spilled SGPRs in VGPR lanes, and a kernel that also spills VGPRs inside divergent control
     flow can lose them -- in particular lanes.  The hand-tuned rollout kernels keep that spilling (it is what makes cfg2 110 us instead of
     157); those of their instantiations that HAVE VGPR scratch are compared here with the oracle on EVERY lane: 512 envs = 8 full
-    waves, rollouts with in-step resets (a step limit where episodes would otherwise be long), single steps, both stream kinds."""
+    waves, rollouts with in-step resets (a step limit where episodes would otherwise be long), single steps, both stream kinds.
+    The k_continuous_rollout_fast cases also prove that resets diverge inside waves (a target radius large against the state
+    space: episodes end at per-env times), the hazard's trigger; every such kernel has its own case in test_gpu_spill_lanes.py."""
     import warnings
+    import spill_exposed as sx
     cfg, kw, kernel = _EVERY_LANE[name]
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         env = _venv(num_envs=512, **kw, **cfg)
     assert env.rollout_kernel_name(72).startswith(kernel), env.rollout_kernel_name(72)
     mode = "next_step" if kw["autoreset"] == "next_step" else "timelimit" if kw.get("max_episode_steps") else "same_step"
-    _check_vs_oracle(env, name, cfg, mode, kw, 321, stride=1)
+    ends = []
+    _check_vs_oracle(env, name, cfg, mode, kw, 321, stride=1, flags=ends)
     assert not (env.status() & 0x80000000).any()
     env.close()
+    if name in ("cfast_philox_noise", "cfast_numpy_noise_limit"):
+        sx.assert_resets_diverge(ends, single=False)
