@@ -695,9 +695,6 @@ struct DevTemp {
     }
 };
 
-// generator scratch per launch (sequence bitsets, picks, value permutations): envs go in chunks below this
-static const size_t kGenScratchCap = (size_t)256 << 20;
-
 extern "C" int mdpp_generate_discrete(mdpp_env *h, const uint64_t *seeds, const mdpp_gen_params *p,
                                       const uint8_t *is_term, const double *init_cdf, const double *noise_cdf) {
     if (!h) return MDPP_EINVAL;
@@ -708,34 +705,11 @@ extern "C" int mdpp_generate_discrete(mdpp_env *h, const uint64_t *seeds, const 
     if (c.num_tables != c.num_envs || c.irrelevant || c.S > 255 || c.reward_kind != MDPP_REWARD_SEQUENCES)
         return fail(h, MDPP_EUNSUPPORTED, "generate_discrete: needs one table per env, no irrelevant sub-space, S <= 255 and "
                                           "rewardable sequences");
-    // the parameters must describe this handle's shape: every key and P entry the kernel writes is then in range
-    const int d = p->diameter, n_term = p->n_term, L = c.L;
-    const uint32_t nn = (uint32_t)(c.A - n_term);
-    bool ok = d >= 1 && c.S == c.A * d && n_term >= 0 && n_term < c.A && p->n_sel >= 1 && p->n_sel <= p->total &&
-              (p->image != 0) == (c.image != 0);
-    if (ok && p->repeats) {
-        uint64_t t = 1;
-        for (int i = 0; i < L; i++) t *= nn;
-        ok = p->total == t;
-    } else if (ok) {
-        uint64_t t = 1;
-        ok = p->n_radices == L;
-        for (int i = 0; ok && i < L; i++) {
-            ok = p->radices[i] == nn - (uint32_t)(i / d) && p->radices[i] >= 1;
-            t *= p->radices[i];
-        }
-        ok = ok && p->total == t;
-    }
-    const uint64_t n_seqs = (uint64_t)d * p->n_sel;
-    if (ok && p->rews) ok = p->n_rews >= n_seqs && p->n_rews > 1;
-    if (!ok) return fail(h, MDPP_EINVAL, "generate_discrete: parameters do not match the handle");
     GenArgs a;
-    memset(&a, 0, sizeof(a));
-    a.set_words = (p->total + 63u) / 64u;
-    a.perm_off = a.set_words + (uint64_t)(p->repeats ? 1 : d) * p->n_sel;
-    a.scratch_words = a.perm_off + (p->rews ? ((uint64_t)p->n_rews + 1u) / 2u : 0u);
+    const char *err = nullptr;
+    const int prc = gen_args_init(p, c.S, c.A, c.L, c.image != 0, c.unit_rewards != 0, h->nkeys, h->rbits_stride, a, &err);
+    if (prc != MDPP_OK) return fail(h, prc, err);
     const size_t per_env = (size_t)a.scratch_words * 8u;
-    if (per_env > kGenScratchCap) return fail(h, MDPP_EUNSUPPORTED, "generate_discrete: scratch per env above the cap");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t N = (size_t)c.num_envs, S = (size_t)c.S, A = (size_t)c.A;
     const int chunk = (int)std::min(N, std::max<size_t>(1, kGenScratchCap / std::max<size_t>(per_env, 8)));
@@ -753,12 +727,7 @@ extern "C" int mdpp_generate_discrete(mdpp_env *h, const uint64_t *seeds, const 
     HIPCHK(h, hipMemset(h->d_P, 0, N * S * A));
     if (c.unit_rewards) HIPCHK(h, hipMemset(h->d_rbits, 0, N * h->rbits_stride));
     else HIPCHK(h, hipMemset(h->d_rtable, 0, N * (size_t)h->nkeys * sizeof(double)));
-    a.S = c.S; a.A = c.A; a.L = L; a.diameter = d; a.n_term = n_term; a.maxc = p->maximally_connected ? 1 : 0;
-    a.repeats = p->repeats ? 1 : 0; a.unit = c.unit_rewards ? 1 : 0;
-    a.total = p->total; a.n_sel = p->n_sel;
-    for (int i = 0; i < 16; i++) a.radix[i] = p->repeats ? 0u : p->radices[i];
-    a.rews = d_rews; a.n_rews = p->rews ? p->n_rews : 0u;
-    a.nkeys = h->nkeys; a.rbits_stride = h->rbits_stride;
+    a.rews = d_rews;
     a.seeds = d_seeds; a.P = (uint8_t *)h->d_P; a.rbits = (uint8_t *)h->d_rbits; a.rtable = (double *)h->d_rtable;
     a.sd = d_sd;
     if (c.rng_mode == MDPP_RNG_NUMPY_PCG64) {          // (Philox handles keep no stream state)

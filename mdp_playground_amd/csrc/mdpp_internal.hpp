@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <string>
 
@@ -335,6 +336,52 @@ struct GenArgs {
     uint64_t *scratch;          // [count][scratch_words]: bitset of `total` bits, picks, permutation of the values
     uint64_t scratch_words, set_words, perm_off;
 };
+
+// generator scratch per launch (sequence bitsets, picks, value permutations): envs go in chunks below this
+constexpr size_t kGenScratchCap = (size_t)256 << 20;
+
+// The checks of mdpp_gen_params against a handle's shape (S, A, L, image, unit rewards, nkeys, rbits stride) and the
+// scalar fields of GenArgs they give; every pointer is left null for the caller.  MDPP_OK, or an error code with *err
+// set.  Shared by mdpp_generate_discrete and the tests' host build of the generator, so both run one set of rules.
+inline int gen_args_init(const mdpp_gen_params *p, int S, int A, int L, bool image, bool unit, uint32_t nkeys,
+                         uint32_t rbits_stride, GenArgs &a, const char **err) {
+    // the parameters must describe this handle's shape: every key and P entry the kernel writes is then in range
+    const int d = p->diameter, n_term = p->n_term;
+    const uint32_t nn = (uint32_t)(A - n_term);
+    bool ok = d >= 1 && S == A * d && n_term >= 0 && n_term < A && p->n_sel >= 1 && p->n_sel <= p->total &&
+              (p->image != 0) == image;
+    if (ok && p->repeats) {
+        uint64_t t = 1;
+        for (int i = 0; i < L; i++) t *= nn;
+        ok = p->total == t;
+    } else if (ok) {
+        uint64_t t = 1;
+        ok = p->n_radices == L;
+        for (int i = 0; ok && i < L; i++) {
+            ok = p->radices[i] == nn - (uint32_t)(i / d) && p->radices[i] >= 1;
+            t *= p->radices[i];
+        }
+        ok = ok && p->total == t;
+    }
+    const uint64_t n_seqs = (uint64_t)d * p->n_sel;
+    if (ok && p->rews) ok = p->n_rews >= n_seqs && p->n_rews > 1;
+    if (!ok) { *err = "generate_discrete: parameters do not match the handle"; return MDPP_EINVAL; }
+    memset(&a, 0, sizeof(a));
+    a.set_words = (p->total + 63u) / 64u;
+    a.perm_off = a.set_words + (uint64_t)(p->repeats ? 1 : d) * p->n_sel;
+    a.scratch_words = a.perm_off + (p->rews ? ((uint64_t)p->n_rews + 1u) / 2u : 0u);
+    if ((size_t)a.scratch_words * 8u > kGenScratchCap) {
+        *err = "generate_discrete: scratch per env above the cap";
+        return MDPP_EUNSUPPORTED;
+    }
+    a.S = S; a.A = A; a.L = L; a.diameter = d; a.n_term = n_term; a.maxc = p->maximally_connected ? 1 : 0;
+    a.repeats = p->repeats ? 1 : 0; a.unit = unit ? 1 : 0;
+    a.total = p->total; a.n_sel = p->n_sel;
+    for (int i = 0; i < 16; i++) a.radix[i] = p->repeats ? 0u : p->radices[i];
+    a.n_rews = p->rews ? p->n_rews : 0u;
+    a.nkeys = nkeys; a.rbits_stride = rbits_stride;
+    return MDPP_OK;
+}
 
 // implemented in the kernel translation units
 // name_out != nullptr: a dry run -- the launcher writes the name of the kernel it would launch (at most

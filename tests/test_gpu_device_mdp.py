@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import gen_configs as gc
 import golden_util as gu
 from mdp_playground_amd import _capi as capi
 from mdp_playground_amd import mdp
@@ -68,11 +69,15 @@ def _check_env(env, cfg, seeds, idx):
     for i in idx:
         m = _build(cfg, seeds[i])
         assert np.array_equal(tabs["P"][i], m.P), i
-        t = m.reward_table()
-        if "rbits" in tabs:
-            assert np.array_equal(tabs["rbits"][i], np.packbits((t != 0).astype(np.uint8), bitorder="little")), i
+        if m.S ** m.sequence_length > gc.DENSE_KEYS:      # key by key: no dense host table of every env
+            gc.assert_reward_row(m, rbits=tabs["rbits"][i] if "rbits" in tabs else None,
+                                 rtable=tabs["rtable"][i] if "rtable" in tabs else None, tag=i)
         else:
-            assert np.array_equal(tabs["rtable"][i], t), i
+            t = m.reward_table()
+            if "rbits" in tabs:
+                assert np.array_equal(tabs["rbits"][i], np.packbits((t != 0).astype(np.uint8), bitorder="little")), i
+            else:
+                assert np.array_equal(tabs["rtable"][i], t), i
         assert np.array_equal(tabs["is_term"][i], m.is_terminal_table()), i
         assert np.array_equal(tabs["init_cdf"][i], m.init_cdf()), i
         assert sd[i].tolist() == [seeds[i]] + [m.seed_dict[k] for k in mdp._SEED_KEYS], i
@@ -147,7 +152,11 @@ def _host_twin(cfg, seeds, **kw):
 @pytest.mark.parametrize("autoreset", ["same_step", "next_step", "disabled"])
 @pytest.mark.parametrize("name", ["cfg2", "noise", "s50", "rdist_l1", "diam2"])
 def test_device_built_handle_behaves_like_host_built(name, autoreset, rng):
-    cfg = CONFIGS[name]
+    _compare_with_host_twin(CONFIGS[name], autoreset, rng)
+
+
+def _compare_with_host_twin(cfg, autoreset, rng):
+    """A device-built handle and a host-built one of the same seeds select the same kernels and behave the same."""
     N = 256
     seeds = _seeds(N, salt=7)
     kw = dict(autoreset=autoreset, rng=rng, max_episode_steps=30)
@@ -188,6 +197,96 @@ def test_device_built_handle_behaves_like_host_built(name, autoreset, rng):
     assert int(dev.status().sum()) == 0 and int(host.status().sum()) == 0
     dev.close()
     host.close()
+
+
+# L = 5 and the long kernel (L 8 ... 15), several independent sets without maximal connection, the largest state
+# space with transition noise, no terminal states
+TWINS = {
+    "l5": dict(BASE, action_space_size=8, sequence_length=5, reward_density=0.01),
+    "l8_rep_rdist": dict(BASE, action_space_size=4, sequence_length=8, repeats_in_sequences=True, reward_density=0.01,
+                         terminal_state_density=0, reward_dist=[0.25, 1.0]),
+    "l12_rep": dict(BASE, action_space_size=3, sequence_length=12, repeats_in_sequences=True, reward_density=0.001,
+                    terminal_state_density=0),
+    "l15_rep": dict(BASE, action_space_size=2, sequence_length=15, repeats_in_sequences=True, reward_density=0.01),
+    "diam3_not_maxc": dict(BASE, action_space_size=5, diameter=3, maximally_connected=False, sequence_length=3,
+                           reward_dist=[0.2, 1.0]),
+    "s255_noise": dict(BASE, action_space_size=255, sequence_length=1, reward_density=0.1, transition_noise=0.1),
+    "no_term": dict(BASE, action_space_size=8, sequence_length=3, terminal_state_density=0, reward_density=0.1),
+}
+
+
+@pytest.mark.parametrize("rng", ["numpy", "philox"])
+@pytest.mark.parametrize("name", sorted(TWINS))
+def test_device_built_handle_behaves_like_host_built_beyond_the_short_kernels(name, rng):
+    cfg = TWINS[name]
+    assert mdp.device_coverage(cfg, [0])[0]
+    _compare_with_host_twin(cfg, "same_step", rng)
+
+
+def _device_family():
+    """The Floyd edges and every fifth config of the family, each with 64 ... 512 seeds: cheap host builds get more,
+    and no config's tables take much more than 1 GiB."""
+    fam = gc.family()
+    out = []
+    for i, (name, cfg) in enumerate(fam[:len(gc.FLOYD_EDGES)] + fam[len(gc.FLOYD_EDGES)::5]):
+        p = mdp.device_gen_params(cfg)
+        r = np.random.default_rng(i)
+        cheap = p["diameter"] * p["n_sel"] * p["L"] + p["S"] * p["A"] <= 4000
+        N = int(np.exp(r.uniform(np.log(64), np.log(513)))) if cheap else 64
+        keys = p["S"] ** p["L"]
+        per_env = (keys + 7) // 8 if p["unit_rewards"] else 8 * keys
+        out.append((name, cfg, max(64, min(N, (1 << 30) // per_env))))
+    return out
+
+
+DEVICE_FAMILY = _device_family()
+
+
+@pytest.mark.parametrize("name, cfg, N", DEVICE_FAMILY, ids=[f[0] for f in DEVICE_FAMILY])
+def test_device_tables_equal_host_builder_on_the_config_family(name, cfg, N):
+    seeds = _seeds(N, salt=sum(map(ord, name)))
+    env = _venv(seeds=seeds, autoreset="same_step", **cfg)
+    assert env.tables_built_on == "device"
+    _check_env(env, cfg, seeds, range(N))
+    assert int(env.status().sum()) == 0
+    env.close()
+
+
+def _launches(cfg, N):
+    per_env = 8 * mdp.device_gen_params(cfg)["scratch_words"]
+    chunk = min(N, max(1, mdp.DEVICE_SCRATCH_CAP // per_env))
+    return chunk, -(-N // chunk)
+
+
+def test_device_generation_in_several_launches():
+    # 2 028 120 B of scratch per env: 132 envs a launch, 400 envs in launches of 132 + 132 + 132 + 4
+    cfg = dict(BASE, action_space_size=64, sequence_length=4, terminal_state_density=0, reward_density=0.001)
+    N = 400
+    chunk, launches = _launches(cfg, N)
+    assert launches >= 3 and N % chunk != 0, (chunk, launches)
+    seeds = _seeds(N, salt=11)
+    env = _venv(seeds=seeds, autoreset="same_step", **cfg)
+    assert env.tables_built_on == "device"
+    edges = {k for c in range(launches) for k in (c * chunk, min(N, (c + 1) * chunk) - 1)}
+    others = set(np.random.default_rng(2).choice(N, size=16, replace=False).tolist())
+    _check_env(env, cfg, seeds, sorted(edges | others))
+    assert int(env.status().sum()) == 0
+    env.close()
+
+
+def test_device_generation_one_env_per_launch():
+    # 194 MB of scratch per env (a bitset of 200 * 199 * 198 * 197 sequence numbers): every launch holds one env; the
+    # reward bits are 200 MB an env, compared key by key
+    cfg = dict(BASE, action_space_size=200, sequence_length=4, terminal_state_density=0, reward_density=1e-6)
+    N = 3
+    assert 8 * mdp.device_gen_params(cfg)["scratch_words"] > mdp.DEVICE_SCRATCH_CAP // 2
+    assert _launches(cfg, N) == (1, N)
+    seeds = [0, 2 ** 64 - 1, 5874934615388537134]
+    env = _venv(seeds=seeds, autoreset="same_step", **cfg)
+    assert env.tables_built_on == "device"
+    _check_env(env, cfg, seeds, range(N))
+    assert int(env.status().sum()) == 0
+    env.close()
 
 
 @pytest.mark.parametrize("name", ["cfg2", "s50"])

@@ -86,6 +86,18 @@ def test_uncovered_goldens_and_why():
     assert len(COVERED) >= 100
 
 
+FLOYD_TOTAL_10000 = dict(BASE, action_space_size=13, sequence_length=4, repeats_in_sequences=True)   # 10^4 numbers
+
+
+def _at_scratch_cap(extra):
+    """A = 200, L = 4 without repeats: a bitset of ceil(total / 64) words plus n_sel picks, n_sel chosen so the scratch
+    is DEVICE_SCRATCH_CAP bytes, plus `extra` picks."""
+    total = 200 * 199 * 198 * 197
+    n_sel = mdp.DEVICE_SCRATCH_CAP // 8 - -(-total // 64) + extra
+    return dict(BASE, action_space_size=200, sequence_length=4, terminal_state_density=0,
+                reward_density=(n_sel + 0.5) / total)
+
+
 @pytest.mark.parametrize("cfg, seeds, why", [
     (dict(BASE, action_space_size=8), [0, 2 ** 64 - 1], ""),
     (dict(BASE, action_space_size=8), [0, 2 ** 64], "a seed is not an int in [0, 2^64)"),
@@ -105,9 +117,28 @@ def test_uncovered_goldens_and_why():
     (dict(BASE, action_space_size=16, sequence_length=4, repeats_in_sequences=True), [0],
      "the sequence draw takes choice's tail-shuffle branch"),
     (dict(BASE, action_space_size=16, sequence_length=4, repeats_in_sequences=True, reward_density=0.01), [0], ""),
+    # the exact edges of Floyd's branch: a population of 10 000, and n_sel == total // 50 above it
+    (FLOYD_TOTAL_10000, [0], ""),
+    (dict(BASE, action_space_size=14, sequence_length=4, repeats_in_sequences=True, reward_density=0.02), [0], ""),
+    (dict(BASE, action_space_size=14, sequence_length=4, repeats_in_sequences=True, reward_density=0.0201), [0],
+     "the sequence draw takes choice's tail-shuffle branch"),
+    # generator scratch of exactly the cap, and one pick more
+    (_at_scratch_cap(0), [0], ""),
+    (_at_scratch_cap(1), [0], "generator scratch per env above the cap"),
 ])
 def test_coverage_rule(cfg, seeds, why):
     assert mdp.device_coverage(cfg, seeds) == (why == "", why)
+
+
+def test_coverage_rule_edges_are_exact():
+    p = mdp.device_gen_params(FLOYD_TOTAL_10000)
+    assert p["total"] == 10000 and p["n_sel"] > p["total"] // 50
+    for rd, n_sel in ((0.02, 292), (0.0201, 294)):
+        p = mdp.device_gen_params(dict(BASE, action_space_size=14, sequence_length=4, repeats_in_sequences=True,
+                                       reward_density=rd))
+        assert (p["total"], p["n_sel"], p["total"] // 50) == (14641, n_sel, 292)
+    assert 8 * mdp.device_gen_params(_at_scratch_cap(0))["scratch_words"] == mdp.DEVICE_SCRATCH_CAP
+    assert 8 * mdp.device_gen_params(_at_scratch_cap(1))["scratch_words"] == mdp.DEVICE_SCRATCH_CAP + 8
 
 
 def test_reward_values_and_unit_flag():
