@@ -1195,12 +1195,21 @@ static int step_common(mdpp_env *h, int K, const void *actions, void *obs, float
         return fail(h, MDPP_EUNSUPPORTED, "step: mdpp_set_state_continuous on a move_along_a_line handle must be followed by mdpp_set_line_history (the window of the line fit)");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
+    // the caller's buffers; a picture handle's `obs` / `final_obs` are its pictures
+    const DiscreteIO io{K, (const int32_t *)actions, obs, reward, term, trunc, final_obs, s, nullptr};
+    const size_t N = (size_t)h->cfg.num_envs;
+    // a batch of a picture pipeline is a piece of the caller's buffers (aw action elements, isz picture bytes per env-step); its
+    // state kernel takes that piece with the states going to a scratch set instead, on the batch's stream
+    auto states_of = [](auto p, auto *so, auto *sf, hipStream_t st) {
+        p.obs = so; p.final_obs = sf; p.s = st;
+        return p;
+    };
     if (h->cfg.kind == MDPP_KIND_DISCRETE) {
         if (h->cfg.image) {
             // batches of up to img_chunk env steps: one state kernel (states only, a few bytes per
             // env step), one transform-draw kernel, one render kernel over steps x envs images
             // (W*H bytes each)
-            const size_t N = (size_t)h->cfg.num_envs, aw = h->cfg.irrelevant ? 2 : 1;
+            const size_t aw = h->cfg.irrelevant ? 2 : 1;
             const size_t isz = aw * h->cfg.img_w * h->cfg.img_h;
             const size_t sset = (size_t)h->img_chunk * N * aw;            // int32 per scratch set
             auto scratch = [&](int buf, int32_t **so, int32_t **sf) {
@@ -1211,7 +1220,7 @@ static int step_common(mdpp_env *h, int K, const void *actions, void *obs, float
                 // one step: the state kernel, then ONE kernel that draws, builds the record and renders (k_image_step1)
                 int32_t *so, *sf;
                 scratch(0, &so, &sf);
-                int r = launch_discrete_step(h, 1, (const int32_t *)actions, so, reward, term, trunc, sf, s);
+                int r = launch_discrete_step(h, states_of(io, (void *)so, (void *)sf, s));
                 if (r) return r;
                 r = launch_image_step1(h, so, sf, term, trunc, (uint8_t *)obs, (uint8_t *)final_obs, s);
                 if (r != 0) return r < 0 ? r : MDPP_OK;
@@ -1225,67 +1234,62 @@ static int step_common(mdpp_env *h, int K, const void *actions, void *obs, float
             return image_batches(
                 h, K, s,
                 [&](int k0, int kc, int buf, hipStream_t st) {
-                    const size_t off = (size_t)k0 * N;
+                    const DiscreteIO p = io.piece(k0, kc, N, aw, isz);
                     int32_t *so, *sf;
                     scratch(buf, &so, &sf);
-                    int r = launch_discrete_step(h, kc, (const int32_t *)actions + off * aw, so, reward + off, term + off,
-                                                 trunc + off, sf, st);
+                    int r = launch_discrete_step(h, states_of(p, (void *)so, (void *)sf, st));
                     if (r) return r;
-                    return launch_image_obs(h, kc, so, sf, term + off, trunc + off, nullptr, nullptr, nullptr, st, 1, buf);
+                    return launch_image_obs(h, kc, so, sf, p.term, p.trunc, nullptr, nullptr, nullptr, st, 1, buf);
                 },
                 [&](int k0, int kc, int buf, hipStream_t st, bool overlap) {
-                    const size_t off = (size_t)k0 * N;
+                    const DiscreteIO p = io.piece(k0, kc, N, aw, isz);
                     int32_t *so, *sf;
                     scratch(buf, &so, &sf);
                     // (phase 2 leaves render slots free for the next batch's state kernel: only when pipelined)
-                    return launch_image_obs(h, kc, so, sf, term + off, trunc + off, nullptr, (uint8_t *)obs + off * isz,
-                                            final_obs ? (uint8_t *)final_obs + off * isz : nullptr, st, overlap ? 2 : 6, buf);
+                    return launch_image_obs(h, kc, so, sf, p.term, p.trunc, nullptr, (uint8_t *)p.obs, (uint8_t *)p.final_obs, st,
+                                            overlap ? 2 : 6, buf);
                 });
         }
-        return launch_discrete_step(h, K, (const int32_t *)actions, obs, reward, term, trunc, final_obs, s);
+        return launch_discrete_step(h, io);
     }
-    if (h->cfg.kind == MDPP_KIND_GRID && !h->cfg.image)
-        return launch_grid_step(h, K, (const int32_t *)actions, obs, reward, term, trunc, final_obs, s);
+    if (h->cfg.kind == MDPP_KIND_GRID && !h->cfg.image) return launch_grid_step(h, io);
     if (h->cfg.kind == MDPP_KIND_GRID) {
-        const size_t N = (size_t)h->cfg.num_envs, G = (size_t)h->cfg.grid_dims;
+        const size_t G = (size_t)h->cfg.grid_dims;
         const size_t isz = (G / 2) * h->cfg.img_w * h->cfg.img_h * 3;
         const size_t sset = (size_t)h->img_chunk * N * G;                 // int32 per scratch set
         return image_batches(
             h, K, s,
             [&](int k0, int kc, int buf, hipStream_t st) {
-                const size_t off = (size_t)k0 * N;
-                return launch_grid_step(h, kc, (const int32_t *)actions + off * G, (int32_t *)h->d_img_state_out + buf * sset,
-                                        reward + off, term + off, trunc + off, (int32_t *)h->d_img_state_final + buf * sset, st);
+                return launch_grid_step(h, states_of(io.piece(k0, kc, N, G, isz), (void *)((int32_t *)h->d_img_state_out + buf * sset),
+                                                     (void *)((int32_t *)h->d_img_state_final + buf * sset), st));
             },
             [&](int k0, int kc, int buf, hipStream_t st, bool) {
-                const size_t off = (size_t)k0 * N;
+                const DiscreteIO p = io.piece(k0, kc, N, G, isz);
                 return launch_imagec_obs(h, kc, (int32_t *)h->d_img_state_out + buf * sset,
-                                         (int32_t *)h->d_img_state_final + buf * sset, term + off, trunc + off, nullptr,
-                                         (uint8_t *)obs + off * isz, final_obs ? (uint8_t *)final_obs + off * isz : nullptr, st);
+                                         (int32_t *)h->d_img_state_final + buf * sset, p.term, p.trunc, nullptr,
+                                         (uint8_t *)p.obs, (uint8_t *)p.final_obs, st);
             });
     }
+    const ContinuousIO cio{K, (const float *)actions, (float *)obs, reward, term, trunc, (float *)final_obs, s, nullptr};
     if (h->cfg.image) {
         // batches of up to img_chunk env steps: one state kernel, one render kernel over steps x envs
         // pictures (3 W H bytes per 2-D sub-space each)
-        const size_t N = (size_t)h->cfg.num_envs, D = (size_t)h->cfg.D;
+        const size_t D = (size_t)h->cfg.D;
         const size_t isz = (size_t)(D > 2 ? 2 : 1) * h->cfg.img_w * h->cfg.img_h * 3;
         const size_t sset = (size_t)h->img_chunk * N * D;                 // floats per scratch set
         return image_batches(
             h, K, s,
             [&](int k0, int kc, int buf, hipStream_t st) {
-                const size_t off = (size_t)k0 * N;
-                return launch_continuous_step(h, kc, (const float *)actions + off * D, (float *)h->d_img_state_out + buf * sset,
-                                              reward + off, term + off, trunc + off, (float *)h->d_img_state_final + buf * sset, st);
+                return launch_continuous_step(h, states_of(cio.piece(k0, kc, N, D, isz), (float *)h->d_img_state_out + buf * sset,
+                                                           (float *)h->d_img_state_final + buf * sset, st));
             },
             [&](int k0, int kc, int buf, hipStream_t st, bool) {
-                const size_t off = (size_t)k0 * N;
+                const ContinuousIO p = cio.piece(k0, kc, N, D, isz);
                 return launch_imagec_obs(h, kc, (float *)h->d_img_state_out + buf * sset, (float *)h->d_img_state_final + buf * sset,
-                                         term + off, trunc + off, nullptr, (uint8_t *)obs + off * isz,
-                                         final_obs ? (uint8_t *)final_obs + off * isz : nullptr, st);
+                                         p.term, p.trunc, nullptr, (uint8_t *)p.obs, (uint8_t *)p.final_obs, st);
             });
     }
-    return launch_continuous_step(h, K, (const float *)actions, (float *)obs, reward, term, trunc,
-                                  (float *)final_obs, s);
+    return launch_continuous_step(h, cio);
 }
 
 extern "C" int mdpp_step(mdpp_env *h, const void *actions, void *obs, float *reward, uint8_t *term,
@@ -1307,12 +1311,14 @@ extern "C" const char *mdpp_kernel_name(mdpp_env *h, int K) {
                  : h->cfg.kind == MDPP_KIND_GRID ? "k_imagec_obs<GRID=1>" : "k_imagec_obs<GRID=0>");
         return h->kname;
     }
-    if (h->cfg.kind == MDPP_KIND_DISCRETE)
-        (void)launch_discrete_step(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
-    else if (h->cfg.kind == MDPP_KIND_GRID)
-        (void)launch_grid_step(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
-    else
-        (void)launch_continuous_step(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
+    // (a dry run: the launcher writes the name and launches nothing)
+    DiscreteIO dry{};
+    dry.K = K; dry.name_out = h->kname;
+    ContinuousIO cdry{};
+    cdry.K = K; cdry.name_out = h->kname;
+    if (h->cfg.kind == MDPP_KIND_DISCRETE) (void)launch_discrete_step(h, dry);
+    else if (h->cfg.kind == MDPP_KIND_GRID) (void)launch_grid_step(h, dry);
+    else (void)launch_continuous_step(h, cdry);
     return h->kname;
 }
 

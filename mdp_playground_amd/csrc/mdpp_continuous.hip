@@ -864,41 +864,33 @@ __global__ __launch_bounds__(kBlock) void k_continuous_reset(ContinuousArgs a, u
 
 // ---- dispatch on (padded D, padded order) -------------------------------------------------
 template <int DMAX, int OMAX, int NL = 4>
-static void launch_step_t(const ContinuousArgs &a, int K, const float *actions, float *obs,
-                          float *reward, uint8_t *term, uint8_t *trunc, float *final_obs,
-                          hipStream_t s, char *name_out) {
+static void launch_step_t(const ContinuousArgs &a, const ContinuousIO &io) {
     const int grid = (a.N + kBlock - 1) / kBlock;
-    if (name_out) {
-        if (NL == 4) snprintf(name_out, kNameLen, "k_continuous_step<DMAX=%d,OMAX=%d,PHILOX=%d>", DMAX, OMAX, a.philox != 0);
-        else snprintf(name_out, kNameLen, "k_continuous_step<DMAX=%d,OMAX=%d,PHILOX=%d,NL=%d>", DMAX, OMAX, a.philox != 0, NL);
-        return;
-    }
-    // move_along_a_line with L <= 16 (rows of 4), rollouts: the L points of every lane mirrored in (dynamic) LDS for the launch
-    ContinuousArgs al = a;
-    al.line_lds = (NL == 4 && !a.line_ws && a.line_L > 0 && a.line_L <= 16 && K >= 4) ? 1 : 0;
-    size_t lds = al.line_lds ? (size_t)a.line_L * kBlock * sizeof(float4) : 0;
-    const void *kern = a.philox ? (const void *)k_continuous_step<DMAX, OMAX, true, NL> : (const void *)k_continuous_step<DMAX, OMAX, false, NL>;
-    if (!dynamic_lds_ok(kern, lds)) { al.line_lds = 0; lds = 0; }        // (no room: the points stay in HBM)
-    if (a.philox)
-        hipLaunchKernelGGL((k_continuous_step<DMAX, OMAX, true, NL>), dim3(grid), dim3(kBlock), lds, s, al,
-                           K, actions, obs, reward, term, trunc, final_obs);
-    else
-        hipLaunchKernelGGL((k_continuous_step<DMAX, OMAX, false, NL>), dim3(grid), dim3(kBlock), lds, s, al,
-                           K, actions, obs, reward, term, trunc, final_obs);
+    with_bools([&](auto PH) {
+        if (io.name_out) {
+            if (NL == 4) snprintf(io.name_out, kNameLen, "k_continuous_step<DMAX=%d,OMAX=%d,PHILOX=%d>", DMAX, OMAX, PH());
+            else snprintf(io.name_out, kNameLen, "k_continuous_step<DMAX=%d,OMAX=%d,PHILOX=%d,NL=%d>", DMAX, OMAX, PH(), NL);
+            return;
+        }
+        // move_along_a_line with L <= 16 (rows of 4), rollouts: the L points of every lane mirrored in (dynamic) LDS for the launch
+        ContinuousArgs al = a;
+        al.line_lds = (NL == 4 && !a.line_ws && a.line_L > 0 && a.line_L <= 16 && io.K >= 4) ? 1 : 0;
+        size_t lds = al.line_lds ? (size_t)a.line_L * kBlock * sizeof(float4) : 0;
+        if (!dynamic_lds_ok((const void *)k_continuous_step<DMAX, OMAX, PH(), NL>, lds)) { al.line_lds = 0; lds = 0; }        // (no room: the points stay in HBM)
+        launch_rollout(k_continuous_step<DMAX, OMAX, PH(), NL>, grid, kBlock, lds, al, io);
+    }, a.philox != 0);
 }
 #if MDPP_CONT_TU_LINE8
 // move_along_a_line with 5 to 8 relevant dimensions (state_space_dim <= 12): rows of 8, an 8 x 8 scatter matrix in registers
-bool launch_continuous_step_line8(const ContinuousArgs &a, int K, const float *actions, float *obs, float *reward,
-                                  uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out) {
+bool launch_continuous_step_line8(const ContinuousArgs &a, const ContinuousIO &io) {
     if (a.line_NL != 8 || a.D > 12 || a.order > 4) return false;
-    if (a.order <= 1) launch_step_t<12, 1, 8>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    else if (a.order <= 2) launch_step_t<12, 2, 8>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    else launch_step_t<12, 4, 8>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
+    if (a.order <= 1) launch_step_t<12, 1, 8>(a, io);
+    else if (a.order <= 2) launch_step_t<12, 2, 8>(a, io);
+    else launch_step_t<12, 4, 8>(a, io);
     return true;
 }
 #else
-bool launch_continuous_step_line8(const ContinuousArgs &a, int K, const float *actions, float *obs, float *reward,
-                                  uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out);
+bool launch_continuous_step_line8(const ContinuousArgs &a, const ContinuousIO &io);
 template <int DMAX, int OMAX>
 static void launch_reset_t(const ContinuousArgs &a, uint64_t reset_tick, const uint8_t *mask,
                            float *obs, hipStream_t s) {
@@ -926,70 +918,39 @@ static void launch_reset_t(const ContinuousArgs &a, uint64_t reset_tick, const u
         else { return MDPP_EUNSUPPORTED; }                                          \
     } while (0)
 
-int launch_continuous_step(mdpp_env *h, int K, const float *actions, float *obs, float *reward,
-                           uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out) {
+int launch_continuous_step(mdpp_env *h, const ContinuousIO &io) {
+    const int K = io.K;
     ContinuousArgs a = h->cargs;
-    a.opts = h->opts;
-    a.ptick = h->tick;
-    a.dtick = h->graph_capture ? (const uint64_t *)h->d_tick_off : nullptr;     // (launches being captured into a HIP graph)
-    a.tick = a.delay > 0 ? (uint32_t)(h->tick % (uint64_t)a.delay) : 0u;
-    if (K == 1 && launch_continuous_step1(a, actions, obs, reward, term, trunc, final_obs, s, name_out)) {
-        // mdpp_step on the fast shape: the one-step form of the rollout kernel (mdpp_continuous_step1.hip)
-        if (name_out) return MDPP_OK;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("k_continuous_step1 launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-        h->tick += 1;
-        return MDPP_OK;
-    }
+    stamp_step(a, h);
+    // mdpp_step on the fast shape: the one-step form of the rollout kernel (mdpp_continuous_step1.hip)
+    if (K == 1 && launch_continuous_step1(a, io)) return io.name_out ? MDPP_OK : step_done(h, 1, "k_continuous_step1");
     if (a.fast_ok) {
         // common shape: dedicated rollout kernel (mdpp_continuous_fast.hip); its buffer descriptors
         // address < 4 GiB per array, so long rollouts go out as several launches
         const long long kmax = ((1LL << 32) - 1) / ((long long)a.N * a.D * 4);
-        bool served = kmax >= 1;
-        for (int k0 = 0; served && k0 < K;) {
-            const int kc = (int)((K - k0) < kmax ? (K - k0) : kmax);
-            const size_t off = (size_t)k0 * a.N;
-            a.ptick = h->tick + (uint64_t)k0;
-            a.tick = a.delay > 0 ? (uint32_t)(a.ptick % (uint64_t)a.delay) : 0u;   // head of the delay ring for this piece
-            served = launch_continuous_fast(a, kc, actions + off * a.D, obs + off * a.D, reward + off,
-                                            term + off, trunc + off,
-                                            final_obs ? final_obs + off * a.D : nullptr, s, name_out);
-            if (served && name_out) return MDPP_OK;      // (the first piece names the launch)
-            if (!served && k0 > 0) { h->err = "k_continuous_rollout_fast: inconsistent dispatch"; return MDPP_EHIP; }
-            k0 += kc;
-        }
-        if (served) {
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { h->err = std::string("k_continuous_rollout_fast launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-            h->tick += (uint64_t)K;
-            return MDPP_OK;
-        }
-        a.ptick = h->tick;
-        a.tick = a.delay > 0 ? (uint32_t)(h->tick % (uint64_t)a.delay) : 0u;
+        bool inconsistent = false;
+        const bool served = kmax >= 1 && for_each_piece(a, h, io, kmax, [&](const ContinuousIO &p, int k0) {
+            const bool ok = launch_continuous_fast(a, p);
+            if (!ok && k0 > 0) inconsistent = true;
+            return ok;
+        });
+        if (inconsistent) { h->err = "k_continuous_rollout_fast: inconsistent dispatch"; return MDPP_EHIP; }
+        if (served) return io.name_out ? MDPP_OK : step_done(h, K, "k_continuous_rollout_fast");
+        stamp_piece(a, h, 0);
     }
     // move_along_a_line in its common shape: the dedicated rollout kernel (mdpp_continuous_line.hip)
-    if (launch_continuous_line(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out)) {
-        if (name_out) return MDPP_OK;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("k_continuous_line_rollout launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-        h->tick += (uint64_t)K;
-        return MDPP_OK;
-    }
+    if (launch_continuous_line(a, io)) return io.name_out ? MDPP_OK : step_done(h, K, "k_continuous_line_rollout");
     if (a.line_L && a.line_NL == 8 && !a.line_ws) {
-        if (!launch_continuous_step_line8(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out)) {
+        if (!launch_continuous_step_line8(a, io)) {
             h->err = "k_continuous_step<NL=8>: move_along_a_line with 5 to 8 relevant dimensions needs state_space_dim <= 12";
             return MDPP_EUNSUPPORTED;
         }
     } else {
-#define CALL_STEP(DM, OM) launch_step_t<DM, OM>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out)
+#define CALL_STEP(DM, OM) launch_step_t<DM, OM>(a, io)
         MDPP_C_DISPATCH(CALL_STEP);
 #undef CALL_STEP
     }
-    if (name_out) return MDPP_OK;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("k_continuous_step launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-    h->tick += (uint64_t)K;
-    return MDPP_OK;
+    return io.name_out ? MDPP_OK : step_done(h, K, "k_continuous_step");
 }
 
 int launch_continuous_reset(mdpp_env *h, const uint8_t *mask, float *obs, hipStream_t s) {

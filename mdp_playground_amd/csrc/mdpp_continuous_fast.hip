@@ -1331,13 +1331,25 @@ __global__ __launch_bounds__(HELPER ? (1 + NPROD) * kBlock : kBlock, PAR ? 4 : 1
 #ifndef MDPP_CFAST_TU_K1
 #define MDPP_CFAST_TU_K1 0         // 1: this translation unit holds the one-step instantiations (mdpp_continuous_step1.hip)
 #endif
+// The (D, ORDER, NREL) shapes this file is built for: f(shape) for the one the handle has; false when there is none
+template <int D_, int ORDER_, int NREL_> struct CShape { static constexpr int D = D_, ORDER = ORDER_, NREL = NREL_; };
+template <class F> static bool with_shape(const ContinuousArgs &a, F &&f) {
+#define MDPP_CF(DD, OO, RR) if (a.D == DD && a.order == OO && a.n_rel == RR) { f(CShape<DD, OO, RR>{}); return true; }
+    MDPP_CF(12, 1, 4) MDPP_CF(12, 2, 4)
+    MDPP_CF(2, 1, 2) MDPP_CF(2, 2, 2) MDPP_CF(4, 1, 4) MDPP_CF(4, 2, 4)
+    MDPP_CF(8, 1, 8) MDPP_CF(8, 2, 8) MDPP_CF(12, 1, 12) MDPP_CF(12, 2, 12)
+    MDPP_CF(4, 1, 2) MDPP_CF(4, 2, 2) MDPP_CF(8, 1, 4) MDPP_CF(8, 2, 4)
+    MDPP_CF(2, 3, 2)                // (the reference's *_move_to_a_point_p_order_3 sweeps)
+#undef MDPP_CF
+    return false;
+}
+
 #if MDPP_CFAST_TU_K1
 // mdpp_step (K = 1) on the fast shape: k_continuous_rollout_fast<..., K1 = true>.  Returns false when the shape is not built
 // here or the launch needs what K1 leaves out (numpy noise streams: whole 256-env blocks) -- the caller then launches the
 // rollout kernel with K = 1 as before.
 template <int D, int ORDER, int NREL, bool NOISE, bool GEN, bool PHILOX>
-static bool launch_k1(const ContinuousArgs &a, const float *actions, float *obs, float *reward, uint8_t *term, uint8_t *trunc,
-                      float *final_obs, hipStream_t s, char *name_out) {
+static bool launch_k1(const ContinuousArgs &a, const ContinuousIO &io) {
     constexpr bool ZIG = NOISE && !PHILOX;
     constexpr int WG = ZIG ? kBlock : 64;
     // numpy streams with transition noise: the step's draws side by side (PAR: 64 envs per 256-thread workgroup)
@@ -1345,58 +1357,36 @@ static bool launch_k1(const ContinuousArgs &a, const float *actions, float *obs,
     //  step in a replayed graph against 6.4 for the rollout kernel with K = 1; the sequential one-step form below serves small D)
     if constexpr (ZIG && D + 1 <= 16 && D >= 8) {
         if (a.has_p_noise && (a.N % 64) == 0 && !(a.opts & MDPP_OPT_NO_HELPER)) {
-            if (name_out) {
-                snprintf(name_out, kNameLen, "k_continuous_step1<D=%d,ORDER=%d,NREL=%d,NOISE=%d,GEN=%d,PHILOX=%d,PAR=1>", D, ORDER, NREL, NOISE, GEN, PHILOX);
-                return true;
-            }
-            hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, NOISE, false, GEN, PHILOX, 1, true, true>), dim3(a.N / 64), dim3(kBlock),
-                               0, s, a, 1, actions, obs, reward, term, trunc, final_obs);
+            if (io.name_out) snprintf(io.name_out, kNameLen, "k_continuous_step1<D=%d,ORDER=%d,NREL=%d,NOISE=%d,GEN=%d,PHILOX=%d,PAR=1>", D, ORDER, NREL, NOISE, GEN, PHILOX);
+            else launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, NOISE, false, GEN, PHILOX, 1, true, true>, a.N / 64, kBlock, 0, a, io);
             return true;
         }
     }
     if (ZIG && (a.N % kBlock) != 0) return false;
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_continuous_step1<D=%d,ORDER=%d,NREL=%d,NOISE=%d,GEN=%d,PHILOX=%d,WG=%d>", D, ORDER, NREL, NOISE, GEN, PHILOX, WG);
-        return true;
-    }
-    hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, NOISE, false, GEN, PHILOX, 1, true>), dim3((a.N + WG - 1) / WG), dim3(WG),
-                       0, s, a, 1, actions, obs, reward, term, trunc, final_obs);
+    if (io.name_out) snprintf(io.name_out, kNameLen, "k_continuous_step1<D=%d,ORDER=%d,NREL=%d,NOISE=%d,GEN=%d,PHILOX=%d,WG=%d>", D, ORDER, NREL, NOISE, GEN, PHILOX, WG);
+    else launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, NOISE, false, GEN, PHILOX, 1, true>, (a.N + WG - 1) / WG, WG, 0, a, io);
     return true;
 }
 
-bool launch_continuous_step1(const ContinuousArgs &a, const float *actions, float *obs, float *reward, uint8_t *term,
-                             uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out) {
+bool launch_continuous_step1(const ContinuousArgs &a, const ContinuousIO &io) {
     if (!a.fast_ok || (a.opts & (MDPP_OPT_NO_CFAST | MDPP_OPT_NO_STEP1)) || (a.philox && (a.opts & MDPP_OPT_NO_PHILOX_FAST))) return false;
     const bool gen = a.delay > 0 || a.every_n != 1 || a.n_boxes > 0 || !a.bounded;
     // (Philox streams carry no state: noise keys whose sigma is 0 add +0.0 whatever the normal is -- the noise-free instantiation serves them)
     const bool sig0 = a.philox && (!a.has_p_noise || a.p_noise == 0.0) && (!a.has_r_noise || a.r_noise == 0.0) && !(a.opts & MDPP_OPT_NO_SIGMA0);
     const bool noise = (a.has_p_noise || a.has_r_noise) && !sig0;
-#define MDPP_K1(DD, OO, RR)                                                                                                  \
-    if (a.D == DD && a.order == OO && a.n_rel == RR) {                                                                        \
-        const int sel = (noise ? 4 : 0) | (gen ? 2 : 0) | (a.philox ? 1 : 0);                                                \
-        switch (sel) {                                                                                                        \
-        case 0: return launch_k1<DD, OO, RR, false, false, false>(a, actions, obs, reward, term, trunc, final_obs, s, name_out); \
-        case 1: return launch_k1<DD, OO, RR, false, false, true>(a, actions, obs, reward, term, trunc, final_obs, s, name_out);  \
-        case 2: return launch_k1<DD, OO, RR, false, true, false>(a, actions, obs, reward, term, trunc, final_obs, s, name_out);  \
-        case 3: return launch_k1<DD, OO, RR, false, true, true>(a, actions, obs, reward, term, trunc, final_obs, s, name_out);   \
-        case 4: return launch_k1<DD, OO, RR, true, false, false>(a, actions, obs, reward, term, trunc, final_obs, s, name_out);  \
-        case 5: return launch_k1<DD, OO, RR, true, false, true>(a, actions, obs, reward, term, trunc, final_obs, s, name_out);   \
-        case 6: return launch_k1<DD, OO, RR, true, true, false>(a, actions, obs, reward, term, trunc, final_obs, s, name_out);   \
-        default: return launch_k1<DD, OO, RR, true, true, true>(a, actions, obs, reward, term, trunc, final_obs, s, name_out);   \
-        }                                                                                                                     \
-    }
-    MDPP_K1(12, 1, 4) MDPP_K1(12, 2, 4)
-    MDPP_K1(2, 1, 2) MDPP_K1(2, 2, 2) MDPP_K1(4, 1, 4) MDPP_K1(4, 2, 4)
-    MDPP_K1(8, 1, 8) MDPP_K1(8, 2, 8) MDPP_K1(12, 1, 12) MDPP_K1(12, 2, 12)
-    MDPP_K1(4, 1, 2) MDPP_K1(4, 2, 2) MDPP_K1(8, 1, 4) MDPP_K1(8, 2, 4)
-    MDPP_K1(2, 3, 2)                // (the reference's *_move_to_a_point_p_order_3 sweeps)
-#undef MDPP_K1
-    return false;
+    bool served = false;
+    with_shape(a, [&](auto sh) {
+        using S = decltype(sh);
+        with_bools([&](auto NOISE, auto GEN, auto PHILOX) {
+            served = launch_k1<S::D, S::ORDER, S::NREL, NOISE(), GEN(), PHILOX()>(a, io);
+        }, noise, gen, a.philox != 0);
+    });
+    return served;
 }
 #else
 template <int D, int ORDER, int NREL, bool GEN, bool PHILOX>
-static void launch_g(const ContinuousArgs &a, int K, const float *actions, float *obs, float *reward,
-                     uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out) {
+static void launch_g(const ContinuousArgs &a, const ContinuousIO &io) {
+    const int K = io.K;
     const int grid = (a.N + kBlock - 1) / kBlock;
     constexpr bool can_help = (size_t)kNRing * (D + 1) * kBlock * 8 <= 120 * 1024;
     // (Philox streams carry no state: noise keys whose sigma is 0 add +0.0 whatever the normal is -- the noise-free instantiation serves them)
@@ -1413,8 +1403,8 @@ static void launch_g(const ContinuousArgs &a, int K, const float *actions, float
     const int nprod = (PHILOX && helper && D >= 8 && !(a.opts & MDPP_OPT_NO_TRIO)) ? kPhiloxProducers : (walk ? 2 : 1);
     // sigma-0 noise keys (kernel header, Z0): the D = 2 walker kernels without their normals ring
     const bool z0 = walk && D == 2 && (!a.has_p_noise || a.p_noise == 0.0) && (!a.has_r_noise || a.r_noise == 0.0) && !(a.opts & MDPP_OPT_NO_SIGMA0);
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_continuous_rollout_fast<D=%d,ORDER=%d,NREL=%d,NOISE=%d,HELPER=%d,GEN=%d,PHILOX=%d,NPROD=%d%s>", D,
+    if (io.name_out) {
+        snprintf(io.name_out, kNameLen, "k_continuous_rollout_fast<D=%d,ORDER=%d,NREL=%d,NOISE=%d,HELPER=%d,GEN=%d,PHILOX=%d,NPROD=%d%s>", D,
                  ORDER, NREL, noise, helper, GEN, PHILOX, helper ? nprod : 0, z0 ? ",Z0=1" : "");
         return;
     }
@@ -1422,54 +1412,31 @@ static void launch_g(const ContinuousArgs &a, int K, const float *actions, float
         ContinuousArgs ap = a;
         ap.park = (a.opts & MDPP_OPT_NO_PARK) ? 0 : 1;
         if (can_help && helper && PHILOX && nprod > 1)
-            hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, true, can_help, GEN, PHILOX, PHILOX ? kPhiloxProducers : 1>),
-                               dim3(grid), dim3((1 + kPhiloxProducers) * kBlock), 0, s, ap, K, actions, obs, reward, term,
-                               trunc, final_obs);
+            launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, true, can_help, GEN, PHILOX, PHILOX ? kPhiloxProducers : 1>, grid,
+                           (1 + kPhiloxProducers) * kBlock, 0, ap, io);
         else if (can_help && helper && walk && D == 2 && z0)
-            hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, true, can_help && kWalkD, GEN, false, (can_help && kWalkD && !PHILOX) ? 2 : 1, false, false,
-                                                          D == 2 && can_help && !PHILOX>), dim3(grid),
-                               dim3(3 * kBlock), 0, s, ap, K, actions, obs, reward, term, trunc, final_obs);
+            launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, true, can_help && kWalkD, GEN, false, (can_help && kWalkD && !PHILOX) ? 2 : 1, false, false,
+                                                     D == 2 && can_help && !PHILOX>, grid, 3 * kBlock, 0, ap, io);
         else if (can_help && helper && walk)
-            hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, true, can_help && kWalkD, GEN, false, (can_help && kWalkD && !PHILOX) ? 2 : 1>), dim3(grid),
-                               dim3(3 * kBlock), 0, s, ap, K, actions, obs, reward, term, trunc, final_obs);
+            launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, true, can_help && kWalkD, GEN, false, (can_help && kWalkD && !PHILOX) ? 2 : 1>, grid,
+                           3 * kBlock, 0, ap, io);
         else if (can_help && helper)
-            hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, true, can_help, GEN, PHILOX>), dim3(grid),
-                               dim3(2 * kBlock), 0, s, ap, K, actions, obs, reward, term, trunc, final_obs);
+            launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, true, can_help, GEN, PHILOX>, grid, 2 * kBlock, 0, ap, io);
         else
-            hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, true, false, GEN, PHILOX>), dim3(grid),
-                               dim3(kBlock), 0, s, a, K, actions, obs, reward, term, trunc, final_obs);
+            launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, true, false, GEN, PHILOX>, grid, kBlock, 0, a, io);
     } else {
-        hipLaunchKernelGGL((k_continuous_rollout_fast<D, ORDER, NREL, false, false, GEN, PHILOX>), dim3(grid), dim3(kBlock),
-                           0, s, a, K, actions, obs, reward, term, trunc, final_obs);
-    }
-}
-
-template <int D, int ORDER, int NREL>
-static void launch_t(const ContinuousArgs &a, int K, const float *actions, float *obs, float *reward,
-                     uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out) {
-    const bool gen = a.delay > 0 || a.every_n != 1 || a.n_boxes > 0 || !a.bounded;
-    if (a.philox) {
-        if (gen) launch_g<D, ORDER, NREL, true, true>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-        else launch_g<D, ORDER, NREL, false, true>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    } else {
-        if (gen) launch_g<D, ORDER, NREL, true, false>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-        else launch_g<D, ORDER, NREL, false, false>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
+        launch_rollout(k_continuous_rollout_fast<D, ORDER, NREL, false, false, GEN, PHILOX>, grid, kBlock, 0, a, io);
     }
 }
 
 // Returns false when the shape does not qualify (caller falls back to k_continuous_step).
-bool launch_continuous_fast(const ContinuousArgs &a, int K, const float *actions, float *obs,
-                            float *reward, uint8_t *term, uint8_t *trunc, float *final_obs,
-                            hipStream_t s, char *name_out) {
+bool launch_continuous_fast(const ContinuousArgs &a, const ContinuousIO &io) {
     if (!a.fast_ok || (a.opts & MDPP_OPT_NO_CFAST) || (a.philox && (a.opts & MDPP_OPT_NO_PHILOX_FAST))) return false;
-#define MDPP_CF(DD, OO, RR) if (a.D == DD && a.order == OO && a.n_rel == RR) { launch_t<DD, OO, RR>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out); return true; }
-    MDPP_CF(12, 1, 4) MDPP_CF(12, 2, 4)
-    MDPP_CF(2, 1, 2) MDPP_CF(2, 2, 2) MDPP_CF(4, 1, 4) MDPP_CF(4, 2, 4)
-    MDPP_CF(8, 1, 8) MDPP_CF(8, 2, 8) MDPP_CF(12, 1, 12) MDPP_CF(12, 2, 12)
-    MDPP_CF(4, 1, 2) MDPP_CF(4, 2, 2) MDPP_CF(8, 1, 4) MDPP_CF(8, 2, 4)
-    MDPP_CF(2, 3, 2)                // (the reference's *_move_to_a_point_p_order_3 sweeps)
-#undef MDPP_CF
-    return false;
+    const bool gen = a.delay > 0 || a.every_n != 1 || a.n_boxes > 0 || !a.bounded;
+    return with_shape(a, [&](auto sh) {
+        using S = decltype(sh);
+        with_bools([&](auto GEN, auto PHILOX) { launch_g<S::D, S::ORDER, S::NREL, GEN(), PHILOX()>(a, io); }, gen, a.philox != 0);
+    });
 }
 #endif   // !MDPP_CFAST_TU_K1
 

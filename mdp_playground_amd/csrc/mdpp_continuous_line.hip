@@ -398,34 +398,24 @@ __global__ __launch_bounds__(kBlock) void k_continuous_line_rollout(ContinuousAr
 }
 
 // Returns false when the shape does not qualify (the caller goes on to k_continuous_step).
-bool launch_continuous_line(const ContinuousArgs &a, int K, const float *actions, float *obs, float *reward, uint8_t *term,
-                            uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out) {
+bool launch_continuous_line(const ContinuousArgs &a, const ContinuousIO &io) {
+    const int K = io.K;
     if (!a.line_L || a.line_L < 2 || a.line_L > kLineMaxL || (a.opts & MDPP_OPT_NO_CFAST)) return false;
     if (a.philox && (a.opts & MDPP_OPT_NO_PHILOX_FAST)) return false;
     if (a.n_rel != a.D || !a.rel_prefix || (a.D != 2 && a.D != 4) || a.order > 2) return false;
     if (a.has_p_noise || a.has_r_noise || a.delay != 0 || a.every_n != 1 || a.n_boxes != 0 || !a.bounded || a.image_quirk) return false;
     if (a.autoreset == MDPP_AUTORESET_NEXT_STEP || a.est.cur || K < 4) return false;
     if ((unsigned long long)K * a.N * a.D * 4ULL >= (1ULL << 32)) return false;
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_continuous_line_rollout<D=%d,ORDER=%d,PHILOX=%d>", a.D, a.order, a.philox != 0);
-        return true;
-    }
     const int grid = (a.N + kBlock - 1) / kBlock;
     const size_t lds = (size_t)a.line_L * kBlock * sizeof(float4);
-#define MDPP_LINE_GO(DD, OO, PH)                                                                                              \
-    do {                                                                                                                      \
-        if (!dynamic_lds_ok((const void *)k_continuous_line_rollout<DD, OO, PH>, lds)) return false;   /* -> k_continuous_step */ \
-        hipLaunchKernelGGL((k_continuous_line_rollout<DD, OO, PH>), dim3(grid), dim3(kBlock), lds, s, a, K, actions, obs, reward, \
-                           term, trunc, final_obs);                                                                           \
-    } while (0)
-#define MDPP_LINE_PH(DD, OO) do { if (a.philox) MDPP_LINE_GO(DD, OO, true); else MDPP_LINE_GO(DD, OO, false); } while (0)
-    if (a.D == 4 && a.order == 1) MDPP_LINE_PH(4, 1);
-    else if (a.D == 4) MDPP_LINE_PH(4, 2);
-    else if (a.order == 1) MDPP_LINE_PH(2, 1);
-    else MDPP_LINE_PH(2, 2);
-#undef MDPP_LINE_PH
-#undef MDPP_LINE_GO
-    return true;
+    bool served = true;
+    with_bools([&](auto D4, auto O1, auto PH) {
+        constexpr int DD = D4() ? 4 : 2, OO = O1() ? 1 : 2;         // (D is 2 or 4, the order 1 or 2 here)
+        if (io.name_out) snprintf(io.name_out, kNameLen, "k_continuous_line_rollout<D=%d,ORDER=%d,PHILOX=%d>", DD, OO, PH());
+        else if (!dynamic_lds_ok((const void *)k_continuous_line_rollout<DD, OO, PH()>, lds)) served = false;   // -> k_continuous_step
+        else launch_rollout(k_continuous_line_rollout<DD, OO, PH()>, grid, kBlock, lds, a, io);
+    }, a.D == 4, a.order == 1, a.philox != 0);
+    return served;
 }
 
 } // namespace mdpp

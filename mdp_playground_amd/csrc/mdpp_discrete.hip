@@ -24,7 +24,6 @@
 #define d_reset_draw d_reset_draw_wide
 #define DTables DTablesWide
 #define DHist DHistWide
-#define launch_step_t launch_step_wide_t
 #define launch_discrete_step_var launch_discrete_step_wide
 #define launch_discrete_reset_var launch_discrete_reset_wide
 #define MDPP_D_VARIANT "wide"
@@ -35,7 +34,6 @@
 #define d_reset_draw d_reset_draw_long
 #define DTables DTablesLong
 #define DHist DHistLong
-#define launch_step_t launch_step_long_t
 #define launch_discrete_step_var launch_discrete_step_long
 #define launch_discrete_reset_var launch_discrete_reset_long
 #define MDPP_D_VARIANT "long"
@@ -475,10 +473,15 @@ __global__ __launch_bounds__(kBlock) void k_discrete_reset(DiscreteArgs a, uint6
     }
 }
 
-template <bool PHILOX, bool NOISE>
-static void launch_step_t(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                          float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                          hipStream_t s, char *name_out) {
+#ifdef MDPP_D_VARIANT
+#define MDPP_D_SUFFIX "_" MDPP_D_VARIANT
+#else
+#define MDPP_D_SUFFIX ""
+#endif
+
+// The general kernel: serves every handle (of this build of the file).
+static void launch_general(const DiscreteArgs &a, const DiscreteIO &io) {
+    const int K = io.K;
     const int grid = (a.N + kBlock - 1) / kBlock;
     // (tables beyond the default dynamic-LDS limit -- a large action space -- are read from HBM / L2)
     // (one MDP per env: each lane's tables in its own LDS slot when 256 slots fit 96 KiB and the rollout is long enough to pay
@@ -490,64 +493,27 @@ static void launch_step_t(const DiscreteArgs &a, int K, const int32_t *actions, 
 #ifdef MDPP_D_VARIANT
     ldsenv = ldstab = false;            // (wide: 16-bit table entries; long: up to S^15 keys -- read where they are, in HBM / L2)
 #endif
-    if (ldsenv) {                       // (also when only the name is asked for: the name is the launch's)
-        const void *kern = a.unit_rewards ? (const void *)k_discrete_step<PHILOX, NOISE, true, true, false>
-                                          : (const void *)k_discrete_step<PHILOX, NOISE, false, true, false>;
-        if (!dynamic_lds_ok(kern, env_lds)) ldsenv = false;
-    }
-    if (ldsenv) ldstab = true;
-    const size_t lds = ldsenv ? env_lds : (ldstab ? a.lds_bytes : 0);
-    if (name_out) {
+    with_bools([&](auto PH, auto NZ, auto UNIT, auto IRR) {
+        // (also when only the name is asked for: the name is the launch's)
+        if (ldsenv && !dynamic_lds_ok((const void *)k_discrete_step<PH(), NZ(), UNIT(), true, false>, env_lds)) ldsenv = false;
+        if (ldsenv) ldstab = true;
+        const size_t lds = ldsenv ? env_lds : (ldstab ? a.lds_bytes : 0);
+        with_bools([&](auto LDSTAB) {
 #ifdef MDPP_D_VARIANT
-        snprintf(name_out, kNameLen, "k_discrete_step_" MDPP_D_VARIANT "<PHILOX=%d,NOISE=%d,UNIT=%d,IRR=%d>", PHILOX, NOISE, a.unit_rewards != 0, a.irr != 0);
+            if constexpr (!LDSTAB()) {
+                if (io.name_out) snprintf(io.name_out, kNameLen, "k_discrete_step" MDPP_D_SUFFIX "<PHILOX=%d,NOISE=%d,UNIT=%d,IRR=%d>", PH(), NZ(), UNIT(), IRR());
+                else launch_rollout(k_discrete_step<PH(), NZ(), UNIT(), false, IRR()>, grid, kBlock, lds, a, io);
+            }
 #else
-        snprintf(name_out, kNameLen, "k_discrete_step<PHILOX=%d,NOISE=%d,UNIT=%d,LDSTAB=%d,IRR=%d>", PHILOX, NOISE,
-                 a.unit_rewards != 0, ldsenv ? 2 : (int)ldstab, a.irr != 0);
+            if (io.name_out) snprintf(io.name_out, kNameLen, "k_discrete_step<PHILOX=%d,NOISE=%d,UNIT=%d,LDSTAB=%d,IRR=%d>", PH(), NZ(), UNIT(), ldsenv ? 2 : (int)LDSTAB(), IRR());
+            else launch_rollout(k_discrete_step<PH(), NZ(), UNIT(), LDSTAB(), IRR()>, grid, kBlock, lds, a, io);
 #endif
-        return;
-    }
-#define MDPP_D_LAUNCH(UNIT, LDSTAB, IRR)                                                               \
-    hipLaunchKernelGGL((k_discrete_step<PHILOX, NOISE, UNIT, LDSTAB, IRR>), dim3(grid), dim3(kBlock), \
-                       lds, s, a, K, actions, obs, reward, term, trunc, final_obs)
-#ifdef MDPP_D_VARIANT
-    if (a.irr) { if (a.unit_rewards) MDPP_D_LAUNCH(true, false, true); else MDPP_D_LAUNCH(false, false, true); }
-    else { if (a.unit_rewards) MDPP_D_LAUNCH(true, false, false); else MDPP_D_LAUNCH(false, false, false); }
-#else
-    if (a.irr) {
-        if (a.unit_rewards) { if (ldstab) MDPP_D_LAUNCH(true, true, true); else MDPP_D_LAUNCH(true, false, true); }
-        else { if (ldstab) MDPP_D_LAUNCH(false, true, true); else MDPP_D_LAUNCH(false, false, true); }
-    } else {
-        if (a.unit_rewards) { if (ldstab) MDPP_D_LAUNCH(true, true, false); else MDPP_D_LAUNCH(true, false, false); }
-        else { if (ldstab) MDPP_D_LAUNCH(false, true, false); else MDPP_D_LAUNCH(false, false, false); }
-    }
-#endif
-#undef MDPP_D_LAUNCH
+        }, ldstab);
+    }, a.philox != 0, a.has_p_noise || a.has_r_noise, a.unit_rewards != 0, a.irr != 0);
 }
 
-#ifdef MDPP_D_VARIANT
-int launch_discrete_step_var(mdpp_env *h, int K, const int32_t *actions, void *obs, float *reward,
-                              uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out) {
-    DiscreteArgs a = h->dargs;
-    a.opts = h->opts;
-    a.ptick = h->tick;
-    a.dtick = h->graph_capture ? (const uint64_t *)h->d_tick_off : nullptr;
-    a.tick = a.delay > 0 ? (uint32_t)(h->tick % (uint64_t)a.delay) : 0u;
-    const bool noise = a.has_p_noise || a.has_r_noise;
-    if (a.philox) {
-        if (noise) launch_step_t<true, true>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-        else launch_step_t<true, false>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    } else {
-        if (noise) launch_step_t<false, true>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-        else launch_step_t<false, false>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    }
-    if (name_out) return MDPP_OK;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("k_discrete_step_" MDPP_D_VARIANT " launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-    h->tick += (uint64_t)K;
-    return MDPP_OK;
-}
-
-int launch_discrete_reset_var(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s) {
+// (this build of the file: k_discrete_reset, _wide or _long)
+static int discrete_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s) {
     DiscreteArgs a = h->dargs;
     const int grid = (a.N + kBlock - 1) / kBlock;
     if (a.philox)
@@ -555,116 +521,79 @@ int launch_discrete_reset_var(mdpp_env *h, const uint8_t *mask, void *obs, hipSt
     else
         hipLaunchKernelGGL(k_discrete_reset<false>, dim3(grid), dim3(kBlock), 0, s, a, h->reset_tick, mask, obs);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("k_discrete_reset_" MDPP_D_VARIANT " launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
+    if (e != hipSuccess) { h->err = std::string("k_discrete_reset" MDPP_D_SUFFIX " launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
     h->reset_tick += 1;
     return MDPP_OK;
 }
+
+#ifdef MDPP_D_VARIANT
+int launch_discrete_step_var(mdpp_env *h, const DiscreteIO &io) {
+    DiscreteArgs a = h->dargs;
+    stamp_step(a, h);
+    launch_general(a, io);
+    return io.name_out ? MDPP_OK : step_done(h, io.K, "k_discrete_step" MDPP_D_SUFFIX);
+}
+
+int launch_discrete_reset_var(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s) { return discrete_reset(h, mask, obs, s); }
 #else
 
-int launch_discrete_step(mdpp_env *h, int K, const int32_t *actions, void *obs, float *reward,
-                         uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out) {
-    if (h->cfg.S > 255) return launch_discrete_step_wide(h, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    if (h->cfg.L > 7) return launch_discrete_step_long(h, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
+int launch_discrete_step(mdpp_env *h, const DiscreteIO &io) {
+    if (h->cfg.S > 255) return launch_discrete_step_wide(h, io);
+    if (h->cfg.L > 7) return launch_discrete_step_long(h, io);
+    const int K = io.K;
     DiscreteArgs a = h->dargs;
-    a.opts = h->opts;
+    stamp_step(a, h);
     // image handles: this is the state kernel of a batch of the image pipeline, which runs BESIDE the persistent renderer of the
     // previous batch (mdpp_capi.hip image_batches).  The role-split kernels want most of a CU's LDS and wait for the renderer's
     // workgroups to leave (k_discrete_rollout_pipe: 38 us alone, 308 us average beside the renderer, and the batch's draw and
     // record kernels queue behind it); the single-role kernel needs a kilobyte and always fits.
     if (h->cfg.image) a.opts |= MDPP_OPT_NO_PIPE | MDPP_OPT_NO_LEAN;
-    a.ptick = h->tick;
-    a.dtick = h->graph_capture ? (const uint64_t *)h->d_tick_off : nullptr;     // (launches being captured into a HIP graph)
-    a.tick = a.delay > 0 ? (uint32_t)(h->tick % (uint64_t)a.delay) : 0u;
-    const bool noise = a.has_p_noise || a.has_r_noise;
-    // Philox handles of the common shape: k_discrete_rollout_lean with its H waves on Philox blocks
-    // (mdpp_discrete_lean.hip); pieces it does not take (a short last one) go to the quiet kernel
-    bool lean_philox = false;
+    // Pieces: the specialised kernels' buffer descriptors address < 4 GiB per output array (8 bytes per env-step, 16 with an
+    // irrelevant sub-space), so very long rollouts go out as several launches; the quiet and the general kernel take any K
+    long long kmax = K;
+    // Philox / irrelevant / next-step / noisy handles of the common shape: k_discrete_rollout_lean with its H waves on Philox
+    // blocks (mdpp_discrete_lean.hip), when the first piece qualifies; pieces it does not take (a short last one) go to the
+    // quiet kernel, then (a short last piece of a next-step handle) to the general kernel
+    // (final observations are forwarded piece by piece: the lean kernel declines a launch that asks for them, the quiet and
+    //  general kernels write them -- ADVICE r2: nothing is dropped silently)
+    bool lean_first = false;
     if (!a.fast_ok && ((a.philox && (a.shape_ok || a.shape_ok_noise)) || a.shape_ok_noise_np || a.shape_ok_irr || a.lean_next_ok)) {
-        const long long kmax = ((1LL << 32) - 1) / ((a.irr ? 16LL : 8LL) * a.N);
+        const long long kmax_lean = ((1LL << 32) - 1) / ((a.irr ? 16LL : 8LL) * a.N);
         char dry[kNameLen];
-        const int k_first = (int)(K < kmax ? K : kmax);
-        // (final observations are forwarded piece by piece like in the fast_ok branch below: the lean kernel declines a
-        //  launch that asks for them, the quiet and general kernels write them -- ADVICE r2: nothing is dropped silently)
-        if (kmax >= 32 && launch_discrete_lean(a, k_first, actions, obs, reward, term, trunc, final_obs, s, dry)) {
-            lean_philox = true;
-            const size_t osz = a.obs_i32 ? 4 : 8;
-            for (int k0 = 0; k0 < K;) {
-                const int kc = (int)((K - k0) < kmax ? (K - k0) : kmax);
-                const size_t off = (size_t)k0 * a.N;
-                a.ptick = h->tick + (uint64_t)k0;
-                a.tick = a.delay > 0 ? (uint32_t)(a.ptick % (uint64_t)a.delay) : 0u;
-                const size_t aoff = off * (a.irr ? 2 : 1);     // (an irrelevant sub-space: action pairs, observation pairs)
-                char *op = (char *)obs + off * osz * (a.irr ? 2 : 1);
-                void *fo = final_obs ? (void *)((char *)final_obs + off * osz * (a.irr ? 2 : 1)) : nullptr;
-                if (!launch_discrete_lean(a, kc, actions + aoff, op, reward + off, term + off, trunc + off, fo, s, name_out) &&
-                    !launch_discrete_quiet(a, kc, actions + aoff, op, reward + off, term + off, trunc + off, fo, s, name_out)) {
-                    // (a short last piece of a next-step handle: the general kernel)
-                    if (a.philox && noise) launch_step_t<true, true>(a, kc, actions + aoff, op, reward + off, term + off, trunc + off, fo, s, name_out);
-                    else if (a.philox) launch_step_t<true, false>(a, kc, actions + aoff, op, reward + off, term + off, trunc + off, fo, s, name_out);
-                    else if (noise) launch_step_t<false, true>(a, kc, actions + aoff, op, reward + off, term + off, trunc + off, fo, s, name_out);
-                    else launch_step_t<false, false>(a, kc, actions + aoff, op, reward + off, term + off, trunc + off, fo, s, name_out);
-                }
-                if (name_out) return MDPP_OK;
-                k0 += kc;
-            }
-        }
+        DiscreteIO probe = piece_of(a, io, 0, (int)(K < kmax_lean ? K : kmax_lean));
+        probe.name_out = dry;
+        lean_first = kmax_lean >= 32 && launch_discrete_lean(a, probe);
+        if (lean_first) kmax = kmax_lean;
     }
-    if (lean_philox) {
-    } else if (K == 1 && launch_discrete_step1(a, h->s1args, actions, obs, reward, term, trunc, final_obs, s, name_out)) {
-        // mdpp_step on the common shape: the kernel made for a launch of one step (mdpp_discrete_step1.hip)
-    } else if (a.fast_ok) {
-        // common shape: dedicated rollout kernel (mdpp_discrete_fast.hip); its buffer descriptors
-        // address < 4 GiB per output array, so very long rollouts go out as several launches
-        const long long kmax = ((1LL << 32) - 1) / (8LL * a.N);
+    // mdpp_step on the common shape: the kernel made for a launch of one step (mdpp_discrete_step1.hip)
+    // (never a lean handle's: the probe above declines any K < 32)
+    if (K == 1 && launch_discrete_step1(a, h->s1args, io)) return io.name_out ? MDPP_OK : step_done(h, K, "k_discrete_step");
+    if (a.fast_ok) {                    // (excludes lean_first)
+        kmax = ((1LL << 32) - 1) / (8LL * a.N);
         if (kmax < 1) { h->err = "k_discrete_rollout_fast: num_envs too large"; return MDPP_EUNSUPPORTED; }
-        const size_t osz = a.obs_i32 ? 4 : 8;
-        for (int k0 = 0; k0 < K;) {
-            const int kc = (int)((K - k0) < kmax ? (K - k0) : kmax);
-            const size_t off = (size_t)k0 * a.N;
-            a.ptick = h->tick + (uint64_t)k0;
-            a.tick = a.delay > 0 ? (uint32_t)(a.ptick % (uint64_t)a.delay) : 0u;
-            void *fo = final_obs ? (void *)((char *)final_obs + off * osz) : nullptr;
-            // long rollouts of full blocks: three-role pipelined kernel (mdpp_discrete_pipe.hip)
-            // (at most 8 states: its leaner re-encoding, mdpp_discrete_lean.hip)
-            if (!launch_discrete_lean(a, kc, actions + off, (char *)obs + off * osz, reward + off,
-                                      term + off, trunc + off, fo, s, name_out) &&
-                !launch_discrete_pipe(a, kc, actions + off, (char *)obs + off * osz, reward + off,
-                                      term + off, trunc + off, fo, s, name_out))
-                launch_discrete_fast(a, kc, actions + off, (char *)obs + off * osz, reward + off,
-                                     term + off, trunc + off, fo, s, name_out);
-            if (name_out) return MDPP_OK;     // (the first piece names the launch)
-            k0 += kc;
-        }
-    } else if (!a.est.cur && launch_discrete_quiet(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out)) {
-        // quiet shapes beyond the specialised kernels (larger S / L, irrelevant sub-space):
-        // mdpp_discrete_quiet.hip
-    } else if (a.philox) {
-        if (noise) launch_step_t<true, true>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-        else launch_step_t<true, false>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    } else {
-        if (noise) launch_step_t<false, true>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-        else launch_step_t<false, false>(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
     }
-    if (name_out) return MDPP_OK;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("k_discrete_step launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-    h->tick += (uint64_t)K;
-    return MDPP_OK;
+    for_each_piece(a, h, io, kmax, [&](const DiscreteIO &p, int) {
+        if ((lean_first || a.fast_ok) && launch_discrete_lean(a, p)) {
+            // at most 8 states: the leaner re-encoding of the pipelined kernel (mdpp_discrete_lean.hip)
+        } else if (a.fast_ok) {
+            // common shape: long rollouts of full blocks go to the three-role pipelined kernel (mdpp_discrete_pipe.hip), the
+            // rest to the dedicated rollout kernel (mdpp_discrete_fast.hip)
+            if (!launch_discrete_pipe(a, p)) launch_discrete_fast(a, p);
+        } else if ((lean_first || !a.est.cur) && launch_discrete_quiet(a, p)) {
+            // quiet shapes beyond the specialised kernels (larger S / L, irrelevant sub-space): mdpp_discrete_quiet.hip
+            // (episode statistics: the general kernel keeps them)
+        } else {
+            launch_general(a, p);
+        }
+        return true;
+    });
+    return io.name_out ? MDPP_OK : step_done(h, K, "k_discrete_step");
 }
 
 int launch_discrete_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s) {
     if (h->cfg.S > 255) return launch_discrete_reset_wide(h, mask, obs, s);
     if (h->cfg.L > 7) return launch_discrete_reset_long(h, mask, obs, s);
-    DiscreteArgs a = h->dargs;
-    const int grid = (a.N + kBlock - 1) / kBlock;
-    if (a.philox)
-        hipLaunchKernelGGL(k_discrete_reset<true>, dim3(grid), dim3(kBlock), 0, s, a, h->reset_tick, mask, obs);
-    else
-        hipLaunchKernelGGL(k_discrete_reset<false>, dim3(grid), dim3(kBlock), 0, s, a, h->reset_tick, mask, obs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("k_discrete_reset launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-    h->reset_tick += 1;
-    return MDPP_OK;
+    return discrete_reset(h, mask, obs, s);
 }
 #endif   // MDPP_D_VARIANT
 

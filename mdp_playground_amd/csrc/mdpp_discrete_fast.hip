@@ -374,31 +374,15 @@ __global__ __launch_bounds__(HELPER ? 2 * kBlock : kBlock) void k_discrete_rollo
 }
 
 // Returns false when the shape does not qualify (caller falls back to k_discrete_step).
-bool launch_discrete_fast(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                          float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                          hipStream_t s, char *name_out) {
+bool launch_discrete_fast(const DiscreteArgs &a, const DiscreteIO &io) {
     if (!a.fast_ok) return false;
     const int grid = (a.N + kBlock - 1) / kBlock;
-    const bool pow2 = a.s_shift != 0xFFFFFFFFu, dl = a.delay > 0, s8 = a.S <= 8;
     // helper waves pay off on long rollouts of full 256-env blocks
-    const bool helper = K >= 32 && (a.N % kBlock) == 0 && a.autoreset && !(a.opts & MDPP_OPT_NO_HELPER);
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_discrete_rollout_fast<OBS64=%d,POW2=%d,DELAY=%d,S8=%d,HELPER=%d>", !a.obs_i32, pow2, dl, s8, helper);
-        return true;
-    }
-#define MDPP_FAST_LAUNCH(O64, P2, DL, S8, HP)                                                   \
-    hipLaunchKernelGGL((k_discrete_rollout_fast<O64, P2, DL, S8, HP>), dim3(grid),             \
-                       dim3(HP ? 2 * kBlock : kBlock), 0, s, a, K, actions, obs, reward, term, \
-                       trunc, final_obs)
-#define MDPP_FAST_L4(O64, P2, DL, S8) do { if (helper) MDPP_FAST_LAUNCH(O64, P2, DL, S8, true); else MDPP_FAST_LAUNCH(O64, P2, DL, S8, false); } while (0)
-#define MDPP_FAST_L3(O64, P2, DL) do { if (s8) MDPP_FAST_L4(O64, P2, DL, true); else MDPP_FAST_L4(O64, P2, DL, false); } while (0)
-#define MDPP_FAST_L2(O64, P2) do { if (dl) MDPP_FAST_L3(O64, P2, true); else MDPP_FAST_L3(O64, P2, false); } while (0)
-    if (a.obs_i32) { if (pow2) MDPP_FAST_L2(false, true); else MDPP_FAST_L2(false, false); }
-    else { if (pow2) MDPP_FAST_L2(true, true); else MDPP_FAST_L2(true, false); }
-#undef MDPP_FAST_L2
-#undef MDPP_FAST_L3
-#undef MDPP_FAST_L4
-#undef MDPP_FAST_LAUNCH
+    const bool helper = io.K >= 32 && (a.N % kBlock) == 0 && a.autoreset && !(a.opts & MDPP_OPT_NO_HELPER);
+    with_bools([&](auto O64, auto P2, auto DL, auto S8, auto HP) {
+        if (io.name_out) snprintf(io.name_out, kNameLen, "k_discrete_rollout_fast<OBS64=%d,POW2=%d,DELAY=%d,S8=%d,HELPER=%d>", O64(), P2(), DL(), S8(), HP());
+        else launch_rollout(k_discrete_rollout_fast<O64(), P2(), DL(), S8(), HP()>, grid, HP() ? 2 * kBlock : kBlock, 0, a, io);
+    }, !a.obs_i32, a.s_shift != 0xFFFFFFFFu, a.delay > 0, a.S <= 8, helper);
     return true;
 }
 

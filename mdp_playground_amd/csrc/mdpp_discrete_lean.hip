@@ -1245,55 +1245,13 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     if (status) atomicOr(&a.status[i], status);
 }
 
+// This unit's instantiations; nz: the noise bits (1 transition, 2 reward; 0 outside the two noise units).
 // Returns false when the shape does not qualify (caller tries k_discrete_rollout_pipe, then _fast).
-#if MDPP_LEAN_TU_NEXT
-bool launch_discrete_lean_next(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                               float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                               hipStream_t s, char *name_out) {
-    constexpr bool kNext = true;
-    if (a.autoreset != MDPP_AUTORESET_NEXT_STEP) return false;
-    const int nz = 0;
-#elif MDPP_LEAN_TU_NOISE == 1
-bool launch_discrete_lean_noise(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                                float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                                hipStream_t s, char *name_out) {
-    constexpr bool kNext = false;
-    const int nz = (a.has_p_noise ? 1 : 0) | (a.has_r_noise ? 2 : 0);
-    if (nz == 0 || a.autoreset == MDPP_AUTORESET_NEXT_STEP || !a.philox || a.irr) return false;
-#elif MDPP_LEAN_TU_NOISE == 2
-bool launch_discrete_lean_npnoise(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                                  float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                                  hipStream_t s, char *name_out) {
-    constexpr bool kNext = false;
-    const int nz = (a.has_p_noise ? 1 : 0) | (a.has_r_noise ? 2 : 0);
-    if (nz == 0 || a.autoreset == MDPP_AUTORESET_NEXT_STEP || a.philox || a.irr) return false;
-#else
-bool launch_discrete_lean_next(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                               float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                               hipStream_t s, char *name_out);
-bool launch_discrete_lean_noise(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                                float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                                hipStream_t s, char *name_out);
-bool launch_discrete_lean_npnoise(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                                  float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                                  hipStream_t s, char *name_out);
-bool launch_discrete_lean(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                          float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                          hipStream_t s, char *name_out) {
-    constexpr bool kNext = false;
-    if (a.autoreset == MDPP_AUTORESET_NEXT_STEP)
-        return launch_discrete_lean_next(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    if ((a.has_p_noise || a.has_r_noise) && !a.philox)
-        return launch_discrete_lean_npnoise(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    // (Philox streams carry no state: a reward-noise key whose sigma is 0 adds 0.0 + 0.0 z = +0.0 whatever the normal is -- the
-    //  noise-free instantiation, whose reward-value table holds the same float64 arithmetic, serves the handle)
-    const bool ph_sig0 = a.philox && !a.has_p_noise && a.has_r_noise && a.r_noise == 0.0 && !(a.opts & MDPP_OPT_NO_SIGMA0);
-    if ((a.has_p_noise || a.has_r_noise) && !ph_sig0)
-        return launch_discrete_lean_noise(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
-    const int nz = 0;
-#endif
+static bool lean_launch(const DiscreteArgs &a, const DiscreteIO &io, const int nz) {
+    constexpr bool kNext = MDPP_LEAN_TU_NEXT;
+    const int K = io.K;
     const bool ph = a.philox != 0, irr = a.irr != 0;
-    if (final_obs) return false;        // (rollouts of K >= 32 steps never ask for final observations: mdpp_step does, K = 1)
+    if (io.final_obs) return false;        // (rollouts of K >= 32 steps never ask for final observations: mdpp_step does, K = 1)
     const bool shape = a.autoreset == MDPP_AUTORESET_NEXT_STEP ? a.lean_next_ok != 0
                        : (nz && !ph) ? a.shape_ok_noise_np != 0
                        : nz ? a.shape_ok_noise != 0
@@ -1307,54 +1265,64 @@ bool launch_discrete_lean(const DiscreteArgs &a, int K, const int32_t *actions, 
     if (irr && (a.S1 > 8 || a.A1 > 16 || (8ULL * 2 * a.N * (unsigned long long)K) >= (1ULL << 32)))
         return false;
     const int grid = (a.N + kBlock - 1) / kBlock;
-    const bool dl = a.delay > 0, hm = a.max_steps > 0, evn = a.every_n > 1;
+    // the name and the launch of one instantiation (NZ: nz, + 4 for Z0)
+    auto go = [&](auto O64, auto DL, auto HM, auto EV, auto PH, auto IR, auto NZ) {
+        if (io.name_out) {
+            int n = snprintf(io.name_out, kNameLen, "k_discrete_rollout_lean<OBS64=%d,DELAY=%d,HASMAX=%d,EVN=%d,PHILOX=%d,IRR=%d,NEXT=%d", O64(), DL(),
+                             HM(), EV(), PH(), IR(), kNext);
+            if (NZ()) n += snprintf(io.name_out + n, kNameLen - n, ",PN=%d,RN=%d%s", NZ() & 1, (NZ() >> 1) & 1, (NZ() & 4) ? ",Z0=1" : "");
+            snprintf(io.name_out + n, kNameLen - n, ">");
+        } else {
+            launch_rollout(k_discrete_rollout_lean<O64(), DL(), HM(), EV(), PH(), IR(), kNext, NZ()>, grid, kRoles * kBlock, 0, a, io);
+        }
+    };
+#if MDPP_LEAN_TU_NOISE
     // sigma-0 reward noise on numpy streams (kernel header, Z0): the draws without their values
     const bool z0 = MDPP_LEAN_TU_NOISE == 2 && (nz & 2) && a.r_noise == 0.0 && !(a.opts & MDPP_OPT_NO_SIGMA0);
-    (void)z0;
-    if (name_out) {
-        if (nz && z0)
-            snprintf(name_out, kNameLen, "k_discrete_rollout_lean<OBS64=%d,DELAY=%d,HASMAX=%d,EVN=%d,PHILOX=%d,IRR=%d,NEXT=%d,PN=%d,RN=%d,Z0=1>",
-                     !a.obs_i32, dl, hm, evn, ph, irr, kNext, nz & 1, (nz >> 1) & 1);
-        else if (nz)
-            snprintf(name_out, kNameLen, "k_discrete_rollout_lean<OBS64=%d,DELAY=%d,HASMAX=%d,EVN=%d,PHILOX=%d,IRR=%d,NEXT=%d,PN=%d,RN=%d>",
-                     !a.obs_i32, dl, hm, evn, ph, irr, kNext, nz & 1, (nz >> 1) & 1);
-        else
-            snprintf(name_out, kNameLen, "k_discrete_rollout_lean<OBS64=%d,DELAY=%d,HASMAX=%d,EVN=%d,PHILOX=%d,IRR=%d,NEXT=%d>", !a.obs_i32, dl, hm, evn, ph, irr, kNext);
-        return true;
-    }
-#if MDPP_LEAN_TU_NOISE
-#define MDPP_LEAN_GO(O64, DL, HM, EV, NZ_)                                                                   \
-    hipLaunchKernelGGL((k_discrete_rollout_lean<O64, DL, HM, EV, MDPP_LEAN_TU_NOISE == 1, false, false, NZ_>), dim3(grid), dim3(kRoles * kBlock), \
-                       0, s, a, K, actions, obs, reward, term, trunc, final_obs)
-#define MDPP_LEAN_LAUNCH(O64, DL, HM, EV)                                                                   \
-    do {                                                                                                   \
-        if (MDPP_LEAN_TU_NOISE == 2 && z0 && nz == 3) MDPP_LEAN_GO(O64, DL, HM, EV, (MDPP_LEAN_TU_NOISE == 2 ? 7 : 3));   \
-        else if (MDPP_LEAN_TU_NOISE == 2 && z0) MDPP_LEAN_GO(O64, DL, HM, EV, (MDPP_LEAN_TU_NOISE == 2 ? 6 : 2));          \
-        else if (nz == 3) MDPP_LEAN_GO(O64, DL, HM, EV, 3);                                                \
-        else if (nz == 2) MDPP_LEAN_GO(O64, DL, HM, EV, 2);                                                \
-        else MDPP_LEAN_GO(O64, DL, HM, EV, 1);                                                             \
-    } while (0)
+    with_bools([&](auto O64, auto DL, auto HM, auto EV) {
+        with_value<1, 2, 3, 6, 7>(nz | (z0 ? 4 : 0), [&](auto NZ) {
+            if constexpr (NZ() < 4 || MDPP_LEAN_TU_NOISE == 2)
+                go(O64, DL, HM, EV, std::bool_constant<MDPP_LEAN_TU_NOISE == 1>{}, std::false_type{}, NZ);
+        });
+    }, !a.obs_i32, a.delay > 0, a.max_steps > 0, a.every_n > 1);
 #else
-#define MDPP_LEAN_GO(O64, DL, HM, EV, PH, IR)                                                                \
-    hipLaunchKernelGGL((k_discrete_rollout_lean<O64, DL, HM, EV, PH, IR, kNext>), dim3(grid), dim3(kRoles * kBlock), \
-                       0, s, a, K, actions, obs, reward, term, trunc, final_obs)
-#define MDPP_LEAN_LAUNCH(O64, DL, HM, EV)                                                                   \
-    do {                                                                                                   \
-        if (ph && irr) MDPP_LEAN_GO(O64, DL, HM, EV, true, true);                                          \
-        else if (ph) MDPP_LEAN_GO(O64, DL, HM, EV, true, false);                                           \
-        else if (irr) MDPP_LEAN_GO(O64, DL, HM, EV, false, true);                                          \
-        else MDPP_LEAN_GO(O64, DL, HM, EV, false, false);                                                  \
-    } while (0)
+    with_bools([&](auto O64, auto DL, auto HM, auto EV, auto PH, auto IR) {
+        go(O64, DL, HM, EV, PH, IR, std::integral_constant<int, 0>{});
+    }, !a.obs_i32, a.delay > 0, a.max_steps > 0, a.every_n > 1, ph, irr);
 #endif
-#define MDPP_LEAN_L3(O64, DL, HM) do { if (evn) MDPP_LEAN_LAUNCH(O64, DL, HM, true); else MDPP_LEAN_LAUNCH(O64, DL, HM, false); } while (0)
-#define MDPP_LEAN_L2(O64, DL) do { if (hm) MDPP_LEAN_L3(O64, DL, true); else MDPP_LEAN_L3(O64, DL, false); } while (0)
-    if (a.obs_i32) { if (dl) MDPP_LEAN_L2(false, true); else MDPP_LEAN_L2(false, false); }
-    else { if (dl) MDPP_LEAN_L2(true, true); else MDPP_LEAN_L2(true, false); }
-#undef MDPP_LEAN_GO
-#undef MDPP_LEAN_L2
-#undef MDPP_LEAN_L3
-#undef MDPP_LEAN_LAUNCH
     return true;
 }
+
+#if MDPP_LEAN_TU_NEXT
+bool launch_discrete_lean_next(const DiscreteArgs &a, const DiscreteIO &io) {
+    if (a.autoreset != MDPP_AUTORESET_NEXT_STEP) return false;
+    return lean_launch(a, io, 0);
+}
+#elif MDPP_LEAN_TU_NOISE == 1
+bool launch_discrete_lean_noise(const DiscreteArgs &a, const DiscreteIO &io) {
+    const int nz = (a.has_p_noise ? 1 : 0) | (a.has_r_noise ? 2 : 0);
+    if (nz == 0 || a.autoreset == MDPP_AUTORESET_NEXT_STEP || !a.philox || a.irr) return false;
+    return lean_launch(a, io, nz);
+}
+#elif MDPP_LEAN_TU_NOISE == 2
+bool launch_discrete_lean_npnoise(const DiscreteArgs &a, const DiscreteIO &io) {
+    const int nz = (a.has_p_noise ? 1 : 0) | (a.has_r_noise ? 2 : 0);
+    if (nz == 0 || a.autoreset == MDPP_AUTORESET_NEXT_STEP || a.philox || a.irr) return false;
+    return lean_launch(a, io, nz);
+}
+#else
+bool launch_discrete_lean_next(const DiscreteArgs &a, const DiscreteIO &io);
+bool launch_discrete_lean_noise(const DiscreteArgs &a, const DiscreteIO &io);
+bool launch_discrete_lean_npnoise(const DiscreteArgs &a, const DiscreteIO &io);
+bool launch_discrete_lean(const DiscreteArgs &a, const DiscreteIO &io) {
+    if (a.autoreset == MDPP_AUTORESET_NEXT_STEP) return launch_discrete_lean_next(a, io);
+    if ((a.has_p_noise || a.has_r_noise) && !a.philox) return launch_discrete_lean_npnoise(a, io);
+    // (Philox streams carry no state: a reward-noise key whose sigma is 0 adds 0.0 + 0.0 z = +0.0 whatever the normal is -- the
+    //  noise-free instantiation, whose reward-value table holds the same float64 arithmetic, serves the handle)
+    const bool ph_sig0 = a.philox && !a.has_p_noise && a.has_r_noise && a.r_noise == 0.0 && !(a.opts & MDPP_OPT_NO_SIGMA0);
+    if ((a.has_p_noise || a.has_r_noise) && !ph_sig0) return launch_discrete_lean_noise(a, io);
+    return lean_launch(a, io, 0);
+}
+#endif
 
 } // namespace mdpp

@@ -374,26 +374,12 @@ __global__ __launch_bounds__(3 * kBlock) void k_discrete_rollout_pipe(DiscreteAr
 }
 
 // Returns false when the shape does not qualify (caller uses k_discrete_rollout_fast).
-bool launch_discrete_pipe(const DiscreteArgs &a, int K, const int32_t *actions, void *obs,
-                          float *reward, uint8_t *term, uint8_t *trunc, void *final_obs,
-                          hipStream_t s, char *name_out) {
-    if (!a.fast_ok || K < 32 || (a.N % kBlock) != 0 || !a.autoreset || (a.opts & MDPP_OPT_NO_PIPE)) return false;
-    const int grid = a.N / kBlock;
-    const bool pow2 = a.s_shift != 0xFFFFFFFFu, dl = a.delay > 0, s8 = a.S <= 8;
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_discrete_rollout_pipe<OBS64=%d,POW2=%d,DELAY=%d,S8=%d>", !a.obs_i32, pow2, dl, s8);
-        return true;
-    }
-#define MDPP_PIPE_LAUNCH(O64, P2, DL, S8)                                                         \
-    hipLaunchKernelGGL((k_discrete_rollout_pipe<O64, P2, DL, S8>), dim3(grid), dim3(3 * kBlock), \
-                       0, s, a, K, actions, obs, reward, term, trunc, final_obs)
-#define MDPP_PIPE_L3(O64, P2, DL) do { if (s8) MDPP_PIPE_LAUNCH(O64, P2, DL, true); else MDPP_PIPE_LAUNCH(O64, P2, DL, false); } while (0)
-#define MDPP_PIPE_L2(O64, P2) do { if (dl) MDPP_PIPE_L3(O64, P2, true); else MDPP_PIPE_L3(O64, P2, false); } while (0)
-    if (a.obs_i32) { if (pow2) MDPP_PIPE_L2(false, true); else MDPP_PIPE_L2(false, false); }
-    else { if (pow2) MDPP_PIPE_L2(true, true); else MDPP_PIPE_L2(true, false); }
-#undef MDPP_PIPE_L2
-#undef MDPP_PIPE_L3
-#undef MDPP_PIPE_LAUNCH
+bool launch_discrete_pipe(const DiscreteArgs &a, const DiscreteIO &io) {
+    if (!a.fast_ok || io.K < 32 || (a.N % kBlock) != 0 || !a.autoreset || (a.opts & MDPP_OPT_NO_PIPE)) return false;
+    with_bools([&](auto O64, auto P2, auto DL, auto S8) {
+        if (io.name_out) snprintf(io.name_out, kNameLen, "k_discrete_rollout_pipe<OBS64=%d,POW2=%d,DELAY=%d,S8=%d>", O64(), P2(), DL(), S8());
+        else launch_rollout(k_discrete_rollout_pipe<O64(), P2(), DL(), S8()>, a.N / kBlock, 3 * kBlock, 0, a, io);
+    }, !a.obs_i32, a.s_shift != 0xFFFFFFFFu, a.delay > 0, a.S <= 8);
     return true;
 }
 

@@ -1072,8 +1072,12 @@ __global__ __launch_bounds__((ROLES + NPH) * kBlock) void k_discrete_rollout_qui
 #define MDPP_QUIET_TU_NU 0         // 1: this translation unit holds the non-unit-reward instantiations (mdpp_discrete_quiet_nu.hip)
 #endif
 template <bool O64, bool IR, int ROLES, bool PN, bool RN, bool PH = false, int NPH = 0, bool UR = true, bool SF = false, bool PE = false>
-static void quiet_launch(const DiscreteArgs &a, int K, size_t lds, const int32_t *actions, void *obs, float *reward,
-                         uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s) {
+static void quiet_launch(const DiscreteArgs &a, const DiscreteIO &io, size_t lds) {
+    if (io.name_out) {              // (trailing default arguments are named only when set)
+        snprintf(io.name_out, kNameLen, "k_discrete_rollout_quiet<OBS64=%d,IRR=%d,ROLES=%d,PN=%d,RN=%d,PHILOX=%d,NPH=%d%s%s%s>", O64, IR, ROLES, PN, RN,
+                 PH, NPH, UR ? "" : ",UNIT=0", SF ? ",SF=1" : "", PE ? ",PE=1" : "");
+        return;
+    }
     auto kern = k_discrete_rollout_quiet<O64, IR, ROLES, PN, RN, PH, NPH, UR, SF, PE>;
     if (lds > 48 * 1024) {                        // tables + record ring beyond the default dynamic-LDS limit
         static size_t allowed = 0;                // (per instantiation)
@@ -1083,14 +1087,14 @@ static void quiet_launch(const DiscreteArgs &a, int K, size_t lds, const int32_t
         }
     }
     const int grid = (a.N + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3((ROLES + NPH) * kBlock), lds, s, a, K, actions, obs, reward, term, trunc, final_obs);
+    launch_rollout(kern, grid, (ROLES + NPH) * kBlock, lds, a, io);
 }
 
 #if MDPP_QUIET_TU_NU
 // The non-unit-reward form (UR = false): numpy streams, no irrelevant sub-space, sequence rewards (not the custom R(s, a)
 // matrix, whose key E does not make).  Same role rules as below.
-bool launch_discrete_quiet_nu(const DiscreteArgs &a, int K, const int32_t *actions, void *obs, float *reward,
-                              uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out) {
+bool launch_discrete_quiet_nu(const DiscreteArgs &a, const DiscreteIO &io) {
+    const int K = io.K;
     if (!a.shared_tables || a.unit_rewards || a.rew_sa || !a.rew_in_lds || a.irr || a.philox || K < 16 || (a.opts & MDPP_OPT_NO_QUIET))
         return false;
     if (a.nkeys >= (1u << 27) || (a.delay > 0 && !a.ring_keys)) return false;       // (the record carries 27 bits of key)
@@ -1117,39 +1121,22 @@ bool launch_discrete_quiet_nu(const DiscreteArgs &a, int K, const int32_t *actio
     // SF (kernel header): the reference's sweep defaults fixed at compile time
     const bool sf = roles == 3 && !pn && a.L == 1 && a.autoreset == MDPP_AUTORESET_SAME_STEP && a.max_steps == 0 && a.every_n == 1 &&
                     a.S <= 128 && !(a.opts & MDPP_OPT_NO_QUIET_SF);
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_discrete_rollout_quiet<OBS64=%d,IRR=0,ROLES=%d,PN=%d,RN=%d,PHILOX=0,NPH=0,UNIT=0%s>", !a.obs_i32, roles, pn, rn, sf ? ",SF=1" : "");
-        return true;
-    }
     const size_t l = roles == 1 ? lds : lds_duo + (xr ? xr_val_bytes : 0);
-#define MDPP_QN_ARGS a, K, l, actions, obs, reward, term, trunc, final_obs, s
-#define MDPP_QN_ROLES(O64, PN_, RN_)                                                                      \
-    do {                                                                                                  \
-        if (roles == 3 && sf) { if constexpr (!PN_) quiet_launch<O64, false, 3, PN_, RN_, false, 0, false, !PN_>(MDPP_QN_ARGS); } \
-        else if (roles == 3) { if constexpr (!RN_ || !PN_) quiet_launch<O64, false, 3, PN_, RN_, false, 0, false>(MDPP_QN_ARGS); } \
-        else if (roles == 2) quiet_launch<O64, false, 2, PN_, RN_, false, 0, false>(MDPP_QN_ARGS);        \
-        else quiet_launch<O64, false, 1, PN_, RN_, false, 0, false>(MDPP_QN_ARGS);                        \
-    } while (0)
-#define MDPP_QN_NOISE(O64)                                                                                \
-    do {                                                                                                  \
-        if (pn && rn) MDPP_QN_ROLES(O64, true, true);                                                     \
-        else if (pn) MDPP_QN_ROLES(O64, true, false);                                                     \
-        else if (rn) MDPP_QN_ROLES(O64, false, true);                                                     \
-        else MDPP_QN_ROLES(O64, false, false);                                                            \
-    } while (0)
-    if (a.obs_i32) MDPP_QN_NOISE(false); else MDPP_QN_NOISE(true);
-#undef MDPP_QN_NOISE
-#undef MDPP_QN_ROLES
-#undef MDPP_QN_ARGS
+    with_bools([&](auto O64, auto PN, auto RN, auto SF) {
+        with_value<1, 2, 3>(roles, [&](auto R) {
+            if constexpr (SF()) { if constexpr (R() == 3 && !PN()) quiet_launch<O64(), false, 3, PN(), RN(), false, 0, false, true>(a, io, l); }
+            else if constexpr (R() == 3) { if constexpr (!RN() || !PN()) quiet_launch<O64(), false, 3, PN(), RN(), false, 0, false>(a, io, l); }
+            else quiet_launch<O64(), false, R(), PN(), RN(), false, 0, false>(a, io, l);
+        });
+    }, !a.obs_i32, pn, rn, sf);
     return true;
 }
 #else
-bool launch_discrete_quiet_nu(const DiscreteArgs &a, int K, const int32_t *actions, void *obs, float *reward,
-                              uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out);
+bool launch_discrete_quiet_nu(const DiscreteArgs &a, const DiscreteIO &io);
 // Serves the launch if the handle and the launch shape qualify; false = not taken.
-bool launch_discrete_quiet(const DiscreteArgs &a, int K, const int32_t *actions, void *obs, float *reward,
-                           uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out) {
-    if (!a.unit_rewards) return launch_discrete_quiet_nu(a, K, actions, obs, reward, term, trunc, final_obs, s, name_out);
+bool launch_discrete_quiet(const DiscreteArgs &a, const DiscreteIO &io) {
+    if (!a.unit_rewards) return launch_discrete_quiet_nu(a, io);
+    const int K = io.K;
     if (!a.shared_tables) {
         // PE (kernel header): one MDP per env, each lane's tables in its slot of the workgroup's LDS, three roles
         const bool rn = a.has_r_noise != 0;
@@ -1167,17 +1154,9 @@ bool launch_discrete_quiet(const DiscreteArgs &a, int K, const int32_t *actions,
         if (l + (rn ? 32u : 20u) * 1024u > 160u * 1024u) return false;     // (+ the instantiation's static LDS: X's meta ring, ziggurat tables, counters)
         const bool sf = a.L == 1 && a.autoreset == MDPP_AUTORESET_SAME_STEP && a.max_steps == 0 && a.every_n == 1 &&
                         !(a.opts & MDPP_OPT_NO_QUIET_SF);
-        if (name_out) {
-            snprintf(name_out, kNameLen, "k_discrete_rollout_quiet<OBS64=%d,IRR=0,ROLES=3,PN=0,RN=%d,PHILOX=0,NPH=0%s,PE=1>", !a.obs_i32, rn,
-                     sf ? ",SF=1" : "");
-            return true;
-        }
-#define MDPP_QPE(O64, RN_, SF_) quiet_launch<O64, false, 3, false, RN_, false, 0, true, SF_, true>(a, K, l, actions, obs, reward, term, trunc, final_obs, s)
-#define MDPP_QPE2(O64) do { if (rn) { if (sf) MDPP_QPE(O64, true, true); else MDPP_QPE(O64, true, false); } \
-                            else { if (sf) MDPP_QPE(O64, false, true); else MDPP_QPE(O64, false, false); } } while (0)
-        if (a.obs_i32) MDPP_QPE2(false); else MDPP_QPE2(true);
-#undef MDPP_QPE2
-#undef MDPP_QPE
+        with_bools([&](auto O64, auto RN, auto SF) {
+            quiet_launch<O64(), false, 3, false, RN(), false, 0, true, SF(), true>(a, io, l);
+        }, !a.obs_i32, rn, sf);
         return true;
     }
     if (!a.shared_tables || !a.unit_rewards || !a.rew_in_lds || a.fast_ok || K < 16 || (a.opts & MDPP_OPT_NO_QUIET))
@@ -1214,37 +1193,18 @@ bool launch_discrete_quiet(const DiscreteArgs &a, int K, const int32_t *actions,
     // Philox handles in two roles without an irrelevant sub-space: two producer waves on top (see NPH)
     const int nph = (ph && duo && !a.irr && a.autoreset && lds_duo + 72 * 1024 <= 150 * 1024 &&
                      !(a.opts & MDPP_OPT_NO_TRIO)) ? 2 : 0;
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_discrete_rollout_quiet<OBS64=%d,IRR=%d,ROLES=%d,PN=%d,RN=%d,PHILOX=%d,NPH=%d%s>", !a.obs_i32,
-                 a.irr != 0, roles, pn, rn, ph, nph, sf ? ",SF=1" : "");
-        return true;
-    }
     const size_t l = roles == 1 ? lds : lds_duo + (xr ? xr_val_bytes : 0);
-#define MDPP_Q_ARGS a, K, l, actions, obs, reward, term, trunc, final_obs, s
-#define MDPP_Q_ROLES(O64, IR, PN_, RN_)                                                           \
-    do {                                                                                          \
-        if (ph) {                                                                                 \
-            if (nph == 2) { if constexpr (!IR) quiet_launch<O64, IR, 2, PN_, RN_, true, 2>(MDPP_Q_ARGS); } \
-            else if (roles == 2) quiet_launch<O64, IR, 2, PN_, RN_, true>(MDPP_Q_ARGS);           \
-            else quiet_launch<O64, IR, 1, PN_, RN_, true>(MDPP_Q_ARGS);                           \
-        }                                                                                         \
-        else if (roles == 3 && sf) { if constexpr (!PN_ && !IR) quiet_launch<O64, IR, 3, PN_, RN_, false, 0, true, !PN_ && !IR>(MDPP_Q_ARGS); }  \
-        else if (roles == 3) { if constexpr (!RN_ || (!PN_ && !IR)) quiet_launch<O64, IR, 3, PN_, RN_>(MDPP_Q_ARGS); }  \
-        else if (roles == 2) quiet_launch<O64, IR, 2, PN_, RN_>(MDPP_Q_ARGS);                     \
-        else quiet_launch<O64, IR, 1, PN_, RN_>(MDPP_Q_ARGS);                                     \
-    } while (0)
-#define MDPP_Q_NOISE(O64, IR)                                                                     \
-    do {                                                                                          \
-        if (pn && rn) MDPP_Q_ROLES(O64, IR, true, true);                                          \
-        else if (pn) MDPP_Q_ROLES(O64, IR, true, false);                                          \
-        else if (rn) MDPP_Q_ROLES(O64, IR, false, true);                                          \
-        else MDPP_Q_ROLES(O64, IR, false, false);                                                 \
-    } while (0)
-    if (a.irr) { if (a.obs_i32) MDPP_Q_NOISE(false, true); else MDPP_Q_NOISE(true, true); }
-    else { if (a.obs_i32) MDPP_Q_NOISE(false, false); else MDPP_Q_NOISE(true, false); }
-#undef MDPP_Q_NOISE
-#undef MDPP_Q_ROLES
-#undef MDPP_Q_ARGS
+    with_bools([&](auto O64, auto IR, auto PN, auto RN, auto PH, auto NPH2, auto SF) {
+        with_value<1, 2, 3>(roles, [&](auto R) {
+            if constexpr (PH()) {       // (Philox: one or two roles; SF is a numpy-stream form)
+                if constexpr (NPH2()) { if constexpr (!IR() && R() == 2 && !SF()) quiet_launch<O64(), IR(), 2, PN(), RN(), true, 2>(a, io, l); }
+                else if constexpr (R() < 3 && !SF()) quiet_launch<O64(), IR(), R(), PN(), RN(), true>(a, io, l);
+            }
+            else if constexpr (SF()) { if constexpr (R() == 3 && !PN() && !IR()) quiet_launch<O64(), IR(), 3, PN(), RN(), false, 0, true, true>(a, io, l); }
+            else if constexpr (R() == 3) { if constexpr (!RN() || (!PN() && !IR())) quiet_launch<O64(), IR(), 3, PN(), RN()>(a, io, l); }
+            else quiet_launch<O64(), IR(), R(), PN(), RN()>(a, io, l);
+        });
+    }, !a.obs_i32, a.irr != 0, pn, rn, ph, nph == 2, sf);
     return true;
 }
 #endif   // !MDPP_QUIET_TU_NU

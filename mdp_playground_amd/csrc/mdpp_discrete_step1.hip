@@ -361,51 +361,32 @@ __global__ __launch_bounds__(64) void k_discrete_step1w(Step1Args a) {
     }
 }
 
-bool launch_discrete_step1(const DiscreteArgs &d, const Step1Args &proto, const int32_t *actions, void *obs, float *reward,
-                           uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out) {
+bool launch_discrete_step1(const DiscreteArgs &d, const Step1Args &proto, const DiscreteIO &io) {
     if (!proto.blob || (d.opts & MDPP_OPT_NO_STEP1)) return false;
+    const bool noise = proto.has_p_noise || proto.has_r_noise;
     if (proto.wide) {                               // state spaces beyond 16 states: k_discrete_step1w
         if (d.philox && (d.opts & MDPP_OPT_NO_PHILOX_FAST)) return false;
-        if (proto.blob_rounds > ((proto.has_p_noise || proto.has_r_noise) ? kS1wRoundsNoise : kS1wRounds)) return false;
-        if (name_out) {
-            if (proto.has_p_noise || proto.has_r_noise)
-                snprintf(name_out, kNameLen, "k_discrete_step1w<OBS64=%d,PHILOX=%d,UNIT=1,PN=%d,RN=%d>", !d.obs_i32, d.philox, proto.has_p_noise, proto.has_r_noise);
-            else
-            snprintf(name_out, kNameLen, "k_discrete_step1w<OBS64=%d,PHILOX=%d,UNIT=%d>", !d.obs_i32, d.philox, proto.unit);
-            return true;
-        }
-        Step1Args a = proto;
-        a.actions = actions; a.obs = obs; a.reward = reward; a.term = term; a.trunc = trunc; a.final_obs = final_obs;
-        a.ptick = d.ptick; a.dtick = d.dtick; a.ring_head = d.tick;
-        const int grid = (a.N + 63) / 64;
-        const size_t lds = (size_t)a.blob_rounds * 1024;
-#define MDPP_S1W(O64, PH)                                                                                           \
-    do {                                                                                                            \
-        if (a.has_p_noise || a.has_r_noise) hipLaunchKernelGGL((k_discrete_step1w<O64, PH, true, true>), dim3(grid), dim3(64), lds, s, a); \
-        else if (a.unit) hipLaunchKernelGGL((k_discrete_step1w<O64, PH, true>), dim3(grid), dim3(64), lds, s, a);   \
-        else hipLaunchKernelGGL((k_discrete_step1w<O64, PH, false>), dim3(grid), dim3(64), lds, s, a);             \
-    } while (0)
-        if (d.philox) { if (d.obs_i32) MDPP_S1W(false, true); else MDPP_S1W(true, true); }
-        else { if (d.obs_i32) MDPP_S1W(false, false); else MDPP_S1W(true, false); }
-#undef MDPP_S1W
-        return true;
-    }
-    if (d.philox ? (!d.shape_ok || (d.opts & MDPP_OPT_NO_PHILOX_FAST)) : !d.fast_ok) return false;
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_discrete_step1<OBS64=%d,PHILOX=%d>", !d.obs_i32, d.philox);
-        return true;
+        if (proto.blob_rounds > (noise ? kS1wRoundsNoise : kS1wRounds)) return false;
+    } else if (d.philox ? (!d.shape_ok || (d.opts & MDPP_OPT_NO_PHILOX_FAST)) : !d.fast_ok) {
+        return false;
     }
     Step1Args a = proto;
-    a.actions = actions; a.obs = obs; a.reward = reward; a.term = term; a.trunc = trunc; a.final_obs = final_obs;
+    a.actions = io.actions; a.obs = io.obs; a.reward = io.reward; a.term = io.term; a.trunc = io.trunc; a.final_obs = io.final_obs;
     a.ptick = d.ptick; a.dtick = d.dtick;
+    if (proto.wide) a.ring_head = d.tick;
     const int grid = (a.N + 63) / 64;
-    if (d.philox) {
-        if (d.obs_i32) hipLaunchKernelGGL((k_discrete_step1<false, true>), dim3(grid), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((k_discrete_step1<true, true>), dim3(grid), dim3(64), 0, s, a);
-    } else {
-        if (d.obs_i32) hipLaunchKernelGGL((k_discrete_step1<false, false>), dim3(grid), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((k_discrete_step1<true, false>), dim3(grid), dim3(64), 0, s, a);
-    }
+    with_bools([&](auto O64, auto PH, auto WIDE, auto NZ, auto UNIT) {
+        if constexpr (!WIDE()) {
+            if (io.name_out) snprintf(io.name_out, kNameLen, "k_discrete_step1<OBS64=%d,PHILOX=%d>", O64(), PH());
+            else hipLaunchKernelGGL((k_discrete_step1<O64(), PH()>), dim3(grid), dim3(64), 0, io.s, a);
+        } else if constexpr (NZ()) {                // (noisy handles: unit rewards)
+            if (io.name_out) snprintf(io.name_out, kNameLen, "k_discrete_step1w<OBS64=%d,PHILOX=%d,UNIT=1,PN=%d,RN=%d>", O64(), PH(), a.has_p_noise, a.has_r_noise);
+            else hipLaunchKernelGGL((k_discrete_step1w<O64(), PH(), true, true>), dim3(grid), dim3(64), (size_t)a.blob_rounds * 1024, io.s, a);
+        } else {
+            if (io.name_out) snprintf(io.name_out, kNameLen, "k_discrete_step1w<OBS64=%d,PHILOX=%d,UNIT=%d>", O64(), PH(), UNIT());
+            else hipLaunchKernelGGL((k_discrete_step1w<O64(), PH(), UNIT()>), dim3(grid), dim3(64), (size_t)a.blob_rounds * 1024, io.s, a);
+        }
+    }, !d.obs_i32, d.philox != 0, proto.wide != 0, noise, proto.unit != 0);
     return true;
 }
 

@@ -482,62 +482,27 @@ __global__ __launch_bounds__(kBlock) void k_grid_rollout_fast(GridArgs a, int K,
     if (status) atomicOr(&a.status[i], status);
 }
 
-int launch_grid_step(mdpp_env *h, int K, const int32_t *actions, void *obs, float *reward, uint8_t *term,
-                     uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out) {
+int launch_grid_step(mdpp_env *h, const DiscreteIO &io) {
+    const int K = io.K;
     GridArgs a = h->gargs;
-    a.opts = h->opts;
-    a.ptick = h->tick;
-    a.dtick = h->graph_capture ? (const uint64_t *)h->d_tick_off : nullptr;     // (launches being captured into a HIP graph)
+    stamp_step(a, h);
     const int grid = (a.N + kBlock - 1) / kBlock;
-    const bool noise = a.has_p_noise || a.has_r_noise;
+    const bool pn = a.has_p_noise != 0, rn = a.has_r_noise != 0, noise = pn || rn;
     // quiet numpy-stream handles: the fused rollout kernel (< 4 GiB per output array per launch)
     if (!a.est.cur && !(a.philox && (a.opts & MDPP_OPT_NO_PHILOX_FAST)) &&
         !(noise && (a.opts & MDPP_OPT_NO_GFAST_NOISE)) && !(a.opts & MDPP_OPT_NO_GFAST) &&
         (unsigned long long)K * a.N * a.G * 8ULL < (1ULL << 32)) {
-        const bool pn = a.has_p_noise != 0, rn = a.has_r_noise != 0;
-        if (name_out) {
-            snprintf(name_out, kNameLen, "k_grid_rollout_fast<OBS64=%d,G4=%d,DENSE=%d,PN=%d,RN=%d,PHILOX=%d>", !a.obs_i32, a.G == 4,
-                     a.make_denser != 0, pn, rn, a.philox != 0);
-            return MDPP_OK;
-        }
-#define MDPP_GF_LAUNCH(O64, G4, DN, PN_, RN_)                                                                                   \
-    do {                                                                                                                        \
-        if (a.philox) hipLaunchKernelGGL((k_grid_rollout_fast<O64, G4, DN, PN_, RN_, true>), dim3(grid), dim3(kBlock), 0, s, a, \
-                                         K, actions, obs, reward, term, trunc, final_obs);                                      \
-        else hipLaunchKernelGGL((k_grid_rollout_fast<O64, G4, DN, PN_, RN_, false>), dim3(grid), dim3(kBlock), 0, s, a, K,      \
-                                actions, obs, reward, term, trunc, final_obs);                                                  \
-    } while (0)
-#define MDPP_GF_NZ(O64, G4, DN)                                                  \
-    do {                                                                         \
-        if (pn && rn) MDPP_GF_LAUNCH(O64, G4, DN, true, true);                   \
-        else if (pn) MDPP_GF_LAUNCH(O64, G4, DN, true, false);                   \
-        else if (rn) MDPP_GF_LAUNCH(O64, G4, DN, false, true);                   \
-        else MDPP_GF_LAUNCH(O64, G4, DN, false, false);                          \
-    } while (0)
-#define MDPP_GF_DN(O64, G4) do { if (a.make_denser) MDPP_GF_NZ(O64, G4, true); else MDPP_GF_NZ(O64, G4, false); } while (0)
-        if (a.obs_i32) { if (a.G == 4) MDPP_GF_DN(false, true); else MDPP_GF_DN(false, false); }
-        else { if (a.G == 4) MDPP_GF_DN(true, true); else MDPP_GF_DN(true, false); }
-#undef MDPP_GF_DN
-#undef MDPP_GF_NZ
-#undef MDPP_GF_LAUNCH
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("k_grid_rollout_fast launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-        h->tick += (uint64_t)K;
-        return MDPP_OK;
+        with_bools([&](auto O64, auto G4, auto DN, auto PN, auto RN, auto PH) {
+            if (io.name_out) snprintf(io.name_out, kNameLen, "k_grid_rollout_fast<OBS64=%d,G4=%d,DENSE=%d,PN=%d,RN=%d,PHILOX=%d>", O64(), G4(), DN(), PN(), RN(), PH());
+            else launch_rollout(k_grid_rollout_fast<O64(), G4(), DN(), PN(), RN(), PH()>, grid, kBlock, 0, a, io);
+        }, !a.obs_i32, a.G == 4, a.make_denser != 0, pn, rn, a.philox != 0);
+        return io.name_out ? MDPP_OK : step_done(h, K, "k_grid_rollout_fast");
     }
-    if (name_out) {
-        snprintf(name_out, kNameLen, "k_grid_step<PHILOX=%d,NOISE=%d>", a.philox != 0, noise);
-        return MDPP_OK;
-    }
-#define MDPP_G_LAUNCH(PH, NZ) hipLaunchKernelGGL((k_grid_step<PH, NZ>), dim3(grid), dim3(kBlock), 0, s, a, K, actions, \
-                                                 obs, reward, term, trunc, final_obs)
-    if (a.philox) { if (noise) MDPP_G_LAUNCH(true, true); else MDPP_G_LAUNCH(true, false); }
-    else { if (noise) MDPP_G_LAUNCH(false, true); else MDPP_G_LAUNCH(false, false); }
-#undef MDPP_G_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("k_grid_step launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-    h->tick += (uint64_t)K;
-    return MDPP_OK;
+    with_bools([&](auto PH, auto NZ) {
+        if (io.name_out) snprintf(io.name_out, kNameLen, "k_grid_step<PHILOX=%d,NOISE=%d>", PH(), NZ());
+        else launch_rollout(k_grid_step<PH(), NZ()>, grid, kBlock, 0, a, io);
+    }, a.philox != 0, noise);
+    return io.name_out ? MDPP_OK : step_done(h, K, "k_grid_step");
 }
 
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s) {

@@ -874,29 +874,22 @@ int launch_image_step1(mdpp_env *h, const int32_t *state_out, const int32_t *sta
     (void)c;
     ImageArgs a = image_args(h, 1, false, 0);
     const size_t lds_bytes = image_fast_lds(h, a);
-    if (a.colb != 64) {                          // wide templates: two waves per workgroup (render_wide)
-        const dim3 wgrid((unsigned)((a.N + kWideBlock / 64 - 1) / (kWideBlock / 64)));
-        if (a.philox) hipLaunchKernelGGL((k_image_step1<0, true, true>), wgrid, dim3(kWideBlock), lds_bytes, s, a, state_out, state_final,
-                                         term, trunc, img_out, img_final);
-        else hipLaunchKernelGGL((k_image_step1<0, false, true>), wgrid, dim3(kWideBlock), lds_bytes, s, a, state_out, state_final,
-                                term, trunc, img_out, img_final);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("k_image_step1 launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
-        return 1;
-    }
-    const dim3 grid((unsigned)((a.N + kBlock / 64 - 1) / (kBlock / 64)));
-    const int nst = (int)(((size_t)a.W * a.H / 16 + 63) / 64);
-#define MDPP_IMG_S1(NST_)                                                                                                     \
-    do {                                                                                                                      \
-        if (a.philox) hipLaunchKernelGGL((k_image_step1<NST_, true>), grid, dim3(kBlock), lds_bytes, s, a, state_out, state_final, \
-                                         term, trunc, img_out, img_final);                                                    \
-        else hipLaunchKernelGGL((k_image_step1<NST_, false>), grid, dim3(kBlock), lds_bytes, s, a, state_out, state_final,   \
-                                term, trunc, img_out, img_final);                                                             \
-    } while (0)
-    if (nst == 7) MDPP_IMG_S1(7);          // 84 x 84
-    else if (nst == 4) MDPP_IMG_S1(4);     // 64 x 64
-    else MDPP_IMG_S1(0);
-#undef MDPP_IMG_S1
+    with_bools([&](auto PH) {
+        if (a.colb != 64) {                          // wide templates: two waves per workgroup (render_wide)
+            const dim3 wgrid((unsigned)((a.N + kWideBlock / 64 - 1) / (kWideBlock / 64)));
+            hipLaunchKernelGGL((k_image_step1<0, PH(), true>), wgrid, dim3(kWideBlock), lds_bytes, s, a, state_out, state_final, term, trunc,
+                               img_out, img_final);
+            return;
+        }
+        const dim3 grid((unsigned)((a.N + kBlock / 64 - 1) / (kBlock / 64)));
+        const int nst = (int)(((size_t)a.W * a.H / 16 + 63) / 64);
+        auto go = [&](auto NST) {
+            hipLaunchKernelGGL((k_image_step1<NST(), PH()>), grid, dim3(kBlock), lds_bytes, s, a, state_out, state_final, term, trunc, img_out,
+                               img_final);
+        };
+        // (7: 84 x 84; 4: 64 x 64; any other size: 0)
+        if (!with_value<7, 4>(nst, go)) go(std::integral_constant<int, 0>{});
+    }, a.philox != 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->err = std::string("k_image_step1 launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
     return 1;

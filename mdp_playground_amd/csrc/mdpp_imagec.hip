@@ -203,12 +203,11 @@ int launch_imagec_obs(mdpp_env *h, int K, const void *states, const void *final_
     const size_t lds = (size_t)per_block * (((((size_t)a.n_sub * a.W * a.H + 15) / 16 + 3) & ~(size_t)3) + 768) * 4;
     if (lds > 64 * 1024) { h->err = "k_imagec_obs: image too large for the LDS colour map"; return MDPP_EUNSUPPORTED; }
     const dim3 grd((unsigned)((M + per_block - 1) / per_block));
-#define MDPP_IC_LAUNCH(GR, st, te, tr, im) hipLaunchKernelGGL((k_imagec_obs<GR>), grd, dim3(kBlock), lds, s, a, M, st, te, tr, mask, im)
-    if (img_out) { if (grid) MDPP_IC_LAUNCH(true, states, nullptr, nullptr, img_out); else MDPP_IC_LAUNCH(false, states, nullptr, nullptr, img_out); }
-    if (img_final && final_states && term) {
-        if (grid) MDPP_IC_LAUNCH(true, final_states, term, trunc, img_final); else MDPP_IC_LAUNCH(false, final_states, term, trunc, img_final);
-    }
-#undef MDPP_IC_LAUNCH
+    with_bools([&](auto GR) {
+        if (img_out) hipLaunchKernelGGL((k_imagec_obs<GR()>), grd, dim3(kBlock), lds, s, a, M, states, nullptr, nullptr, mask, img_out);
+        if (img_final && final_states && term)
+            hipLaunchKernelGGL((k_imagec_obs<GR()>), grd, dim3(kBlock), lds, s, a, M, final_states, term, trunc, mask, img_final);
+    }, grid);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->err = std::string("k_imagec_obs launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
     return MDPP_OK;

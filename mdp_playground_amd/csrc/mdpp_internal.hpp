@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 
 #include "../../include/mdpp.h"
 
@@ -383,44 +384,122 @@ inline int gen_args_init(const mdpp_gen_params *p, int S, int A, int L, bool ima
     return MDPP_OK;
 }
 
-// implemented in the kernel translation units
-// name_out != nullptr: a dry run -- the launcher writes the name of the kernel it would launch (at most
-// kNameLen bytes) and launches nothing
+// ---- host side: run-time values -> template arguments ------------------------------------------------------------
+// with_bools(f, b0, b1, ...) calls f(c0, c1, ...) with ci = std::true_type / std::false_type for bi: inside the (generic)
+// lambda ci() is a compile-time constant.  A launcher formats its kernel's name and instantiates the kernel from the SAME
+// constants, in the same lambda, so the two cannot disagree; a combination that is not built is left out by an
+// `if constexpr` inside the lambda.
+template <class F> inline void with_bools(F &&f) { f(); }
+template <class F, class... Bs> inline void with_bools(F &&f, bool b, Bs... rest) {
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+// with_value<V0, V1, ...>(v, f) calls f(std::integral_constant<int, Vi>{}) for the Vi that equals v; false (f not called)
+// when none does
+template <int... Vs, class F> inline bool with_value(int v, F &&f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// ---- what a step launch carries besides the handle's argument block -------------------------------------------------
+// K steps x N envs, every array time-major.  name_out != nullptr: a dry run -- the launcher writes the name of the kernel
+// it would launch (at most kNameLen bytes) and launches nothing
 constexpr int kNameLen = 192;
-int launch_discrete_step(mdpp_env *h, int K, const int32_t *actions, void *obs, float *reward,
-                         uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out = nullptr);
+template <class Act, class Obs>
+struct StepIO {
+    int K;
+    const Act *actions;
+    Obs *obs;
+    float *reward;
+    uint8_t *term, *trunc;
+    Obs *final_obs;             // null: not asked for
+    hipStream_t s;
+    char *name_out;
+    // steps [k0, k0 + kc) of this launch: an env-step has act_elems action elements and obs_bytes bytes of observation
+    StepIO piece(int k0, int kc, size_t N, size_t act_elems, size_t obs_bytes) const {
+        const size_t off = (size_t)k0 * N;
+        StepIO p = *this;
+        p.K = kc;
+        p.actions = actions + off * act_elems;
+        p.obs = (Obs *)((char *)obs + off * obs_bytes);
+        p.reward = reward + off; p.term = term + off; p.trunc = trunc + off;
+        p.final_obs = final_obs ? (Obs *)((char *)final_obs + off * obs_bytes) : nullptr;
+        return p;
+    }
+};
+using DiscreteIO = StepIO<int32_t, void>;       // observations int32 or int64 (obs_i32); the grid's too
+using ContinuousIO = StepIO<float, float>;
+// (an irrelevant sub-space: action pairs, observation pairs)
+inline DiscreteIO piece_of(const DiscreteArgs &a, const DiscreteIO &io, int k0, int kc) {
+    const size_t w = a.irr ? 2 : 1;
+    return io.piece(k0, kc, (size_t)a.N, w, w * (a.obs_i32 ? 4 : 8));
+}
+inline ContinuousIO piece_of(const ContinuousArgs &a, const ContinuousIO &io, int k0, int kc) {
+    return io.piece(k0, kc, (size_t)a.N, (size_t)a.D, (size_t)a.D * sizeof(float));
+}
+// every step / rollout kernel takes (args, K, actions, obs, reward, term, trunc, final_obs)
+template <class Kern, class A, class IO>
+inline void launch_rollout(Kern kern, int grid, int block, size_t lds, const A &a, const IO &io) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, io.s, a, io.K, io.actions, io.obs, io.reward, io.term, io.trunc,
+                       io.final_obs);
+}
+
+// The per-launch fields of an argument block: the kernel-selection switches, the step counter (Philox keys), its device
+// offset while launches are captured into a HIP graph, the head of the delay ring -- for a launch that starts k0 steps
+// into this call
+inline void stamp_piece(GridArgs &a, const mdpp_env *h, int k0) { a.ptick = h->tick + (uint64_t)k0; }
+template <class A> inline void stamp_piece(A &a, const mdpp_env *h, int k0) {
+    a.ptick = h->tick + (uint64_t)k0;
+    a.tick = a.delay > 0 ? (uint32_t)(a.ptick % (uint64_t)a.delay) : 0u;
+}
+template <class A> inline void stamp_step(A &a, const mdpp_env *h) {
+    a.opts = h->opts;
+    a.dtick = h->graph_capture ? (const uint64_t *)h->d_tick_off : nullptr;     // (launches being captured into a HIP graph)
+    stamp_piece(a, h, 0);
+}
+// The rollout kernels' buffer descriptors address < 4 GiB per array, so a long rollout goes out as several launches of at
+// most kmax steps: body(piece, k0) launches one piece; false from it ends the loop (and is returned).  A dry run ends
+// after the first piece: it names the launch.
+template <class A, class IO, class Body>
+inline bool for_each_piece(A &a, const mdpp_env *h, const IO &io, long long kmax, Body &&body) {
+    for (int k0 = 0; k0 < io.K;) {
+        const int kc = (int)((io.K - k0) < kmax ? (io.K - k0) : kmax);
+        stamp_piece(a, h, k0);
+        if (!body(piece_of(a, io, k0, kc), k0)) return false;
+        if (io.name_out) return true;
+        k0 += kc;
+    }
+    return true;
+}
+// After the launches of a step: the error check, then the handle's step counter
+inline int step_done(mdpp_env *h, int K, const char *kernel) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { h->err = std::string(kernel) + " launch: " + hipGetErrorString(e); return MDPP_EHIP; }
+    h->tick += (uint64_t)K;
+    return MDPP_OK;
+}
+
+// implemented in the kernel translation units
+int launch_discrete_step(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // state spaces of 256 ... 65 535 states: the general kernel alone, 16-bit table entries and history fields (mdpp_discrete_wide.hip)
-int launch_discrete_step_wide(mdpp_env *h, int K, const int32_t *actions, void *obs, float *reward,
-                              uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out);
+int launch_discrete_step_wide(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_reset_wide(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // sequence_length 8 ... 15: the same with a history of sixteen byte fields (mdpp_discrete_long.hip)
-int launch_discrete_step_long(mdpp_env *h, int K, const int32_t *actions, void *obs, float *reward,
-                              uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out);
+int launch_discrete_step_long(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_reset_long(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
-bool launch_discrete_fast(const DiscreteArgs &a, int K, const int32_t *actions, void *obs, float *reward,
-                          uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out = nullptr);
-int launch_continuous_step(mdpp_env *h, int K, const float *actions, float *obs, float *reward,
-                           uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out = nullptr);
+bool launch_discrete_fast(const DiscreteArgs &a, const DiscreteIO &io);
+int launch_continuous_step(mdpp_env *h, const ContinuousIO &io);
 int launch_continuous_reset(mdpp_env *h, const uint8_t *mask, float *obs, hipStream_t s);
-bool launch_discrete_step1(const DiscreteArgs &d, const Step1Args &proto, const int32_t *actions, void *obs, float *reward,
-                           uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out = nullptr);
-bool launch_discrete_quiet(const DiscreteArgs &a, int K, const int32_t *actions, void *obs, float *reward,
-                           uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out = nullptr);
-bool launch_discrete_pipe(const DiscreteArgs &a, int K, const int32_t *actions, void *obs, float *reward,
-                          uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out = nullptr);
-bool launch_discrete_lean(const DiscreteArgs &a, int K, const int32_t *actions, void *obs, float *reward,
-                          uint8_t *term, uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out = nullptr);
-bool launch_continuous_fast(const ContinuousArgs &a, int K, const float *actions, float *obs, float *reward,
-                            uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out = nullptr);
-bool launch_continuous_step1(const ContinuousArgs &a, const float *actions, float *obs, float *reward, uint8_t *term,
-                             uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out = nullptr);
-bool launch_continuous_line(const ContinuousArgs &a, int K, const float *actions, float *obs, float *reward,
-                            uint8_t *term, uint8_t *trunc, float *final_obs, hipStream_t s, char *name_out = nullptr);
+bool launch_discrete_step1(const DiscreteArgs &d, const Step1Args &proto, const DiscreteIO &io);
+bool launch_discrete_quiet(const DiscreteArgs &a, const DiscreteIO &io);
+bool launch_discrete_pipe(const DiscreteArgs &a, const DiscreteIO &io);
+bool launch_discrete_lean(const DiscreteArgs &a, const DiscreteIO &io);
+bool launch_continuous_fast(const ContinuousArgs &a, const ContinuousIO &io);
+bool launch_continuous_step1(const ContinuousArgs &a, const ContinuousIO &io);
+bool launch_continuous_line(const ContinuousArgs &a, const ContinuousIO &io);
 int launch_imagec_obs(mdpp_env *h, int K, const void *states, const void *final_states, const uint8_t *term,
                       const uint8_t *trunc, const uint8_t *mask, uint8_t *img_out, uint8_t *img_final, hipStream_t s);
-int launch_grid_step(mdpp_env *h, int K, const int32_t *actions, void *obs, float *reward, uint8_t *term,
-                     uint8_t *trunc, void *final_obs, hipStream_t s, char *name_out = nullptr);
+int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // phase bits: 1 = draw + records, 2 = render (phase == 2 exactly: pipelined, the persistent grid leaves slots
 // free for the next batch's state kernel; 6 = render only on the full grid); buf: scratch set (0 / 1)

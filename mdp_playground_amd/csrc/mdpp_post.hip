@@ -635,19 +635,17 @@ extern "C" int mdpp_post_step_n(mdpp_post *h, int K, const void *obs_in_dev, con
     PostArgs a = make_args(h);
     const int grid = (a.N + kBlock - 1) / kBlock;
     const int ring = a.delay >= 1 && a.delay <= kPostRegDelay ? 2 : (a.delay >= 1 && a.delay <= kPostLdsDelay ? 1 : 0);
-#define MDPP_POST_LAUNCH(PH, LR, DC) hipLaunchKernelGGL((k_post_step<PH, LR, DC>), dim3(grid), dim3(kBlock), 0, s, a, K, obs_in_dev, \
-                                                        reward_in_dev, done_dev, obs_out_dev, reward_out_dev)
-#define MDPP_POST_REG(PH)                                                                        \
-    switch (a.delay) {                                                                           \
-    case 1: MDPP_POST_LAUNCH(PH, 2, 1); break; case 2: MDPP_POST_LAUNCH(PH, 2, 2); break;        \
-    case 3: MDPP_POST_LAUNCH(PH, 2, 3); break; case 4: MDPP_POST_LAUNCH(PH, 2, 4); break;        \
-    case 5: MDPP_POST_LAUNCH(PH, 2, 5); break; case 6: MDPP_POST_LAUNCH(PH, 2, 6); break;        \
-    case 7: MDPP_POST_LAUNCH(PH, 2, 7); break; default: MDPP_POST_LAUNCH(PH, 2, 8); break;       \
-    }
-    if (a.philox) { if (ring == 2) { MDPP_POST_REG(true); } else if (ring == 1) MDPP_POST_LAUNCH(true, 1, 0); else MDPP_POST_LAUNCH(true, 0, 0); }
-    else { if (ring == 2) { MDPP_POST_REG(false); } else if (ring == 1) MDPP_POST_LAUNCH(false, 1, 0); else MDPP_POST_LAUNCH(false, 0, 0); }
-#undef MDPP_POST_REG
-#undef MDPP_POST_LAUNCH
+    // (the register FIFO takes its delay as a compile-time constant, DC)
+    with_bools([&](auto PH) {
+        auto go = [&](auto RING, auto DC) {
+            hipLaunchKernelGGL((k_post_step<PH(), RING(), DC()>), dim3(grid), dim3(kBlock), 0, s, a, K, obs_in_dev, reward_in_dev, done_dev, obs_out_dev,
+                               reward_out_dev);
+        };
+        using std::integral_constant;
+        if (ring == 2) with_value<1, 2, 3, 4, 5, 6, 7, 8>(a.delay, [&](auto DC) { go(integral_constant<int, 2>{}, DC); });
+        else if (ring == 1) go(integral_constant<int, 1>{}, integral_constant<int, 0>{});
+        else go(integral_constant<int, 0>{}, integral_constant<int, 0>{});
+    }, a.philox != 0);
     if (h->cfg.image) launch_post_image(h, a, (long)K * a.N, obs_in_dev, obs_out_dev, s);
     PHIP(h, hipGetLastError());
     h->tick += (uint64_t)K;
