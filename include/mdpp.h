@@ -285,6 +285,30 @@ int mdpp_step(mdpp_env *h, const void *actions_dev, void *obs_dev, float *reward
 int mdpp_step_n(mdpp_env *h, int K, const void *actions_dev, void *obs_dev, float *reward_dev,
                 uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
 
+/* Closed-loop fused rollouts: a handle may carry ONE tabular policy, and mdpp_step_n_policy samples a ~ pi(. | s) in the
+ * launch that steps the envs -- K steps of an agent acting on what it observes in one launch, nothing between steps.
+ * The policy is a table of thresholds thr uint32 [S][A] with non-decreasing rows, thr[s][j] = ceil(cdf_s[j] 2^31) (so
+ * thr[s][A-1] = 2^31), and a 64-bit seed.  Env i (global id g = cfg.env_id_offset + i) at step counter t (mdpp_tick; a
+ * graph's tick offset applies) draws
+ *   w = word (t & 3) of block 0 of the Philox4x32-10 stream (policy_seed, g, t >> 2, stream id 14), m = w >> 1,
+ *   a = min(#{ j < A : thr[s][j] <= m }, A - 1) = searchsorted(cdf_s, m 2^-31, 'right'),
+ * s the state the env is in (the last observation returned for it), and the step is mdpp_step_n's with that action;
+ * actions_out_dev int32 [K][N] receives the actions (on the reset call of a next-step-autoreset env the action is drawn
+ * and written, and ignored like a caller's).  The policy reads none of the env's streams: the launch leaves the handle
+ * where mdpp_step_n fed with actions_out leaves it, whichever RNG mode, and the two kinds of launch mix freely.
+ * Served: discrete handles with one shared MDP (num_tables = 1), S <= 255, L <= 7, no irrelevant sub-space, no image
+ * observations, no episode_stats, no transition- or reward-noise key, tables + thresholds within 64 KiB of LDS; any
+ * reward form, delay, every_n, autoreset mode and RNG mode.  Anything else: MDPP_EUNSUPPORTED with the reason in
+ * mdpp_last_error, from mdpp_set_policy already; there is no other path.
+ * mdpp_set_policy copies thr_dev (device) into a buffer of the handle ON `stream`: ordered behind the work queued there
+ * and ahead of later launches, so a policy is replaced between rollouts without a host round trip.
+ * mdpp_step_n_policy without a policy: MDPP_ESTATE.  mdpp_policy_kernel_name: as mdpp_kernel_name, for that launch. */
+int mdpp_set_policy(mdpp_env *h, const uint32_t *thr_dev, uint64_t policy_seed, void *stream);
+int mdpp_clear_policy(mdpp_env *h);
+int mdpp_step_n_policy(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                       uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+const char *mdpp_policy_kernel_name(mdpp_env *h, int K);
+
 /* Per-env internal state <-> host (synchronous; checkpoint / set_augmented_state).
  * Discrete: hist int32[N][L+1] (-1 = NaN slot), steps int32[N], ring double[N][delay].
  * Continuous: derivs float[N][order+1][D], cur float[N][D], steps int32[N],

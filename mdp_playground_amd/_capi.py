@@ -16,6 +16,7 @@ AUTORESET_DISABLED, AUTORESET_SAME_STEP, AUTORESET_NEXT_STEP = 0, 1, 2
 OBS_I64, OBS_I32, OBS_F32, OBS_IMAGE_U8 = 0, 1, 2, 3
 STREAM_ENV, STREAM_SPACE, STREAM_IMAGE, STREAM_SPACE_IRR, STREAM_ACTION = 0, 1, 2, 3, 4
 STATUS_BAD_ACTION = 1
+EUNSUPPORTED = -5         # MDPP_EUNSUPPORTED
 PEER_HANDLE_BYTES = 64
 # MDPP_OPT_* kernel-selection switches (mdpp_set_options)
 OPTIONS = {"NO_PIPE": 1 << 0, "NO_HELPER": 1 << 1, "NO_PARK": 1 << 2, "NO_CFAST": 1 << 3, "NO_QUIET": 1 << 4,
@@ -40,6 +41,7 @@ EXPORTS = [
     "mdpp_peer_create", "mdpp_peer_handle", "mdpp_peer_open", "mdpp_peer_push", "mdpp_peer_fence", "mdpp_peer_wait", "mdpp_peer_buffer",
     "mdpp_peer_status", "mdpp_peer_last_error", "mdpp_peer_destroy",
     "mdpp_generate_discrete", "mdpp_get_discrete_tables", "mdpp_seed_streams_seedseq",
+    "mdpp_set_policy", "mdpp_clear_policy", "mdpp_step_n_policy", "mdpp_policy_kernel_name",
 ]
 
 
@@ -147,6 +149,11 @@ def load():
     L.mdpp_set_options.argtypes = [vp, C.c_uint32]
     L.mdpp_kernel_name.argtypes = [vp, i32]
     L.mdpp_kernel_name.restype = C.c_char_p
+    L.mdpp_set_policy.argtypes = [vp, vp, C.c_uint64, vp]
+    L.mdpp_clear_policy.argtypes = [vp]
+    L.mdpp_step_n_policy.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_policy_kernel_name.argtypes = [vp, i32]
+    L.mdpp_policy_kernel_name.restype = C.c_char_p
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

@@ -56,7 +56,7 @@ static void free_all(mdpp_env *h) {
                     h->d_P1, h->d_init_cdf1, h->d_noise_cdf1, h->d_irr_state,
                     h->d_img_tpl, h->d_img_tplp, h->d_img_clsx, h->d_img_clsy, h->d_img_rot, h->d_img_state_out,
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
-                    h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi};
+                    h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -114,6 +114,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_img_near = nullptr;
     h->d_s1_blob = nullptr;
     memset(&h->s1args, 0, sizeof(h->s1args));
+    h->d_policy_thr = nullptr; h->policy_seed = 0; h->policy_ready = false;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
     h->d_hist_hi = nullptr;
@@ -1319,6 +1320,49 @@ extern "C" const char *mdpp_kernel_name(mdpp_env *h, int K) {
     if (h->cfg.kind == MDPP_KIND_DISCRETE) (void)launch_discrete_step(h, dry);
     else if (h->cfg.kind == MDPP_KIND_GRID) (void)launch_grid_step(h, dry);
     else (void)launch_continuous_step(h, cdry);
+    return h->kname;
+}
+
+// ---- closed-loop rollouts under a tabular policy (mdpp_discrete_policy.hip) ----
+extern "C" int mdpp_set_policy(mdpp_env *h, const uint32_t *thr_dev, uint64_t policy_seed, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!thr_dev) return fail(h, MDPP_EINVAL, "mdpp_set_policy: null thresholds");
+    if (const char *why = discrete_policy_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_policy: ") + why);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)h->cfg.S * (size_t)h->cfg.A * sizeof(uint32_t);
+    if (!h->d_policy_thr) HIPCHK(h, hipMalloc(&h->d_policy_thr, bytes));
+    // (device to device on the caller's stream: behind the rollouts already queued there, ahead of the next one)
+    HIPCHK(h, hipMemcpyAsync(h->d_policy_thr, thr_dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    h->policy_seed = policy_seed;
+    h->policy_ready = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_policy(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->policy_ready = false;     // (the buffer stays: a launch queued earlier may still read it)
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_step_n_policy(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                                  uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_policy: K < 1");
+    if (!actions_out_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev)
+        return fail(h, MDPP_EINVAL, "mdpp_step_n_policy: null buffer");
+    if (const char *why = discrete_policy_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_step_n_policy: ") + why);
+    if (!h->policy_ready) return fail(h, MDPP_ESTATE, "mdpp_step_n_policy: no policy set (mdpp_set_policy)");
+    int rc = check_ready(h, "mdpp_step_n_policy");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_discrete_policy(h, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, (hipStream_t)stream, nullptr);
+}
+
+extern "C" const char *mdpp_policy_kernel_name(mdpp_env *h, int K) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1 || check_ready(h, "mdpp_policy_kernel_name")) return h->kname;
+    (void)launch_discrete_policy(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
     return h->kname;
 }
 

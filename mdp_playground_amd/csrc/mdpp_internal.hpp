@@ -32,6 +32,7 @@ constexpr uint32_t kPhiloxStartStream = 9;    // discrete: start state of an in-
 constexpr uint32_t kPhiloxStartIrrStream = 10; // ... of the irrelevant sub-space
 constexpr uint32_t kPhiloxPNoiseStream = 12;  // discrete: transition noise, one word per tick (mdpp_rng.hpp)
 constexpr uint32_t kPhiloxRNoiseStream = 13;  // discrete: reward noise, one float32 normal per tick (four per block)
+constexpr uint32_t kPhiloxPolicyStream = 14;  // discrete: the tabular policy's action, one word per tick, keyed by the POLICY's seed (mdpp_discrete_policy.hip)
 
 // ---- per-episode noise statistics (cfg.episode_stats; general kernels only) ------------------------------------
 // What the reference accumulates per env object and logs at every reset() (rl_toy_env.py:2231-2247; cleared
@@ -313,6 +314,10 @@ struct mdpp_env {
     mdpp::DiscreteArgs dargs;
     mdpp::Step1Args s1args;     // k_discrete_step1's argument block (blob == nullptr: the shape does not qualify)
     void *d_s1_blob;
+    // the tabular policy of closed-loop rollouts (mdpp_set_policy): thresholds uint32 [S][A] on the device, the seed of its stream
+    void *d_policy_thr;
+    uint64_t policy_seed;
+    bool policy_ready;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -499,6 +504,11 @@ bool launch_continuous_step1(const ContinuousArgs &a, const ContinuousIO &io);
 bool launch_continuous_line(const ContinuousArgs &a, const ContinuousIO &io);
 int launch_imagec_obs(mdpp_env *h, int K, const void *states, const void *final_states, const uint8_t *term,
                       const uint8_t *trunc, const uint8_t *mask, uint8_t *img_out, uint8_t *img_final, hipStream_t s);
+// closed-loop rollout under the handle's tabular policy (mdpp_discrete_policy.hip): why the handle has none (null: it is
+// served); K steps, the sampled actions to actions_out (name_out != nullptr: a dry run, the kernel's name only)
+const char *discrete_policy_refusal(const mdpp_env *h);
+int launch_discrete_policy(mdpp_env *h, int K, int32_t *actions_out, void *obs, float *reward, uint8_t *term, uint8_t *trunc,
+                           hipStream_t s, char *name_out);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // phase bits: 1 = draw + records, 2 = render (phase == 2 exactly: pipelined, the persistent grid leaves slots

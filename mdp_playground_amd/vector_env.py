@@ -28,6 +28,7 @@ import torch
 
 from . import _capi as capi
 from . import mdp as mdp_mod
+from . import policy as policy_mod
 from .spaces import BatchedSpace, BoxSpace, DiscreteSpace, ImageSpace, TupleSpace
 
 _AUTORESET = {"disabled": capi.AUTORESET_DISABLED, "same_step": capi.AUTORESET_SAME_STEP,
@@ -639,6 +640,77 @@ class RLToyVectorEnv:
         capi.check(self._lib, self._h, rc, "mdpp_step_n")
         self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
         return obs, rew, term.view(torch.bool), trunc.view(torch.bool)
+
+    # ------------------------------------------------------------------ closed-loop rollouts under a tabular policy
+    def set_policy(self, policy=None, *, thresholds=None, seed=0):
+        """The handle's tabular policy for rollout_policy(): ``policy`` float [S, A] probabilities or integer [S] actions
+        (policy.policy_thresholds makes the kernel's thresholds from it on the host), or ``thresholds`` -- a device uint32
+        [S, A] tensor with non-decreasing rows, used as given (copied on the current stream: a policy is replaced between
+        rollouts without a host round trip).  ``seed``: the 64-bit key of the policy's own Philox stream.  Neither
+        argument: the policy is cleared.  Handles the kernel does not serve raise NotImplementedError with the reason."""
+        if policy is not None and thresholds is not None:
+            raise ValueError("set_policy: give policy or thresholds, not both")
+        if policy is None and thresholds is None:
+            capi.check(self._lib, self._h, self._lib.mdpp_clear_policy(self._h), "mdpp_clear_policy")
+            return
+        self._policy_check_config()
+        S, A = self.mdps[0].S, self.mdps[0].A
+        if thresholds is None:
+            thr = torch.from_numpy(policy_mod.policy_thresholds(policy, S, A).view(np.int32)).to(self.device).view(torch.uint32)
+        else:
+            thr = thresholds
+            if not (torch.is_tensor(thr) and thr.dtype == torch.uint32 and thr.device == self.device
+                    and tuple(thr.shape) == (S, A)):
+                raise ValueError(f"set_policy: thresholds must be a uint32 tensor of shape ({S}, {A}) on {self.device}")
+            thr = thr.contiguous()
+        rc = self._lib.mdpp_set_policy(self._h, C.c_void_p(thr.data_ptr()), C.c_uint64(int(seed) & (2 ** 64 - 1)), self._stream())
+        if rc == capi.EUNSUPPORTED:
+            msg = self._lib.mdpp_last_error(self._h)
+            raise NotImplementedError(msg.decode() if msg else "mdpp_set_policy: unsupported")
+        capi.check(self._lib, self._h, rc, "mdpp_set_policy")
+        self._policy_thr = thr           # (kept until the copy queued on the stream has certainly been made)
+
+    def _policy_check_config(self):
+        """What the config alone rules out, before the library is asked: the env kind, and a noise key -- a config that
+        names transition_noise or reward_noise is refused even at 0 (the library sees no transition-noise key at 0.0)."""
+        if self.kind != "discrete":
+            raise NotImplementedError("policy rollouts serve discrete envs only (this env is %s)" % self.kind)
+        for key in ("transition_noise", "reward_noise"):
+            if self.config.get(key) is not None:
+                raise NotImplementedError("policy rollouts do not serve a %s key (config[%r] = %r)" % (key, key, self.config[key]))
+
+    def alloc_rollout_policy(self, K):
+        """Output buffers of rollout_policy(K): alloc_rollout(K) and the actions, int32 [K, N]."""
+        return self.alloc_rollout(K) + (torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device),)
+
+    def rollout_policy(self, K, out=None):
+        """K closed-loop steps in ONE kernel launch: at every step each env draws its action from the policy's row of the
+        state it is in and takes it.  Returns (obs, reward, terminated, truncated, actions), each with a leading K axis;
+        rollout(actions) on an identically built env returns the same first four, bit for bit."""
+        K = int(K)
+        self._policy_check_config()
+        if out is None:
+            out = self.alloc_rollout_policy(K)
+        obs, rew, term, trunc, act = out
+        rc = self._lib.mdpp_step_n_policy(self._h, K, C.c_void_p(act.data_ptr()), C.c_void_p(obs.data_ptr()),
+                                          C.c_void_p(rew.data_ptr()), C.c_void_p(term.data_ptr()),
+                                          C.c_void_p(trunc.data_ptr()), self._stream())
+        if rc == capi.EUNSUPPORTED:
+            msg = self._lib.mdpp_last_error(self._h)
+            raise NotImplementedError(msg.decode() if msg else "mdpp_step_n_policy: unsupported")
+        capi.check(self._lib, self._h, rc, "mdpp_step_n_policy")
+        self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
+        return obs, rew, term.view(torch.bool), trunc.view(torch.bool), act
+
+    def policy_kernel_name(self, K):
+        """Name (with template arguments) of the kernel rollout_policy(K) launches (mdpp_policy_kernel_name; nothing is
+        launched); empty for a handle it does not serve."""
+        try:
+            self._policy_check_config()
+        except NotImplementedError:
+            return ""
+        name = self._lib.mdpp_policy_kernel_name(self._h, int(K))
+        return name.decode() if name else ""
 
     def rollout_kernel_name(self, K):
         """Name (with template arguments) of the kernel mdpp_step_n(K) launches for this handle, as
