@@ -94,8 +94,14 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
        MDPP_OPT_NO_IMG_NEARTAB = 1u << 14, /* polygon images: k_image_obs_fast walks the bounding box instead of the near-dword table */
        MDPP_OPT_NO_STEP1 = 1u << 15,       /* mdpp_step (K = 1): the rollout kernels with K = 1 instead of k_discrete_step1 / k_continuous_step1 */
        MDPP_OPT_NO_QUIET_SF = 1u << 17,    /* k_discrete_rollout_quiet: no compile-time form of the sweep defaults (sequence_length 1, same-step autoreset, ...) */
-       MDPP_OPT_NO_SIGMA0 = 1u << 16       /* noise keys present with sigma 0 (the reference draws rng.normal(0, 0): rl_toy_env.py:398-403, :1982):
-                                              form the normals' values anyway instead of advancing the streams alone */ };
+       MDPP_OPT_NO_SIGMA0 = 1u << 16,      /* noise keys present with sigma 0 (the reference draws rng.normal(0, 0): rl_toy_env.py:398-403, :1982):
+                                              form the normals' values anyway instead of advancing the streams alone */
+       MDPP_OPT_NO_LEARN_LDS = 1u << 18,   /* k_discrete_learn_rollout: the Q-tables stay in global memory (QLDS=0) */
+       MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19 }; /* mdpp_step_n_learn goes out in launches of at most 5 steps (the hand-over
+                                              between the pieces of a very long call, at a size a test can run) */
+
+/* the tabular learner's algorithm (mdpp_set_learner); 2 is kept for double Q-learning */
+enum { MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1 };
 
 /* what a discrete env's reward table is keyed by */
 enum { MDPP_REWARD_SEQUENCES = 0,     /* the last L states (rewardable_sequences, rl_toy_env.py:1837-1841) */
@@ -308,6 +314,43 @@ int mdpp_clear_policy(mdpp_env *h);
 int mdpp_step_n_policy(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
                        uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
 const char *mdpp_policy_kernel_name(mdpp_env *h, int K);
+
+/* In-kernel tabular TD learners: a discrete handle may carry ONE learner -- algo (MDPP_LEARN_*), float32 alpha in (0, 1], gamma
+ * and epsilon in [0, 1], a 64-bit seed and one table Q float32 [S][A] PER ENV -- and mdpp_step_n_learn runs K steps of "select
+ * epsilon-greedily from the env's own Q, step, update that Q" in one launch.  Env i (global id g = cfg.env_id_offset + i) at step
+ * counter t (mdpp_tick; a graph's tick offset applies) in state s:
+ *   sel(s, t): wE = word (t & 3) of block 0 of the Philox4x32-10 stream (seed, g, t >> 2, stream id 15); with
+ *     E = ceil((double)epsilon 2^31), (wE >> 1) < E explores: a = (uint64(wA) A) >> 32, wA the same word of stream id 16;
+ *     otherwise a = the lowest j maximising Q[s][j];
+ *   the step is mdpp_step_n's with that action (transition and reward noise included): float32 reward r as written,
+ *     terminated, truncated, the true next state s' (before any autoreset);
+ *   target (float32, one rounding per operation): terminated: y = r; q_learning: y = r + gamma max_j Q[s'][j];
+ *     sarsa: y = r + gamma Q[s'][a'], a' = sel(s', t + 1) on Q before this step's update;
+ *   update: q = Q[s][a], d = y - q, u = alpha d, Q[s][a] = q + u;
+ *   sarsa: when the env's next step of the same call starts from s' (no termination, no reset in between) it takes a' and does
+ *     not select again; a call's first step always selects afresh -- the one departure from textbook SARSA: there is no
+ *     per-env learner state besides Q;
+ *   the reset call of a next-step-autoreset env: an action is selected from the state in the record, written and ignored;
+ *     no update.
+ * The learner reads none of the env's streams: the launch leaves the handle where mdpp_step_n fed with actions_out leaves it.
+ * Non-finite Q: unspecified.
+ * Served: discrete handles with one shared MDP, S <= 255, L <= 7, no irrelevant sub-space, no image observations, no
+ * episode_stats, the MDP's tables within 64 KiB of LDS; any reward form, delay, every_n, max_episode_steps, autoreset mode,
+ * RNG mode, with or without the transition- and reward-noise keys.  Anything else: MDPP_EUNSUPPORTED with the reason in
+ * mdpp_last_error, from mdpp_set_learner already.
+ * mdpp_set_learner (re)starts the learner: Q = q_init_dev ([N][S][A], device; copied on `stream`) or zeros.
+ * mdpp_set_learner_rates changes alpha and epsilon only (no device work: a host-side decay schedule costs nothing).
+ * mdpp_get_q / mdpp_set_q: device pointers, float32 [N][S][A], ordered on `stream`.  Without a learner: MDPP_ESTATE, as
+ * mdpp_step_n_learn.  mdpp_learn_kernel_name: as mdpp_kernel_name, for that launch (QLDS=1: the tables are staged in LDS). */
+int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma, float epsilon, uint64_t seed, const float *q_init_dev,
+                     void *stream);
+int mdpp_clear_learner(mdpp_env *h);
+int mdpp_set_learner_rates(mdpp_env *h, float alpha, float epsilon);
+int mdpp_step_n_learn(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                      uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+int mdpp_get_q(mdpp_env *h, float *q_out_dev, void *stream);
+int mdpp_set_q(mdpp_env *h, const float *q_in_dev, void *stream);
+const char *mdpp_learn_kernel_name(mdpp_env *h, int K);
 
 /* Per-env internal state <-> host (synchronous; checkpoint / set_augmented_state).
  * Discrete: hist int32[N][L+1] (-1 = NaN slot), steps int32[N], ring double[N][delay].

@@ -22,7 +22,9 @@ PEER_HANDLE_BYTES = 64
 OPTIONS = {"NO_PIPE": 1 << 0, "NO_HELPER": 1 << 1, "NO_PARK": 1 << 2, "NO_CFAST": 1 << 3, "NO_QUIET": 1 << 4,
            "NO_QUIET_NOISE": 1 << 5, "NO_DUO": 1 << 6, "NO_TRIO": 1 << 7, "NO_GFAST": 1 << 8,
            "NO_GFAST_NOISE": 1 << 9, "NO_IMGFAST": 1 << 10, "NO_IMG_OVERLAP": 1 << 11, "NO_PHILOX_FAST": 1 << 12, "NO_LEAN": 1 << 13,
-           "NO_IMG_NEARTAB": 1 << 14, "NO_STEP1": 1 << 15, "NO_SIGMA0": 1 << 16, "NO_QUIET_SF": 1 << 17}
+           "NO_IMG_NEARTAB": 1 << 14, "NO_STEP1": 1 << 15, "NO_SIGMA0": 1 << 16, "NO_QUIET_SF": 1 << 17,
+           "NO_LEARN_LDS": 1 << 18, "LEARN_SHORT_PIECES": 1 << 19}
+LEARN_ALGOS = {"q_learning": 0, "sarsa": 1}        # MDPP_LEARN_*
 
 EXPORTS = [
     "mdpp_abi_version", "mdpp_create", "mdpp_destroy", "mdpp_last_error",
@@ -42,6 +44,8 @@ EXPORTS = [
     "mdpp_peer_status", "mdpp_peer_last_error", "mdpp_peer_destroy",
     "mdpp_generate_discrete", "mdpp_get_discrete_tables", "mdpp_seed_streams_seedseq",
     "mdpp_set_policy", "mdpp_clear_policy", "mdpp_step_n_policy", "mdpp_policy_kernel_name",
+    "mdpp_set_learner", "mdpp_clear_learner", "mdpp_set_learner_rates", "mdpp_step_n_learn", "mdpp_get_q", "mdpp_set_q",
+    "mdpp_learn_kernel_name",
 ]
 
 
@@ -154,6 +158,14 @@ def load():
     L.mdpp_step_n_policy.argtypes = [vp, i32] + [vp] * 6
     L.mdpp_policy_kernel_name.argtypes = [vp, i32]
     L.mdpp_policy_kernel_name.restype = C.c_char_p
+    L.mdpp_set_learner.argtypes = [vp, i32, C.c_float, C.c_float, C.c_float, C.c_uint64, vp, vp]
+    L.mdpp_clear_learner.argtypes = [vp]
+    L.mdpp_set_learner_rates.argtypes = [vp, C.c_float, C.c_float]
+    L.mdpp_step_n_learn.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_get_q.argtypes = [vp, vp, vp]
+    L.mdpp_set_q.argtypes = [vp, vp, vp]
+    L.mdpp_learn_kernel_name.argtypes = [vp, i32]
+    L.mdpp_learn_kernel_name.restype = C.c_char_p
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

@@ -56,7 +56,7 @@ static void free_all(mdpp_env *h) {
                     h->d_P1, h->d_init_cdf1, h->d_noise_cdf1, h->d_irr_state,
                     h->d_img_tpl, h->d_img_tplp, h->d_img_clsx, h->d_img_clsy, h->d_img_rot, h->d_img_state_out,
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
-                    h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr};
+                    h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -115,6 +115,8 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_s1_blob = nullptr;
     memset(&h->s1args, 0, sizeof(h->s1args));
     h->d_policy_thr = nullptr; h->policy_seed = 0; h->policy_ready = false;
+    h->d_learn_q = h->d_learn_carry = nullptr; h->learn_seed = 0; h->learn_E = 0; h->learn_alpha = h->learn_gamma = 0.0f;
+    h->learn_algo = MDPP_LEARN_Q_LEARNING; h->learn_ready = false;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
     h->d_hist_hi = nullptr;
@@ -1363,6 +1365,87 @@ extern "C" const char *mdpp_policy_kernel_name(mdpp_env *h, int K) {
     h->kname[0] = 0;
     if (K < 1 || check_ready(h, "mdpp_policy_kernel_name")) return h->kname;
     (void)launch_discrete_policy(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
+    return h->kname;
+}
+
+// ---- in-kernel tabular TD learners (mdpp_discrete_learn.hip) ----
+static bool learner_rates_ok(float alpha, float epsilon) {
+    return alpha > 0.0f && alpha <= 1.0f && epsilon >= 0.0f && epsilon <= 1.0f;      // (NaN fails both)
+}
+
+extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma, float epsilon, uint64_t seed,
+                                const float *q_init_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (const char *why = discrete_learn_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_learner: ") + why);
+    if (algo != MDPP_LEARN_Q_LEARNING && algo != MDPP_LEARN_SARSA) return fail(h, MDPP_EINVAL, "mdpp_set_learner: unknown algo");
+    if (!learner_rates_ok(alpha, epsilon) || !(gamma >= 0.0f && gamma <= 1.0f))
+        return fail(h, MDPP_EINVAL, "mdpp_set_learner: need alpha in (0, 1], gamma and epsilon in [0, 1]");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t N = (size_t)h->cfg.num_envs, bytes = N * (size_t)h->cfg.S * (size_t)h->cfg.A * sizeof(float);
+    if (!h->d_learn_q) HIPCHK(h, hipMalloc(&h->d_learn_q, bytes));
+    if (!h->d_learn_carry) HIPCHK(h, hipMalloc(&h->d_learn_carry, N * sizeof(int32_t)));
+    // (on the caller's stream: behind the rollouts already queued there, ahead of the next one)
+    if (q_init_dev) {
+        int rc = launch_learn_q_copy(h, const_cast<float *>(q_init_dev), true, (hipStream_t)stream);
+        if (rc) return rc;
+    } else {
+        HIPCHK(h, hipMemsetAsync(h->d_learn_q, 0, bytes, (hipStream_t)stream));
+    }
+    h->learn_algo = algo; h->learn_alpha = alpha; h->learn_gamma = gamma; h->learn_seed = seed;
+    h->learn_E = (uint32_t)ceil((double)epsilon * 2147483648.0);
+    h->learn_ready = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_learner(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->learn_ready = false;      // (the buffers stay: a launch queued earlier may still use them)
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_learner_rates(mdpp_env *h, float alpha, float epsilon) {
+    if (!h) return MDPP_EINVAL;
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_set_learner_rates: no learner set (mdpp_set_learner)");
+    if (!learner_rates_ok(alpha, epsilon)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_rates: need alpha in (0, 1] and epsilon in [0, 1]");
+    h->learn_alpha = alpha;
+    h->learn_E = (uint32_t)ceil((double)epsilon * 2147483648.0);
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_step_n_learn(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                                 uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_learn: K < 1");
+    if (!actions_out_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev)
+        return fail(h, MDPP_EINVAL, "mdpp_step_n_learn: null buffer");
+    if (const char *why = discrete_learn_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_step_n_learn: ") + why);
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_step_n_learn: no learner set (mdpp_set_learner)");
+    int rc = check_ready(h, "mdpp_step_n_learn");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_discrete_learn(h, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, (hipStream_t)stream, nullptr);
+}
+
+static int learner_q_copy(mdpp_env *h, float *q_dev, bool to_handle, void *stream, const char *what) {
+    if (!h) return MDPP_EINVAL;
+    if (!q_dev) return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_learner)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_learn_q_copy(h, q_dev, to_handle, (hipStream_t)stream);
+}
+
+extern "C" int mdpp_get_q(mdpp_env *h, float *q_out_dev, void *stream) { return learner_q_copy(h, q_out_dev, false, stream, "mdpp_get_q"); }
+
+extern "C" int mdpp_set_q(mdpp_env *h, const float *q_in_dev, void *stream) {
+    return learner_q_copy(h, const_cast<float *>(q_in_dev), true, stream, "mdpp_set_q");
+}
+
+extern "C" const char *mdpp_learn_kernel_name(mdpp_env *h, int K) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1 || check_ready(h, "mdpp_learn_kernel_name")) return h->kname;
+    (void)hipSetDevice(h->device);
+    (void)launch_discrete_learn(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
     return h->kname;
 }
 

@@ -33,6 +33,8 @@ constexpr uint32_t kPhiloxStartIrrStream = 10; // ... of the irrelevant sub-spac
 constexpr uint32_t kPhiloxPNoiseStream = 12;  // discrete: transition noise, one word per tick (mdpp_rng.hpp)
 constexpr uint32_t kPhiloxRNoiseStream = 13;  // discrete: reward noise, one float32 normal per tick (four per block)
 constexpr uint32_t kPhiloxPolicyStream = 14;  // discrete: the tabular policy's action, one word per tick, keyed by the POLICY's seed (mdpp_discrete_policy.hip)
+constexpr uint32_t kPhiloxLearnExploreStream = 15; // discrete: the tabular learner's explore-or-not word, one per tick, keyed by the LEARNER's seed (mdpp_discrete_learn.hip)
+constexpr uint32_t kPhiloxLearnActionStream = 16;  // ... and the word of its exploring action
 
 // ---- per-episode noise statistics (cfg.episode_stats; general kernels only) ------------------------------------
 // What the reference accumulates per env object and logs at every reset() (rl_toy_env.py:2231-2247; cleared
@@ -318,6 +320,14 @@ struct mdpp_env {
     void *d_policy_thr;
     uint64_t policy_seed;
     bool policy_ready;
+    // the tabular TD learner of mdpp_step_n_learn (mdpp_set_learner): one Q-table per env, entry-major float32 [S A][N]; the
+    // sarsa action carried between the pieces of one call, int32 [N]
+    void *d_learn_q, *d_learn_carry;
+    uint64_t learn_seed;
+    uint32_t learn_E;           // ceil(epsilon 2^31)
+    float learn_alpha, learn_gamma;
+    int32_t learn_algo;
+    bool learn_ready;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -509,6 +519,12 @@ int launch_imagec_obs(mdpp_env *h, int K, const void *states, const void *final_
 const char *discrete_policy_refusal(const mdpp_env *h);
 int launch_discrete_policy(mdpp_env *h, int K, int32_t *actions_out, void *obs, float *reward, uint8_t *term, uint8_t *trunc,
                            hipStream_t s, char *name_out);
+// K steps of the handle's tabular learner (mdpp_discrete_learn.hip), as above; Q between the caller's [N][S][A] and the handle's
+// entry-major buffer
+const char *discrete_learn_refusal(const mdpp_env *h);
+int launch_discrete_learn(mdpp_env *h, int K, int32_t *actions_out, void *obs, float *reward, uint8_t *term, uint8_t *trunc,
+                          hipStream_t s, char *name_out);
+int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // phase bits: 1 = draw + records, 2 = render (phase == 2 exactly: pipelined, the persistent grid leaves slots

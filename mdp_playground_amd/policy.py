@@ -10,10 +10,16 @@ last entry): T[s][j] = ceil(cdf[j] * 2^31).  m * 2^-31 and cdf[j] * 2^31 are exa
 searchsorted(cdf, m * 2^-31, 'right') -- the rule the library uses for start states on Philox streams.  T[s][A-1] = 2^31
 is never <= m; a one-hot row gives thresholds 0 and 2^31 and is exactly deterministic; an action of probability zero has
 T[j] == T[j-1] and is never drawn.
+
+Host helpers of the in-kernel tabular learners (set_learner / rollout_learn) live here too: epsilon_threshold makes the
+integer the kernel compares the explore word with, explore_action is its rule for the exploring action, and
+check_learner_params is the validation set_learner applies.
 """
 import numpy as np
 
-__all__ = ["policy_thresholds"]
+__all__ = ["policy_thresholds", "epsilon_threshold", "explore_action", "check_learner_params", "LEARN_ALGOS"]
+
+LEARN_ALGOS = ("q_learning", "sarsa")
 
 
 def _to_numpy(policy):
@@ -53,3 +59,27 @@ def policy_thresholds(policy, S, A):
     cdf /= cdf[:, -1:]
     return np.ceil(cdf * 2.0 ** 31).astype(np.uint32)
 
+
+def epsilon_threshold(eps):
+    """E = ceil(epsilon * 2^31) in float64, epsilon rounded to float32 first (the C ABI takes a float): a step explores iff
+    (wE >> 1) < E, so epsilon = 0 never explores and epsilon = 1 always does."""
+    e = float(np.float32(eps))
+    if not 0.0 <= e <= 1.0:
+        raise ValueError(f"epsilon must lie in [0, 1], got {eps!r}")
+    return int(np.ceil(np.float64(e) * 2147483648.0))
+
+
+def explore_action(word, A):
+    """The exploring action of a 32-bit word: (uint64(word) * A) >> 32."""
+    return (np.asarray(word, dtype=np.uint64) * np.uint64(A)) >> np.uint64(32)
+
+
+def check_learner_params(algo, alpha, gamma, epsilon):
+    """ValueError unless algo is known, alpha in (0, 1], gamma and epsilon in [0, 1] (None: not checked)."""
+    if algo is not None and algo not in LEARN_ALGOS:
+        raise ValueError(f"algo must be one of {LEARN_ALGOS}, got {algo!r}")
+    if alpha is not None and not 0.0 < float(np.float32(alpha)) <= 1.0:
+        raise ValueError(f"alpha must lie in (0, 1], got {alpha!r}")
+    for name, v in (("gamma", gamma), ("epsilon", epsilon)):
+        if v is not None and not 0.0 <= float(np.float32(v)) <= 1.0:
+            raise ValueError(f"{name} must lie in [0, 1], got {v!r}")

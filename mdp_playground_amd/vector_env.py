@@ -87,6 +87,8 @@ class RLToyVectorEnv:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.config = copy.deepcopy(config)   # the reference mutates its config (:339,...); we do not
         self._gen = None                      # mdp.device_gen_params when the per-env tables are generated on the device
+        self._learn_rates = None              # [alpha, epsilon] of the learner (set_learner); None: no learner
+        self._learn_q_init = None             # the tensor last handed to set_learner / set_q, kept until its copy has been made
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
                 raise ValueError("num_envs != len(seeds)")
@@ -710,6 +712,101 @@ class RLToyVectorEnv:
         except NotImplementedError:
             return ""
         name = self._lib.mdpp_policy_kernel_name(self._h, int(K))
+        return name.decode() if name else ""
+
+    # ------------------------------------------------------------------ in-kernel tabular TD learners
+    def _learn_call(self, rc, what):
+        if rc == capi.EUNSUPPORTED:
+            msg = self._lib.mdpp_last_error(self._h)
+            raise NotImplementedError(msg.decode() if msg else what + ": unsupported")
+        capi.check(self._lib, self._h, rc, what)
+
+    def _learn_check_kind(self):
+        if self.kind != "discrete":
+            raise NotImplementedError("learner rollouts serve discrete envs only (this env is %s)" % self.kind)
+
+    def _learn_q_arg(self, q, what):
+        S, A = self.mdps[0].S, self.mdps[0].A
+        if not (torch.is_tensor(q) and q.dtype == torch.float32 and q.device == self.device
+                and tuple(q.shape) == (self.num_envs, S, A)):
+            raise ValueError(f"{what}: q must be a float32 tensor of shape ({self.num_envs}, {S}, {A}) on {self.device}")
+        return q.contiguous()
+
+    def set_learner(self, algo="q_learning", *, alpha=None, gamma=None, epsilon=None, seed=0, q=None):
+        """The handle's tabular TD learner for rollout_learn(): one independent agent PER ENV, ``algo`` "q_learning" or "sarsa",
+        float32 ``alpha`` in (0, 1], ``gamma`` and ``epsilon`` in [0, 1], ``seed`` the 64-bit key of the learner's own Philox
+        streams, ``q`` the initial tables (float32 [N, S, A] on the device; zeros when None).  ``set_learner(None)`` clears the
+        learner.  Handles the kernel does not serve raise NotImplementedError with the reason (include/mdpp.h: the rule)."""
+        if algo is None:
+            capi.check(self._lib, self._h, self._lib.mdpp_clear_learner(self._h), "mdpp_clear_learner")
+            self._learn_rates = None
+            return
+        if alpha is None or gamma is None or epsilon is None:
+            raise ValueError("set_learner: alpha, gamma and epsilon are required")
+        policy_mod.check_learner_params(algo, alpha, gamma, epsilon)
+        self._learn_check_kind()
+        if q is not None:
+            q = self._learn_q_arg(q, "set_learner")
+        rc = self._lib.mdpp_set_learner(self._h, capi.LEARN_ALGOS[algo], float(alpha), float(gamma), float(epsilon),
+                                        C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                        C.c_void_p(q.data_ptr()) if q is not None else None, self._stream())
+        self._learn_call(rc, "mdpp_set_learner")
+        self._learn_q_init = q           # (kept until the copy queued on the stream has certainly been made)
+        self._learn_rates = [float(alpha), float(epsilon)]
+
+    def set_learner_rates(self, alpha=None, epsilon=None):
+        """New alpha and / or epsilon for the learner (parameters only, no device work: a decay schedule on the host costs
+        nothing between launches)."""
+        policy_mod.check_learner_params(None, alpha, None, epsilon)
+        if self._learn_rates is None:
+            raise capi.MdppError("set_learner_rates: no learner set (set_learner)")
+        if alpha is not None:
+            self._learn_rates[0] = float(alpha)
+        if epsilon is not None:
+            self._learn_rates[1] = float(epsilon)
+        self._learn_call(self._lib.mdpp_set_learner_rates(self._h, *self._learn_rates), "mdpp_set_learner_rates")
+
+    def alloc_rollout_learn(self, K):
+        """Output buffers of rollout_learn(K): alloc_rollout(K) and the actions, int32 [K, N]."""
+        return self.alloc_rollout(K) + (torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device),)
+
+    def rollout_learn(self, K, out=None):
+        """K steps of "select epsilon-greedily from the env's own Q, step, update that Q" in ONE kernel launch.  Returns (obs,
+        reward, terminated, truncated, actions), each with a leading K axis; rollout(actions) on an identically built env
+        returns the same first four, bit for bit.  SARSA carries its next action from step to step inside a call only: the
+        first step of every call selects afresh."""
+        K = int(K)
+        self._learn_check_kind()
+        if out is None:
+            out = self.alloc_rollout_learn(K)
+        obs, rew, term, trunc, act = out
+        rc = self._lib.mdpp_step_n_learn(self._h, K, C.c_void_p(act.data_ptr()), C.c_void_p(obs.data_ptr()),
+                                         C.c_void_p(rew.data_ptr()), C.c_void_p(term.data_ptr()),
+                                         C.c_void_p(trunc.data_ptr()), self._stream())
+        self._learn_call(rc, "mdpp_step_n_learn")
+        self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
+        return obs, rew, term.view(torch.bool), trunc.view(torch.bool), act
+
+    def get_q(self):
+        """The learner's tables, float32 [N, S, A] (a copy, made on the current stream)."""
+        self._learn_check_kind()
+        q = torch.empty((self.num_envs, self.mdps[0].S, self.mdps[0].A), dtype=torch.float32, device=self.device)
+        self._learn_call(self._lib.mdpp_get_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_get_q")
+        return q
+
+    def set_q(self, q):
+        """Replace the learner's tables: float32 [N, S, A] on the device (copied on the current stream)."""
+        self._learn_check_kind()
+        q = self._learn_q_arg(q, "set_q")
+        self._learn_call(self._lib.mdpp_set_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_set_q")
+        self._learn_q_init = q
+
+    def learn_kernel_name(self, K):
+        """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
+        launched; QLDS=1: the Q-tables are staged in LDS); empty for a handle it does not serve."""
+        if self.kind != "discrete":
+            return ""
+        name = self._lib.mdpp_learn_kernel_name(self._h, int(K))
         return name.decode() if name else ""
 
     def rollout_kernel_name(self, K):
