@@ -97,8 +97,8 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
        MDPP_OPT_NO_SIGMA0 = 1u << 16,      /* noise keys present with sigma 0 (the reference draws rng.normal(0, 0): rl_toy_env.py:398-403, :1982):
                                               form the normals' values anyway instead of advancing the streams alone */
        MDPP_OPT_NO_LEARN_LDS = 1u << 18,   /* k_discrete_learn_rollout: the Q-tables stay in global memory (QLDS=0) */
-       MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19 }; /* mdpp_step_n_learn goes out in launches of at most 5 steps (the hand-over
-                                              between the pieces of a very long call, at a size a test can run) */
+       MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19 }; /* mdpp_step_n_policy and mdpp_step_n_learn go out in launches of at most 5 steps
+                                              (the hand-over between the pieces of a very long call, at a size a test can run) */
 
 /* the tabular learner's algorithm (mdpp_set_learner); 2 is kept for double Q-learning */
 enum { MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1 };

@@ -1325,11 +1325,39 @@ extern "C" const char *mdpp_kernel_name(mdpp_env *h, int K) {
     return h->kname;
 }
 
-// ---- closed-loop rollouts under a tabular policy (mdpp_discrete_policy.hip) ----
+// ---- closed-loop rollouts: the agent acts inside the launch (mdpp_discrete_closed.hpp) ----
+// mdpp_step_n_policy / mdpp_step_n_learn: the argument checks, then the launch.  why: the handle's refusal (empty: served);
+// ready / unready: the agent has been set, or what to say
+static int step_n_closed(mdpp_env *h, const char *what, const std::string &why, bool ready, const char *unready,
+                         int (*launch)(mdpp_env *, const DiscreteIO &), int K, int32_t *actions, void *obs, float *reward,
+                         uint8_t *term, uint8_t *trunc, void *stream) {
+    if (K < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": K < 1");
+    if (!actions || !obs || !reward || !term || !trunc) return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
+    if (!ready) return fail(h, MDPP_ESTATE, std::string(what) + ": " + unready);
+    int rc = check_ready(h, what);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch(h, DiscreteIO{K, actions, obs, reward, term, trunc, nullptr, (hipStream_t)stream, nullptr});
+}
+// (a dry run: the launcher writes the kernel's name and launches nothing)
+static const char *closed_kernel_name(mdpp_env *h, int K, const char *what, int (*launch)(mdpp_env *, const DiscreteIO &)) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1 || check_ready(h, what)) return h->kname;
+    (void)hipSetDevice(h->device);
+    DiscreteIO dry{};
+    dry.K = K; dry.name_out = h->kname;
+    (void)launch(h, dry);
+    return h->kname;
+}
+
+// ---- ... under a tabular policy (mdpp_discrete_policy.hip) ----
 extern "C" int mdpp_set_policy(mdpp_env *h, const uint32_t *thr_dev, uint64_t policy_seed, void *stream) {
     if (!h) return MDPP_EINVAL;
     if (!thr_dev) return fail(h, MDPP_EINVAL, "mdpp_set_policy: null thresholds");
-    if (const char *why = discrete_policy_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_policy: ") + why);
+    const std::string why = discrete_policy_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_policy: " + why);
     HIPCHK(h, hipSetDevice(h->device));
     const size_t bytes = (size_t)h->cfg.S * (size_t)h->cfg.A * sizeof(uint32_t);
     if (!h->d_policy_thr) HIPCHK(h, hipMalloc(&h->d_policy_thr, bytes));
@@ -1349,26 +1377,15 @@ extern "C" int mdpp_clear_policy(mdpp_env *h) {
 extern "C" int mdpp_step_n_policy(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
                                   uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
     if (!h) return MDPP_EINVAL;
-    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_policy: K < 1");
-    if (!actions_out_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev)
-        return fail(h, MDPP_EINVAL, "mdpp_step_n_policy: null buffer");
-    if (const char *why = discrete_policy_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_step_n_policy: ") + why);
-    if (!h->policy_ready) return fail(h, MDPP_ESTATE, "mdpp_step_n_policy: no policy set (mdpp_set_policy)");
-    int rc = check_ready(h, "mdpp_step_n_policy");
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    return launch_discrete_policy(h, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, (hipStream_t)stream, nullptr);
+    return step_n_closed(h, "mdpp_step_n_policy", discrete_policy_refusal(h), h->policy_ready, "no policy set (mdpp_set_policy)",
+                         launch_discrete_policy, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, stream);
 }
 
 extern "C" const char *mdpp_policy_kernel_name(mdpp_env *h, int K) {
-    if (!h) return "";
-    h->kname[0] = 0;
-    if (K < 1 || check_ready(h, "mdpp_policy_kernel_name")) return h->kname;
-    (void)launch_discrete_policy(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
-    return h->kname;
+    return closed_kernel_name(h, K, "mdpp_policy_kernel_name", launch_discrete_policy);
 }
 
-// ---- in-kernel tabular TD learners (mdpp_discrete_learn.hip) ----
+// ---- ... of in-kernel tabular TD learners (mdpp_discrete_learn.hip) ----
 static bool learner_rates_ok(float alpha, float epsilon) {
     return alpha > 0.0f && alpha <= 1.0f && epsilon >= 0.0f && epsilon <= 1.0f;      // (NaN fails both)
 }
@@ -1376,7 +1393,8 @@ static bool learner_rates_ok(float alpha, float epsilon) {
 extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma, float epsilon, uint64_t seed,
                                 const float *q_init_dev, void *stream) {
     if (!h) return MDPP_EINVAL;
-    if (const char *why = discrete_learn_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_learner: ") + why);
+    const std::string why = discrete_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_learner: " + why);
     if (algo != MDPP_LEARN_Q_LEARNING && algo != MDPP_LEARN_SARSA) return fail(h, MDPP_EINVAL, "mdpp_set_learner: unknown algo");
     if (!learner_rates_ok(alpha, epsilon) || !(gamma >= 0.0f && gamma <= 1.0f))
         return fail(h, MDPP_EINVAL, "mdpp_set_learner: need alpha in (0, 1], gamma and epsilon in [0, 1]");
@@ -1415,15 +1433,8 @@ extern "C" int mdpp_set_learner_rates(mdpp_env *h, float alpha, float epsilon) {
 extern "C" int mdpp_step_n_learn(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
                                  uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
     if (!h) return MDPP_EINVAL;
-    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_learn: K < 1");
-    if (!actions_out_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev)
-        return fail(h, MDPP_EINVAL, "mdpp_step_n_learn: null buffer");
-    if (const char *why = discrete_learn_refusal(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_step_n_learn: ") + why);
-    if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_step_n_learn: no learner set (mdpp_set_learner)");
-    int rc = check_ready(h, "mdpp_step_n_learn");
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    return launch_discrete_learn(h, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, (hipStream_t)stream, nullptr);
+    return step_n_closed(h, "mdpp_step_n_learn", discrete_learn_refusal(h), h->learn_ready, "no learner set (mdpp_set_learner)",
+                         launch_discrete_learn, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, stream);
 }
 
 static int learner_q_copy(mdpp_env *h, float *q_dev, bool to_handle, void *stream, const char *what) {
@@ -1441,12 +1452,7 @@ extern "C" int mdpp_set_q(mdpp_env *h, const float *q_in_dev, void *stream) {
 }
 
 extern "C" const char *mdpp_learn_kernel_name(mdpp_env *h, int K) {
-    if (!h) return "";
-    h->kname[0] = 0;
-    if (K < 1 || check_ready(h, "mdpp_learn_kernel_name")) return h->kname;
-    (void)hipSetDevice(h->device);
-    (void)launch_discrete_learn(h, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
-    return h->kname;
+    return closed_kernel_name(h, K, "mdpp_learn_kernel_name", launch_discrete_learn);
 }
 
 // Python round(v, 15) for |v| <= 1: correctly rounded decimal conversion, like Pillow's rotate().

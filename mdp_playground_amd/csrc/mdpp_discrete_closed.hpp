@@ -1,0 +1,283 @@
+// The closed-loop step of a discrete env, stated once: K steps of "an agent picks a from the state the env is in, the env
+// steps, the agent sees the transition" in ONE launch.  k_discrete_policy_rollout (mdpp_discrete_policy.hip) and
+// k_discrete_learn_rollout (mdpp_discrete_learn.hip) are this body around their own Agent; so is the launcher and the rule
+// for which handles are served.
+//
+// The step restates k_discrete_step (mdpp_discrete.hip) without its IRR branches and episode statistics, on the same lines
+// of the reference's mdp_playground/envs/rl_toy_env.py:
+//   D1 P lookup            :1602-1603      D5 delay FIFO        :1968-1973
+//   D2 transition noise    :1605-1625      D6 every-n / affine  :1975-1990
+//   D3 history shift       :2050-2058      D7 terminal + reward :2102-2109
+//   D4 sequence reward     :1821-1845      R1 reset             :2250-2278, :2354-2369
+// NOISE = true adds D2 (the categorical's cdf / philox_pnoise_state) and the reward noise (numpy's ziggurat with the tables
+// in LDS / PhiloxTickNormals).  The agent reads no stream of the env, so the launch leaves every stream, the state record
+// and the step counter where mdpp_step_n fed with the same actions leaves them.
+//
+// One lane per env, 256-thread workgroups, the general 16-byte record {hist bytes 0-3, hist bytes 4-7, steps, ring bits}.
+// fast_ok handles (mdpp_discrete_fast.hip) keep their queue of start states drawn ahead in word 1 of the record instead of
+// history bytes 4-7 (they have L <= 3): a reset here pops the queue first, in order, and draws from the env stream only when
+// it is empty, as k_discrete_reset does -- so any kernel of the handle can follow this one and the other way round.
+// The shared MDP's tables are staged in LDS in the handle's own carve (DiscreteArgs::lds_*); what the agent stages goes
+// behind them (from lds + a.lds_bytes).  Outputs leave through range-checked non-temporal buffer stores.
+//
+// An Agent is a struct of force-inlined members (no virtual calls, no function pointers):
+//   stage(tid)                 cooperative LDS staging, before the barrier
+//   begin(i, genv, ptick0)     per lane, after the `i >= N` return
+//   next_block(genv, ptick)    at a launch's first step and at every tick that starts a Philox block (wave-uniform)
+//   act(cur, ptick)            the action of this step; also called on a reset call, from the state in the record
+//   learn(cur, action, nxt, reward, done, truncated_with_reset, ptick)
+//                              after the reward is formed, before a same-step reset: nxt is the true next state
+//   finish(i)                  per lane, after the last step
+#pragma once
+#include "mdpp_internal.hpp"
+#include "mdpp_rng.hpp"
+
+namespace mdpp {
+
+constexpr int kClosedRsrcFlags = 0x00020000;
+typedef unsigned int closed_u32x2 __attribute__((ext_vector_type(2)));
+
+// (a is the kernel's by-value argument, taken by const reference: see tick_now in mdpp_internal.hpp for what a write costs)
+template <bool PHILOX, bool NOISE, bool UNIT, class Agent>
+__device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K, const bool obs64, int32_t *actions,
+                                                    void *__restrict__ obs, float *__restrict__ reward,
+                                                    uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
+                                                    unsigned char *lds, const ZigLds &zig, Agent &agent) {
+    const uint64_t ptick0 = tick_now(a);               // the step counter at this launch (through the device-side offset of a graph replay)
+    const uint32_t rhead0 = ring_head_now(a, ptick0);  // ... and the head of a delay line kept in memory
+    const int tid = threadIdx.x;
+    const uint32_t i = blockIdx.x * kBlock + tid;
+    const int S = a.S, A = a.A, L = a.L;
+    const uint32_t N = (uint32_t)a.N;
+    // stage the shared MDP (and the noise categoricals), then what the agent keeps in LDS
+    for (uint32_t k = tid; k < (uint32_t)S * (uint32_t)A; k += kBlock) lds[a.lds_P + k] = a.P[k];
+    for (int k = tid; k < S; k += kBlock) {
+        lds[a.lds_term + k] = a.is_term[k];
+        ((double *)(lds + a.lds_init))[k] = a.init_cdf[k];
+    }
+    if (UNIT)
+        for (uint32_t k = tid; k < a.rbits_stride; k += kBlock) lds[a.lds_rew + k] = a.rbits[k];
+    else
+        for (uint32_t k = tid; k < a.nkeys; k += kBlock) ((double *)(lds + a.lds_rew))[k] = a.rtable[k];
+    const bool pn_lds = NOISE && a.has_p_noise && a.noise_in_lds;
+    if (pn_lds)
+        for (int k = tid; k < S * S; k += kBlock) ((double *)(lds + a.lds_noise))[k] = a.noise_cdf[k];
+    agent.stage(tid);
+    __syncthreads();
+    if (i >= N) return;
+    const uint8_t *const tP = lds + a.lds_P, *const tterm = lds + a.lds_term, *const trbits = lds + a.lds_rew;
+    const double *const trtable = (const double *)(lds + a.lds_rew), *const tinit = (const double *)(lds + a.lds_init);
+    const double *const tnoise = (const double *)(lds + a.lds_noise);
+    const uint64_t genv = (uint64_t)(a.env_id_offset + (int64_t)i);
+    agent.begin(i, genv, ptick0);
+
+    const uint4 st = a.state[i];
+    // fast_ok handles: word 1 is the queue of start states {24 bits of 4-bit entries, next one lowest; count in bits 24-26},
+    // and history bytes 4-7 do not exist (L <= 3: never read)
+    const bool queued = a.fast_ok != 0;
+    uint64_t hist = ((uint64_t)(queued ? 0xFFFFFFFFu : st.y) << 32) | st.x;      // newest state in byte 0, 0xFF = NaN
+    uint32_t qv = st.y & 0x00FFFFFFu, qc = (st.y >> 24) & 7u;
+    uint32_t steps = st.z, ringbits = st.w;
+    const bool next_step = a.autoreset == MDPP_AUTORESET_NEXT_STEP;
+    bool pending = next_step && (steps >> 31) != 0;     // bit 31 of the step counter: the next call is this env's reset
+    steps &= 0x7FFFFFFFu;
+    uint32_t phase = steps % (uint32_t)a.every_n;       // steps % every_n, kept incrementally below
+
+    Pcg64 env_pcg, sp_pcg;
+    PhiloxTickWords pn_w;                               // Philox streams: the current four ticks' noise words / normals
+    PhiloxTickNormals rn_z;
+    const bool use_env = !PHILOX && ((NOISE && a.has_r_noise) || a.autoreset != 0);   // reward noise, in-rollout resets
+    const bool use_sp = !PHILOX && NOISE && a.has_p_noise;
+    if (use_env) env_pcg.load(a.env_s, a.env_inc, i);
+    if (use_sp) sp_pcg.load(a.sp_s, a.sp_inc, i);
+
+    // the four rewards of the noise-free unit path {paid, not paid} x {terminal, not}, formed once in the reference's float64
+    // order (:1987-1990, :2107) and selected per step
+    auto unit_reward = [&](bool paid, bool terminal) -> float {
+        double r = paid ? 1.0 : 0.0;
+        r *= a.scale;
+        r += a.shift;
+        if (terminal) r += a.term_add;
+        return (float)r;
+    };
+    const float rs0 = unit_reward(false, false), rs1 = unit_reward(false, true), rs2 = unit_reward(true, false), rs3 = unit_reward(true, true);
+    auto reward_noise = [&](uint64_t ptick) -> double {
+        return 0.0 + a.r_noise * (PHILOX ? (double)rn_z.normal(a.philox_seed, genv, ptick, kPhiloxRNoiseStream) : np_standard_normal_lds(env_pcg, zig));
+    };
+
+    const uint32_t total = (uint32_t)K * N;             // (the launcher keeps 8 K N below 2^32)
+    auto r_act = __builtin_amdgcn_make_buffer_rsrc((void *)actions, 0, total * 4u, kClosedRsrcFlags);
+    auto r_obs = __builtin_amdgcn_make_buffer_rsrc(obs, 0, total * (obs64 ? 8u : 4u), kClosedRsrcFlags);
+    auto r_rew = __builtin_amdgcn_make_buffer_rsrc((void *)reward, 0, total * 4u, kClosedRsrcFlags);
+    auto r_term = __builtin_amdgcn_make_buffer_rsrc((void *)term, 0, total, kClosedRsrcFlags);
+    auto r_trunc = __builtin_amdgcn_make_buffer_rsrc((void *)trunc, 0, total, kClosedRsrcFlags);
+    const uint32_t v1 = i, v4 = i * 4u, v8 = i * 8u;
+    auto put_obs = [&](uint32_t s, uint32_t so) {       // (the width: a constant or wave-uniform)
+        if (obs64) __builtin_amdgcn_raw_buffer_store_b64(closed_u32x2{s, 0u}, r_obs, v8, so * 8u, MDPP_ST_NT);
+        else __builtin_amdgcn_raw_buffer_store_b32(s, r_obs, v4, so * 4u, MDPP_ST_NT);
+    };
+
+    // reset(): the first state of the next episode (:2255: one uniform, searchsorted(cdf, u, 'right'))
+    auto start_state = [&](uint64_t ptick) -> uint32_t {
+        if (PHILOX)          // one word of the start-state stream per tick (mdpp_rng.hpp)
+            return (uint32_t)searchsorted_right(tinit, S, philox_start_uniform(philox_start_m31(a.philox_seed, genv, ptick, kPhiloxStartStream)));
+        if (queued && qc != 0) {                        // the next draws of the stream, made ahead by another kernel
+            const uint32_t s0 = qv & 0xFu;
+            qv >>= 4; qc -= 1;
+            return s0;
+        }
+        return (uint32_t)searchsorted_right(tinit, S, np_random(env_pcg));
+    };
+    auto episode_start = [&](uint32_t s0) {
+        hist = 0xFFFFFFFFFFFFFF00ULL | (uint64_t)s0;
+        steps = 0; phase = 0; ringbits = 0;
+        if (!UNIT)
+            for (int d = 0; d < a.delay; d++) a.ring_keys[(size_t)d * N + i] = kNoKey;
+    };
+
+    for (int k = 0; k < K; k++) {
+        const uint64_t ptick = ptick0 + (uint64_t)k;
+        const uint32_t so = (uint32_t)k * N;
+        if (k == 0 || (ptick & 3u) == 0u) agent.next_block(genv, ptick);            // (wave-uniform)
+        const uint32_t cur = (uint32_t)hist & 0xFFu;
+        const uint32_t action = agent.act(cur, ptick);
+        __builtin_amdgcn_raw_buffer_store_b32(action, r_act, v4, so * 4u, MDPP_ST_NT);
+        if (pending) {               // next-step autoreset: this call is the env's reset(), :2250-2278; the action is ignored, nothing is learnt
+            const uint32_t s0 = start_state(ptick);
+            episode_start(s0);
+            put_obs(s0, so);
+            __builtin_amdgcn_raw_buffer_store_b32(0u, r_rew, v4, so * 4u, MDPP_ST_NT);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, r_term, v1, so, MDPP_ST_NT);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, r_trunc, v1, so, MDPP_ST_NT);
+            pending = false;
+            continue;
+        }
+        uint32_t nxt = tP[cur * (uint32_t)A + action];                              // D1
+        if (NOISE && a.has_p_noise) {                                               // D2
+            // (Philox streams: one word of the tick decides "noisy" and which other state; numpy streams: the state space's own
+            //  generator and the categorical's cdf, as in the reference)
+            if (PHILOX) nxt = philox_pnoise_state(pn_w.word(a.philox_seed, genv, ptick, kPhiloxPNoiseStream), a.pn_T, a.pn_M, nxt);
+            else if (pn_lds) nxt = (uint32_t)searchsorted_right(tnoise + (size_t)nxt * S, S, np_random(sp_pcg));
+            else nxt = (uint32_t)searchsorted_right(a.noise_cdf + (size_t)nxt * S, S, np_random(sp_pcg));
+        }
+        hist = (hist << 8) | nxt;                                                   // D3
+        steps += 1;
+        phase = (phase + 1 == (uint32_t)a.every_n) ? 0u : phase + 1;
+        uint32_t key = kNoKey;                                                      // D4 (NaN gate: L transitions since reset, :1822)
+        if (((hist >> (8 * L)) & 0xFFu) != 0xFFu) {
+            key = 0;
+            for (int j = L - 1; j >= 0; j--) key = key * (uint32_t)S + (uint32_t)((hist >> (8 * j)) & 0xFFu);
+        }
+        // custom reward matrix: R(s, a) of this transition, whatever s' (noise included) was (:1259-1267)
+        if (!UNIT && a.rew_sa) key = cur * (uint32_t)A + action;
+        const bool done = tterm[nxt] != 0;                                          // D7
+        float rout;
+        if (UNIT) {
+            uint32_t bit = 0;
+            if (key != kNoKey) bit = (trbits[key >> 3] >> (key & 7u)) & 1u;
+            if (a.delay > 0) {                                                      // D5 (shift register)
+                const uint32_t out = (ringbits >> (a.delay - 1)) & 1u;
+                ringbits = (ringbits << 1) | bit;
+                bit = out;
+            }
+            if (phase != 0) bit = 0;                                                // D6
+            if (NOISE && a.has_r_noise) {
+                double r = bit ? 1.0 : 0.0;
+                r += reward_noise(ptick);
+                r *= a.scale;
+                r += a.shift;
+                if (done) r += a.term_add;
+                rout = (float)r;
+            } else {
+                rout = done ? (bit ? rs3 : rs1) : (bit ? rs2 : rs0);
+            }
+        } else {
+            if (a.delay > 0) {                                                      // D5 (key ring)
+                uint32_t *slot = a.ring_keys + (size_t)((rhead0 + (uint32_t)k) % (uint32_t)a.delay) * N + i;
+                const uint32_t out = *slot;
+                *slot = key;
+                key = out;
+            }
+            double r = (key != kNoKey) ? trtable[key] : 0.0;
+            if (phase != 0) r = 0.0;                                                // D6
+            if (NOISE && a.has_r_noise) r += reward_noise(ptick);
+            r *= a.scale;
+            r += a.shift;
+            if (done) r += a.term_add;
+            rout = (float)r;
+        }
+        const bool truncated = (a.max_steps > 0) && (steps >= (uint32_t)a.max_steps);
+        agent.learn(cur, action, nxt, rout, done, truncated && a.autoreset != MDPP_AUTORESET_DISABLED, ptick);
+
+        uint32_t out_state = nxt;
+        if (next_step) pending = done || truncated;
+        if (a.autoreset == MDPP_AUTORESET_SAME_STEP && (done || truncated)) {
+            // same-step autoreset: the terminal transition's reward and flags, the first observation of the next episode
+            out_state = start_state(ptick);
+            episode_start(out_state);
+        }
+        put_obs(out_state, so);
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rout), r_rew, v4, so * 4u, MDPP_ST_NT);
+        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(done ? 1 : 0), r_term, v1, so, MDPP_ST_NT);
+        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(truncated ? 1 : 0), r_trunc, v1, so, MDPP_ST_NT);
+    }
+
+    agent.finish(i);
+    a.state[i] = make_uint4((uint32_t)hist, queued ? (qv | (qc << 24)) : (uint32_t)(hist >> 32),
+                            steps | (pending ? 0x80000000u : 0u), ringbits);
+    if (use_env) env_pcg.store(a.env_s, i);
+    if (use_sp) sp_pcg.store(a.sp_s, i);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+constexpr size_t kZigLdsBytes = 3u * 256u * 8u;        // a NOISE kernel's static LDS: the ziggurat tables
+
+// Why this handle has no closed-loop launch ("<noun> rollouts ..."), or empty: the kernel serves it.  agent_lds: the LDS
+// the agent needs whatever the launch (bytes), tables: what has to fit, for the message
+inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool serves_noise, uint64_t agent_lds, const char *tables) {
+    const mdpp_config &c = h->cfg;
+    const DiscreteArgs &a = h->dargs;
+    const char *why = nullptr;
+    const bool noise = c.has_transition_noise || c.has_reward_noise;
+    if (c.kind != MDPP_KIND_DISCRETE) why = "serve discrete envs only (this handle is continuous or a grid)";
+    else if (c.image) why = "do not serve image observations";
+    else if (c.irrelevant) why = "do not serve an irrelevant sub-space (irrelevant_features)";
+    else if (c.num_tables != 1) why = "need one shared MDP (this handle has one MDP per env: seeds=[...])";
+    else if (c.S > 255) why = "need at most 255 states (state_space_size)";
+    else if (c.L > 7) why = "need sequence_length <= 7";
+    else if (!serves_noise && c.has_transition_noise) why = "do not serve a transition_noise key";
+    else if (!serves_noise && c.has_reward_noise) why = "do not serve a reward_noise key";
+    else if (c.episode_stats) why = "do not keep episode_stats";
+    else if (!a.rew_in_lds || (uint64_t)a.lds_bytes + agent_lds + (noise ? kZigLdsBytes : 0u) > 64u * 1024u)
+        return std::string(noun) + " rollouts need " + tables + " within 64 KiB of LDS";
+    return why ? std::string(noun) + " rollouts " + why : std::string();
+}
+
+// K closed-loop steps of kern with lds bytes of dynamic LDS.  name: the kernel's, with its template arguments -- a dry run
+// (io.name_out) writes it and launches nothing.  agent_args(k0, kc, actions) makes the kernel's second argument for the
+// launch of steps [k0, k0 + kc), whose actions go to `actions`.  lds_granted: the caller has asked dynamic_lds_ok for this
+// kernel and size already.
+template <class Kern, class AgentArgs>
+inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size_t lds, bool lds_granted, const char *name,
+                              AgentArgs &&agent_args) {
+    const std::string kernel(name, strcspn(name, "<"));
+    DiscreteArgs a = h->dargs;
+    stamp_step(a, h);
+    // pieces: the buffer descriptors address < 4 GiB per output array (8 bytes per env-step at most)
+    long long kmax = ((1LL << 32) - 1) / (8LL * a.N);
+    if (kmax < 1) { h->err = kernel + ": num_envs too large"; return MDPP_EUNSUPPORTED; }
+    if ((a.opts & MDPP_OPT_LEARN_SHORT_PIECES) && kmax > 5) kmax = 5;      // (tests: the pieces' hand-over at a small size)
+    if (io.name_out) { snprintf(io.name_out, kNameLen, "%s", name); return MDPP_OK; }
+    if (!lds_granted && !dynamic_lds_ok((const void *)kern, lds)) { h->err = kernel + ": the device refuses the launch's LDS"; return MDPP_EUNSUPPORTED; }
+    const int grid = (a.N + kBlock - 1) / kBlock;
+    // (io.actions, an input of every other launcher, is this one's OUTPUT: the caller's buffer for the actions taken; piece_of
+    //  offsets it like the other arrays -- these handles have no irrelevant sub-space -- and the const comes off at the launch)
+    for_each_piece(a, h, io, kmax, [&](const DiscreteIO &p, int k0) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, io.s, a, agent_args(k0, p.K, const_cast<int32_t *>(p.actions)), p.K,
+                           p.obs, p.reward, p.term, p.trunc);
+        return true;
+    });
+    return step_done(h, io.K, kernel.c_str());
+}
+
+} // namespace mdpp

@@ -422,7 +422,7 @@ constexpr int kNameLen = 192;
 template <class Act, class Obs>
 struct StepIO {
     int K;
-    const Act *actions;
+    const Act *actions;         // (the closed-loop launchers, mdpp_discrete_closed.hpp, WRITE the actions taken here)
     Obs *obs;
     float *reward;
     uint8_t *term, *trunc;
@@ -514,16 +514,15 @@ bool launch_continuous_step1(const ContinuousArgs &a, const ContinuousIO &io);
 bool launch_continuous_line(const ContinuousArgs &a, const ContinuousIO &io);
 int launch_imagec_obs(mdpp_env *h, int K, const void *states, const void *final_states, const uint8_t *term,
                       const uint8_t *trunc, const uint8_t *mask, uint8_t *img_out, uint8_t *img_final, hipStream_t s);
-// closed-loop rollout under the handle's tabular policy (mdpp_discrete_policy.hip): why the handle has none (null: it is
-// served); K steps, the sampled actions to actions_out (name_out != nullptr: a dry run, the kernel's name only)
-const char *discrete_policy_refusal(const mdpp_env *h);
-int launch_discrete_policy(mdpp_env *h, int K, int32_t *actions_out, void *obs, float *reward, uint8_t *term, uint8_t *trunc,
-                           hipStream_t s, char *name_out);
-// K steps of the handle's tabular learner (mdpp_discrete_learn.hip), as above; Q between the caller's [N][S][A] and the handle's
-// entry-major buffer
-const char *discrete_learn_refusal(const mdpp_env *h);
-int launch_discrete_learn(mdpp_env *h, int K, int32_t *actions_out, void *obs, float *reward, uint8_t *term, uint8_t *trunc,
-                          hipStream_t s, char *name_out);
+// closed-loop rollout under the handle's tabular policy (mdpp_discrete_policy.hip; the step and the launcher they share:
+// mdpp_discrete_closed.hpp): why the handle has none (empty: it is served); io.K steps, the sampled actions written to
+// io.actions
+std::string discrete_policy_refusal(const mdpp_env *h);
+int launch_discrete_policy(mdpp_env *h, const DiscreteIO &io);
+// io.K steps of the handle's tabular learner (mdpp_discrete_learn.hip), as above; Q between the caller's [N][S][A] and the
+// handle's entry-major buffer
+std::string discrete_learn_refusal(const mdpp_env *h);
+int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io);
 int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);

@@ -666,10 +666,7 @@ class RLToyVectorEnv:
                 raise ValueError(f"set_policy: thresholds must be a uint32 tensor of shape ({S}, {A}) on {self.device}")
             thr = thr.contiguous()
         rc = self._lib.mdpp_set_policy(self._h, C.c_void_p(thr.data_ptr()), C.c_uint64(int(seed) & (2 ** 64 - 1)), self._stream())
-        if rc == capi.EUNSUPPORTED:
-            msg = self._lib.mdpp_last_error(self._h)
-            raise NotImplementedError(msg.decode() if msg else "mdpp_set_policy: unsupported")
-        capi.check(self._lib, self._h, rc, "mdpp_set_policy")
+        self._closed_call(rc, "mdpp_set_policy")
         self._policy_thr = thr           # (kept until the copy queued on the stream has certainly been made)
 
     def _policy_check_config(self):
@@ -681,28 +678,37 @@ class RLToyVectorEnv:
             if self.config.get(key) is not None:
                 raise NotImplementedError("policy rollouts do not serve a %s key (config[%r] = %r)" % (key, key, self.config[key]))
 
+    def _closed_call(self, rc, what):
+        """The return code of a closed-loop call: a handle the kernel does not serve raises NotImplementedError with the reason."""
+        if rc == capi.EUNSUPPORTED:
+            msg = self._lib.mdpp_last_error(self._h)
+            raise NotImplementedError(msg.decode() if msg else what + ": unsupported")
+        capi.check(self._lib, self._h, rc, what)
+
+    def _alloc_rollout_closed(self, K):
+        return self.alloc_rollout(K) + (torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device),)
+
+    def _rollout_closed(self, step_n, what, K, out):
+        """K closed-loop steps through step_n (mdpp_step_n_policy / mdpp_step_n_learn)."""
+        if out is None:
+            out = self._alloc_rollout_closed(K)
+        obs, rew, term, trunc, act = out
+        rc = step_n(self._h, K, C.c_void_p(act.data_ptr()), C.c_void_p(obs.data_ptr()), C.c_void_p(rew.data_ptr()),
+                    C.c_void_p(term.data_ptr()), C.c_void_p(trunc.data_ptr()), self._stream())
+        self._closed_call(rc, what)
+        self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
+        return obs, rew, term.view(torch.bool), trunc.view(torch.bool), act
+
     def alloc_rollout_policy(self, K):
         """Output buffers of rollout_policy(K): alloc_rollout(K) and the actions, int32 [K, N]."""
-        return self.alloc_rollout(K) + (torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device),)
+        return self._alloc_rollout_closed(K)
 
     def rollout_policy(self, K, out=None):
         """K closed-loop steps in ONE kernel launch: at every step each env draws its action from the policy's row of the
         state it is in and takes it.  Returns (obs, reward, terminated, truncated, actions), each with a leading K axis;
         rollout(actions) on an identically built env returns the same first four, bit for bit."""
-        K = int(K)
         self._policy_check_config()
-        if out is None:
-            out = self.alloc_rollout_policy(K)
-        obs, rew, term, trunc, act = out
-        rc = self._lib.mdpp_step_n_policy(self._h, K, C.c_void_p(act.data_ptr()), C.c_void_p(obs.data_ptr()),
-                                          C.c_void_p(rew.data_ptr()), C.c_void_p(term.data_ptr()),
-                                          C.c_void_p(trunc.data_ptr()), self._stream())
-        if rc == capi.EUNSUPPORTED:
-            msg = self._lib.mdpp_last_error(self._h)
-            raise NotImplementedError(msg.decode() if msg else "mdpp_step_n_policy: unsupported")
-        capi.check(self._lib, self._h, rc, "mdpp_step_n_policy")
-        self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
-        return obs, rew, term.view(torch.bool), trunc.view(torch.bool), act
+        return self._rollout_closed(self._lib.mdpp_step_n_policy, "mdpp_step_n_policy", int(K), out)
 
     def policy_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_policy(K) launches (mdpp_policy_kernel_name; nothing is
@@ -715,12 +721,6 @@ class RLToyVectorEnv:
         return name.decode() if name else ""
 
     # ------------------------------------------------------------------ in-kernel tabular TD learners
-    def _learn_call(self, rc, what):
-        if rc == capi.EUNSUPPORTED:
-            msg = self._lib.mdpp_last_error(self._h)
-            raise NotImplementedError(msg.decode() if msg else what + ": unsupported")
-        capi.check(self._lib, self._h, rc, what)
-
     def _learn_check_kind(self):
         if self.kind != "discrete":
             raise NotImplementedError("learner rollouts serve discrete envs only (this env is %s)" % self.kind)
@@ -750,7 +750,7 @@ class RLToyVectorEnv:
         rc = self._lib.mdpp_set_learner(self._h, capi.LEARN_ALGOS[algo], float(alpha), float(gamma), float(epsilon),
                                         C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                         C.c_void_p(q.data_ptr()) if q is not None else None, self._stream())
-        self._learn_call(rc, "mdpp_set_learner")
+        self._closed_call(rc, "mdpp_set_learner")
         self._learn_q_init = q           # (kept until the copy queued on the stream has certainly been made)
         self._learn_rates = [float(alpha), float(epsilon)]
 
@@ -764,41 +764,32 @@ class RLToyVectorEnv:
             self._learn_rates[0] = float(alpha)
         if epsilon is not None:
             self._learn_rates[1] = float(epsilon)
-        self._learn_call(self._lib.mdpp_set_learner_rates(self._h, *self._learn_rates), "mdpp_set_learner_rates")
+        self._closed_call(self._lib.mdpp_set_learner_rates(self._h, *self._learn_rates), "mdpp_set_learner_rates")
 
     def alloc_rollout_learn(self, K):
         """Output buffers of rollout_learn(K): alloc_rollout(K) and the actions, int32 [K, N]."""
-        return self.alloc_rollout(K) + (torch.empty((K, self.num_envs), dtype=torch.int32, device=self.device),)
+        return self._alloc_rollout_closed(K)
 
     def rollout_learn(self, K, out=None):
         """K steps of "select epsilon-greedily from the env's own Q, step, update that Q" in ONE kernel launch.  Returns (obs,
         reward, terminated, truncated, actions), each with a leading K axis; rollout(actions) on an identically built env
         returns the same first four, bit for bit.  SARSA carries its next action from step to step inside a call only: the
         first step of every call selects afresh."""
-        K = int(K)
         self._learn_check_kind()
-        if out is None:
-            out = self.alloc_rollout_learn(K)
-        obs, rew, term, trunc, act = out
-        rc = self._lib.mdpp_step_n_learn(self._h, K, C.c_void_p(act.data_ptr()), C.c_void_p(obs.data_ptr()),
-                                         C.c_void_p(rew.data_ptr()), C.c_void_p(term.data_ptr()),
-                                         C.c_void_p(trunc.data_ptr()), self._stream())
-        self._learn_call(rc, "mdpp_step_n_learn")
-        self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
-        return obs, rew, term.view(torch.bool), trunc.view(torch.bool), act
+        return self._rollout_closed(self._lib.mdpp_step_n_learn, "mdpp_step_n_learn", int(K), out)
 
     def get_q(self):
         """The learner's tables, float32 [N, S, A] (a copy, made on the current stream)."""
         self._learn_check_kind()
         q = torch.empty((self.num_envs, self.mdps[0].S, self.mdps[0].A), dtype=torch.float32, device=self.device)
-        self._learn_call(self._lib.mdpp_get_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_get_q")
+        self._closed_call(self._lib.mdpp_get_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_get_q")
         return q
 
     def set_q(self, q):
         """Replace the learner's tables: float32 [N, S, A] on the device (copied on the current stream)."""
         self._learn_check_kind()
         q = self._learn_q_arg(q, "set_q")
-        self._learn_call(self._lib.mdpp_set_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_set_q")
+        self._closed_call(self._lib.mdpp_set_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_set_q")
         self._learn_q_init = q
 
     def learn_kernel_name(self, K):

@@ -31,6 +31,8 @@ CASES = {
     "cfg2_next_step": (CFG2, dict(autoreset="next_step")),
     "cfg2_disabled_max5": (CFG2, dict(autoreset="disabled", max_episode_steps=5)),
     "every3": (dict(CFG2, reward_every_n_steps=3), {}),
+    "s8_obs_int32": (dict(_D, state_space_size=8, action_space_size=8, delay=0, sequence_length=1, dtype_o=np.int32,
+                          seed=0), {}),                                     # 4-byte observations: OBS64=0
 }
 
 
@@ -111,6 +113,8 @@ def test_replay_by_an_open_loop_twin_and_the_action_law(case, rng):
         policies.append(np.random.default_rng(12).integers(0, A, S))
     assert a.policy_kernel_name(K).startswith("k_discrete_policy_rollout<PHILOX=%d," % (rng == "philox"))
     assert ("A8=%d" % (A <= 8)) in a.policy_kernel_name(K)
+    assert ("OBS64=%d" % ("dtype_o" not in cfg)) in a.policy_kernel_name(K)
+    assert a._obs.dtype == (torch.int32 if "dtype_o" in cfg else torch.int64)
     obs_before = _np(a._obs)
     assert np.array_equal(obs_before, _np(b._obs))
     set_for = None
@@ -192,6 +196,29 @@ def test_two_shards_equal_one_env(rng):
                 assert torch.equal(g, w[:, lo:lo + N // 2]), (rng, lo, launch)
         sh.close()
     whole.close()
+
+
+@pytest.mark.parametrize("rng", ["numpy", "philox"])
+def test_a_policy_call_sent_out_in_pieces_equals_one_launch(rng):
+    """LEARN_SHORT_PIECES: launches of at most 5 steps, as a call beyond the buffer descriptors' range is split.  Two calls of
+    K = 37 are 8 pieces each: pieces start mid Philox block and k0 steps into the delay line (cfg2: the shift register in
+    the record; rdist_delay3: the key ring in memory, read at rhead0 + k).  Outputs, actions and handles are those of the
+    single launch.  (An equality test: that the option does split a call is observed by the learner's twin of this test,
+    tests/test_gpu_learn_rollout.py, through SARSA's carried action -- both entry points go through one launcher.)"""
+    for case in ("cfg2", "rdist_delay3"):
+        cfg, kw = CASES[case]
+        one, many = _mk(cfg, rng, **kw), _mk(cfg, rng, **kw)
+        many.set_kernel_options("LEARN_SHORT_PIECES")
+        pol = _policy(41, one.mdps[0].S, one.mdps[0].A)
+        for e in (one, many):
+            e.set_policy(pol, seed=SEED)
+        for launch in range(2):
+            want, got = one.rollout_policy(K), many.rollout_policy(K)
+            _assert_same_outputs(got[:4], want[:4], (case, rng, launch))
+            assert torch.equal(got[4], want[4]), (case, rng, launch)
+            assert _np(want[2]).any()                # (episodes ended inside the launches: resets ran)
+        _assert_same_handles(one, many, rng)
+        one.close(); many.close()
 
 
 _CONT = dict(state_space_type="continuous", state_space_dim=4, target_point=[0, 0, 0, 0], target_radius=0.05,
