@@ -100,8 +100,8 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
        MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19 }; /* mdpp_step_n_policy and mdpp_step_n_learn go out in launches of at most 5 steps
                                               (the hand-over between the pieces of a very long call, at a size a test can run) */
 
-/* the tabular learner's algorithm (mdpp_set_learner); 2 is kept for double Q-learning */
-enum { MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1 };
+/* the tabular learner's algorithm (mdpp_set_learner); 2 is double Q-learning: two tables per env */
+enum { MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1, MDPP_LEARN_DOUBLE_Q = 2 };
 
 /* what a discrete env's reward table is keyed by */
 enum { MDPP_REWARD_SEQUENCES = 0,     /* the last L states (rewardable_sequences, rl_toy_env.py:1837-1841) */
@@ -351,6 +351,31 @@ int mdpp_step_n_learn(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_de
 int mdpp_get_q(mdpp_env *h, float *q_out_dev, void *stream);
 int mdpp_set_q(mdpp_env *h, const float *q_in_dev, void *stream);
 const char *mdpp_learn_kernel_name(mdpp_env *h, int K);
+
+/* Per-env learner hyper-parameters: alpha, gamma and epsilon are each either launch-uniform (mdpp_set_learner,
+ * mdpp_set_learner_rates) or one float32 per env.  mdpp_set_learner_params takes HOST pointers to float32 [N]; NULL leaves
+ * that parameter as it is (uniform or per-env).  Every element is range-checked like the scalar (alpha in (0, 1], gamma and
+ * epsilon in [0, 1], NaN refused: MDPP_EINVAL, nothing changed); E[i] = ceil((double)epsilon[i] 2^31) is formed on the host;
+ * the arrays are copied into buffers of the handle, ordered on `stream`.  Env i of the handle (its LOCAL index: only the
+ * Philox streams use the global id) then learns with alpha[i], gamma[i], E[i]; everything else above holds word for word.
+ * Without a learner: MDPP_ESTATE.  mdpp_set_learner makes all three uniform again, mdpp_set_learner_rates alpha and epsilon,
+ * mdpp_set_learner_gamma (a new uniform gamma in [0, 1]; no device work) gamma.
+ * While any parameter is per-env the launch is the kernel's PE form (the name gains ",PE=1"): the lane loads its three
+ * values once per launch; the uniform parameters travel as arrays of equal entries.
+ *
+ * Double Q-learning (algo = MDPP_LEARN_DOUBLE_Q): TWO tables per env, QA and QB, float32 [S][A] each.
+ *   sel(s, t): explore-or-not and the exploring action as above (stream ids 15, 16); greedy: the lowest j maximising
+ *     QA[s][j] + QB[s][j] (one float32 addition per j, scanned from j = 0 with a strict >);
+ *   wU = the tick's word of stream id 17 (same key and counter layout, the learner's seed): wU >> 31 == 0 updates A, else B.
+ *     With X the updated table and Y the other: terminated: y = r; otherwise a* = the lowest argmax_j X[s'][j],
+ *     y = r + gamma Y[s'][a*];  q = X[s][a], d = y - q, u = alpha d, X[s][a] = q + u (float32, one rounding per operation);
+ *   nothing is carried from step to step; on the reset call of a next-step-autoreset env an action is selected, written
+ *     and ignored, no update is made and that tick's wU is unused.
+ * q_init_dev, mdpp_get_q and mdpp_set_q are float32 [N][2][S][A] for this algorithm (A first); [N][S][A] for the other two.
+ * Served handles and refusals: as above.  The kernel's name gains ",DOUBLE=1"; QLDS=1 when a workgroup's 256 x 2 tables fit
+ * in LDS beside the MDP's. */
+int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream);
+int mdpp_set_learner_gamma(mdpp_env *h, float gamma);
 
 /* Per-env internal state <-> host (synchronous; checkpoint / set_augmented_state).
  * Discrete: hist int32[N][L+1] (-1 = NaN slot), steps int32[N], ring double[N][delay].

@@ -24,7 +24,8 @@ OPTIONS = {"NO_PIPE": 1 << 0, "NO_HELPER": 1 << 1, "NO_PARK": 1 << 2, "NO_CFAST"
            "NO_GFAST_NOISE": 1 << 9, "NO_IMGFAST": 1 << 10, "NO_IMG_OVERLAP": 1 << 11, "NO_PHILOX_FAST": 1 << 12, "NO_LEAN": 1 << 13,
            "NO_IMG_NEARTAB": 1 << 14, "NO_STEP1": 1 << 15, "NO_SIGMA0": 1 << 16, "NO_QUIET_SF": 1 << 17,
            "NO_LEARN_LDS": 1 << 18, "LEARN_SHORT_PIECES": 1 << 19}
-LEARN_ALGOS = {"q_learning": 0, "sarsa": 1}        # MDPP_LEARN_*
+LEARN_ALGOS = {"q_learning": 0, "sarsa": 1}        # MDPP_LEARN_*: the one-table algorithms
+MDPP_LEARN_DOUBLE_Q = 2                            # "double_q": two tables per env
 
 EXPORTS = [
     "mdpp_abi_version", "mdpp_create", "mdpp_destroy", "mdpp_last_error",
@@ -45,7 +46,7 @@ EXPORTS = [
     "mdpp_generate_discrete", "mdpp_get_discrete_tables", "mdpp_seed_streams_seedseq",
     "mdpp_set_policy", "mdpp_clear_policy", "mdpp_step_n_policy", "mdpp_policy_kernel_name",
     "mdpp_set_learner", "mdpp_clear_learner", "mdpp_set_learner_rates", "mdpp_step_n_learn", "mdpp_get_q", "mdpp_set_q",
-    "mdpp_learn_kernel_name",
+    "mdpp_learn_kernel_name", "mdpp_set_learner_params", "mdpp_set_learner_gamma",
 ]
 
 
@@ -161,6 +162,8 @@ def load():
     L.mdpp_set_learner.argtypes = [vp, i32, C.c_float, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.mdpp_clear_learner.argtypes = [vp]
     L.mdpp_set_learner_rates.argtypes = [vp, C.c_float, C.c_float]
+    L.mdpp_set_learner_params.argtypes = [vp, vp, vp, vp, vp]
+    L.mdpp_set_learner_gamma.argtypes = [vp, C.c_float]
     L.mdpp_step_n_learn.argtypes = [vp, i32] + [vp] * 6
     L.mdpp_get_q.argtypes = [vp, vp, vp]
     L.mdpp_set_q.argtypes = [vp, vp, vp]

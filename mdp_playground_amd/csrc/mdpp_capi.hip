@@ -56,7 +56,8 @@ static void free_all(mdpp_env *h) {
                     h->d_P1, h->d_init_cdf1, h->d_noise_cdf1, h->d_irr_state,
                     h->d_img_tpl, h->d_img_tplp, h->d_img_clsx, h->d_img_clsy, h->d_img_rot, h->d_img_state_out,
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
-                    h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry};
+                    h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
+                    h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -117,6 +118,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_policy_thr = nullptr; h->policy_seed = 0; h->policy_ready = false;
     h->d_learn_q = h->d_learn_carry = nullptr; h->learn_seed = 0; h->learn_E = 0; h->learn_alpha = h->learn_gamma = 0.0f;
     h->learn_algo = MDPP_LEARN_Q_LEARNING; h->learn_ready = false;
+    h->learn_q_tables = 0; h->d_learn_alpha = h->d_learn_gamma = h->d_learn_E = nullptr; h->learn_pe = h->learn_pe_stale = 0;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
     h->d_hist_hi = nullptr;
@@ -1395,22 +1397,33 @@ extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma,
     if (!h) return MDPP_EINVAL;
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_learner: " + why);
-    if (algo != MDPP_LEARN_Q_LEARNING && algo != MDPP_LEARN_SARSA) return fail(h, MDPP_EINVAL, "mdpp_set_learner: unknown algo");
+    if (algo != MDPP_LEARN_Q_LEARNING && algo != MDPP_LEARN_SARSA && algo != MDPP_LEARN_DOUBLE_Q)
+        return fail(h, MDPP_EINVAL, "mdpp_set_learner: unknown algo");
     if (!learner_rates_ok(alpha, epsilon) || !(gamma >= 0.0f && gamma <= 1.0f))
         return fail(h, MDPP_EINVAL, "mdpp_set_learner: need alpha in (0, 1], gamma and epsilon in [0, 1]");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t N = (size_t)h->cfg.num_envs, bytes = N * (size_t)h->cfg.S * (size_t)h->cfg.A * sizeof(float);
-    if (!h->d_learn_q) HIPCHK(h, hipMalloc(&h->d_learn_q, bytes));
+    const int tables = algo == MDPP_LEARN_DOUBLE_Q ? 2 : 1;      // (double Q-learning: A then B)
+    const size_t N = (size_t)h->cfg.num_envs, bytes = N * (size_t)h->cfg.S * (size_t)h->cfg.A * sizeof(float) * (size_t)tables;
+    if (h->d_learn_q && h->learn_q_tables < tables) {            // (hipFree waits for the launches that still use it)
+        HIPCHK(h, hipFree(h->d_learn_q));
+        h->d_learn_q = nullptr;
+    }
+    if (!h->d_learn_q) {
+        HIPCHK(h, hipMalloc(&h->d_learn_q, bytes));
+        h->learn_q_tables = tables;
+    }
     if (!h->d_learn_carry) HIPCHK(h, hipMalloc(&h->d_learn_carry, N * sizeof(int32_t)));
     // (on the caller's stream: behind the rollouts already queued there, ahead of the next one)
+    h->learn_algo = algo;        // (the copy below goes by the algorithm's number of tables)
     if (q_init_dev) {
         int rc = launch_learn_q_copy(h, const_cast<float *>(q_init_dev), true, (hipStream_t)stream);
-        if (rc) return rc;
+        if (rc) { h->learn_ready = false; return rc; }
     } else {
         HIPCHK(h, hipMemsetAsync(h->d_learn_q, 0, bytes, (hipStream_t)stream));
     }
-    h->learn_algo = algo; h->learn_alpha = alpha; h->learn_gamma = gamma; h->learn_seed = seed;
+    h->learn_alpha = alpha; h->learn_gamma = gamma; h->learn_seed = seed;
     h->learn_E = (uint32_t)ceil((double)epsilon * 2147483648.0);
+    h->learn_pe = h->learn_pe_stale = 0;                         // all three uniform
     h->learn_ready = true;
     return MDPP_OK;
 }
@@ -1427,6 +1440,49 @@ extern "C" int mdpp_set_learner_rates(mdpp_env *h, float alpha, float epsilon) {
     if (!learner_rates_ok(alpha, epsilon)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_rates: need alpha in (0, 1] and epsilon in [0, 1]");
     h->learn_alpha = alpha;
     h->learn_E = (uint32_t)ceil((double)epsilon * 2147483648.0);
+    // alpha and epsilon are uniform again; while gamma stays per-env the next launch fills their arrays with these values
+    h->learn_pe &= ~5u;
+    h->learn_pe_stale = h->learn_pe ? (h->learn_pe_stale | 5u) : 0u;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_learner_gamma(mdpp_env *h, float gamma) {
+    if (!h) return MDPP_EINVAL;
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_set_learner_gamma: no learner set (mdpp_set_learner)");
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_gamma: need gamma in [0, 1]");
+    h->learn_gamma = gamma;
+    h->learn_pe &= ~2u;
+    h->learn_pe_stale = h->learn_pe ? (h->learn_pe_stale | 2u) : 0u;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_set_learner_params: no learner set (mdpp_set_learner)");
+    const size_t N = (size_t)h->cfg.num_envs;
+    for (size_t i = 0; i < N; i++) {                             // (NaN fails every comparison)
+        if (alpha && !(alpha[i] > 0.0f && alpha[i] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_params: need every alpha in (0, 1]");
+        if (gamma && !(gamma[i] >= 0.0f && gamma[i] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_params: need every gamma in [0, 1]");
+        if (epsilon && !(epsilon[i] >= 0.0f && epsilon[i] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_params: need every epsilon in [0, 1]");
+    }
+    if (!alpha && !gamma && !epsilon) return MDPP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
+    const uint32_t was = h->learn_pe;
+    // (host to device from the caller's pageable memory: the runtime has read the source when the call returns)
+    if (alpha) HIPCHK(h, hipMemcpyAsync(h->d_learn_alpha, alpha, N * 4u, hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (gamma) HIPCHK(h, hipMemcpyAsync(h->d_learn_gamma, gamma, N * 4u, hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (epsilon) {
+        std::vector<uint32_t> E(N);
+        for (size_t i = 0; i < N; i++) E[i] = (uint32_t)ceil((double)epsilon[i] * 2147483648.0);
+        HIPCHK(h, hipMemcpyAsync(h->d_learn_E, E.data(), N * 4u, hipMemcpyHostToDevice, (hipStream_t)stream));
+        HIPCHK(h, hipStreamSynchronize((hipStream_t)stream));    // (E is this call's own: gone at return)
+    }
+    const uint32_t now = (alpha ? 1u : 0u) | (gamma ? 2u : 0u) | (epsilon ? 4u : 0u);
+    h->learn_pe = was | now;
+    // the parameters that stay uniform travel as arrays too: filled on the stream of the next launch
+    h->learn_pe_stale = ((was ? h->learn_pe_stale : 7u) & ~now) & ~h->learn_pe;
     return MDPP_OK;
 }
 

@@ -1,0 +1,4 @@
+// The double Q-learning (DOUBLE = 1) instantiations of k_discrete_learn_rollout (see mdpp_discrete_learn.hip), in
+// their own translation unit so that the learner's forms compile in parallel.
+#define MDPP_LEARN_TU_DOUBLE 1
+#include "mdpp_discrete_learn.hip"

@@ -35,6 +35,7 @@ constexpr uint32_t kPhiloxRNoiseStream = 13;  // discrete: reward noise, one flo
 constexpr uint32_t kPhiloxPolicyStream = 14;  // discrete: the tabular policy's action, one word per tick, keyed by the POLICY's seed (mdpp_discrete_policy.hip)
 constexpr uint32_t kPhiloxLearnExploreStream = 15; // discrete: the tabular learner's explore-or-not word, one per tick, keyed by the LEARNER's seed (mdpp_discrete_learn.hip)
 constexpr uint32_t kPhiloxLearnActionStream = 16;  // ... and the word of its exploring action
+constexpr uint32_t kPhiloxLearnUpdateStream = 17;  // ... double Q-learning: the word whose top bit says which table learns (0: A, 1: B)
 
 // ---- per-episode noise statistics (cfg.episode_stats; general kernels only) ------------------------------------
 // What the reference accumulates per env object and logs at every reset() (rl_toy_env.py:2231-2247; cleared
@@ -328,6 +329,14 @@ struct mdpp_env {
     float learn_alpha, learn_gamma;
     int32_t learn_algo;
     bool learn_ready;
+    // double Q-learning keeps two tables, A then B: [2 S A][N] (learn_q_tables: how many the buffer was allocated for).
+    // Per-env alpha / gamma / E (mdpp_set_learner_params): float32 / float32 / uint32 [N] on the device; learn_pe: which
+    // parameters are per-env (bit 0 alpha, 1 gamma, 2 epsilon) -- any bit set: the launch takes the PE form and reads all
+    // three arrays; learn_pe_stale: the arrays of these parameters do not hold the uniform value yet (filled on the stream
+    // of the next launch)
+    int32_t learn_q_tables;
+    void *d_learn_alpha, *d_learn_gamma, *d_learn_E;
+    uint32_t learn_pe, learn_pe_stale;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -524,6 +533,11 @@ int launch_discrete_policy(mdpp_env *h, const DiscreteIO &io);
 std::string discrete_learn_refusal(const mdpp_env *h);
 int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io);
 int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t s);
+// the PE and DOUBLE forms of the learner kernel (mdpp_discrete_learn_pe.hip, mdpp_discrete_learn_double.hip,
+// mdpp_discrete_learn_double_pe.hip: one translation unit each); launch_discrete_learn hands over to them
+int launch_discrete_learn_pe(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_double(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_double_pe(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // phase bits: 1 = draw + records, 2 = render (phase == 2 exactly: pipelined, the persistent grid leaves slots

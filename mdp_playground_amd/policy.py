@@ -13,13 +13,15 @@ T[j] == T[j-1] and is never drawn.
 
 Host helpers of the in-kernel tabular learners (set_learner / rollout_learn) live here too: epsilon_threshold makes the
 integer the kernel compares the explore word with, explore_action is its rule for the exploring action, and
-check_learner_params is the validation set_learner applies.
+check_learner_params is the validation set_learner applies.  alpha, gamma and epsilon are each a Python scalar (uniform over
+the handle) or a 1-D array with one float32 per env (numpy, or a torch tensor on any device): learner_param_array tells the
+two apart and validates the array.
 """
 import numpy as np
 
-__all__ = ["policy_thresholds", "epsilon_threshold", "explore_action", "check_learner_params", "LEARN_ALGOS"]
+__all__ = ["policy_thresholds", "epsilon_threshold", "explore_action", "check_learner_params", "learner_param_array", "LEARN_ALGOS"]
 
-LEARN_ALGOS = ("q_learning", "sarsa")
+LEARN_ALGOS = ("q_learning", "sarsa", "double_q")
 
 
 def _to_numpy(policy):
@@ -62,7 +64,12 @@ def policy_thresholds(policy, S, A):
 
 def epsilon_threshold(eps):
     """E = ceil(epsilon * 2^31) in float64, epsilon rounded to float32 first (the C ABI takes a float): a step explores iff
-    (wE >> 1) < E, so epsilon = 0 never explores and epsilon = 1 always does."""
+    (wE >> 1) < E, so epsilon = 0 never explores and epsilon = 1 always does.  An array gives np.uint32 thresholds, element-wise."""
+    if _is_array(eps):
+        e = _to_numpy(eps).astype(np.float32)
+        if not np.all((e >= 0.0) & (e <= 1.0)):
+            raise ValueError("every epsilon must lie in [0, 1]")
+        return np.ceil(e.astype(np.float64) * 2147483648.0).astype(np.uint32)
     e = float(np.float32(eps))
     if not 0.0 <= e <= 1.0:
         raise ValueError(f"epsilon must lie in [0, 1], got {eps!r}")
@@ -74,10 +81,42 @@ def explore_action(word, A):
     return (np.asarray(word, dtype=np.uint64) * np.uint64(A)) >> np.uint64(32)
 
 
-def check_learner_params(algo, alpha, gamma, epsilon):
-    """ValueError unless algo is known, alpha in (0, 1], gamma and epsilon in [0, 1] (None: not checked)."""
+def _is_array(v):
+    return isinstance(v, (np.ndarray, list, tuple)) or (hasattr(v, "detach") and hasattr(v, "cpu"))
+
+
+def learner_param_array(name, v, num_envs=None):
+    """None for a scalar (or None); for an array its float32 numpy copy, after the checks: 1-D, num_envs entries (when given),
+    every element in range -- alpha in (0, 1], gamma and epsilon in [0, 1]; NaN fails.  ValueError otherwise."""
+    if v is None or not _is_array(v):
+        return None
+    a = _to_numpy(v)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"{name} must be a number or a 1-D array of numbers, got dtype {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"a per-env {name} must be 1-D, got shape {a.shape}")
+    if num_envs is not None and a.shape[0] != int(num_envs):
+        raise ValueError(f"a per-env {name} must have num_envs = {int(num_envs)} entries, got {a.shape[0]}")
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    ok = (a > 0.0) & (a <= 1.0) if name == "alpha" else (a >= 0.0) & (a <= 1.0)       # (NaN fails both)
+    if not np.all(ok):
+        bad = int(np.argmin(ok))
+        raise ValueError(f"{name} must lie in {'(0, 1]' if name == 'alpha' else '[0, 1]'}, got {a[bad]!r} at env {bad}")
+    return a
+
+
+def check_learner_params(algo, alpha, gamma, epsilon, num_envs=None):
+    """ValueError unless algo is known, alpha in (0, 1], gamma and epsilon in [0, 1] (None: not checked).  Each of the three
+    is a scalar or a per-env array (learner_param_array: 1-D, num_envs entries when num_envs is given, every element in range)."""
     if algo is not None and algo not in LEARN_ALGOS:
         raise ValueError(f"algo must be one of {LEARN_ALGOS}, got {algo!r}")
+    arrays = [n for n, v in (("alpha", alpha), ("gamma", gamma), ("epsilon", epsilon)) if _is_array(v)]
+    for n, v in (("alpha", alpha), ("gamma", gamma), ("epsilon", epsilon)):
+        if n in arrays:
+            learner_param_array(n, v, num_envs)
+    alpha = None if "alpha" in arrays else alpha
+    gamma = None if "gamma" in arrays else gamma
+    epsilon = None if "epsilon" in arrays else epsilon
     if alpha is not None and not 0.0 < float(np.float32(alpha)) <= 1.0:
         raise ValueError(f"alpha must lie in (0, 1], got {alpha!r}")
     for name, v in (("gamma", gamma), ("epsilon", epsilon)):

@@ -89,6 +89,8 @@ class RLToyVectorEnv:
         self._gen = None                      # mdp.device_gen_params when the per-env tables are generated on the device
         self._learn_rates = None              # [alpha, epsilon] of the learner (set_learner); None: no learner
         self._learn_q_init = None             # the tensor last handed to set_learner / set_q, kept until its copy has been made
+        self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
+        self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
                 raise ValueError("num_envs != len(seeds)")
@@ -725,46 +727,77 @@ class RLToyVectorEnv:
         if self.kind != "discrete":
             raise NotImplementedError("learner rollouts serve discrete envs only (this env is %s)" % self.kind)
 
-    def _learn_q_arg(self, q, what):
+    def _learn_q_shape(self, algo=None):
         S, A = self.mdps[0].S, self.mdps[0].A
-        if not (torch.is_tensor(q) and q.dtype == torch.float32 and q.device == self.device
-                and tuple(q.shape) == (self.num_envs, S, A)):
-            raise ValueError(f"{what}: q must be a float32 tensor of shape ({self.num_envs}, {S}, {A}) on {self.device}")
+        return (self.num_envs, 2, S, A) if (algo or self._learn_algo) == "double_q" else (self.num_envs, S, A)
+
+    def _learn_q_arg(self, q, what, algo=None):
+        shape = self._learn_q_shape(algo)
+        if not (torch.is_tensor(q) and q.dtype == torch.float32 and q.device == self.device and tuple(q.shape) == shape):
+            raise ValueError(f"{what}: q must be a float32 tensor of shape {shape} on {self.device}")
         return q.contiguous()
 
+    def _learn_send_arrays(self, alpha, gamma, epsilon):
+        """per-env parameters (validated float32 arrays, or None) -> mdpp_set_learner_params"""
+        if alpha is None and gamma is None and epsilon is None:
+            return
+        rc = self._lib.mdpp_set_learner_params(self._h, capi.nptr(alpha), capi.nptr(gamma), capi.nptr(epsilon), self._stream())
+        self._closed_call(rc, "mdpp_set_learner_params")
+
     def set_learner(self, algo="q_learning", *, alpha=None, gamma=None, epsilon=None, seed=0, q=None):
-        """The handle's tabular TD learner for rollout_learn(): one independent agent PER ENV, ``algo`` "q_learning" or "sarsa",
-        float32 ``alpha`` in (0, 1], ``gamma`` and ``epsilon`` in [0, 1], ``seed`` the 64-bit key of the learner's own Philox
-        streams, ``q`` the initial tables (float32 [N, S, A] on the device; zeros when None).  ``set_learner(None)`` clears the
-        learner.  Handles the kernel does not serve raise NotImplementedError with the reason (include/mdpp.h: the rule)."""
+        """The handle's tabular TD learner for rollout_learn(): one independent agent PER ENV, ``algo`` "q_learning", "sarsa" or
+        "double_q", float32 ``alpha`` in (0, 1], ``gamma`` and ``epsilon`` in [0, 1] -- each a scalar (uniform) or a 1-D array of
+        num_envs entries (numpy, or a torch tensor on any device; env i of THIS handle learns with entry i), ``seed`` the 64-bit
+        key of the learner's own Philox streams, ``q`` the initial tables (float32 [N, S, A] on the device, [N, 2, S, A] -- A
+        then B -- for "double_q"; zeros when None).  ``set_learner(None)`` clears the learner.  Handles the kernel does not
+        serve raise NotImplementedError with the reason (include/mdpp.h: the rule)."""
         if algo is None:
             capi.check(self._lib, self._h, self._lib.mdpp_clear_learner(self._h), "mdpp_clear_learner")
             self._learn_rates = None
             return
         if alpha is None or gamma is None or epsilon is None:
             raise ValueError("set_learner: alpha, gamma and epsilon are required")
-        policy_mod.check_learner_params(algo, alpha, gamma, epsilon)
+        policy_mod.check_learner_params(algo, alpha, gamma, epsilon, self.num_envs)
+        arrays = [policy_mod.learner_param_array(n, v, self.num_envs) for n, v in (("alpha", alpha), ("gamma", gamma), ("epsilon", epsilon))]
         self._learn_check_kind()
         if q is not None:
-            q = self._learn_q_arg(q, "set_learner")
-        rc = self._lib.mdpp_set_learner(self._h, capi.LEARN_ALGOS[algo], float(alpha), float(gamma), float(epsilon),
-                                        C.c_uint64(int(seed) & (2 ** 64 - 1)),
+            q = self._learn_q_arg(q, "set_learner", algo)
+        # (a per-env parameter's scalar slot: any valid value -- the kernel's PE form does not read it)
+        scalars = [float(v) if a is None else float(a[0]) for v, a in zip((alpha, gamma, epsilon), arrays)]
+        code = dict(capi.LEARN_ALGOS, double_q=capi.MDPP_LEARN_DOUBLE_Q)[algo]
+        rc = self._lib.mdpp_set_learner(self._h, code, *scalars, C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                         C.c_void_p(q.data_ptr()) if q is not None else None, self._stream())
         self._closed_call(rc, "mdpp_set_learner")
         self._learn_q_init = q           # (kept until the copy queued on the stream has certainly been made)
-        self._learn_rates = [float(alpha), float(epsilon)]
+        self._learn_rates = [scalars[0], scalars[2]]
+        self._learn_algo = algo
+        self._learn_pe = dict(zip(("alpha", "gamma", "epsilon"), arrays))     # the per-env arrays in force (None: uniform)
+        self._learn_send_arrays(*arrays)
 
-    def set_learner_rates(self, alpha=None, epsilon=None):
-        """New alpha and / or epsilon for the learner (parameters only, no device work: a decay schedule on the host costs
-        nothing between launches)."""
-        policy_mod.check_learner_params(None, alpha, None, epsilon)
+    def set_learner_rates(self, alpha=None, epsilon=None, *, gamma=None):
+        """New alpha, epsilon and / or gamma for the learner, each a scalar (uniform from now on) or a per-env array as in
+        set_learner (scalars: parameters only, no device work -- a decay schedule on the host costs nothing between launches;
+        arrays: one small copy on the current stream)."""
+        policy_mod.check_learner_params(None, alpha, gamma, epsilon, self.num_envs)
         if self._learn_rates is None:
             raise capi.MdppError("set_learner_rates: no learner set (set_learner)")
-        if alpha is not None:
+        given = {"alpha": alpha, "gamma": gamma, "epsilon": epsilon}
+        arrays = {n: policy_mod.learner_param_array(n, v, self.num_envs) for n, v in given.items()}
+        scalar = {n: v is not None and arrays[n] is None for n, v in given.items()}
+        for n, v in given.items():
+            if v is not None:
+                self._learn_pe[n] = arrays[n]
+        if scalar["alpha"]:
             self._learn_rates[0] = float(alpha)
-        if epsilon is not None:
+        if scalar["epsilon"]:
             self._learn_rates[1] = float(epsilon)
-        self._closed_call(self._lib.mdpp_set_learner_rates(self._h, *self._learn_rates), "mdpp_set_learner_rates")
+        if scalar["alpha"] or scalar["epsilon"]:
+            # (mdpp_set_learner_rates makes BOTH uniform: the one of the two that stays per-env goes out again below)
+            self._closed_call(self._lib.mdpp_set_learner_rates(self._h, *self._learn_rates), "mdpp_set_learner_rates")
+            arrays["alpha"], arrays["epsilon"] = self._learn_pe["alpha"], self._learn_pe["epsilon"]
+        if scalar["gamma"]:
+            self._closed_call(self._lib.mdpp_set_learner_gamma(self._h, float(gamma)), "mdpp_set_learner_gamma")
+        self._learn_send_arrays(arrays["alpha"], arrays["gamma"], arrays["epsilon"])
 
     def alloc_rollout_learn(self, K):
         """Output buffers of rollout_learn(K): alloc_rollout(K) and the actions, int32 [K, N]."""
@@ -779,14 +812,15 @@ class RLToyVectorEnv:
         return self._rollout_closed(self._lib.mdpp_step_n_learn, "mdpp_step_n_learn", int(K), out)
 
     def get_q(self):
-        """The learner's tables, float32 [N, S, A] (a copy, made on the current stream)."""
+        """The learner's tables, float32 [N, S, A] ([N, 2, S, A], A then B, for "double_q"); a copy, made on the current stream."""
         self._learn_check_kind()
-        q = torch.empty((self.num_envs, self.mdps[0].S, self.mdps[0].A), dtype=torch.float32, device=self.device)
+        q = torch.empty(self._learn_q_shape(), dtype=torch.float32, device=self.device)
         self._closed_call(self._lib.mdpp_get_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_get_q")
         return q
 
     def set_q(self, q):
-        """Replace the learner's tables: float32 [N, S, A] on the device (copied on the current stream)."""
+        """Replace the learner's tables: float32 [N, S, A] ([N, 2, S, A] for "double_q") on the device (copied on the current
+        stream)."""
         self._learn_check_kind()
         q = self._learn_q_arg(q, "set_q")
         self._closed_call(self._lib.mdpp_set_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_set_q")
@@ -794,7 +828,8 @@ class RLToyVectorEnv:
 
     def learn_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
-        launched; QLDS=1: the Q-tables are staged in LDS); empty for a handle it does not serve."""
+        launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning); empty for a
+        handle it does not serve."""
         if self.kind != "discrete":
             return ""
         name = self._lib.mdpp_learn_kernel_name(self._h, int(K))

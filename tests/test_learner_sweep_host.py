@@ -1,0 +1,270 @@
+"""Double Q-learning and per-env learner hyper-parameters on the host (no GPU): the restatement tests/learner_sweep_ref.py against
+tests/learner_ref.py on arbitrary launch arrays and against double-Q updates worked out by hand on the 3-state chain of
+test_learner_host.py (alpha = gamma = 0.5: every figure is exact in float32), array validation, the names of the C ABI, and
+a CPU closed loop (the oracle env driven by the restatement, 32 envs) showing that what tests/test_gpu_learn_sweep.py asserts
+about its own coverage can be met by every handle it uses."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import learner_ref as old
+import learner_sweep_cases as cases
+import learner_sweep_ref as ref
+from mdp_playground_amd import _capi
+from mdp_playground_amd import policy
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GREEDY, EXPLORE = 0xFFFFFFFF, 0          # explore words: never below E <= 2^31 - 1 / below every E >= 1
+UPD_A, UPD_B = 0x7FFFFFFF, 0x80000000    # update words: top bit 0 -> A learns, 1 -> B
+P3 = np.array([[1, 0], [2, 0], [2, 2]])  # 0 -a0-> 1 -a0-> 2 (terminal); action 1 leads back to 0
+
+
+def _words(*rows):
+    return np.array(rows, np.uint32).reshape(len(rows), 1)
+
+
+# ---- (a) the restatement equals learner_ref.run for the one-table algorithms with uniform parameters
+@pytest.mark.parametrize("autoreset", [old.DISABLED, old.SAME_STEP, old.NEXT_STEP])
+@pytest.mark.parametrize("algo", ["q_learning", "sarsa"])
+def test_restatement_equals_learner_ref_on_synthetic_launches(algo, autoreset):
+    rs = np.random.default_rng(11)
+    n, K, S, A = 24, 23, 5, 3
+    P = rs.integers(0, S, (S, A))
+    Q = rs.normal(size=(n, S, A)).astype(np.float32)
+    Q[rs.random((n, S, A)) < 0.3] = 0.0                      # (ties)
+    pending = rs.random(n) < 0.2 if autoreset == old.NEXT_STEP else None
+    before = rs.integers(0, S, n)
+    for launch in range(2):
+        obs = rs.integers(0, S, (K, n))
+        rew = rs.normal(size=(K, n)).astype(np.float32)
+        term, trunc = rs.random((K, n)) < 0.15, rs.random((K, n)) < 0.1
+        w_e = rs.integers(0, 2 ** 32, (K + 1, n), dtype=np.uint64).astype(np.uint32)
+        w_a = rs.integers(0, 2 ** 32, (K + 1, n), dtype=np.uint64).astype(np.uint32)
+        want = old.run(algo, 0.3, 0.9, 0.25, Q, before, obs, rew, term, trunc, P, autoreset, w_e, w_a, pending)
+        got = ref.run(algo, 0.3, 0.9, 0.25, Q, before, obs, rew, term, trunc, P, autoreset, w_e, w_a, None, pending)
+        assert np.array_equal(got[0], want[0])
+        assert np.array_equal(got[1].view(np.int32), want[1].view(np.int32))
+        assert np.array_equal(got[2], want[2])
+        for key in ("greedy_ties", "greedy_strict", "carried", "carried_differs", "updates"):
+            assert got[3][key] == want[3][key], key
+        # arrays of equal entries are the uniform parameters
+        al, ga, ep = np.full(n, 0.3), np.full(n, 0.9, np.float32), np.full(n, 0.25)
+        arr = ref.run(algo, al, ga, ep, Q, before, obs, rew, term, trunc, P, autoreset, w_e, w_a, None, pending)
+        assert np.array_equal(arr[0], want[0]) and np.array_equal(arr[1].view(np.int32), want[1].view(np.int32))
+        Q, pending, before = want[1], want[2], obs[-1]
+
+
+def test_restatement_per_env_parameters_are_indexed_by_env():
+    """two envs fed the same arrays differ only through their own alpha / gamma / epsilon"""
+    Q0 = np.zeros((2, 3, 2), np.float32)
+    obs = np.array([[1, 1]])
+    rew = np.array([[1.0, 1.0]], np.float32)
+    flags = np.zeros((1, 2), bool)
+    w_e = np.array([[0x40000000] * 2] * 2, np.uint32)        # (w >> 1) = 2^29: explores iff E > 2^29 iff epsilon > 0.25
+    w_a = np.array([[0x80000000] * 2] * 2, np.uint32)        # the exploring action: 1
+    act, Q, _, info = ref.run("q_learning", np.array([0.5, 0.25]), np.array([0.5, 0.5]), np.array([0.25, 0.5]), Q0, np.array([0, 0]),
+                              obs, rew, flags, flags, P3, ref.DISABLED, w_e, w_a)
+    assert act.tolist() == [[0, 1]]
+    assert Q[0, 0].tolist() == [0.5, 0.0] and Q[1, 0].tolist() == [0.0, 0.25]
+    assert info["explored_env"].tolist() == [0, 1] and info["selections_env"].tolist() == [1, 1]
+    assert ref.epsilon_threshold([0.0, 0.25, 1.0, 0.1]).tolist() == [0, 2 ** 29, 2 ** 31, 13421773 * 16]
+
+
+# ---- (b) double Q-learning by hand
+def test_double_q_by_hand_both_coin_sides_the_cross_table_target_and_the_terminated_target():
+    Q0 = np.zeros((1, 2, 3, 2), np.float32)
+    Q0[0, 0, 1] = [1.0, 0.0]            # QA[1]
+    Q0[0, 1, 1] = [0.0, 2.0]            # QB[1]
+    w_e = _words(GREEDY, GREEDY, GREEDY, EXPLORE, GREEDY)
+    w_a = _words(0, 0, 0, 0x7FFFFFFF, 0)
+    w_u = _words(UPD_A, UPD_B, UPD_B, 0)
+    obs = np.array([[1], [0], [1], [2]])
+    rew = np.array([[1.0], [0.0], [1.0], [2.0]], np.float32)
+    term = np.array([[0], [0], [0], [1]], bool)
+    act, Q, pend, info = ref.run("double_q", 0.5, 0.5, 0.25, Q0, np.array([0]), obs, rew, term, np.zeros_like(term), P3, ref.DISABLED,
+                                 w_e, w_a, w_u)
+    # step 0: s = 0, QA + QB = [0, 0]: tie -> 0; s' = 1; coin A: a* = argmax QA[1] = 0, target from the OTHER table QB[1][0] = 0
+    #         (not max QB[1] = 2);  y = 1 + .5 * 0;  QA[0][0] = 0 + .5 * 1 = .5
+    # step 1: s = 1, QA + QB = [1, 2] -> 1 (argmax QA[1] alone is 0); s' = 0; coin B: a* = argmax QB[0] = 0 (tie), QA[0][0] = .5;
+    #         y = 0 + .5 * .5 = .25;  QB[1][1] = 2 + .5 * (.25 - 2) = 1.125
+    # step 2: s = 0, QA + QB = [.5, 0] -> 0; s' = 1; coin B: a* = argmax QB[1] = [0, 1.125] = 1, QA[1][1] = 0 (max QA[1] = 1);
+    #         y = 1;  QB[0][0] = 0 + .5 * 1 = .5
+    # step 3: explores -> (0x7FFFFFFF * 2) >> 32 = 0; s' = 2 terminated: y = 2; coin A (word 0): QA[1][0] = 1 + .5 * (2 - 1) = 1.5
+    assert act[:, 0].tolist() == [0, 1, 0, 0]
+    assert Q.dtype == np.float32
+    assert Q[0, 0].tolist() == [[0.5, 0.0], [1.5, 0.0], [0.0, 0.0]]
+    assert Q[0, 1].tolist() == [[0.5, 0.0], [0.0, 1.125], [0.0, 0.0]]
+    assert not pend.any()
+    assert info["updates_a"] == 2 and info["updates_b"] == 2 and info["updates"] == 4
+    assert info["cross_differs"] == 2 and info["sum_differs"] == 1 and info["explored"] == 1
+    assert info["carried"] == 0
+
+
+def test_double_q_greedy_takes_the_lowest_index_among_ties_of_the_summed_tables():
+    Q = np.zeros((3, 2, 3, 2), np.float32)
+    Q[0, 0, 0], Q[0, 1, 0] = [1.0, 0.0], [0.0, 1.0]          # sums [1, 1]: tie -> 0 although QB alone says 1
+    Q[1, 0, 0], Q[1, 1, 0] = [0.0, 1.0], [1.0, 0.0]          # sums [1, 1]: tie -> 0 although QA alone says 1
+    Q[2, 0, 0], Q[2, 1, 0] = [0.25, 0.5], [0.5, 0.5]         # sums [.75, 1] -> 1
+    info = ref.new_info(3)
+    a, x = ref.select("double_q", Q, np.zeros(3, np.int64), np.full(3, GREEDY, np.uint32), np.zeros(3, np.uint32), np.full(3, 2 ** 29), info)
+    assert a.tolist() == [0, 0, 1] and not x.any()
+    assert info["greedy_ties"] == 2 and info["greedy_strict"] == 1 and info["sum_differs"] == 1
+    # one float32 addition per entry: 2^24 + 1 is not a float32, so [2^24, 2^24] + [1, 0] ties and the lowest index wins
+    Q[2, 0, 0], Q[2, 1, 0] = [2.0 ** 24, 2.0 ** 24], [0.0, 1.0]
+    assert ref.select("double_q", Q, np.zeros(3, np.int64), np.full(3, GREEDY, np.uint32), np.zeros(3, np.uint32), np.full(3, 0))[0][2] == 0
+
+
+def test_double_q_reset_call_selects_an_action_and_learns_nothing():
+    Q0 = np.zeros((2, 2, 3, 2), np.float32)
+    Q0[0, 0, 1], Q0[0, 1, 1] = [0.0, 0.5], [0.0, 0.5]        # env 0: QA[1] + QB[1] = [0, 1]
+    Q0[1, 0, 1] = [1.0, 0.0]                                 # env 1: QA[1] = [1, 0]
+    w_e = np.full((3, 2), GREEDY, np.uint32)
+    w_a = np.zeros((3, 2), np.uint32)
+    w_u = np.array([[UPD_B, 0], [UPD_B, UPD_B]], np.uint32)  # (env 0's word of its reset call and env 1's of its own are unused)
+    obs = np.array([[0, 2], [1, 0]])                         # env 0: its reset call, then a step; env 1: a terminating step, then its reset call
+    rew = np.array([[0.0, 2.0], [1.0, 0.0]], np.float32)
+    term = np.array([[0, 1], [0, 0]], bool)
+    act, Q, pend, info = ref.run("double_q", 0.5, 0.5, 0.25, Q0, np.array([1, 1]), obs, rew, term, np.zeros_like(term), P3, ref.NEXT_STEP,
+                                 w_e, w_a, w_u, pending=np.array([True, False]))
+    assert act.tolist() == [[1, 0], [0, 0]]                  # (selected from the recorded state on the reset call too)
+    assert info["updates"] == 2 and info["updates_a"] == 1 and info["updates_b"] == 1
+    # env 0, step 1: s = 0 -a0-> 1, coin B: a* = argmax QB[1] = 1, QA[1][1] = .5; y = 1 + .25; QB[0][0] = .625; nothing else moved
+    assert Q[0, 1, 0].tolist() == [0.625, 0.0] and np.array_equal(Q[0, 0], Q0[0, 0]) and np.array_equal(Q[0, 1, 1:], Q0[0, 1, 1:])
+    # env 1, step 0: terminated, coin A: QA[1][0] = 1 + .5 * (2 - 1) = 1.5; its reset call changed nothing
+    assert Q[1, 0, 1].tolist() == [1.5, 0.0] and not Q[1, 1].any()
+    assert pend.tolist() == [False, False]
+
+
+# ---- (c) validation
+def test_check_learner_params_accepts_arrays_under_the_scalar_rules():
+    ok = dict(algo="double_q", alpha=np.array([0.1, 1.0, 0.5]), gamma=[0.0, 1.0, 0.9], epsilon=np.array([0.0, 1.0, 1e-3], np.float64))
+    policy.check_learner_params(**ok)
+    policy.check_learner_params(num_envs=3, **ok)
+    policy.check_learner_params("sarsa", 0.3, np.array([0.5, 0.5]), 0.1, num_envs=2)          # scalars and arrays mix
+    import torch
+    policy.check_learner_params("q_learning", torch.tensor([0.1, 0.2]), 0.9, torch.tensor([0.0, 1.0], dtype=torch.float64), num_envs=2)
+    a = policy.learner_param_array("alpha", torch.tensor([0.1, 0.2], dtype=torch.float64), 2)
+    assert a.dtype == np.float32 and a.tolist() == [float(np.float32(0.1)), float(np.float32(0.2))]
+    assert policy.learner_param_array("alpha", 0.3) is None and policy.learner_param_array("alpha", None) is None
+    for bad in (dict(alpha=np.array([0.1, 0.0, 0.5])), dict(alpha=np.array([0.1, 1.5, 0.5])), dict(alpha=np.array([0.1, np.nan, 0.5])),
+                dict(gamma=np.array([0.1, -0.1, 0.5])), dict(gamma=np.array([0.1, 1.01, 0.5])), dict(gamma=np.array([np.nan, 0.1, 0.5])),
+                dict(epsilon=np.array([0.1, 0.2, 2.0])), dict(epsilon=np.array([-1e-3, 0.2, 1.0])), dict(epsilon=np.array([0.1, 0.2, np.nan])),
+                dict(alpha=np.full((3, 1), 0.5)), dict(epsilon=np.full((1, 3), 0.5)), dict(gamma=np.array(["a", "b", "c"])),
+                dict(alpha=np.array([True, True, True]))):
+        with pytest.raises(ValueError):
+            policy.check_learner_params(**dict(ok, **bad))
+    for bad in (dict(alpha=np.full(2, 0.5)), dict(gamma=np.full(4, 0.5)), dict(epsilon=np.zeros(0))):
+        with pytest.raises(ValueError):
+            policy.check_learner_params(num_envs=3, **dict(ok, **bad))
+    # element-wise thresholds
+    E = policy.epsilon_threshold(np.array([0.0, 0.25, 1.0, 0.1, 1e-3]))
+    assert E.dtype == np.uint32 and E.tolist() == [policy.epsilon_threshold(e) for e in (0.0, 0.25, 1.0, 0.1, 1e-3)]
+    assert E.tolist() == ref.epsilon_threshold([0.0, 0.25, 1.0, 0.1, 1e-3]).tolist()
+    with pytest.raises(ValueError):
+        policy.epsilon_threshold(np.array([0.5, 1.5]))
+
+
+def test_double_q_is_a_known_algorithm_and_double_q_learning_is_not():
+    assert policy.LEARN_ALGOS == ("q_learning", "sarsa", "double_q") == ref.ALGOS
+    policy.check_learner_params("double_q", 0.3, 0.9, 0.25)
+    with pytest.raises(ValueError):
+        policy.check_learner_params("double_q_learning", 0.3, 0.9, 0.25)
+    assert _capi.LEARN_ALGOS == {"q_learning": 0, "sarsa": 1} and _capi.MDPP_LEARN_DOUBLE_Q == 2
+
+
+# ---- (d), (e) names
+def test_the_update_stream_is_named_and_distinct_from_every_other_stream_id():
+    src = open(os.path.join(ROOT, "mdp_playground_amd", "csrc", "mdpp_internal.hpp")).read()
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"constexpr uint32_t (kPhilox\w+Stream) = (\d+);", src)}
+    assert ids["kPhiloxLearnUpdateStream"] == ref.UPDATE_STREAM == 17
+    assert ids["kPhiloxLearnExploreStream"] == ref.EXPLORE_STREAM and ids["kPhiloxLearnActionStream"] == ref.ACTION_STREAM
+    assert len(set(ids.values())) == len(ids)
+    img = open(os.path.join(ROOT, "mdp_playground_amd", "csrc", "mdpp_image.hip")).read()
+    others = {int(m.group(1)) for m in re.finditer(r"constexpr uint32_t kPhilox\w+Stream = (\d+);", img)} | {6, 7, 8}
+    assert 17 not in others
+
+
+def test_the_new_entry_points_are_declared_and_bound():
+    src = open(os.path.join(ROOT, "include", "mdpp.h")).read()
+    for name in ("mdpp_set_learner_params", "mdpp_set_learner_gamma"):
+        assert name in _capi.EXPORTS
+        assert re.search(r"\b%s\s*\(" % name, src), name
+    assert "MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1, MDPP_LEARN_DOUBLE_Q = 2" in src
+    lib = _capi.load()
+    assert len(lib.mdpp_set_learner_params.argtypes) == 5 and len(lib.mdpp_set_learner_gamma.argtypes) == 2
+    assert len(lib.mdpp_set_learner.argtypes) == 8 and len(lib.mdpp_set_learner_rates.argtypes) == 3
+    assert _capi.MDPP_ABI_VERSION == 8
+    from mdp_playground_amd import build
+    for unit in ("mdpp_discrete_learn_pe.hip", "mdpp_discrete_learn_double.hip", "mdpp_discrete_learn_double_pe.hip"):
+        assert unit in build.SOURCES and build.INCLUDED_SOURCES[unit] == ["mdpp_discrete_learn.hip"]
+
+
+# ---- (f) the coverage the GPU test asserts can be met: a closed loop on the CPU
+def _closed_loop(cfg, kw, algo, alpha, gamma, epsilon, n, q0=None):
+    """n oracle envs (Philox streams, same-step / next-step / no autoreset as the handle) driven by the restatement for
+    LAUNCHES x K steps; returns (info, Q)"""
+    from oracle import oracle as ora
+    from mdp_playground_amd import mdp as mdp_mod
+    m = mdp_mod.build_mdp(dict(cfg))
+    autoreset, max_steps = kw.get("autoreset", ref.SAME_STEP), kw.get("max_episode_steps", 0)
+    envs = []
+    for i in range(n):
+        o = ora.DiscreteOracle(m.S, m.A, m.sequence_length, m.delay, m.reward_every_n_steps, m.P, m.reward_table(), m.terminal_states,
+                               m.init_dist, m.transition_noise, m.reward_noise, m.reward_scale, m.reward_shift, m.term_state_reward)
+        o.set_philox(77, i)
+        envs.append(o)
+    s = np.array([o.reset() for o in envs], np.int64)
+    al, ga, E = ref.per_env(n, alpha, gamma, epsilon)
+    Q = (np.zeros((n, 2, m.S, m.A) if algo == "double_q" else (n, m.S, m.A), np.float32) if q0 is None else q0.copy())
+    pending, steps = np.zeros(n, bool), np.zeros(n, np.int64)
+    info = ref.new_info(n)
+    total = cases.LAUNCHES * cases.K
+    w = {st: ref.tick_words(cases.SEED, 0, 0, total + 1, n, st) for st in (ref.EXPLORE_STREAM, ref.ACTION_STREAM, ref.UPDATE_STREAM)}
+    have_carry, carry = np.zeros(n, bool), np.zeros(n, np.int64)
+    for t in range(total):
+        if t % cases.K == 0:
+            have_carry[:] = False                            # (a launch's first step selects afresh)
+        fresh, _ = ref.select(algo, Q, s, w[ref.EXPLORE_STREAM][t], w[ref.ACTION_STREAM][t], E, info, ~have_carry)
+        a = np.where(have_carry, carry, fresh)
+        s2, r, te = s.copy(), np.zeros(n, np.float32), np.zeros(n, bool)
+        live = ~pending
+        for i in np.flatnonzero(live):
+            o, rr, d = envs[i].step(int(a[i]))
+            s2[i], r[i], te[i] = o, np.float32(rr), d
+        steps[live] += 1
+        tr = live & (max_steps > 0) & (steps >= max_steps)
+        a2 = ref.select(algo, Q, s2, w[ref.EXPLORE_STREAM][t + 1], w[ref.ACTION_STREAM][t + 1], E)[0] if algo == "sarsa" else None
+        ref.update(algo, Q, s, a, r, s2, te, live, al, ga, w[ref.UPDATE_STREAM][t], a2, info)
+        have_carry = live & (algo == "sarsa") & ~te & ~(tr & (autoreset != ref.DISABLED))
+        carry = a2 if a2 is not None else carry
+        ended = live & (te | tr)
+        reset_now = pending | (ended & (autoreset == ref.SAME_STEP))
+        for i in np.flatnonzero(reset_now):
+            s2[i] = envs[i].reset(explicit=False)
+            steps[i] = 0
+        pending = ended & (autoreset == ref.NEXT_STEP)
+        s = s2
+    return info, Q
+
+
+@pytest.mark.parametrize("case", list(cases.DOUBLE_CASES))
+def test_cpu_closed_loop_meets_the_double_q_coverage_the_gpu_test_asserts(case):
+    cfg, kw = cases.DOUBLE_CASES[case]
+    rand = case == "cfg2_random_q"
+    q0 = cases.random_q(5, 32, cfg["state_space_size"], cfg["action_space_size"], True) if rand else None
+    info, Q = _closed_loop(cfg, kw, "double_q", cases.ALPHA, cases.GAMMA, cases.EPS, 32, q0)
+    cases.double_honest(info, Q, rand)
+
+
+@pytest.mark.parametrize("algo", ref.ALGOS)
+@pytest.mark.parametrize("case", list(cases.PE_CASES))
+def test_cpu_closed_loop_meets_the_per_env_coverage_the_gpu_test_asserts(case, algo):
+    cfg, kw = cases.PE_CASES[case]
+    al, ga, ep = cases.pe_arrays(32)
+    assert len({(x, y) for x, y in zip(al, ep)}) == 16       # 32 envs hold every (alpha, epsilon) pair, twice
+    info, _ = _closed_loop(cfg, kw, algo, al, ga, ep, 32)
+    cases.pe_honest(info, ep)
+    a64, g64, e64 = cases.pe_arrays(64, 64)                  # any wave of 64: all 48 combinations
+    assert len(set(zip(a64.tolist(), g64.tolist(), e64.tolist()))) == 48
