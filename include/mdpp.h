@@ -377,6 +377,40 @@ const char *mdpp_learn_kernel_name(mdpp_env *h, int K);
 int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream);
 int mdpp_set_learner_gamma(mdpp_env *h, float gamma);
 
+/* Greedy evaluation of the learner's tables: mdpp_step_n_eval runs K steps in which env i in state s takes
+ *   one table:  a = the lowest j maximising Q[s][j] (scanned from j = 0 with a strict >),
+ *   double Q:   a = the lowest j maximising QA[s][j] + QB[s][j] (one float32 addition per j) -- the greedy branch of sel above,
+ * and the step is mdpp_step_n's with that action (transition and reward noise included).  There is no exploration, no
+ * target, no update and no carry: the tables are left bit for bit as they were, no word of stream ids 15, 16, 17 is used,
+ * alpha, gamma and epsilon (uniform or per-env) are not read.  On the reset call of a next-step-autoreset env the action is
+ * selected from the state in the record, written and ignored.  The launch leaves the handle where mdpp_step_n fed with
+ * actions_out leaves it.  The handle needs a learner (any algorithm; MDPP_ESTATE without one); served handles and refusals
+ * are mdpp_step_n_learn's.  To evaluate on a separate env, create a second handle and give it the tables (mdpp_get_q, then
+ * q_init_dev or mdpp_set_q).  mdpp_eval_kernel_name: as mdpp_kernel_name, for that launch (QLDS=1: the tables are staged in
+ * LDS, and not written back; DOUBLE=1: two tables per env).
+ *
+ * Episode summaries: mdpp_step_n_learn_summary / mdpp_step_n_eval_summary run the K steps of mdpp_step_n_learn / mdpp_step_n_eval
+ * with the same effect on the handle (state, streams, step counter, tables) and write NO [K][N] array.  Instead they keep
+ * five arrays of the caller, [N] each on the device -- ret float64, len int32 (the running episode's return and length),
+ * episodes int32, return_sum float64, length_sum int32 (finished episodes: their count, the sums of their returns and
+ * lengths).  Per env, in step order, for every step that is not the reset call of a next-step-autoreset env:
+ *   ret += (double)r (r the float32 reward the full-output launch writes; one float64 addition);  len += 1;
+ *   terminated or truncated:  episodes += 1;  return_sum += ret;  length_sum += len;  ret = 0;  len = 0.
+ * A reset call changes nothing.  The launch loads the five values before its first step and stores them after its last:
+ * the caller zeroes them (all five at an episode boundary it makes itself, mdpp_reset; the three sums when it has read
+ * them).  Nothing of them is kept in the handle.  Without [K][N] arrays a call is one launch whatever K.
+ * mdpp_current_obs writes the observation each env shows now (what the last step or reset returned for it), taken from the
+ * state record, to obs_dev [N] in the handle's observation type, ordered on `stream`: what a caller needs after a launch
+ * that wrote no observations.  Served: the handles of mdpp_step_n_learn. */
+int mdpp_step_n_eval(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                     uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+const char *mdpp_eval_kernel_name(mdpp_env *h, int K);
+int mdpp_step_n_learn_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                              double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+int mdpp_step_n_eval_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                             double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream);
+
 /* Per-env internal state <-> host (synchronous; checkpoint / set_augmented_state).
  * Discrete: hist int32[N][L+1] (-1 = NaN slot), steps int32[N], ring double[N][delay].
  * Continuous: derivs float[N][order+1][D], cur float[N][D], steps int32[N],

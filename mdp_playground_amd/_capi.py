@@ -47,6 +47,7 @@ EXPORTS = [
     "mdpp_set_policy", "mdpp_clear_policy", "mdpp_step_n_policy", "mdpp_policy_kernel_name",
     "mdpp_set_learner", "mdpp_clear_learner", "mdpp_set_learner_rates", "mdpp_step_n_learn", "mdpp_get_q", "mdpp_set_q",
     "mdpp_learn_kernel_name", "mdpp_set_learner_params", "mdpp_set_learner_gamma",
+    "mdpp_step_n_eval", "mdpp_eval_kernel_name", "mdpp_step_n_learn_summary", "mdpp_step_n_eval_summary", "mdpp_current_obs",
 ]
 
 
@@ -169,6 +170,12 @@ def load():
     L.mdpp_set_q.argtypes = [vp, vp, vp]
     L.mdpp_learn_kernel_name.argtypes = [vp, i32]
     L.mdpp_learn_kernel_name.restype = C.c_char_p
+    L.mdpp_step_n_eval.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_eval_kernel_name.argtypes = [vp, i32]
+    L.mdpp_eval_kernel_name.restype = C.c_char_p
+    L.mdpp_step_n_learn_summary.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_step_n_eval_summary.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_current_obs.argtypes = [vp, vp, vp]
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

@@ -16,6 +16,8 @@ OUT = os.path.join(CSRC, "libmdpp_hip.so")
 SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp_discrete_long.hip", "mdpp_discrete_fast.hip", "mdpp_discrete_step1.hip", "mdpp_discrete_pipe.hip", "mdpp_discrete_lean.hip", "mdpp_discrete_lean_next.hip", "mdpp_discrete_lean_noise.hip", "mdpp_discrete_lean_npnoise.hip",
            "mdpp_discrete_quiet.hip", "mdpp_discrete_quiet_nu.hip", "mdpp_discrete_policy.hip", "mdpp_discrete_learn.hip",
            "mdpp_discrete_learn_pe.hip", "mdpp_discrete_learn_double.hip", "mdpp_discrete_learn_double_pe.hip",
+           "mdpp_discrete_learn_summary.hip", "mdpp_discrete_learn_pe_summary.hip", "mdpp_discrete_learn_double_summary.hip",
+           "mdpp_discrete_learn_double_pe_summary.hip", "mdpp_discrete_eval.hip", "mdpp_discrete_eval_summary.hip",
            "mdpp_continuous.hip", "mdpp_continuous_line8.hip",
            "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
            "mdpp_generate.hip"]
@@ -24,7 +26,11 @@ HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdp
 INCLUDED_SOURCES = {"mdpp_discrete_wide.hip": ["mdpp_discrete.hip"], "mdpp_discrete_long.hip": ["mdpp_discrete.hip"], "mdpp_discrete_lean_next.hip": ["mdpp_discrete_lean.hip"], "mdpp_discrete_lean_noise.hip": ["mdpp_discrete_lean.hip"], "mdpp_discrete_lean_npnoise.hip": ["mdpp_discrete_lean.hip"],
                     "mdpp_continuous_line8.hip": ["mdpp_continuous.hip"], "mdpp_continuous_step1.hip": ["mdpp_continuous_fast.hip"], "mdpp_discrete_quiet_nu.hip": ["mdpp_discrete_quiet.hip"],
                     "mdpp_discrete_learn_pe.hip": ["mdpp_discrete_learn.hip"], "mdpp_discrete_learn_double.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_double_pe.hip": ["mdpp_discrete_learn.hip"]}   # a .hip that #includes another one
+                    "mdpp_discrete_learn_double_pe.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_learn_summary.hip": ["mdpp_discrete_learn.hip"], "mdpp_discrete_learn_pe_summary.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_learn_double_summary.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_learn_double_pe_summary.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_eval_summary.hip": ["mdpp_discrete_eval.hip"]}   # a .hip that #includes another one
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # The GENERAL kernels keep whole state vectors in registers and spill (k_continuous_step<DMAX=32, OMAX=4>: 3 KB of scratch per lane).

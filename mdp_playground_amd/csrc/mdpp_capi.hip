@@ -1511,6 +1511,56 @@ extern "C" const char *mdpp_learn_kernel_name(mdpp_env *h, int K) {
     return closed_kernel_name(h, K, "mdpp_learn_kernel_name", launch_discrete_learn);
 }
 
+// ---- ... of greedy evaluation of the learner's tables (mdpp_discrete_eval.hip), and the launches that keep episode summaries ----
+extern "C" int mdpp_step_n_eval(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                                uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    return step_n_closed(h, "mdpp_step_n_eval", discrete_learn_refusal(h), h->learn_ready, "no learner set (mdpp_set_learner)",
+                         launch_discrete_eval, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, stream);
+}
+
+extern "C" const char *mdpp_eval_kernel_name(mdpp_env *h, int K) {
+    if (h && !h->learn_ready) { h->kname[0] = 0; return h->kname; }      // (which form depends on the learner's algorithm)
+    return closed_kernel_name(h, K, "mdpp_eval_kernel_name", launch_discrete_eval);
+}
+
+// the checks of step_n_closed for a launch that keeps the caller's five [N] summary arrays and writes nothing else
+static int step_n_summary(mdpp_env *h, const char *what, int (*launch)(mdpp_env *, const DiscreteIO &), int K, double *ret,
+                          int32_t *len, int32_t *episodes, double *return_sum, int32_t *length_sum, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": K < 1");
+    if (!ret || !len || !episodes || !return_sum || !length_sum) return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    const std::string why = discrete_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_learner)");
+    int rc = check_ready(h, what);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const EpisodeSummaryArgs sm{ret, len, episodes, return_sum, length_sum};
+    DiscreteIO io{};
+    io.K = K; io.s = (hipStream_t)stream; io.summary = &sm;
+    return launch(h, io);
+}
+
+extern "C" int mdpp_step_n_learn_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                         double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
+    return step_n_summary(h, "mdpp_step_n_learn_summary", launch_discrete_learn, K, ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, stream);
+}
+
+extern "C" int mdpp_step_n_eval_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                        double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
+    return step_n_summary(h, "mdpp_step_n_eval_summary", launch_discrete_eval, K, ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, stream);
+}
+
+extern "C" int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!obs_dev) return fail(h, MDPP_EINVAL, "mdpp_current_obs: null buffer");
+    int rc = check_ready(h, "mdpp_current_obs");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_discrete_current_obs(h, obs_dev, (hipStream_t)stream);
+}
+
 // Python round(v, 15) for |v| <= 1: correctly rounded decimal conversion, like Pillow's rotate().
 static double round15(double v) {
     char buf[64];

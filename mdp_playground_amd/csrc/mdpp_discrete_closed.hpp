@@ -28,6 +28,12 @@
 //   learn(cur, action, nxt, reward, done, truncated_with_reset, ptick)
 //                              after the reward is formed, before a same-step reset: nxt is the true next state
 //   finish(i)                  per lane, after the last step
+//
+// SUMMARY = true (mdpp_step_n_learn_summary / mdpp_step_n_eval_summary): the same K steps with no [K][N] output.  The lane
+// loads the five values of its env from sm after begin(), applies at every step that is not a reset call
+//   ret += (double)reward;  len += 1;  terminated or truncated: episodes += 1, return_sum += ret, length_sum += len, ret = len = 0
+// and stores them after finish().  The five output pointers are unused (null).  A compile-time choice: the SUMMARY = false
+// instantiations are the code they were.
 #pragma once
 #include "mdpp_internal.hpp"
 #include "mdpp_rng.hpp"
@@ -38,11 +44,12 @@ constexpr int kClosedRsrcFlags = 0x00020000;
 typedef unsigned int closed_u32x2 __attribute__((ext_vector_type(2)));
 
 // (a is the kernel's by-value argument, taken by const reference: see tick_now in mdpp_internal.hpp for what a write costs)
-template <bool PHILOX, bool NOISE, bool UNIT, class Agent>
+template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, class Agent>
 __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K, const bool obs64, int32_t *actions,
                                                     void *__restrict__ obs, float *__restrict__ reward,
                                                     uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
-                                                    unsigned char *lds, const ZigLds &zig, Agent &agent) {
+                                                    unsigned char *lds, const ZigLds &zig, Agent &agent,
+                                                    const EpisodeSummaryArgs &sm = EpisodeSummaryArgs{}) {
     const uint64_t ptick0 = tick_now(a);               // the step counter at this launch (through the device-side offset of a graph replay)
     const uint32_t rhead0 = ring_head_now(a, ptick0);  // ... and the head of a delay line kept in memory
     const int tid = threadIdx.x;
@@ -70,6 +77,12 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     const double *const tnoise = (const double *)(lds + a.lds_noise);
     const uint64_t genv = (uint64_t)(a.env_id_offset + (int64_t)i);
     agent.begin(i, genv, ptick0);
+    double ep_ret = 0.0, ep_return_sum = 0.0;           // SUMMARY: this env's five values
+    int32_t ep_len = 0, ep_count = 0, ep_length_sum = 0;
+    if constexpr (SUMMARY) {
+        ep_ret = sm.ret[i]; ep_len = sm.len[i];
+        ep_count = sm.episodes[i]; ep_return_sum = sm.return_sum[i]; ep_length_sum = sm.length_sum[i];
+    }
 
     const uint4 st = a.state[i];
     // fast_ok handles: word 1 is the queue of start states {24 bits of 4-bit entries, next one lowest; count in bits 24-26},
@@ -105,7 +118,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
         return 0.0 + a.r_noise * (PHILOX ? (double)rn_z.normal(a.philox_seed, genv, ptick, kPhiloxRNoiseStream) : np_standard_normal_lds(env_pcg, zig));
     };
 
-    const uint32_t total = (uint32_t)K * N;             // (the launcher keeps 8 K N below 2^32)
+    const uint32_t total = SUMMARY ? 0u : (uint32_t)K * N;     // (the launcher keeps 8 K N below 2^32; SUMMARY: nothing is stored)
     auto r_act = __builtin_amdgcn_make_buffer_rsrc((void *)actions, 0, total * 4u, kClosedRsrcFlags);
     auto r_obs = __builtin_amdgcn_make_buffer_rsrc(obs, 0, total * (obs64 ? 8u : 4u), kClosedRsrcFlags);
     auto r_rew = __builtin_amdgcn_make_buffer_rsrc((void *)reward, 0, total * 4u, kClosedRsrcFlags);
@@ -113,7 +126,8 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     auto r_trunc = __builtin_amdgcn_make_buffer_rsrc((void *)trunc, 0, total, kClosedRsrcFlags);
     const uint32_t v1 = i, v4 = i * 4u, v8 = i * 8u;
     auto put_obs = [&](uint32_t s, uint32_t so) {       // (the width: a constant or wave-uniform)
-        if (obs64) __builtin_amdgcn_raw_buffer_store_b64(closed_u32x2{s, 0u}, r_obs, v8, so * 8u, MDPP_ST_NT);
+        if constexpr (SUMMARY) { (void)s; (void)so; }
+        else if (obs64) __builtin_amdgcn_raw_buffer_store_b64(closed_u32x2{s, 0u}, r_obs, v8, so * 8u, MDPP_ST_NT);
         else __builtin_amdgcn_raw_buffer_store_b32(s, r_obs, v4, so * 4u, MDPP_ST_NT);
     };
 
@@ -141,14 +155,16 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
         if (k == 0 || (ptick & 3u) == 0u) agent.next_block(genv, ptick);            // (wave-uniform)
         const uint32_t cur = (uint32_t)hist & 0xFFu;
         const uint32_t action = agent.act(cur, ptick);
-        __builtin_amdgcn_raw_buffer_store_b32(action, r_act, v4, so * 4u, MDPP_ST_NT);
+        if constexpr (!SUMMARY) __builtin_amdgcn_raw_buffer_store_b32(action, r_act, v4, so * 4u, MDPP_ST_NT);
         if (pending) {               // next-step autoreset: this call is the env's reset(), :2250-2278; the action is ignored, nothing is learnt
             const uint32_t s0 = start_state(ptick);
             episode_start(s0);
             put_obs(s0, so);
-            __builtin_amdgcn_raw_buffer_store_b32(0u, r_rew, v4, so * 4u, MDPP_ST_NT);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, r_term, v1, so, MDPP_ST_NT);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, r_trunc, v1, so, MDPP_ST_NT);
+            if constexpr (!SUMMARY) {
+                __builtin_amdgcn_raw_buffer_store_b32(0u, r_rew, v4, so * 4u, MDPP_ST_NT);
+                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, r_term, v1, so, MDPP_ST_NT);
+                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)0, r_trunc, v1, so, MDPP_ST_NT);
+            }
             pending = false;
             continue;
         }
@@ -217,12 +233,27 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
             episode_start(out_state);
         }
         put_obs(out_state, so);
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rout), r_rew, v4, so * 4u, MDPP_ST_NT);
-        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(done ? 1 : 0), r_term, v1, so, MDPP_ST_NT);
-        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(truncated ? 1 : 0), r_trunc, v1, so, MDPP_ST_NT);
+        if constexpr (SUMMARY) {
+            ep_ret += (double)rout;
+            ep_len += 1;
+            if (done || truncated) {
+                ep_count += 1;
+                ep_return_sum += ep_ret;
+                ep_length_sum += ep_len;
+                ep_ret = 0.0; ep_len = 0;
+            }
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rout), r_rew, v4, so * 4u, MDPP_ST_NT);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(done ? 1 : 0), r_term, v1, so, MDPP_ST_NT);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(truncated ? 1 : 0), r_trunc, v1, so, MDPP_ST_NT);
+        }
     }
 
     agent.finish(i);
+    if constexpr (SUMMARY) {
+        sm.ret[i] = ep_ret; sm.len[i] = ep_len;
+        sm.episodes[i] = ep_count; sm.return_sum[i] = ep_return_sum; sm.length_sum[i] = ep_length_sum;
+    }
     a.state[i] = make_uint4((uint32_t)hist, queued ? (qv | (qc << 24)) : (uint32_t)(hist >> 32),
                             steps | (pending ? 0x80000000u : 0u), ringbits);
     if (use_env) env_pcg.store(a.env_s, i);
@@ -256,7 +287,8 @@ inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool
 // K closed-loop steps of kern with lds bytes of dynamic LDS.  name: the kernel's, with its template arguments -- a dry run
 // (io.name_out) writes it and launches nothing.  agent_args(k0, kc, actions) makes the kernel's second argument for the
 // launch of steps [k0, k0 + kc), whose actions go to `actions`.  lds_granted: the caller has asked dynamic_lds_ok for this
-// kernel and size already.
+// kernel and size already.  io.summary: kern is a SUMMARY kernel, taking (args, agent args, K, summary) -- it addresses no
+// [K][N] array, so the call is one launch (MDPP_OPT_LEARN_SHORT_PIECES still cuts it).
 template <class Kern, class AgentArgs>
 inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size_t lds, bool lds_granted, const char *name,
                               AgentArgs &&agent_args) {
@@ -264,7 +296,7 @@ inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size
     DiscreteArgs a = h->dargs;
     stamp_step(a, h);
     // pieces: the buffer descriptors address < 4 GiB per output array (8 bytes per env-step at most)
-    long long kmax = ((1LL << 32) - 1) / (8LL * a.N);
+    long long kmax = io.summary ? (long long)INT32_MAX : ((1LL << 32) - 1) / (8LL * a.N);
     if (kmax < 1) { h->err = kernel + ": num_envs too large"; return MDPP_EUNSUPPORTED; }
     if ((a.opts & MDPP_OPT_LEARN_SHORT_PIECES) && kmax > 5) kmax = 5;      // (tests: the pieces' hand-over at a small size)
     if (io.name_out) { snprintf(io.name_out, kNameLen, "%s", name); return MDPP_OK; }
@@ -273,8 +305,11 @@ inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size
     // (io.actions, an input of every other launcher, is this one's OUTPUT: the caller's buffer for the actions taken; piece_of
     //  offsets it like the other arrays -- these handles have no irrelevant sub-space -- and the const comes off at the launch)
     for_each_piece(a, h, io, kmax, [&](const DiscreteIO &p, int k0) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, io.s, a, agent_args(k0, p.K, const_cast<int32_t *>(p.actions)), p.K,
-                           p.obs, p.reward, p.term, p.trunc);
+        if constexpr (std::is_invocable_v<Kern, DiscreteArgs, decltype(agent_args(0, 0, nullptr)), int, EpisodeSummaryArgs>)
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, io.s, a, agent_args(k0, p.K, nullptr), p.K, *io.summary);
+        else
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, io.s, a, agent_args(k0, p.K, const_cast<int32_t *>(p.actions)), p.K,
+                               p.obs, p.reward, p.term, p.trunc);
         return true;
     });
     return step_done(h, io.K, kernel.c_str());

@@ -38,6 +38,10 @@
 // PE and DOUBLE are template parameters: the uniform q_learning / sarsa instantiations are the code they were.  Each
 // (PE, DOUBLE) pair other than (0, 0) is instantiated in a translation unit of its own (mdpp_discrete_learn_pe.hip,
 // mdpp_discrete_learn_double.hip, mdpp_discrete_learn_double_pe.hip define the macros below and include this file).
+//
+// k_discrete_learn_summary (mdpp_step_n_learn_summary) is the same agent around closed_loop_rollout's SUMMARY form: the same
+// steps, selections and updates, five per-env episode numbers instead of the [K][N] arrays.  Its instantiations live in four
+// further translation units (mdpp_discrete_learn*_summary.hip: MDPP_LEARN_TU_SUMMARY), one per (PE, DOUBLE) pair.
 #include "mdpp_discrete_closed.hpp"
 
 #ifndef MDPP_LEARN_TU_PE
@@ -45,6 +49,9 @@
 #endif
 #ifndef MDPP_LEARN_TU_DOUBLE
 #define MDPP_LEARN_TU_DOUBLE 0     // 1: ... the DOUBLE = 1 instantiations
+#endif
+#ifndef MDPP_LEARN_TU_SUMMARY
+#define MDPP_LEARN_TU_SUMMARY 0    // 1: ... k_discrete_learn_summary's of that (PE, DOUBLE) pair, and nothing else
 #endif
 
 namespace mdpp {
@@ -229,8 +236,27 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs 
     closed_loop_rollout<PHILOX, NOISE, UNIT>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, ZigLds{s_ki, s_wi, s_fi}, agent);
 }
 
+// ... keeping episode summaries instead of writing the [K][N] arrays (p.actions is unused)
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs a, std::conditional_t<PE, LearnArgsPE, LearnArgs> p, int K,
+                                                                   EpisodeSummaryArgs sm) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ uint64_t s_ki[NOISE ? 256 : 1];
+    __shared__ double s_wi[NOISE ? 256 : 1], s_fi[NOISE ? 256 : 1];
+    if (NOISE) zig_stage(s_ki, s_wi, s_fi, threadIdx.x, kBlock);
+    LearnAgent<QLDS, PE, DOUBLE> agent{p, (float *)(lds + a.lds_bytes) + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, ZigLds{s_ki, s_wi, s_fi}, agent, sm);
+}
+
+// the kernel of one form: full output, or summaries
+template <bool SUMMARY, bool PH, bool NZ, bool UNIT, bool QL, bool PE, bool DOUBLE>
+static constexpr auto learn_kernel() {
+    if constexpr (SUMMARY) return k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE>;
+    else return k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE>;
+}
+
 // K learning steps of one (PE, DOUBLE) form
-template <bool PE, bool DOUBLE>
+template <bool PE, bool DOUBLE, bool SUMMARY = false>
 static int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
     const DiscreteArgs &a = h->dargs;
     const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (DOUBLE ? 2u : 1u);
@@ -238,12 +264,12 @@ static int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
     with_bools([&](auto PH, auto NZ, auto UNIT) {
         // the LDS form when a workgroup's 256 tables fit beside the MDP's (and the device grants it)
         const bool qlds = !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u &&
-                          dynamic_lds_ok((const void *)k_discrete_learn_rollout<PH(), NZ(), UNIT(), true, PE, DOUBLE>, (size_t)a.lds_bytes + q_lds);
+                          dynamic_lds_ok((const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), true, PE, DOUBLE>(), (size_t)a.lds_bytes + q_lds);
         with_bools([&](auto QL) {
             char name[kNameLen];
-            snprintf(name, kNameLen, "k_discrete_learn_rollout<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s>", PH(), NZ(), UNIT(), QL(),
-                     PE ? ",PE=1" : "", DOUBLE ? ",DOUBLE=1" : "");
-            rc = launch_closed_loop(h, io, k_discrete_learn_rollout<PH(), NZ(), UNIT(), QL(), PE, DOUBLE>, (size_t)a.lds_bytes + (QL() ? q_lds : 0u), QL(), name,
+            snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
+                     PH(), NZ(), UNIT(), QL(), PE ? ",PE=1" : "", DOUBLE ? ",DOUBLE=1" : "");
+            rc = launch_closed_loop(h, io, learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE>(), (size_t)a.lds_bytes + (QL() ? q_lds : 0u), QL(), name,
                                     [&](int k0, int kc, int32_t *actions) {
                 const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
                                      h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
@@ -255,7 +281,15 @@ static int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
     return rc;
 }
 
-#if MDPP_LEARN_TU_PE && MDPP_LEARN_TU_DOUBLE
+#if MDPP_LEARN_TU_SUMMARY && MDPP_LEARN_TU_PE && MDPP_LEARN_TU_DOUBLE
+int launch_discrete_learn_double_pe_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<true, true, true>(h, io); }
+#elif MDPP_LEARN_TU_SUMMARY && MDPP_LEARN_TU_DOUBLE
+int launch_discrete_learn_double_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<false, true, true>(h, io); }
+#elif MDPP_LEARN_TU_SUMMARY && MDPP_LEARN_TU_PE
+int launch_discrete_learn_pe_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<true, false, true>(h, io); }
+#elif MDPP_LEARN_TU_SUMMARY
+int launch_discrete_learn_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<false, false, true>(h, io); }
+#elif MDPP_LEARN_TU_PE && MDPP_LEARN_TU_DOUBLE
 int launch_discrete_learn_double_pe(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<true, true>(h, io); }
 #elif MDPP_LEARN_TU_DOUBLE
 int launch_discrete_learn_double(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<false, true>(h, io); }
@@ -300,7 +334,10 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) { h->err = "mdpp_step_n_learn: " + why; return MDPP_EUNSUPPORTED; }
     const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
-    if (!h->learn_pe) return dbl ? launch_discrete_learn_double(h, io) : launch_learn_form<false, false>(h, io);
+    if (!h->learn_pe) {
+        if (io.summary) return dbl ? launch_discrete_learn_double_summary(h, io) : launch_discrete_learn_summary(h, io);
+        return dbl ? launch_discrete_learn_double(h, io) : launch_learn_form<false, false>(h, io);
+    }
     if (h->learn_pe_stale && !io.name_out) {
         const uint32_t N = (uint32_t)h->cfg.num_envs, grid = (N + kBlock - 1) / kBlock;
         uint32_t abits, gbits;
@@ -314,6 +351,7 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
         if (e != hipSuccess) { h->err = std::string("k_learn_fill launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
         h->learn_pe_stale = 0;
     }
+    if (io.summary) return dbl ? launch_discrete_learn_double_pe_summary(h, io) : launch_discrete_learn_pe_summary(h, io);
     return dbl ? launch_discrete_learn_double_pe(h, io) : launch_discrete_learn_pe(h, io);
 }
 #endif

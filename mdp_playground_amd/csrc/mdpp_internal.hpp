@@ -428,6 +428,15 @@ template <int... Vs, class F> inline bool with_value(int v, F &&f) {
 // K steps x N envs, every array time-major.  name_out != nullptr: a dry run -- the launcher writes the name of the kernel
 // it would launch (at most kNameLen bytes) and launches nothing
 constexpr int kNameLen = 192;
+// The episode summaries of a closed-loop launch that writes no [K][N] array (mdpp_step_n_learn_summary /
+// mdpp_step_n_eval_summary): the caller's five [N] arrays on the device -- the running episode's return and length, the
+// finished episodes' count and the sums of their returns and lengths
+struct EpisodeSummaryArgs {
+    double *ret;
+    int32_t *len, *episodes;
+    double *return_sum;
+    int32_t *length_sum;
+};
 template <class Act, class Obs>
 struct StepIO {
     int K;
@@ -438,6 +447,7 @@ struct StepIO {
     Obs *final_obs;             // null: not asked for
     hipStream_t s;
     char *name_out;
+    const EpisodeSummaryArgs *summary = nullptr;    // closed-loop launchers: not null = keep these, the five arrays above are unused
     // steps [k0, k0 + kc) of this launch: an env-step has act_elems action elements and obs_bytes bytes of observation
     StepIO piece(int k0, int kc, size_t N, size_t act_elems, size_t obs_bytes) const {
         const size_t off = (size_t)k0 * N;
@@ -538,6 +548,18 @@ int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t 
 int launch_discrete_learn_pe(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_learn_double(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_learn_double_pe(mdpp_env *h, const DiscreteIO &io);
+// ... their forms that keep episode summaries (io.summary) instead of writing [K][N] arrays, one translation unit each too
+// (mdpp_discrete_learn_summary.hip, ..._pe_summary.hip, ..._double_summary.hip, ..._double_pe_summary.hip)
+int launch_discrete_learn_summary(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_pe_summary(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_double_summary(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_double_pe_summary(mdpp_env *h, const DiscreteIO &io);
+// io.K steps of greedy evaluation of the learner's tables (mdpp_discrete_eval.hip; with io.summary:
+// mdpp_discrete_eval_summary.hip, to which launch_discrete_eval hands over)
+int launch_discrete_eval(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_eval_summary(mdpp_env *h, const DiscreteIO &io);
+// the observation every env shows now, from the state record, to obs [N] (mdpp_discrete_eval.hip)
+int launch_discrete_current_obs(mdpp_env *h, void *obs, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // phase bits: 1 = draw + records, 2 = render (phase == 2 exactly: pipelined, the persistent grid leaves slots

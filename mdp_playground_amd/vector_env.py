@@ -29,7 +29,10 @@ import torch
 from . import _capi as capi
 from . import mdp as mdp_mod
 from . import policy as policy_mod
+from .summary import EpisodeSummary
 from .spaces import BatchedSpace, BoxSpace, DiscreteSpace, ImageSpace, TupleSpace
+
+_OBS_FROM_STATE = object()    # _obs_src after a launch that wrote no observations: take them from the state record
 
 _AUTORESET = {"disabled": capi.AUTORESET_DISABLED, "same_step": capi.AUTORESET_SAME_STEP,
               "next_step": capi.AUTORESET_NEXT_STEP}
@@ -529,7 +532,9 @@ class RLToyVectorEnv:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             mptr = C.c_void_p(mask.data_ptr())
             src = getattr(self, "_obs_src", None)
-            if src is not None:          # the rows of the envs NOT reset: their observation after the last rollout() / graph replay
+            if src is _OBS_FROM_STATE:   # (a summary launch: the observation every env shows, from its state record)
+                self._closed_call(self._lib.mdpp_current_obs(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()), "mdpp_current_obs")
+            elif src is not None:        # the rows of the envs NOT reset: their observation after the last rollout() / graph replay
                 self._obs.copy_(src)
         self._obs_src = None
         rc = self._lib.mdpp_reset(self._h, mptr, C.c_void_p(self._obs.data_ptr()), self._stream())
@@ -701,6 +706,22 @@ class RLToyVectorEnv:
         self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
         return obs, rew, term.view(torch.bool), trunc.view(torch.bool), act
 
+    def _rollout_summary(self, step_n, what, K, summary):
+        """K closed-loop steps that keep ``summary`` and write no [K, N] array (mdpp_step_n_learn_summary / _eval_summary)."""
+        if not isinstance(summary, EpisodeSummary):
+            raise ValueError(f"{what}: summary must be an EpisodeSummary (env.episode_summary())")
+        summary.check(self.num_envs, self.device, what)
+        rc = step_n(self._h, K, *(C.c_void_p(t.data_ptr()) for t in summary.tensors()), self._stream())
+        self._closed_call(rc, what)
+        self._obs_src = _OBS_FROM_STATE
+        return summary
+
+    def episode_summary(self):
+        """A new EpisodeSummary for this handle (summary.py): five zeroed [N] device tensors -- ret, len, episodes, return_sum,
+        length_sum -- for rollout_learn(K, summary=) / rollout_eval(K, summary=); pop() reads and zeroes the finished episodes'
+        three, clear() zeroes all five (call it after reset(): the handle knows nothing of the object)."""
+        return EpisodeSummary(self.num_envs, self.device)
+
     def alloc_rollout_policy(self, K):
         """Output buffers of rollout_policy(K): alloc_rollout(K) and the actions, int32 [K, N]."""
         return self._alloc_rollout_closed(K)
@@ -803,13 +824,46 @@ class RLToyVectorEnv:
         """Output buffers of rollout_learn(K): alloc_rollout(K) and the actions, int32 [K, N]."""
         return self._alloc_rollout_closed(K)
 
-    def rollout_learn(self, K, out=None):
+    def rollout_learn(self, K, out=None, *, summary=None):
         """K steps of "select epsilon-greedily from the env's own Q, step, update that Q" in ONE kernel launch.  Returns (obs,
         reward, terminated, truncated, actions), each with a leading K axis; rollout(actions) on an identically built env
         returns the same first four, bit for bit.  SARSA carries its next action from step to step inside a call only: the
-        first step of every call selects afresh."""
+        first step of every call selects afresh.
+        ``summary`` (episode_summary()): the same K steps with the same effect on the env and the tables, but NO [K, N] array
+        is written -- the kernel keeps the per-env episode numbers in ``summary`` and that object is returned."""
         self._learn_check_kind()
+        if summary is not None:
+            if out is not None:
+                raise ValueError("rollout_learn: give out or summary, not both")
+            return self._rollout_summary(self._lib.mdpp_step_n_learn_summary, "mdpp_step_n_learn_summary", int(K), summary)
         return self._rollout_closed(self._lib.mdpp_step_n_learn, "mdpp_step_n_learn", int(K), out)
+
+    def alloc_rollout_eval(self, K):
+        """Output buffers of rollout_eval(K): alloc_rollout(K) and the actions, int32 [K, N]."""
+        return self._alloc_rollout_closed(K)
+
+    def rollout_eval(self, K, out=None, *, summary=None):
+        """K steps of GREEDY evaluation of the learner's tables in ONE kernel launch: every env takes the lowest action that
+        maximises its own Q[s] (QA[s] + QB[s] for "double_q").  No exploration and no update: the tables stay bit for bit what
+        they were, the learner's Philox streams are not consumed, alpha, gamma and epsilon are not read.  Needs a learner
+        (set_learner, any algorithm).  Returns (obs, reward, terminated, truncated, actions) like rollout_learn; with
+        ``summary`` the episode numbers instead, as there.  The steps are steps of THIS env: to evaluate on a separate one,
+        build a second handle and give it the tables -- set_learner(..., q=train.get_q()) or set_q(train.get_q())."""
+        self._learn_check_kind()
+        if summary is not None:
+            if out is not None:
+                raise ValueError("rollout_eval: give out or summary, not both")
+            return self._rollout_summary(self._lib.mdpp_step_n_eval_summary, "mdpp_step_n_eval_summary", int(K), summary)
+        return self._rollout_closed(self._lib.mdpp_step_n_eval, "mdpp_step_n_eval", int(K), out)
+
+    def eval_kernel_name(self, K):
+        """Name (with template arguments) of the kernel rollout_eval(K) launches (mdpp_eval_kernel_name; nothing is launched;
+        QLDS=1: the Q-tables are staged in LDS; DOUBLE=1: two tables per env); empty for a handle it does not serve or one
+        without a learner."""
+        if self.kind != "discrete":
+            return ""
+        name = self._lib.mdpp_eval_kernel_name(self._h, int(K))
+        return name.decode() if name else ""
 
     def get_q(self):
         """The learner's tables, float32 [N, S, A] ([N, 2, S, A], A then B, for "double_q"); a copy, made on the current stream."""
