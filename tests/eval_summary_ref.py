@@ -15,6 +15,8 @@ with ret, return_sum float64 and len, episodes, length_sum int32.
 """
 import numpy as np
 
+from learner_sweep_ref import scan_best
+
 DISABLED, SAME_STEP, NEXT_STEP = "disabled", "same_step", "next_step"
 FIELDS = (("ret", np.float64), ("len", np.int32), ("episodes", np.int32), ("return_sum", np.float64), ("length_sum", np.int32))
 
@@ -38,18 +40,19 @@ def greedy(Q, s, info=None, live=None):
     idx = np.arange(n)
     s = np.asarray(s).astype(np.int64)
     if Q.ndim == 4:
-        row = Q[idx, 0, s] + Q[idx, 1, s]                    # one float32 addition per entry
+        with np.errstate(invalid="ignore", over="ignore"):
+            row = Q[idx, 0, s] + Q[idx, 1, s]                # one float32 addition per entry
         assert row.dtype == np.float32
     else:
         row = Q[idx, s]
-    a = np.argmax(row, axis=1)                               # (numpy: the first of equal maxima)
+    a, best = scan_best(row)                                 # (the kernel's scan: not np.argmax, which ranks a NaN first)
     if info is not None:
         m = np.ones(n, bool) if live is None else live
-        ties = (row == row.max(axis=1, keepdims=True)).sum(axis=1) > 1
+        ties = (row == best[:, None]).sum(axis=1) > 1
         info["greedy_ties"] += int((m & ties).sum())
         info["greedy_strict"] += int((m & ~ties).sum())
         if Q.ndim == 4:
-            info["sum_differs"] += int((m & (a != np.argmax(Q[idx, 0, s], axis=1))).sum())
+            info["sum_differs"] += int((m & (a != scan_best(Q[idx, 0, s])[0])).sum())
     return a.astype(np.int64)
 
 

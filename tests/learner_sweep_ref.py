@@ -51,7 +51,8 @@ def per_env(n, alpha, gamma, epsilon):
 
 def new_info(n):
     return dict(explored=0, explored_env=np.zeros(n, np.int64), selections_env=np.zeros(n, np.int64), greedy_ties=0, greedy_strict=0,
-                carried=0, carried_differs=0, updates=0, updates_a=0, updates_b=0, cross_differs=0, sum_differs=0)
+                carried=0, carried_differs=0, updates=0, updates_a=0, updates_b=0, cross_differs=0, sum_differs=0,
+                trunc_resets=0, trunc_carry_differs=0, zero_sign_ties=0, denormal_results=0, nans_made=0)
 
 
 def merge_info(total, info):
@@ -60,10 +61,23 @@ def merge_info(total, info):
     return total
 
 
+def scan_best(row):
+    """(arg int64 [n], best [n]) of row [n, A]: best = row[0]; for j = 1 ... A - 1: row[j] > best moves on.  Not np.argmax, which
+    ranks a NaN first wherever it stands."""
+    row = np.asarray(row)
+    best, arg = row[:, 0].copy(), np.zeros(row.shape[0], np.int64)
+    with np.errstate(invalid="ignore"):
+        for j in range(1, row.shape[1]):
+            m = row[:, j] > best
+            best, arg = np.where(m, row[:, j], best), np.where(m, j, arg)
+    return arg, best
+
+
 def _greedy_row(algo, Q, s):
     idx = np.arange(Q.shape[0])
     if algo == "double_q":
-        row = Q[idx, 0, s] + Q[idx, 1, s]
+        with np.errstate(invalid="ignore", over="ignore"):
+            row = Q[idx, 0, s] + Q[idx, 1, s]
         assert row.dtype == np.float32
         return row
     return Q[idx, s]
@@ -75,18 +89,22 @@ def select(algo, Q, s, w_e, w_a, E, info=None, fresh_mask=None):
     explored = (w_e >> np.uint32(1)).astype(np.int64) < E
     a_x = ((w_a.astype(np.uint64) * np.uint64(A)) >> np.uint64(32)).astype(np.int64)
     row = _greedy_row(algo, Q, s)
-    a_g = np.argmax(row, axis=1)
+    a_g, best = scan_best(row)
     if info is not None:
         m = np.ones(n, bool) if fresh_mask is None else fresh_mask
         info["explored"] += int((explored & m).sum())
         info["explored_env"] += explored & m
         info["selections_env"] += m
-        ties = (row == row.max(axis=1, keepdims=True)).sum(axis=1) > 1
+        ties = (row == best[:, None]).sum(axis=1) > 1
         greedy = ~explored & m
         info["greedy_ties"] += int((greedy & ties).sum())
         info["greedy_strict"] += int((greedy & ~ties).sum())
+        # a tie decided between -0.0 and +0.0: the maximum is zero and zeros of both signs attain it
+        zeros = row == 0
+        both = (zeros & np.signbit(row)).any(axis=1) & (zeros & ~np.signbit(row)).any(axis=1)
+        info["zero_sign_ties"] += int((greedy & (best == 0) & both).sum())
         if algo == "double_q":
-            info["sum_differs"] += int((greedy & (a_g != np.argmax(Q[np.arange(n), 0, s], axis=1))).sum())
+            info["sum_differs"] += int((greedy & (a_g != scan_best(Q[np.arange(n), 0, s])[0])).sum())
     return np.where(explored, a_x, a_g), explored
 
 
@@ -99,29 +117,32 @@ def update(algo, Q, s, a, r, s2, terminated, live, alpha, gamma, w_u=None, a2=No
     te = np.asarray(terminated, bool)
     if algo == "double_q":
         b = (w_u >> np.uint32(31)).astype(np.int64)          # 0: A learns, 1: B
-        a_star = np.argmax(Q[idx, b, s2], axis=1)
+        a_star = scan_best(Q[idx, b, s2])[0]
         qn = Q[idx, 1 - b, s2, a_star]
         if info is not None:
-            info["cross_differs"] += int((live & ~te & (qn != Q[idx, 1 - b, s2].max(axis=1))).sum())
+            info["cross_differs"] += int((live & ~te & (qn != scan_best(Q[idx, 1 - b, s2])[1])).sum())
             info["updates_a"] += int((live & (b == 0)).sum())
             info["updates_b"] += int((live & (b == 1)).sum())
     elif algo == "sarsa":
         qn = Q[idx, s2, a2]
     else:
-        qn = Q[idx, s2].max(axis=1)
-    g = gamma * qn
-    y = np.where(te, r, r + g).astype(np.float32)
-    q = Q[idx, b, s, a] if algo == "double_q" else Q[idx, s, a]
-    d = y - q
-    u = alpha * d
-    assert g.dtype == d.dtype == u.dtype == np.float32
-    new = (q + u)[live]
+        qn = scan_best(Q[idx, s2])[1]
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):     # (the tables may hold infinities and denormals)
+        g = gamma * qn
+        y = np.where(te, r, r + g).astype(np.float32)
+        q = Q[idx, b, s, a] if algo == "double_q" else Q[idx, s, a]
+        d = y - q
+        u = alpha * d
+        new = (q + u)[live]
+    assert g.dtype == d.dtype == u.dtype == new.dtype == np.float32
     if algo == "double_q":
         Q[idx[live], b[live], s[live], a[live]] = new
     else:
         Q[idx[live], s[live], a[live]] = new
     if info is not None:
         info["updates"] += int(live.sum())
+        info["denormal_results"] += int(((new != 0) & (np.abs(new) < np.finfo(np.float32).tiny)).sum())
+        info["nans_made"] += int((np.isnan(new) & ~np.isnan(q[live])).sum())
 
 
 def run(algo, alpha, gamma, epsilon, Q, obs_before, obs, reward, terminated, truncated, P, autoreset, w_e, w_a, w_u=None, pending=None):
@@ -139,8 +160,10 @@ def run(algo, alpha, gamma, epsilon, Q, obs_before, obs, reward, terminated, tru
     have_carry, carry = np.zeros(n, bool), np.zeros(n, np.int64)
     actions = np.zeros((K, n), np.int64)
     info = new_info(n)
+    dropped = np.zeros(n, bool)                           # sarsa: the previous step dropped its carry at a truncation with a reset
     for k in range(K):
         fresh, _ = select(algo, Q, s, w_e[k], w_a[k], E, info, ~have_carry)
+        info["trunc_carry_differs"] += int((dropped & (carry != fresh)).sum())
         a = np.where(have_carry, carry, fresh)
         actions[k] = a
         info["carried"] += int(have_carry.sum())
@@ -153,6 +176,9 @@ def run(algo, alpha, gamma, epsilon, Q, obs_before, obs, reward, terminated, tru
         a2 = select(algo, Q, s2, w_e[k + 1], w_a[k + 1], E)[0] if sarsa else np.zeros(n, np.int64)
         update(algo, Q, s, a, reward[k], s2, te, live, al, ga, None if w_u is None else w_u[k], a2, info)
         have_carry = live & sarsa & ~te & ~(tr & (autoreset != DISABLED))
+        cut = live & ~te & tr & (autoreset != DISABLED)
+        info["trunc_resets"] += int(cut.sum())
+        dropped = cut & sarsa
         carry = a2
         pending = live & (autoreset == NEXT_STEP) & (te | tr)
         s = np.asarray(obs[k]).astype(np.int64)

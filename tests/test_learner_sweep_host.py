@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import learner_ref as old
+from closed_loop_cpu import closed_loop
 import learner_sweep_cases as cases
 import learner_sweep_ref as ref
 from mdp_playground_amd import _capi
@@ -204,48 +205,8 @@ def test_the_new_entry_points_are_declared_and_bound():
 # ---- (f) the coverage the GPU test asserts can be met: a closed loop on the CPU
 def _closed_loop(cfg, kw, algo, alpha, gamma, epsilon, n, q0=None):
     """n oracle envs (Philox streams, same-step / next-step / no autoreset as the handle) driven by the restatement for
-    LAUNCHES x K steps; returns (info, Q)"""
-    from oracle import oracle as ora
-    from mdp_playground_amd import mdp as mdp_mod
-    m = mdp_mod.build_mdp(dict(cfg))
-    autoreset, max_steps = kw.get("autoreset", ref.SAME_STEP), kw.get("max_episode_steps", 0)
-    envs = []
-    for i in range(n):
-        o = ora.DiscreteOracle(m.S, m.A, m.sequence_length, m.delay, m.reward_every_n_steps, m.P, m.reward_table(), m.terminal_states,
-                               m.init_dist, m.transition_noise, m.reward_noise, m.reward_scale, m.reward_shift, m.term_state_reward)
-        o.set_philox(77, i)
-        envs.append(o)
-    s = np.array([o.reset() for o in envs], np.int64)
-    al, ga, E = ref.per_env(n, alpha, gamma, epsilon)
-    Q = (np.zeros((n, 2, m.S, m.A) if algo == "double_q" else (n, m.S, m.A), np.float32) if q0 is None else q0.copy())
-    pending, steps = np.zeros(n, bool), np.zeros(n, np.int64)
-    info = ref.new_info(n)
-    total = cases.LAUNCHES * cases.K
-    w = {st: ref.tick_words(cases.SEED, 0, 0, total + 1, n, st) for st in (ref.EXPLORE_STREAM, ref.ACTION_STREAM, ref.UPDATE_STREAM)}
-    have_carry, carry = np.zeros(n, bool), np.zeros(n, np.int64)
-    for t in range(total):
-        if t % cases.K == 0:
-            have_carry[:] = False                            # (a launch's first step selects afresh)
-        fresh, _ = ref.select(algo, Q, s, w[ref.EXPLORE_STREAM][t], w[ref.ACTION_STREAM][t], E, info, ~have_carry)
-        a = np.where(have_carry, carry, fresh)
-        s2, r, te = s.copy(), np.zeros(n, np.float32), np.zeros(n, bool)
-        live = ~pending
-        for i in np.flatnonzero(live):
-            o, rr, d = envs[i].step(int(a[i]))
-            s2[i], r[i], te[i] = o, np.float32(rr), d
-        steps[live] += 1
-        tr = live & (max_steps > 0) & (steps >= max_steps)
-        a2 = ref.select(algo, Q, s2, w[ref.EXPLORE_STREAM][t + 1], w[ref.ACTION_STREAM][t + 1], E)[0] if algo == "sarsa" else None
-        ref.update(algo, Q, s, a, r, s2, te, live, al, ga, w[ref.UPDATE_STREAM][t], a2, info)
-        have_carry = live & (algo == "sarsa") & ~te & ~(tr & (autoreset != ref.DISABLED))
-        carry = a2 if a2 is not None else carry
-        ended = live & (te | tr)
-        reset_now = pending | (ended & (autoreset == ref.SAME_STEP))
-        for i in np.flatnonzero(reset_now):
-            s2[i] = envs[i].reset(explicit=False)
-            steps[i] = 0
-        pending = ended & (autoreset == ref.NEXT_STEP)
-        s = s2
+    LAUNCHES x K steps (tests/closed_loop_cpu.py); returns (info, Q)"""
+    info, Q, _ = closed_loop(cfg, kw, algo, alpha, gamma, epsilon, n, q0, seed=cases.SEED, K=cases.K, launches=cases.LAUNCHES)
     return info, Q
 
 
