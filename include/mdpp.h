@@ -97,8 +97,12 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
        MDPP_OPT_NO_SIGMA0 = 1u << 16,      /* noise keys present with sigma 0 (the reference draws rng.normal(0, 0): rl_toy_env.py:398-403, :1982):
                                               form the normals' values anyway instead of advancing the streams alone */
        MDPP_OPT_NO_LEARN_LDS = 1u << 18,   /* k_discrete_learn_rollout: the Q-tables stay in global memory (QLDS=0) */
-       MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19 }; /* mdpp_step_n_policy and mdpp_step_n_learn go out in launches of at most 5 steps
+       MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19, /* mdpp_step_n_policy and mdpp_step_n_learn go out in launches of at most 5 steps
                                               (the hand-over between the pieces of a very long call, at a size a test can run) */
+       MDPP_OPT_NO_NLEV_LDS = 1u << 20 };  /* per-env noise levels (mdpp_set_noise_levels): the per-level cdfs stay in global memory */
+
+/* transition-noise levels one handle serves at a time (mdpp_set_noise_levels) */
+#define MDPP_MAX_NOISE_LEVELS 16
 
 /* the tabular learner's algorithm (mdpp_set_learner); 2 is double Q-learning: two tables per env */
 enum { MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1, MDPP_LEARN_DOUBLE_Q = 2 };
@@ -410,6 +414,29 @@ int mdpp_step_n_learn_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_
 int mdpp_step_n_eval_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
                              double *return_sum_dev, int32_t *length_sum_dev, void *stream);
 int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream);
+
+/* Per-env noise levels for the learner and evaluation launches.  A handle mdpp_set_learner serves may give each env its own
+ * reward-noise sigma and its own transition-noise probability; mdpp_step_n_learn, mdpp_step_n_eval and their _summary forms
+ * then run ONE launch over all levels (the kernel's name gains ",NLEV=1"; the learner always in its PE form).
+ * mdpp_set_noise_levels takes HOST pointers to float64 [N] (the handle's LOCAL env index); NULL leaves that key as it is.
+ *   reward_noise[i]: finite, >= 0.  Env i's reward-noise term is 0.0 + reward_noise[i] z with z drawn exactly as without
+ *     levels (at sigma 0 too).  Needs a handle created with has_reward_noise.
+ *   transition_noise[i]: in [0, 1].  The distinct values, ascending, are the levels -- at most MDPP_MAX_NOISE_LEVELS; each env
+ *     gets a level byte.  Per level p > 0: T = ceil(p 2^32) and M = ceil(2^64 (S - 1) / T) for Philox streams; for numpy streams
+ *     the S categoricals' cdfs of rl_toy_env.py:1605-1612, and one uniform of the env's space stream per step.  p == 0:
+ *     T = M = 0, NO draw: the space stream of that env does not move.  Needs a handle created with has_transition_noise.
+ *   Env i then behaves bit for bit (outputs, tables, state record, env and space streams, step counter) like env i of a
+ *   handle created with transition_noise[i] and reward_noise[i] and everything else equal.
+ * Errors: MDPP_ESTATE for a handle mdpp_set_learner refuses or one created without the key, MDPP_EINVAL for a value out of
+ * range, NaN, or more than MDPP_MAX_NOISE_LEVELS distinct transition levels (nothing changed; the reason: mdpp_last_error).
+ * The arrays are copied into buffers of the handle, ordered on `stream`.  While levels are set mdpp_step and mdpp_step_n
+ * return MDPP_ESTATE ("per-env noise levels: learner and evaluation launches only; clear_noise_levels() first"); mdpp_reset is
+ * unaffected.  mdpp_get_noise_levels writes the values in force (the creation values while nothing was set) to HOST float64
+ * [N] arrays (NULL: not asked for).  mdpp_clear_noise_levels returns to the creation values and the launches the handle made
+ * before.  Levels are configuration, not state: the state getters / setters neither carry nor disturb them. */
+int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream);
+int mdpp_get_noise_levels(mdpp_env *h, double *transition_noise_out, double *reward_noise_out);
+int mdpp_clear_noise_levels(mdpp_env *h);
 
 /* Per-env internal state <-> host (synchronous; checkpoint / set_augmented_state).
  * Discrete: hist int32[N][L+1] (-1 = NaN slot), steps int32[N], ring double[N][delay].

@@ -18,6 +18,8 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_discrete_learn_pe.hip", "mdpp_discrete_learn_double.hip", "mdpp_discrete_learn_double_pe.hip",
            "mdpp_discrete_learn_summary.hip", "mdpp_discrete_learn_pe_summary.hip", "mdpp_discrete_learn_double_summary.hip",
            "mdpp_discrete_learn_double_pe_summary.hip", "mdpp_discrete_eval.hip", "mdpp_discrete_eval_summary.hip",
+           "mdpp_discrete_learn_pe_nlev.hip", "mdpp_discrete_learn_double_pe_nlev.hip", "mdpp_discrete_learn_pe_nlev_summary.hip",
+           "mdpp_discrete_learn_double_pe_nlev_summary.hip", "mdpp_discrete_eval_nlev.hip", "mdpp_discrete_eval_nlev_summary.hip",
            "mdpp_continuous.hip", "mdpp_continuous_line8.hip",
            "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
            "mdpp_generate.hip"]
@@ -30,6 +32,10 @@ INCLUDED_SOURCES = {"mdpp_discrete_wide.hip": ["mdpp_discrete.hip"], "mdpp_discr
                     "mdpp_discrete_learn_summary.hip": ["mdpp_discrete_learn.hip"], "mdpp_discrete_learn_pe_summary.hip": ["mdpp_discrete_learn.hip"],
                     "mdpp_discrete_learn_double_summary.hip": ["mdpp_discrete_learn.hip"],
                     "mdpp_discrete_learn_double_pe_summary.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_learn_pe_nlev.hip": ["mdpp_discrete_learn.hip"], "mdpp_discrete_learn_double_pe_nlev.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_learn_pe_nlev_summary.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_learn_double_pe_nlev_summary.hip": ["mdpp_discrete_learn.hip"],
+                    "mdpp_discrete_eval_nlev.hip": ["mdpp_discrete_eval.hip"], "mdpp_discrete_eval_nlev_summary.hip": ["mdpp_discrete_eval.hip"],
                     "mdpp_discrete_eval_summary.hip": ["mdpp_discrete_eval.hip"]}   # a .hip that #includes another one
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]

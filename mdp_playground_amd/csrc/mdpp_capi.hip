@@ -1,4 +1,5 @@
 // C ABI of libmdpp_hip.so (see include/mdpp.h): handle lifetime, table/stream upload, dispatch.
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -57,7 +58,8 @@ static void free_all(mdpp_env *h) {
                     h->d_img_tpl, h->d_img_tplp, h->d_img_clsx, h->d_img_clsy, h->d_img_rot, h->d_img_state_out,
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
                     h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
-                    h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E};
+                    h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E,
+                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -119,6 +121,8 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_learn_q = h->d_learn_carry = nullptr; h->learn_seed = 0; h->learn_E = 0; h->learn_alpha = h->learn_gamma = 0.0f;
     h->learn_algo = MDPP_LEARN_Q_LEARNING; h->learn_ready = false;
     h->learn_q_tables = 0; h->d_learn_alpha = h->d_learn_gamma = h->d_learn_E = nullptr; h->learn_pe = h->learn_pe_stale = 0;
+    h->nl_on = false; h->nl_levels = 0; h->nl_fill_valid = false; h->nl_fill_alpha = h->nl_fill_gamma = 0.0f; h->nl_fill_E = 0;
+    h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
     h->d_hist_hi = nullptr;
@@ -1196,6 +1200,7 @@ static int step_common(mdpp_env *h, int K, const void *actions, void *obs, float
     if (!actions || !obs || !reward || !term || !trunc) return fail(h, MDPP_EINVAL, "step: null buffer");
     int rc = check_ready(h, "mdpp_step");
     if (rc) return rc;
+    if (h->nl_on) return fail(h, MDPP_ESTATE, "step: per-env noise levels: learner and evaluation launches only; clear_noise_levels() first");
     if (h->line_hist_stale)
         return fail(h, MDPP_EUNSUPPORTED, "step: mdpp_set_state_continuous on a move_along_a_line handle must be followed by mdpp_set_line_history (the window of the line fit)");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1424,6 +1429,7 @@ extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma,
     h->learn_alpha = alpha; h->learn_gamma = gamma; h->learn_seed = seed;
     h->learn_E = (uint32_t)ceil((double)epsilon * 2147483648.0);
     h->learn_pe = h->learn_pe_stale = 0;                         // all three uniform
+    h->nl_fill_valid = false;
     h->learn_ready = true;
     return MDPP_OK;
 }
@@ -1470,6 +1476,7 @@ extern "C" int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const fl
     for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
         if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
     const uint32_t was = h->learn_pe;
+    h->nl_fill_valid = false;
     // (host to device from the caller's pageable memory: the runtime has read the source when the call returns)
     if (alpha) HIPCHK(h, hipMemcpyAsync(h->d_learn_alpha, alpha, N * 4u, hipMemcpyHostToDevice, (hipStream_t)stream));
     if (gamma) HIPCHK(h, hipMemcpyAsync(h->d_learn_gamma, gamma, N * 4u, hipMemcpyHostToDevice, (hipStream_t)stream));
@@ -1483,6 +1490,98 @@ extern "C" int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const fl
     h->learn_pe = was | now;
     // the parameters that stay uniform travel as arrays too: filled on the stream of the next launch
     h->learn_pe_stale = ((was ? h->learn_pe_stale : 7u) & ~now) & ~h->learn_pe;
+    return MDPP_OK;
+}
+
+// ---- per-env noise levels of the learner and evaluation launches (mdpp_discrete_closed.hpp: NLEV) ----
+extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    const std::string why = discrete_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: " + why);
+    const mdpp_config &c = h->cfg;
+    if (transition_noise && !c.has_transition_noise)
+        return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: transition_noise: the handle was created without the key (it needs transition_noise > 0: the space streams and the NOISE kernels)");
+    if (reward_noise && !c.has_reward_noise)
+        return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: reward_noise: the handle was created without the key");
+    const size_t N = (size_t)c.num_envs, S = (size_t)c.S;
+    for (size_t i = 0; i < N; i++) {                             // (NaN fails every comparison)
+        if (transition_noise && !(transition_noise[i] >= 0.0 && transition_noise[i] <= 1.0))
+            return fail(h, MDPP_EINVAL, "mdpp_set_noise_levels: need every transition_noise in [0, 1]");
+        if (reward_noise && !(reward_noise[i] >= 0.0 && reward_noise[i] <= DBL_MAX))
+            return fail(h, MDPP_EINVAL, "mdpp_set_noise_levels: need every reward_noise finite and >= 0");
+    }
+    if (transition_noise && S < 2) return fail(h, MDPP_EINVAL, "mdpp_set_noise_levels: transition_noise needs at least 2 states");
+    if (!transition_noise && !reward_noise) return MDPP_OK;
+    // the values in force after this call: the creation values, what an earlier call set, what this one gives
+    std::vector<double> tn = h->nl_on ? h->nl_tn : std::vector<double>(N, c.has_transition_noise ? c.transition_noise : 0.0);
+    std::vector<double> rn = h->nl_on ? h->nl_rn : std::vector<double>(N, c.has_reward_noise ? c.reward_noise : 0.0);
+    if (transition_noise)
+        for (size_t i = 0; i < N; i++) tn[i] = transition_noise[i] == 0.0 ? 0.0 : transition_noise[i];       // (-0.0 is level 0.0)
+    if (reward_noise) rn.assign(reward_noise, reward_noise + N);
+    // the levels: the distinct transition_noise values in ascending order, one byte per env
+    std::vector<double> levels(tn);
+    std::sort(levels.begin(), levels.end());
+    levels.erase(std::unique(levels.begin(), levels.end()), levels.end());
+    if (levels.size() > (size_t)MDPP_MAX_NOISE_LEVELS)
+        return fail(h, MDPP_EINVAL, "mdpp_set_noise_levels: transition_noise has " + std::to_string(levels.size()) + " distinct values, at most " +
+                                        std::to_string(MDPP_MAX_NOISE_LEVELS) + " levels are served");
+    const size_t nlev = levels.size();
+    std::vector<uint8_t> level(N);
+    for (size_t i = 0; i < N; i++) level[i] = (uint8_t)(std::lower_bound(levels.begin(), levels.end(), tn[i]) - levels.begin());
+    // per level: Philox's (T, M) and the S categoricals' cdfs as DiscreteMDP.noise_cdf() / rl_toy_env.py:1605-1612 form them
+    // (probs = ones * p / (S - 1), probs[n] = 1 - p, cumsum, / last); a level of value 0 has T = 0, M = 0 and no cdf (zeros)
+    std::vector<uint32_t> T(MDPP_MAX_NOISE_LEVELS, 0u);
+    std::vector<uint64_t> M(MDPP_MAX_NOISE_LEVELS, 0ull);
+    std::vector<double> cdf(nlev * S * S, 0.0);
+    for (size_t l = 0; l < nlev; l++) {
+        const double p = levels[l];
+        if (!(p > 0.0)) continue;
+        T[l] = philox_pnoise_threshold(p);
+        M[l] = philox_pnoise_magic(T[l], (uint32_t)S);
+        const double q = 1.0 * p / (double)(S - 1);
+        for (size_t n = 0; n < S; n++) {
+            double *row = &cdf[(l * S + n) * S];
+            double acc = 0.0;
+            for (size_t j = 0; j < S; j++) { acc += (j == n) ? 1.0 - p : q; row[j] = acc; }
+            const double last = row[S - 1];
+            for (size_t j = 0; j < S; j++) row[j] /= last;
+        }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->d_nl_level) HIPCHK(h, hipMalloc(&h->d_nl_level, N));
+    if (!h->d_nl_sigma) HIPCHK(h, hipMalloc(&h->d_nl_sigma, N * sizeof(double)));
+    if (!h->d_nl_T) HIPCHK(h, hipMalloc(&h->d_nl_T, MDPP_MAX_NOISE_LEVELS * sizeof(uint32_t)));
+    if (!h->d_nl_M) HIPCHK(h, hipMalloc(&h->d_nl_M, MDPP_MAX_NOISE_LEVELS * sizeof(uint64_t)));
+    // (the cdfs of the most levels there can be: a later call with more levels replaces no buffer a queued launch reads)
+    if (!h->d_nl_cdf) HIPCHK(h, hipMalloc(&h->d_nl_cdf, (size_t)MDPP_MAX_NOISE_LEVELS * S * S * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->d_nl_level, level.data(), N, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_nl_sigma, rn.data(), N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_nl_T, T.data(), T.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_nl_M, M.data(), M.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_nl_cdf, cdf.data(), cdf.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));                          // (the sources are this call's own: gone at return)
+    h->nl_tn.swap(tn); h->nl_rn.swap(rn);
+    h->nl_levels = (int32_t)nlev;
+    h->nl_on = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_get_noise_levels(mdpp_env *h, double *transition_noise_out, double *reward_noise_out) {
+    if (!h) return MDPP_EINVAL;
+    const mdpp_config &c = h->cfg;
+    if (c.kind != MDPP_KIND_DISCRETE) return fail(h, MDPP_ESTATE, "mdpp_get_noise_levels: discrete handles only");
+    const size_t N = (size_t)c.num_envs;
+    for (size_t i = 0; i < N; i++) {
+        if (transition_noise_out) transition_noise_out[i] = h->nl_on ? h->nl_tn[i] : (c.has_transition_noise ? c.transition_noise : 0.0);
+        if (reward_noise_out) reward_noise_out[i] = h->nl_on ? h->nl_rn[i] : (c.has_reward_noise ? c.reward_noise : 0.0);
+    }
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_noise_levels(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->nl_on = false;            // (the buffers stay: a launch queued earlier may still read them)
     return MDPP_OK;
 }
 

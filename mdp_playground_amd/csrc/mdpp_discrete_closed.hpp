@@ -34,6 +34,16 @@
 //   ret += (double)reward;  len += 1;  terminated or truncated: episodes += 1, return_sum += ret, length_sum += len, ret = len = 0
 // and stores them after finish().  The five output pointers are unused (null).  A compile-time choice: the SUMMARY = false
 // instantiations are the code they were.
+//
+// NLEV = true (per-env noise levels, mdpp_set_noise_levels; with NOISE only): env i has its own reward-noise sigma and its own
+// transition-noise level.  After the `i >= N` return the lane loads its level byte, its sigma and its level's Philox
+// threshold T -- T == 0 is the level "no transition noise" -- and keeps them in registers.  The reward-noise term is
+// 0.0 + sigma z with the draw every lane makes.  D2: Philox streams take the lane's (T, M) -- the pair is loaded once, the
+// level never changes inside a launch; numpy streams search the lane's own [S][S] block of the per-level cdfs and draw from
+// the space stream only where T != 0 (the reference's `if self.transition_noise:`, lane by lane).  The per-level cdfs are
+// staged in LDS behind the MDP's tables (from lds + a.lds_bytes, nl.lds_bytes of them; the agent's LDS moves behind) when
+// the host found room, else read in global memory.  The handle's own cdf (a.noise_cdf / a.lds_noise) is not staged.
+// A compile-time choice like SUMMARY: the NLEV = false instantiations are the code they were.
 #pragma once
 #include "mdpp_internal.hpp"
 #include "mdpp_rng.hpp"
@@ -43,13 +53,26 @@ namespace mdpp {
 constexpr int kClosedRsrcFlags = 0x00020000;
 typedef unsigned int closed_u32x2 __attribute__((ext_vector_type(2)));
 
+// what an NLEV kernel takes besides the handle's DiscreteArgs (mdpp_set_noise_levels; device pointers)
+struct NoiseLevelArgs {
+    const uint8_t *level;       // [N] the env's transition-noise level
+    const double *sigma;        // [N] the env's reward-noise sigma
+    const double *cdf;          // [levels][S][S] the categoricals' cdfs per level (a level of value 0: never read)
+    const uint32_t *T;          // [levels] philox_pnoise_threshold of the level's value (0 <=> the value is 0)
+    const uint64_t *M;          // [levels] philox_pnoise_magic(T, S)
+    uint32_t levels;
+    uint32_t lds_bytes;         // the cdfs are staged in LDS at lds + a.lds_bytes and take this much (16-aligned); 0: global memory
+};
+
 // (a is the kernel's by-value argument, taken by const reference: see tick_now in mdpp_internal.hpp for what a write costs)
-template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, class Agent>
+template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, bool NLEV = false, class Agent>
 __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K, const bool obs64, int32_t *actions,
                                                     void *__restrict__ obs, float *__restrict__ reward,
                                                     uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
                                                     unsigned char *lds, const ZigLds &zig, Agent &agent,
-                                                    const EpisodeSummaryArgs &sm = EpisodeSummaryArgs{}) {
+                                                    const EpisodeSummaryArgs &sm = EpisodeSummaryArgs{},
+                                                    const NoiseLevelArgs &nl = NoiseLevelArgs{}) {
+    static_assert(NOISE || !NLEV, "per-env noise levels are levels of a NOISE kernel");
     const uint64_t ptick0 = tick_now(a);               // the step counter at this launch (through the device-side offset of a graph replay)
     const uint32_t rhead0 = ring_head_now(a, ptick0);  // ... and the head of a delay line kept in memory
     const int tid = threadIdx.x;
@@ -66,9 +89,13 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
         for (uint32_t k = tid; k < a.rbits_stride; k += kBlock) lds[a.lds_rew + k] = a.rbits[k];
     else
         for (uint32_t k = tid; k < a.nkeys; k += kBlock) ((double *)(lds + a.lds_rew))[k] = a.rtable[k];
-    const bool pn_lds = NOISE && a.has_p_noise && a.noise_in_lds;
+    const bool pn_lds = !NLEV && NOISE && a.has_p_noise && a.noise_in_lds;
     if (pn_lds)
         for (int k = tid; k < S * S; k += kBlock) ((double *)(lds + a.lds_noise))[k] = a.noise_cdf[k];
+    if constexpr (NLEV) {
+        if (!PHILOX && a.has_p_noise && nl.lds_bytes != 0u)
+            for (uint32_t k = tid; k < nl.levels * (uint32_t)(S * S); k += kBlock) ((double *)(lds + a.lds_bytes))[k] = nl.cdf[k];
+    }
     agent.stage(tid);
     __syncthreads();
     if (i >= N) return;
@@ -76,6 +103,17 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     const double *const trtable = (const double *)(lds + a.lds_rew), *const tinit = (const double *)(lds + a.lds_init);
     const double *const tnoise = (const double *)(lds + a.lds_noise);
     const uint64_t genv = (uint64_t)(a.env_id_offset + (int64_t)i);
+    // NLEV: this lane's sigma, its level's (T, M) and where its level's cdfs start (in doubles)
+    double lane_sigma = 0.0;
+    uint32_t lane_T = 0u, lane_cdf = 0u;
+    uint64_t lane_M = 0ull;
+    if constexpr (NLEV) {
+        const uint32_t lev = nl.level[i];
+        lane_sigma = nl.sigma[i];
+        lane_T = nl.T[lev];
+        if (PHILOX) lane_M = nl.M[lev];
+        else lane_cdf = lev * (uint32_t)(S * S);
+    }
     agent.begin(i, genv, ptick0);
     double ep_ret = 0.0, ep_return_sum = 0.0;           // SUMMARY: this env's five values
     int32_t ep_len = 0, ep_count = 0, ep_length_sum = 0;
@@ -115,7 +153,9 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     };
     const float rs0 = unit_reward(false, false), rs1 = unit_reward(false, true), rs2 = unit_reward(true, false), rs3 = unit_reward(true, true);
     auto reward_noise = [&](uint64_t ptick) -> double {
-        return 0.0 + a.r_noise * (PHILOX ? (double)rn_z.normal(a.philox_seed, genv, ptick, kPhiloxRNoiseStream) : np_standard_normal_lds(env_pcg, zig));
+        if constexpr (NLEV)
+            return 0.0 + lane_sigma * (PHILOX ? (double)rn_z.normal(a.philox_seed, genv, ptick, kPhiloxRNoiseStream) : np_standard_normal_lds(env_pcg, zig));
+        else return 0.0 + a.r_noise * (PHILOX ? (double)rn_z.normal(a.philox_seed, genv, ptick, kPhiloxRNoiseStream) : np_standard_normal_lds(env_pcg, zig));
     };
 
     const uint32_t total = SUMMARY ? 0u : (uint32_t)K * N;     // (the launcher keeps 8 K N below 2^32; SUMMARY: nothing is stored)
@@ -172,7 +212,16 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
         if (NOISE && a.has_p_noise) {                                               // D2
             // (Philox streams: one word of the tick decides "noisy" and which other state; numpy streams: the state space's own
             //  generator and the categorical's cdf, as in the reference)
-            if (PHILOX) nxt = philox_pnoise_state(pn_w.word(a.philox_seed, genv, ptick, kPhiloxPNoiseStream), a.pn_T, a.pn_M, nxt);
+            if constexpr (NLEV) {
+                if (PHILOX) nxt = philox_pnoise_state(pn_w.word(a.philox_seed, genv, ptick, kPhiloxPNoiseStream), lane_T, lane_M, nxt);
+                else if (lane_T != 0u) {            // (a lane of level 0 makes no draw: its space stream does not move)
+                    const double u = np_random(sp_pcg);
+                    const uint32_t row = lane_cdf + nxt * (uint32_t)S;
+                    if (nl.lds_bytes != 0u) nxt = (uint32_t)searchsorted_right((const double *)(lds + a.lds_bytes) + row, S, u);
+                    else nxt = (uint32_t)searchsorted_right(nl.cdf + row, S, u);
+                }
+            }
+            else if (PHILOX) nxt = philox_pnoise_state(pn_w.word(a.philox_seed, genv, ptick, kPhiloxPNoiseStream), a.pn_T, a.pn_M, nxt);
             else if (pn_lds) nxt = (uint32_t)searchsorted_right(tnoise + (size_t)nxt * S, S, np_random(sp_pcg));
             else nxt = (uint32_t)searchsorted_right(a.noise_cdf + (size_t)nxt * S, S, np_random(sp_pcg));
         }
@@ -282,6 +331,31 @@ inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool
     else if (!a.rew_in_lds || (uint64_t)a.lds_bytes + agent_lds + (noise ? kZigLdsBytes : 0u) > 64u * 1024u)
         return std::string(noun) + " rollouts need " + tables + " within 64 KiB of LDS";
     return why ? std::string(noun) + " rollouts " + why : std::string();
+}
+
+// ---- per-env noise levels (mdpp_set_noise_levels): what a launch of the NLEV kernels needs from the handle
+// the per-level cdfs as LDS bytes (16-aligned)
+inline uint32_t noise_levels_cdf_lds_bytes(const mdpp_env *h) {
+    return ((uint32_t)h->nl_levels * (uint32_t)h->cfg.S * (uint32_t)h->cfg.S * 8u + 15u) & ~15u;
+}
+// Where the agent's tables (q_lds bytes; 0: it keeps none there, or may not) and the per-level cdfs go: both in LDS, then the
+// agent's alone, then the cdfs alone, then neither -- the agent's tables are touched several times a step, a cdf row once.
+// The cdfs are candidates under noise_in_lds's rule (at most 32 KiB; numpy streams with a transition_noise key only: the others
+// read no cdf).  granted(q, bytes): the device grants `bytes` of dynamic LDS to the kernel with (q) / without the agent's tables.
+template <class Granted>
+inline void noise_levels_lds(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &clds) {
+    const DiscreteArgs &a = h->dargs;
+    const size_t cdf = noise_levels_cdf_lds_bytes(h);
+    const bool c_ok = !a.philox && a.has_p_noise && cdf <= 32u * 1024u && !(h->opts & MDPP_OPT_NO_NLEV_LDS);
+    const bool q_ok = q_lds != 0 && !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u;
+    qlds = clds = false;
+    if (q_ok && c_ok && granted(true, (size_t)a.lds_bytes + cdf + q_lds)) qlds = clds = true;
+    else if (q_ok && granted(true, (size_t)a.lds_bytes + q_lds)) qlds = true;
+    else if (c_ok && granted(false, (size_t)a.lds_bytes + cdf)) clds = true;
+}
+inline NoiseLevelArgs noise_level_args(const mdpp_env *h, uint32_t cdf_lds) {
+    return NoiseLevelArgs{(const uint8_t *)h->d_nl_level, (const double *)h->d_nl_sigma, (const double *)h->d_nl_cdf,
+                          (const uint32_t *)h->d_nl_T, (const uint64_t *)h->d_nl_M, (uint32_t)h->nl_levels, cdf_lds};
 }
 
 // K closed-loop steps of kern with lds bytes of dynamic LDS.  name: the kernel's, with its template arguments -- a dry run

@@ -16,8 +16,15 @@
 //
 // k_discrete_eval_summary (mdpp_step_n_eval_summary) is the same agent around the SUMMARY form of the step; its
 // instantiations live in mdpp_discrete_eval_summary.hip (MDPP_EVAL_TU_SUMMARY), which includes this file.
+//
+// Per-env noise levels (mdpp_set_noise_levels): k_discrete_eval_rollout_nlev / k_discrete_eval_summary_nlev are the same agent
+// around the NLEV form of the step (NOISE = 1 always), kernels of their own names in mdpp_discrete_eval_nlev.hip and
+// mdpp_discrete_eval_nlev_summary.hip (MDPP_EVAL_TU_NLEV), which include this file.
 #include "mdpp_discrete_closed.hpp"
 
+#ifndef MDPP_EVAL_TU_NLEV
+#define MDPP_EVAL_TU_NLEV 0        // 1: this translation unit holds the per-env noise-level kernels (of MDPP_EVAL_TU_SUMMARY's form), and nothing else
+#endif
 #ifndef MDPP_EVAL_TU_SUMMARY
 #define MDPP_EVAL_TU_SUMMARY 0     // 1: this translation unit holds k_discrete_eval_summary's instantiations, and nothing else
 #endif
@@ -115,13 +122,82 @@ static int launch_eval_form(mdpp_env *h, const DiscreteIO &io) {
     return rc;
 }
 
+#if MDPP_EVAL_TU_NLEV
+// ... of the per-env noise-level form
+struct EvalArgsNL : EvalArgs {
+    NoiseLevelArgs nl;
+};
+
+template <bool PHILOX, bool UNIT, bool QLDS, bool DOUBLE>
+__global__ __launch_bounds__(kBlock) void k_discrete_eval_rollout_nlev(DiscreteArgs a, EvalArgsNL p, int K, void *__restrict__ obs,
+                                                                       float *__restrict__ reward, uint8_t *__restrict__ term,
+                                                                       uint8_t *__restrict__ trunc) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ uint64_t s_ki[256];                      // numpy's ziggurat tables (kZigLdsBytes)
+    __shared__ double s_wi[256], s_fi[256];
+    zig_stage(s_ki, s_wi, s_fi, threadIdx.x, kBlock);
+    EvalAgent<QLDS, DOUBLE> agent{p, (float *)(lds + a.lds_bytes + p.nl.lds_bytes) + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, true, UNIT, false, true>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, ZigLds{s_ki, s_wi, s_fi}, agent,
+                                                         EpisodeSummaryArgs{}, p.nl);
+}
+
+template <bool PHILOX, bool UNIT, bool QLDS, bool DOUBLE>
+__global__ __launch_bounds__(kBlock) void k_discrete_eval_summary_nlev(DiscreteArgs a, EvalArgsNL p, int K, EpisodeSummaryArgs sm) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ uint64_t s_ki[256];
+    __shared__ double s_wi[256], s_fi[256];
+    zig_stage(s_ki, s_wi, s_fi, threadIdx.x, kBlock);
+    EvalAgent<QLDS, DOUBLE> agent{p, (float *)(lds + a.lds_bytes + p.nl.lds_bytes) + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, true, UNIT, true, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, ZigLds{s_ki, s_wi, s_fi}, agent, sm, p.nl);
+}
+
+template <bool SUMMARY, bool PH, bool UNIT, bool QL, bool DOUBLE>
+static constexpr auto eval_kernel_nlev() {
+    if constexpr (SUMMARY) return k_discrete_eval_summary_nlev<PH, UNIT, QL, DOUBLE>;
+    else return k_discrete_eval_rollout_nlev<PH, UNIT, QL, DOUBLE>;
+}
+
+// K evaluation steps of a handle with per-env noise levels
+template <bool SUMMARY>
+static int launch_eval_form_nlev(mdpp_env *h, const DiscreteIO &io) {
+    const DiscreteArgs &a = h->dargs;
+    const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
+    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (dbl ? 2u : 1u);
+    int rc = MDPP_OK;
+    with_bools([&](auto PH, auto UNIT, auto DB) {
+        bool qlds = false, clds = false;
+        noise_levels_lds(h, q_lds, [&](bool q, size_t bytes) {
+            return q ? dynamic_lds_ok((const void *)eval_kernel_nlev<SUMMARY, PH(), UNIT(), true, DB()>(), bytes)
+                     : dynamic_lds_ok((const void *)eval_kernel_nlev<SUMMARY, PH(), UNIT(), false, DB()>(), bytes);
+        }, qlds, clds);
+        const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
+        with_bools([&](auto QL) {
+            char name[kNameLen];
+            snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=1,UNIT=%d,QLDS=%d,DOUBLE=%d,NLEV=1>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
+                     PH(), UNIT(), QL(), DB());
+            rc = launch_closed_loop(h, io, eval_kernel_nlev<SUMMARY, PH(), UNIT(), QL(), DB()>(), (size_t)a.lds_bytes + cdf_lds + (QL() ? q_lds : 0u),
+                                    qlds || clds, name, [&](int, int, int32_t *actions) {
+                return EvalArgsNL{EvalArgs{(const float *)h->d_learn_q, actions}, noise_level_args(h, cdf_lds)};
+            });
+        }, qlds);
+    }, a.philox != 0, a.unit_rewards != 0, dbl);
+    return rc;
+}
+
 #if MDPP_EVAL_TU_SUMMARY
+int launch_discrete_eval_nlev_summary(mdpp_env *h, const DiscreteIO &io) { return launch_eval_form_nlev<true>(h, io); }
+#else
+int launch_discrete_eval_nlev(mdpp_env *h, const DiscreteIO &io) { return launch_eval_form_nlev<false>(h, io); }
+#endif
+
+#elif MDPP_EVAL_TU_SUMMARY
 int launch_discrete_eval_summary(mdpp_env *h, const DiscreteIO &io) { return launch_eval_form<true>(h, io); }
 #else
 
 int launch_discrete_eval(mdpp_env *h, const DiscreteIO &io) {
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) { h->err = "mdpp_step_n_eval: " + why; return MDPP_EUNSUPPORTED; }
+    if (h->nl_on) return io.summary ? launch_discrete_eval_nlev_summary(h, io) : launch_discrete_eval_nlev(h, io);
     return io.summary ? launch_discrete_eval_summary(h, io) : launch_eval_form<false>(h, io);
 }
 

@@ -42,8 +42,16 @@
 // k_discrete_learn_summary (mdpp_step_n_learn_summary) is the same agent around closed_loop_rollout's SUMMARY form: the same
 // steps, selections and updates, five per-env episode numbers instead of the [K][N] arrays.  Its instantiations live in four
 // further translation units (mdpp_discrete_learn*_summary.hip: MDPP_LEARN_TU_SUMMARY), one per (PE, DOUBLE) pair.
+//
+// Per-env noise levels (mdpp_set_noise_levels): k_discrete_learn_rollout_nlev / k_discrete_learn_summary_nlev are the PE
+// learner around closed_loop_rollout's NLEV form, NOISE = 1 always -- kernels of their own names, so that every kernel above
+// keeps its symbol.  The per-level cdfs, when staged, lie between the MDP's tables and the Q-tables in LDS.  Four more
+// translation units (mdpp_discrete_learn*_pe_nlev*.hip: MDPP_LEARN_TU_NLEV), one per (DOUBLE, SUMMARY) pair.
 #include "mdpp_discrete_closed.hpp"
 
+#ifndef MDPP_LEARN_TU_NLEV
+#define MDPP_LEARN_TU_NLEV 0       // 1: this translation unit holds the per-env noise-level kernels (PE = 1) of its (DOUBLE, SUMMARY) pair, and nothing else
+#endif
 #ifndef MDPP_LEARN_TU_PE
 #define MDPP_LEARN_TU_PE 0         // 1: this translation unit holds the PE = 1 instantiations
 #endif
@@ -281,7 +289,82 @@ static int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
     return rc;
 }
 
-#if MDPP_LEARN_TU_SUMMARY && MDPP_LEARN_TU_PE && MDPP_LEARN_TU_DOUBLE
+#if MDPP_LEARN_TU_NLEV
+// ... of the per-env noise-level form: the PE parameters and the levels
+struct LearnArgsNL : LearnArgsPE {
+    NoiseLevelArgs nl;
+};
+
+template <bool PHILOX, bool UNIT, bool QLDS, bool DOUBLE>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout_nlev(DiscreteArgs a, LearnArgsNL p, int K, void *__restrict__ obs,
+                                                                        float *__restrict__ reward, uint8_t *__restrict__ term,
+                                                                        uint8_t *__restrict__ trunc) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ uint64_t s_ki[256];                      // numpy's ziggurat tables (kZigLdsBytes)
+    __shared__ double s_wi[256], s_fi[256];
+    zig_stage(s_ki, s_wi, s_fi, threadIdx.x, kBlock);
+    LearnAgent<QLDS, true, DOUBLE> agent{p, (float *)(lds + a.lds_bytes + p.nl.lds_bytes) + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, true, UNIT, false, true>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, ZigLds{s_ki, s_wi, s_fi}, agent,
+                                                         EpisodeSummaryArgs{}, p.nl);
+}
+
+template <bool PHILOX, bool UNIT, bool QLDS, bool DOUBLE>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_summary_nlev(DiscreteArgs a, LearnArgsNL p, int K, EpisodeSummaryArgs sm) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    __shared__ uint64_t s_ki[256];
+    __shared__ double s_wi[256], s_fi[256];
+    zig_stage(s_ki, s_wi, s_fi, threadIdx.x, kBlock);
+    LearnAgent<QLDS, true, DOUBLE> agent{p, (float *)(lds + a.lds_bytes + p.nl.lds_bytes) + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, true, UNIT, true, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, ZigLds{s_ki, s_wi, s_fi}, agent, sm, p.nl);
+}
+
+template <bool SUMMARY, bool PH, bool UNIT, bool QL, bool DOUBLE>
+static constexpr auto learn_kernel_nlev() {
+    if constexpr (SUMMARY) return k_discrete_learn_summary_nlev<PH, UNIT, QL, DOUBLE>;
+    else return k_discrete_learn_rollout_nlev<PH, UNIT, QL, DOUBLE>;
+}
+
+// K learning steps of a handle with per-env noise levels
+template <bool DOUBLE, bool SUMMARY>
+static int launch_learn_form_nlev(mdpp_env *h, const DiscreteIO &io) {
+    const DiscreteArgs &a = h->dargs;
+    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (DOUBLE ? 2u : 1u);
+    int rc = MDPP_OK;
+    with_bools([&](auto PH, auto UNIT) {
+        // Q-tables and per-level cdfs in LDS, then the tables alone, then the cdfs alone, then neither
+        bool qlds = false, clds = false;
+        noise_levels_lds(h, q_lds, [&](bool q, size_t bytes) {
+            return q ? dynamic_lds_ok((const void *)learn_kernel_nlev<SUMMARY, PH(), UNIT(), true, DOUBLE>(), bytes)
+                     : dynamic_lds_ok((const void *)learn_kernel_nlev<SUMMARY, PH(), UNIT(), false, DOUBLE>(), bytes);
+        }, qlds, clds);
+        const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
+        with_bools([&](auto QL) {
+            char name[kNameLen];
+            snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=1,UNIT=%d,QLDS=%d,PE=1%s,NLEV=1>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
+                     PH(), UNIT(), QL(), DOUBLE ? ",DOUBLE=1" : "");
+            rc = launch_closed_loop(h, io, learn_kernel_nlev<SUMMARY, PH(), UNIT(), QL(), DOUBLE>(), (size_t)a.lds_bytes + cdf_lds + (QL() ? q_lds : 0u),
+                                    qlds || clds, name, [&](int k0, int kc, int32_t *actions) {
+                const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
+                                     h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
+                return LearnArgsNL{LearnArgsPE{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E},
+                                   noise_level_args(h, cdf_lds)};
+            });
+        }, qlds);
+    }, a.philox != 0, a.unit_rewards != 0);
+    return rc;
+}
+
+#if MDPP_LEARN_TU_SUMMARY && MDPP_LEARN_TU_DOUBLE
+int launch_discrete_learn_double_pe_nlev_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form_nlev<true, true>(h, io); }
+#elif MDPP_LEARN_TU_SUMMARY
+int launch_discrete_learn_pe_nlev_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form_nlev<false, true>(h, io); }
+#elif MDPP_LEARN_TU_DOUBLE
+int launch_discrete_learn_double_pe_nlev(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form_nlev<true, false>(h, io); }
+#else
+int launch_discrete_learn_pe_nlev(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form_nlev<false, false>(h, io); }
+#endif
+
+#elif MDPP_LEARN_TU_SUMMARY && MDPP_LEARN_TU_PE && MDPP_LEARN_TU_DOUBLE
 int launch_discrete_learn_double_pe_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<true, true, true>(h, io); }
 #elif MDPP_LEARN_TU_SUMMARY && MDPP_LEARN_TU_DOUBLE
 int launch_discrete_learn_double_summary(mdpp_env *h, const DiscreteIO &io) { return launch_learn_form<false, true, true>(h, io); }
@@ -334,7 +417,19 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) { h->err = "mdpp_step_n_learn: " + why; return MDPP_EUNSUPPORTED; }
     const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
-    if (!h->learn_pe) {
+    if (h->nl_on && !h->learn_pe) {
+        // per-env noise levels run the PE form: while all three parameters are uniform their arrays are filled here, and
+        // again when a value has changed since (the scalar setters do not mark them while nothing is per-env)
+        const bool fresh = h->nl_fill_valid && h->nl_fill_alpha == h->learn_alpha && h->nl_fill_gamma == h->learn_gamma && h->nl_fill_E == h->learn_E;
+        if (!fresh && !io.name_out) {
+            for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
+                if (!*d && hipMalloc(d, (size_t)h->cfg.num_envs * 4u) != hipSuccess) { h->err = "mdpp_step_n_learn: hipMalloc of the per-env parameter arrays failed"; return MDPP_EHIP; }
+            h->learn_pe_stale = 7u;
+        }
+    } else {
+        h->nl_fill_valid = false;
+    }
+    if (!h->learn_pe && !h->nl_on) {
         if (io.summary) return dbl ? launch_discrete_learn_double_summary(h, io) : launch_discrete_learn_summary(h, io);
         return dbl ? launch_discrete_learn_double(h, io) : launch_learn_form<false, false>(h, io);
     }
@@ -350,6 +445,11 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { h->err = std::string("k_learn_fill launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
         h->learn_pe_stale = 0;
+        if (!h->learn_pe) { h->nl_fill_valid = true; h->nl_fill_alpha = h->learn_alpha; h->nl_fill_gamma = h->learn_gamma; h->nl_fill_E = h->learn_E; }
+    }
+    if (h->nl_on) {
+        if (io.summary) return dbl ? launch_discrete_learn_double_pe_nlev_summary(h, io) : launch_discrete_learn_pe_nlev_summary(h, io);
+        return dbl ? launch_discrete_learn_double_pe_nlev(h, io) : launch_discrete_learn_pe_nlev(h, io);
     }
     if (io.summary) return dbl ? launch_discrete_learn_double_pe_summary(h, io) : launch_discrete_learn_pe_summary(h, io);
     return dbl ? launch_discrete_learn_double_pe(h, io) : launch_discrete_learn_pe(h, io);

@@ -7,6 +7,7 @@
 
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/mdpp.h"
 
@@ -337,6 +338,17 @@ struct mdpp_env {
     int32_t learn_q_tables;
     void *d_learn_alpha, *d_learn_gamma, *d_learn_E;
     uint32_t learn_pe, learn_pe_stale;
+    // Per-env noise levels (mdpp_set_noise_levels; mdpp_discrete_closed.hpp NoiseLevelArgs): nl_on: the learner and evaluation
+    // launches take their NLEV form and every other step launch is refused.  Device: the level byte and the sigma of every
+    // env, the per-level cdfs [levels][S][S] and (T, M) pairs; host: the values in force, for mdpp_get_noise_levels.
+    // nl_fill_*: the uniform alpha / gamma / E the learner's per-env arrays were last filled with for an NLEV launch.
+    bool nl_on;
+    int32_t nl_levels;
+    void *d_nl_level, *d_nl_sigma, *d_nl_cdf, *d_nl_T, *d_nl_M;
+    std::vector<double> nl_tn, nl_rn;
+    bool nl_fill_valid;
+    float nl_fill_alpha, nl_fill_gamma;
+    uint32_t nl_fill_E;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -554,6 +566,15 @@ int launch_discrete_learn_summary(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_learn_pe_summary(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_learn_double_summary(mdpp_env *h, const DiscreteIO &io);
 int launch_discrete_learn_double_pe_summary(mdpp_env *h, const DiscreteIO &io);
+// ... and the forms of a handle with per-env noise levels (mdpp_set_noise_levels): the PE learner and the evaluation around
+// the NLEV step, one translation unit each (mdpp_discrete_learn_pe_nlev.hip, ..._double_pe_nlev.hip, their _summary twins,
+// mdpp_discrete_eval_nlev.hip, mdpp_discrete_eval_nlev_summary.hip)
+int launch_discrete_learn_pe_nlev(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_double_pe_nlev(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_pe_nlev_summary(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_learn_double_pe_nlev_summary(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_eval_nlev(mdpp_env *h, const DiscreteIO &io);
+int launch_discrete_eval_nlev_summary(mdpp_env *h, const DiscreteIO &io);
 // io.K steps of greedy evaluation of the learner's tables (mdpp_discrete_eval.hip; with io.summary:
 // mdpp_discrete_eval_summary.hip, to which launch_discrete_eval hands over)
 int launch_discrete_eval(mdpp_env *h, const DiscreteIO &io);

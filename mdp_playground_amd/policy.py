@@ -16,12 +16,19 @@ integer the kernel compares the explore word with, explore_action is its rule fo
 check_learner_params is the validation set_learner applies.  alpha, gamma and epsilon are each a Python scalar (uniform over
 the handle) or a 1-D array with one float32 per env (numpy, or a torch tensor on any device): learner_param_array tells the
 two apart and validates the array.
+
+Per-env noise levels (set_noise_levels) are validated and reduced here as the library does it: noise_level_array makes the
+float64 [N] array of one key, noise_levels_reduce the distinct transition levels and each env's level byte,
+noise_level_thresholds the Philox (T, M) pair of every level, noise_level_cdfs the [levels, S, S] table of the
+categoricals' cdfs.
 """
 import numpy as np
 
-__all__ = ["policy_thresholds", "epsilon_threshold", "explore_action", "check_learner_params", "learner_param_array", "LEARN_ALGOS"]
+__all__ = ["policy_thresholds", "epsilon_threshold", "explore_action", "check_learner_params", "learner_param_array", "LEARN_ALGOS",
+           "noise_level_array", "noise_levels_reduce", "noise_level_thresholds", "noise_level_cdfs", "MAX_NOISE_LEVELS"]
 
 LEARN_ALGOS = ("q_learning", "sarsa", "double_q")
+MAX_NOISE_LEVELS = 16        # distinct transition_noise values one handle serves at a time (MDPP_MAX_NOISE_LEVELS)
 
 
 def _to_numpy(policy):
@@ -122,3 +129,75 @@ def check_learner_params(algo, alpha, gamma, epsilon, num_envs=None):
     for name, v in (("gamma", gamma), ("epsilon", epsilon)):
         if v is not None and not 0.0 <= float(np.float32(v)) <= 1.0:
             raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
+
+
+def noise_level_array(name, v, num_envs):
+    """The per-env levels of one noise key, ``name`` "transition_noise" or "reward_noise": None for None; otherwise a float64
+    numpy [num_envs] -- a scalar is broadcast, an array (numpy, or a torch tensor on any device) must be 1-D with num_envs
+    entries.  transition_noise lies in [0, 1] (-0.0 becomes 0.0) with at most MAX_NOISE_LEVELS distinct values, reward_noise is
+    finite and >= 0; NaN fails.  ValueError, naming the key, otherwise."""
+    if name not in ("transition_noise", "reward_noise"):
+        raise ValueError(f"unknown noise key {name!r}")
+    if v is None:
+        return None
+    n = int(num_envs)
+    if _is_array(v):
+        a = _to_numpy(v)
+        if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+            raise ValueError(f"{name} must be a number or a 1-D array of numbers, got dtype {a.dtype}")
+        if a.ndim != 1:
+            raise ValueError(f"per-env {name} must be 1-D, got shape {a.shape}")
+        if a.shape[0] != n:
+            raise ValueError(f"per-env {name} must have num_envs = {n} entries, got {a.shape[0]}")
+        a = np.array(a, dtype=np.float64)
+    else:
+        a = np.full(n, float(v), dtype=np.float64)
+    ok = (a >= 0.0) & (a <= 1.0) if name == "transition_noise" else (a >= 0.0) & np.isfinite(a)      # (NaN fails both)
+    if not np.all(ok):
+        bad = int(np.argmin(ok))
+        raise ValueError(f"{name} must {'lie in [0, 1]' if name == 'transition_noise' else 'be finite and >= 0'}, got {a[bad]!r} at env {bad}")
+    if name == "transition_noise":
+        a[a == 0.0] = 0.0
+        k = len(np.unique(a))
+        if k > MAX_NOISE_LEVELS:
+            raise ValueError(f"transition_noise has {k} distinct values, at most {MAX_NOISE_LEVELS} levels are served")
+    return a
+
+
+def noise_levels_reduce(transition_noise):
+    """(levels, index): the distinct values of a float64 [N] transition_noise array in ascending order, and each env's level
+    as a uint8 index into them.  More than MAX_NOISE_LEVELS levels: ValueError."""
+    a = np.asarray(transition_noise, dtype=np.float64)
+    levels, index = np.unique(a, return_inverse=True)
+    if len(levels) > MAX_NOISE_LEVELS:
+        raise ValueError(f"transition_noise has {len(levels)} distinct values, at most {MAX_NOISE_LEVELS} levels are served")
+    return levels, index.reshape(a.shape).astype(np.uint8)
+
+
+def noise_level_thresholds(levels, S):
+    """(T uint32 [levels], M uint64 [levels]) of Philox streams: T = ceil(p 2^32) capped at 2^32 - 1, M = ceil(2^64 (S - 1) / T),
+    0 when S < 2 or T <= S - 1 (the library's philox_pnoise_threshold / philox_pnoise_magic).  p == 0: T = M = 0, no noise."""
+    T, M = [], []
+    for p in np.asarray(levels, dtype=np.float64):
+        t = min(int(np.ceil(p * 4294967296.0)), 4294967295) if p > 0.0 else 0
+        T.append(t)
+        M.append(0 if (S < 2 or t <= S - 1) else -((-(int(S - 1) << 64)) // t))
+    return np.asarray(T, dtype=np.uint32), np.asarray(M, dtype=np.uint64)
+
+
+def noise_level_cdfs(levels, S):
+    """float64 [levels, S, S]: row n of block l is the normalised cdf numpy's Generator.choice builds for the transition-noise
+    categorical with mode n at p = levels[l] (DiscreteMDP.noise_cdf; rl_toy_env.py:1605-1612).  A level of value 0 is never
+    read (the env makes no draw): zeros."""
+    levels = np.asarray(levels, dtype=np.float64)
+    out = np.zeros((len(levels), S, S), dtype=np.float64)
+    for l, p in enumerate(levels):
+        if not p > 0.0:
+            continue
+        for n in range(S):
+            probs = np.ones(shape=(S,)) * p / (S - 1)
+            probs[n] = 1 - p
+            cdf = probs.cumsum()
+            cdf /= cdf[-1]
+            out[l, n] = cdf
+    return out

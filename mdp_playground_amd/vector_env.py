@@ -91,6 +91,7 @@ class RLToyVectorEnv:
         self.config = copy.deepcopy(config)   # the reference mutates its config (:339,...); we do not
         self._gen = None                      # mdp.device_gen_params when the per-env tables are generated on the device
         self._learn_rates = None              # [alpha, epsilon] of the learner (set_learner); None: no learner
+        self._noise_levels_set = False        # set_noise_levels is in force
         self._learn_q_init = None             # the tensor last handed to set_learner / set_q, kept until its copy has been made
         self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
@@ -579,6 +580,7 @@ class RLToyVectorEnv:
         the launches are captured in the library's capture mode instead: they add a device word to the counter, which
         replay() sets to (counter now - counter at capture) right before the graph (mdpp_graph_capture /
         mdpp_graph_set_tick_offset, round 4; image handles too since round 5)."""
+        self._noise_levels_refuse()
         K = int(actions.shape[0])
         ok = self._lib.mdpp_graph_replay_exact(self._h, K)
         if ok < 0:
@@ -638,6 +640,7 @@ class RLToyVectorEnv:
         """K fused steps in ONE kernel launch (per-env state stays in registers).
         actions: [K, N] int32 or [K, N, D] float32, time-major.  Returns (obs, reward, terminated,
         truncated) with a leading K axis; equivalent to K step() calls."""
+        self._noise_levels_refuse()
         K = int(actions.shape[0])
         a = self._as_actions(actions, K)
         if out is None:
@@ -858,8 +861,8 @@ class RLToyVectorEnv:
 
     def eval_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_eval(K) launches (mdpp_eval_kernel_name; nothing is launched;
-        QLDS=1: the Q-tables are staged in LDS; DOUBLE=1: two tables per env); empty for a handle it does not serve or one
-        without a learner."""
+        QLDS=1: the Q-tables are staged in LDS; DOUBLE=1: two tables per env; NLEV=1: per-env noise levels); empty for a handle
+        it does not serve or one without a learner."""
         if self.kind != "discrete":
             return ""
         name = self._lib.mdpp_eval_kernel_name(self._h, int(K))
@@ -882,12 +885,63 @@ class RLToyVectorEnv:
 
     def learn_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
-        launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning); empty for a
-        handle it does not serve."""
+        launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning; NLEV=1: per-env
+        noise levels, set_noise_levels); empty for a handle it does not serve."""
         if self.kind != "discrete":
             return ""
         name = self._lib.mdpp_learn_kernel_name(self._h, int(K))
         return name.decode() if name else ""
+
+    # ------------------------------------------------------------------ per-env noise levels
+    _NOISE_LEVELS_ONLY = "per-env noise levels: learner and evaluation launches only; clear_noise_levels() first"
+
+    def _noise_levels_refuse(self):
+        if self._noise_levels_set:
+            raise capi.MdppError(self._NOISE_LEVELS_ONLY)
+
+    def set_noise_levels(self, transition_noise=None, reward_noise=None):
+        """Per-env noise levels for rollout_learn / rollout_eval (and their summary= forms): env i of THIS handle (its local
+        index, like the per-env learner parameters: a sharded run gives each shard its slice) steps with
+        ``transition_noise[i]`` in [0, 1] -- at most 16 distinct values per handle -- and ``reward_noise[i]`` finite and >= 0,
+        bit for bit like env i of a handle created with those two values.  Each argument is None (that key stays as it is), a
+        scalar (broadcast) or a 1-D array of num_envs entries (numpy, or a torch tensor on any device; converted to float64).
+        The handle must be one set_learner serves and must have been created with the key: ``reward_noise`` present in the
+        config (any value), ``transition_noise`` > 0.  A noise sweep then runs as ONE launch.  ValueError for a
+        bad array or a key the handle lacks, before any device work.  While levels are set step(), rollout() and step_graph()
+        raise; reset() is unaffected.  Levels are configuration, not state: get_augmented_state / set_augmented_state and
+        checkpoints neither carry nor disturb them -- set them again on a restored handle."""
+        arrays = {}
+        for key, v in (("transition_noise", transition_noise), ("reward_noise", reward_noise)):
+            arrays[key] = policy_mod.noise_level_array(key, v, self.num_envs)
+        self._learn_check_kind()
+        for key, a in arrays.items():
+            if a is None:
+                continue
+            created = self.config.get(key)
+            if created is None or (key == "transition_noise" and not created):
+                raise ValueError("set_noise_levels: %s: the handle was created without the key%s" %
+                                 (key, " (it needs transition_noise > 0)" if key == "transition_noise" else ""))
+        if all(a is None for a in arrays.values()):
+            return
+        rc = self._lib.mdpp_set_noise_levels(self._h, capi.nptr(arrays["transition_noise"]), capi.nptr(arrays["reward_noise"]), self._stream())
+        if rc == -4:                         # MDPP_ESTATE: a handle the learner kernels do not serve
+            msg = self._lib.mdpp_last_error(self._h)
+            raise NotImplementedError(msg.decode() if msg else "mdpp_set_noise_levels: unsupported")
+        capi.check(self._lib, self._h, rc, "mdpp_set_noise_levels")
+        self._noise_levels_set = True
+
+    def noise_levels(self):
+        """(transition_noise, reward_noise) in force, float64 numpy [N] each: what set_noise_levels gave, else the creation
+        values (0 for a key the config does not have)."""
+        self._learn_check_kind()
+        tn, rn = np.empty(self.num_envs, np.float64), np.empty(self.num_envs, np.float64)
+        capi.check(self._lib, self._h, self._lib.mdpp_get_noise_levels(self._h, capi.nptr(tn), capi.nptr(rn)), "mdpp_get_noise_levels")
+        return tn, rn
+
+    def clear_noise_levels(self):
+        """Back to the creation values of both keys: the handle launches the kernels it launched before set_noise_levels."""
+        capi.check(self._lib, self._h, self._lib.mdpp_clear_noise_levels(self._h), "mdpp_clear_noise_levels")
+        self._noise_levels_set = False
 
     def rollout_kernel_name(self, K):
         """Name (with template arguments) of the kernel mdpp_step_n(K) launches for this handle, as
