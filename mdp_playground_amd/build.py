@@ -26,17 +26,10 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
 HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdpp_pcg64_limbs.inc", "np_ziggurat_tables.inc",
            os.path.join("..", "..", "include", "mdpp.h")]
 INCLUDED_SOURCES = {"mdpp_discrete_wide.hip": ["mdpp_discrete.hip"], "mdpp_discrete_long.hip": ["mdpp_discrete.hip"], "mdpp_discrete_lean_next.hip": ["mdpp_discrete_lean.hip"], "mdpp_discrete_lean_noise.hip": ["mdpp_discrete_lean.hip"], "mdpp_discrete_lean_npnoise.hip": ["mdpp_discrete_lean.hip"],
-                    "mdpp_continuous_line8.hip": ["mdpp_continuous.hip"], "mdpp_continuous_step1.hip": ["mdpp_continuous_fast.hip"], "mdpp_discrete_quiet_nu.hip": ["mdpp_discrete_quiet.hip"],
-                    "mdpp_discrete_learn_pe.hip": ["mdpp_discrete_learn.hip"], "mdpp_discrete_learn_double.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_double_pe.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_summary.hip": ["mdpp_discrete_learn.hip"], "mdpp_discrete_learn_pe_summary.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_double_summary.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_double_pe_summary.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_pe_nlev.hip": ["mdpp_discrete_learn.hip"], "mdpp_discrete_learn_double_pe_nlev.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_pe_nlev_summary.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_learn_double_pe_nlev_summary.hip": ["mdpp_discrete_learn.hip"],
-                    "mdpp_discrete_eval_nlev.hip": ["mdpp_discrete_eval.hip"], "mdpp_discrete_eval_nlev_summary.hip": ["mdpp_discrete_eval.hip"],
-                    "mdpp_discrete_eval_summary.hip": ["mdpp_discrete_eval.hip"]}   # a .hip that #includes another one
+                    "mdpp_continuous_line8.hip": ["mdpp_continuous.hip"], "mdpp_continuous_step1.hip": ["mdpp_continuous_fast.hip"], "mdpp_discrete_quiet_nu.hip": ["mdpp_discrete_quiet.hip"],   # a .hip that #includes another one
+                    # ... or a header of its own
+                    **{u: ["mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith("mdpp_discrete_learn")},
+                    **{u: ["mdpp_discrete_eval.hpp"] for u in SOURCES if u.startswith("mdpp_discrete_eval")}}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # The GENERAL kernels keep whole state vectors in registers and spill (k_continuous_step<DMAX=32, OMAX=4>: 3 KB of scratch per lane).
@@ -96,7 +89,7 @@ def build(force=False, verbose=False):
         src = os.path.join(CSRC, s)
         obj = os.path.join(CSRC, s.replace(".hip", ".o"))
         objs.append(obj)
-        extra = [os.path.join(CSRC, d) for d in INCLUDED_SOURCES.get(s, [])]
+        extra = [os.path.join(CSRC, d) for d in INCLUDED_SOURCES.get(s, []) if os.path.exists(os.path.join(CSRC, d))]   # (like srcs: a missing one is hipcc's to report)
         cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(s, []) + ["-c", src, "-o", obj]
         if force or _stale(obj, [src] + extra + hdrs, cmd):
             jobs.append(cmd)

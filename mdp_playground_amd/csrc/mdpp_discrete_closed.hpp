@@ -64,6 +64,15 @@ struct NoiseLevelArgs {
     uint32_t lds_bytes;         // the cdfs are staged in LDS at lds + a.lds_bytes and take this much (16-aligned); 0: global memory
 };
 
+// A NOISE kernel's static LDS (kZigLdsBytes): numpy's ziggurat tables, staged by the workgroup; the step's barrier covers them
+template <bool NOISE>
+__device__ __forceinline__ ZigLds closed_loop_zig_lds() {
+    __shared__ uint64_t s_ki[NOISE ? 256 : 1];
+    __shared__ double s_wi[NOISE ? 256 : 1], s_fi[NOISE ? 256 : 1];
+    if (NOISE) zig_stage(s_ki, s_wi, s_fi, threadIdx.x, kBlock);
+    return ZigLds{s_ki, s_wi, s_fi};
+}
+
 // (a is the kernel's by-value argument, taken by const reference: see tick_now in mdpp_internal.hpp for what a write costs)
 template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, bool NLEV = false, class Agent>
 __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K, const bool obs64, int32_t *actions,
@@ -338,15 +347,16 @@ inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool
 inline uint32_t noise_levels_cdf_lds_bytes(const mdpp_env *h) {
     return ((uint32_t)h->nl_levels * (uint32_t)h->cfg.S * (uint32_t)h->cfg.S * 8u + 15u) & ~15u;
 }
-// Where the agent's tables (q_lds bytes; 0: it keeps none there, or may not) and the per-level cdfs go: both in LDS, then the
-// agent's alone, then the cdfs alone, then neither -- the agent's tables are touched several times a step, a cdf row once.
+// The closed-loop agents' LDS placement: where the agent's tables (q_lds bytes; 0: it keeps none there, or may not) and, on a
+// handle with per-env noise levels, the per-level cdfs go: both in LDS, then the agent's alone, then the cdfs alone, then
+// neither -- the agent's tables are touched several times a step, a cdf row once.  Without levels the rule is its second line.
 // The cdfs are candidates under noise_in_lds's rule (at most 32 KiB; numpy streams with a transition_noise key only: the others
 // read no cdf).  granted(q, bytes): the device grants `bytes` of dynamic LDS to the kernel with (q) / without the agent's tables.
 template <class Granted>
-inline void noise_levels_lds(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &clds) {
+inline void closed_agent_lds(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &clds) {
     const DiscreteArgs &a = h->dargs;
     const size_t cdf = noise_levels_cdf_lds_bytes(h);
-    const bool c_ok = !a.philox && a.has_p_noise && cdf <= 32u * 1024u && !(h->opts & MDPP_OPT_NO_NLEV_LDS);
+    const bool c_ok = h->nl_on && !a.philox && a.has_p_noise && cdf <= 32u * 1024u && !(h->opts & MDPP_OPT_NO_NLEV_LDS);
     const bool q_ok = q_lds != 0 && !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u;
     qlds = clds = false;
     if (q_ok && c_ok && granted(true, (size_t)a.lds_bytes + cdf + q_lds)) qlds = clds = true;
@@ -361,16 +371,16 @@ inline NoiseLevelArgs noise_level_args(const mdpp_env *h, uint32_t cdf_lds) {
 // K closed-loop steps of kern with lds bytes of dynamic LDS.  name: the kernel's, with its template arguments -- a dry run
 // (io.name_out) writes it and launches nothing.  agent_args(k0, kc, actions) makes the kernel's second argument for the
 // launch of steps [k0, k0 + kc), whose actions go to `actions`.  lds_granted: the caller has asked dynamic_lds_ok for this
-// kernel and size already.  io.summary: kern is a SUMMARY kernel, taking (args, agent args, K, summary) -- it addresses no
+// kernel and size already.  SUMMARY: kern is a SUMMARY kernel, taking (args, agent args, K, *io.summary) -- it addresses no
 // [K][N] array, so the call is one launch (MDPP_OPT_LEARN_SHORT_PIECES still cuts it).
-template <class Kern, class AgentArgs>
+template <bool SUMMARY, class Kern, class AgentArgs>
 inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size_t lds, bool lds_granted, const char *name,
                               AgentArgs &&agent_args) {
     const std::string kernel(name, strcspn(name, "<"));
     DiscreteArgs a = h->dargs;
     stamp_step(a, h);
     // pieces: the buffer descriptors address < 4 GiB per output array (8 bytes per env-step at most)
-    long long kmax = io.summary ? (long long)INT32_MAX : ((1LL << 32) - 1) / (8LL * a.N);
+    long long kmax = SUMMARY ? (long long)INT32_MAX : ((1LL << 32) - 1) / (8LL * a.N);
     if (kmax < 1) { h->err = kernel + ": num_envs too large"; return MDPP_EUNSUPPORTED; }
     if ((a.opts & MDPP_OPT_LEARN_SHORT_PIECES) && kmax > 5) kmax = 5;      // (tests: the pieces' hand-over at a small size)
     if (io.name_out) { snprintf(io.name_out, kNameLen, "%s", name); return MDPP_OK; }
@@ -379,7 +389,7 @@ inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size
     // (io.actions, an input of every other launcher, is this one's OUTPUT: the caller's buffer for the actions taken; piece_of
     //  offsets it like the other arrays -- these handles have no irrelevant sub-space -- and the const comes off at the launch)
     for_each_piece(a, h, io, kmax, [&](const DiscreteIO &p, int k0) {
-        if constexpr (std::is_invocable_v<Kern, DiscreteArgs, decltype(agent_args(0, 0, nullptr)), int, EpisodeSummaryArgs>)
+        if constexpr (SUMMARY)
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, io.s, a, agent_args(k0, p.K, nullptr), p.K, *io.summary);
         else
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, io.s, a, agent_args(k0, p.K, const_cast<int32_t *>(p.actions)), p.K,

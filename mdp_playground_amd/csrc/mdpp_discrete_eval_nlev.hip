@@ -1,4 +1,5 @@
-// The per-env noise-level (NLEV = 1; mdpp_set_noise_levels) instantiations of k_discrete_eval_rollout_nlev (see mdpp_discrete_eval.hip): greedy evaluation,
+// The evaluation form <SUMMARY = 0, NLEV = 1> (mdpp_discrete_eval.hpp): greedy evaluation on a handle with per-env noise levels --
 // in a translation unit of its own so that the forms compile in parallel.
-#define MDPP_EVAL_TU_NLEV 1
-#include "mdpp_discrete_eval.hip"
+#include "mdpp_discrete_eval.hpp"
+
+template int mdpp::launch_eval_form<false, true>(mdpp_env *, const mdpp::DiscreteIO &);

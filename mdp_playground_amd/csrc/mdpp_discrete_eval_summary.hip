@@ -1,4 +1,5 @@
-// The instantiations of k_discrete_eval_summary (see mdpp_discrete_eval.hip): greedy evaluation that keeps episode summaries
-// instead of writing [K][N] arrays, in a translation unit of its own so that the two forms compile in parallel.
-#define MDPP_EVAL_TU_SUMMARY 1
-#include "mdpp_discrete_eval.hip"
+// The evaluation form <SUMMARY = 1, NLEV = 0> (mdpp_discrete_eval.hpp): greedy evaluation keeping episode summaries --
+// in a translation unit of its own so that the forms compile in parallel.
+#include "mdpp_discrete_eval.hpp"
+
+template int mdpp::launch_eval_form<true, false>(mdpp_env *, const mdpp::DiscreteIO &);

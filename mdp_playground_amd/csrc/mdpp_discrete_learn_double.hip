@@ -1,4 +1,5 @@
-// The double Q-learning (DOUBLE = 1) instantiations of k_discrete_learn_rollout (see mdpp_discrete_learn.hip), in
-// their own translation unit so that the learner's forms compile in parallel.
-#define MDPP_LEARN_TU_DOUBLE 1
-#include "mdpp_discrete_learn.hip"
+// The learner form <PE = 0, DOUBLE = 1, SUMMARY = 0, NLEV = 0> (mdpp_discrete_learn.hpp): double Q-learning --
+// in a translation unit of its own so that the forms compile in parallel.
+#include "mdpp_discrete_learn.hpp"
+
+template int mdpp::launch_learn_form<false, true, false, false>(mdpp_env *, const mdpp::DiscreteIO &);

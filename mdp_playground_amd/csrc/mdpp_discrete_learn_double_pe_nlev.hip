@@ -1,6 +1,5 @@
-// The per-env noise-level (NLEV = 1; mdpp_set_noise_levels) instantiations of k_discrete_learn_rollout_nlev (see mdpp_discrete_learn.hip): double Q-learning with per-env hyper-parameters (PE = 1, DOUBLE = 1),
+// The learner form <PE = 1, DOUBLE = 1, SUMMARY = 0, NLEV = 1> (mdpp_discrete_learn.hpp): double Q-learning with per-env hyper-parameters on a handle with per-env noise levels --
 // in a translation unit of its own so that the forms compile in parallel.
-#define MDPP_LEARN_TU_NLEV 1
-#define MDPP_LEARN_TU_PE 1
-#define MDPP_LEARN_TU_DOUBLE 1
-#include "mdpp_discrete_learn.hip"
+#include "mdpp_discrete_learn.hpp"
+
+template int mdpp::launch_learn_form<true, true, false, true>(mdpp_env *, const mdpp::DiscreteIO &);

@@ -1,5 +1,5 @@
-// The double Q-learning (DOUBLE = 1) instantiations of k_discrete_learn_summary (see mdpp_discrete_learn.hip): the learner that keeps episode
-// summaries instead of writing [K][N] arrays, in a translation unit of its own so that the learner's forms compile in parallel.
-#define MDPP_LEARN_TU_SUMMARY 1
-#define MDPP_LEARN_TU_DOUBLE 1
-#include "mdpp_discrete_learn.hip"
+// The learner form <PE = 0, DOUBLE = 1, SUMMARY = 1, NLEV = 0> (mdpp_discrete_learn.hpp): double Q-learning, keeping episode summaries --
+// in a translation unit of its own so that the forms compile in parallel.
+#include "mdpp_discrete_learn.hpp"
+
+template int mdpp::launch_learn_form<false, true, true, false>(mdpp_env *, const mdpp::DiscreteIO &);

@@ -1,6 +1,5 @@
-// The per-env noise-level (NLEV = 1; mdpp_set_noise_levels) instantiations of k_discrete_learn_summary_nlev (see mdpp_discrete_learn.hip): Q-learning and SARSA with per-env hyper-parameters (PE = 1), keeping episode summaries,
+// The learner form <PE = 1, DOUBLE = 0, SUMMARY = 1, NLEV = 1> (mdpp_discrete_learn.hpp): Q-learning and SARSA with per-env hyper-parameters on a handle with per-env noise levels, keeping episode summaries --
 // in a translation unit of its own so that the forms compile in parallel.
-#define MDPP_LEARN_TU_NLEV 1
-#define MDPP_LEARN_TU_SUMMARY 1
-#define MDPP_LEARN_TU_PE 1
-#include "mdpp_discrete_learn.hip"
+#include "mdpp_discrete_learn.hpp"
+
+template int mdpp::launch_learn_form<true, false, true, true>(mdpp_env *, const mdpp::DiscreteIO &);

@@ -97,7 +97,7 @@ int launch_discrete_policy(mdpp_env *h, const DiscreteIO &io) {
     with_bools([&](auto PH, auto UNIT, auto O64, auto A8) {
         char name[kNameLen];
         snprintf(name, kNameLen, "k_discrete_policy_rollout<PHILOX=%d,UNIT=%d,OBS64=%d,A8=%d>", PH(), UNIT(), O64(), A8());
-        rc = launch_closed_loop(h, io, k_discrete_policy_rollout<PH(), UNIT(), O64(), A8()>,
+        rc = launch_closed_loop<false>(h, io, k_discrete_policy_rollout<PH(), UNIT(), O64(), A8()>,
                                 (size_t)a.lds_bytes + 4u * (size_t)a.S * policy_row_words(a.A), false, name, [&](int, int, int32_t *actions) {
             return PolicyArgs{(const uint32_t *)h->d_policy_thr, h->policy_seed, actions};
         });

@@ -555,30 +555,12 @@ int launch_discrete_policy(mdpp_env *h, const DiscreteIO &io);
 std::string discrete_learn_refusal(const mdpp_env *h);
 int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io);
 int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t s);
-// the PE and DOUBLE forms of the learner kernel (mdpp_discrete_learn_pe.hip, mdpp_discrete_learn_double.hip,
-// mdpp_discrete_learn_double_pe.hip: one translation unit each); launch_discrete_learn hands over to them
-int launch_discrete_learn_pe(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_double(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_double_pe(mdpp_env *h, const DiscreteIO &io);
-// ... their forms that keep episode summaries (io.summary) instead of writing [K][N] arrays, one translation unit each too
-// (mdpp_discrete_learn_summary.hip, ..._pe_summary.hip, ..._double_summary.hip, ..._double_pe_summary.hip)
-int launch_discrete_learn_summary(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_pe_summary(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_double_summary(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_double_pe_summary(mdpp_env *h, const DiscreteIO &io);
-// ... and the forms of a handle with per-env noise levels (mdpp_set_noise_levels): the PE learner and the evaluation around
-// the NLEV step, one translation unit each (mdpp_discrete_learn_pe_nlev.hip, ..._double_pe_nlev.hip, their _summary twins,
-// mdpp_discrete_eval_nlev.hip, mdpp_discrete_eval_nlev_summary.hip)
-int launch_discrete_learn_pe_nlev(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_double_pe_nlev(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_pe_nlev_summary(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_learn_double_pe_nlev_summary(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_eval_nlev(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_eval_nlev_summary(mdpp_env *h, const DiscreteIO &io);
-// io.K steps of greedy evaluation of the learner's tables (mdpp_discrete_eval.hip; with io.summary:
-// mdpp_discrete_eval_summary.hip, to which launch_discrete_eval hands over)
+// (the learner's forms -- per-env hyper-parameters, double Q-learning, episode summaries with io.summary, per-env noise
+// levels -- are instantiations of mdpp_discrete_learn.hpp's launch_learn_form, one translation unit each
+// (mdpp_discrete_learn_*.hip); launch_discrete_learn picks the handle's)
+// io.K steps of greedy evaluation of the learner's tables (mdpp_discrete_eval.hip; the forms with io.summary or per-env noise
+// levels: mdpp_discrete_eval.hpp's launch_eval_form, in mdpp_discrete_eval_{summary,nlev,nlev_summary}.hip)
 int launch_discrete_eval(mdpp_env *h, const DiscreteIO &io);
-int launch_discrete_eval_summary(mdpp_env *h, const DiscreteIO &io);
 // the observation every env shows now, from the state record, to obs [N] (mdpp_discrete_eval.hip)
 int launch_discrete_current_obs(mdpp_env *h, void *obs, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);

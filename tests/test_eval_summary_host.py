@@ -168,10 +168,10 @@ def test_the_new_entry_points_are_declared_and_bound_and_the_units_are_built():
     assert len(lib.mdpp_step_n_eval.argtypes) == 8
     assert len(lib.mdpp_step_n_learn_summary.argtypes) == 8 and len(lib.mdpp_step_n_eval_summary.argtypes) == 8
     assert _capi.MDPP_ABI_VERSION == 8
-    for unit, parent in (("mdpp_discrete_eval.hip", None), ("mdpp_discrete_eval_summary.hip", "mdpp_discrete_eval.hip"),
-                         ("mdpp_discrete_learn_summary.hip", "mdpp_discrete_learn.hip"), ("mdpp_discrete_learn_pe_summary.hip", "mdpp_discrete_learn.hip"),
-                         ("mdpp_discrete_learn_double_summary.hip", "mdpp_discrete_learn.hip"),
-                         ("mdpp_discrete_learn_double_pe_summary.hip", "mdpp_discrete_learn.hip")):
+    for unit, parent in (("mdpp_discrete_eval.hip", "mdpp_discrete_eval.hpp"), ("mdpp_discrete_eval_summary.hip", "mdpp_discrete_eval.hpp"),
+                         ("mdpp_discrete_learn_summary.hip", "mdpp_discrete_learn.hpp"), ("mdpp_discrete_learn_pe_summary.hip", "mdpp_discrete_learn.hpp"),
+                         ("mdpp_discrete_learn_double_summary.hip", "mdpp_discrete_learn.hpp"),
+                         ("mdpp_discrete_learn_double_pe_summary.hip", "mdpp_discrete_learn.hpp")):
         assert unit in build.SOURCES
         assert build.INCLUDED_SOURCES.get(unit) == ([parent] if parent else None)
 

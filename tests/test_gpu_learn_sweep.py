@@ -299,3 +299,30 @@ def test_bad_arrays_and_bad_double_tables_raise_value_error_and_the_tables_round
     assert tuple(a.get_q().shape) == (N, 2, 8, 8) and not a.get_q().any()
     assert not a.status().any()
     a.close()
+
+
+def test_the_dispatcher_routes_every_state_of_a_handle_to_the_form_of_that_name():
+    """A launch that lands on the wrong form is silent where the forms agree (uniform parameters give the same numbers with and
+    without PE), so the routes are pinned by name: nothing is launched."""
+    cfg = dict(cases._S8, reward_noise=0.5)         # (a reward_noise key: reward levels are admissible)
+    al = np.linspace(0.1, 0.9, 64)
+
+    def names(algo, per_env=False, levels=False):
+        e = _mk(cfg, "numpy", n=64)
+        e.set_learner(algo, alpha=al if per_env else ALPHA, gamma=GAMMA, epsilon=EPS, seed=SEED)
+        if levels:
+            e.set_noise_levels(reward_noise=np.linspace(0.0, 2.0, 64))
+        got = e.learn_kernel_name(K), e.eval_kernel_name(K)
+        e.close()
+        return got
+
+    assert names("q_learning") == ("k_discrete_learn_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1>",
+                                   "k_discrete_eval_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,DOUBLE=0>")
+    assert names("q_learning", per_env=True)[0] == "k_discrete_learn_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,PE=1>"
+    assert names("double_q") == ("k_discrete_learn_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,DOUBLE=1>",
+                                 "k_discrete_eval_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,DOUBLE=1>")
+    assert names("double_q", per_env=True)[0] == "k_discrete_learn_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,PE=1,DOUBLE=1>"
+    assert names("q_learning", levels=True) == ("k_discrete_learn_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,PE=1,NLEV=1>",
+                                                "k_discrete_eval_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,DOUBLE=0,NLEV=1>")
+    assert names("double_q", levels=True) == ("k_discrete_learn_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,PE=1,DOUBLE=1,NLEV=1>",
+                                              "k_discrete_eval_rollout<PHILOX=0,NOISE=1,UNIT=1,QLDS=1,DOUBLE=1,NLEV=1>")

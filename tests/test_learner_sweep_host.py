@@ -199,7 +199,7 @@ def test_the_new_entry_points_are_declared_and_bound():
     assert _capi.MDPP_ABI_VERSION == 8
     from mdp_playground_amd import build
     for unit in ("mdpp_discrete_learn_pe.hip", "mdpp_discrete_learn_double.hip", "mdpp_discrete_learn_double_pe.hip"):
-        assert unit in build.SOURCES and build.INCLUDED_SOURCES[unit] == ["mdpp_discrete_learn.hip"]
+        assert unit in build.SOURCES and build.INCLUDED_SOURCES[unit] == ["mdpp_discrete_learn.hpp"]
 
 
 # ---- (f) the coverage the GPU test asserts can be met: a closed loop on the CPU

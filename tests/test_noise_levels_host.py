@@ -138,10 +138,10 @@ def test_the_entry_points_are_declared_bound_and_their_units_listed():
     assert len(lib.mdpp_set_noise_levels.argtypes) == 4 and len(lib.mdpp_get_noise_levels.argtypes) == 3
     assert _capi.MDPP_ABI_VERSION == 8                                                 # additive: the version stays
     assert "MDPP_OPT_NO_NLEV_LDS = 1u << 20" in src and _capi.OPTIONS["NO_NLEV_LDS"] == 1 << 20
-    for unit, base in (("mdpp_discrete_learn_pe_nlev.hip", "mdpp_discrete_learn.hip"), ("mdpp_discrete_learn_double_pe_nlev.hip", "mdpp_discrete_learn.hip"),
-                       ("mdpp_discrete_learn_pe_nlev_summary.hip", "mdpp_discrete_learn.hip"),
-                       ("mdpp_discrete_learn_double_pe_nlev_summary.hip", "mdpp_discrete_learn.hip"),
-                       ("mdpp_discrete_eval_nlev.hip", "mdpp_discrete_eval.hip"), ("mdpp_discrete_eval_nlev_summary.hip", "mdpp_discrete_eval.hip")):
+    for unit, base in (("mdpp_discrete_learn_pe_nlev.hip", "mdpp_discrete_learn.hpp"), ("mdpp_discrete_learn_double_pe_nlev.hip", "mdpp_discrete_learn.hpp"),
+                       ("mdpp_discrete_learn_pe_nlev_summary.hip", "mdpp_discrete_learn.hpp"),
+                       ("mdpp_discrete_learn_double_pe_nlev_summary.hip", "mdpp_discrete_learn.hpp"),
+                       ("mdpp_discrete_eval_nlev.hip", "mdpp_discrete_eval.hpp"), ("mdpp_discrete_eval_nlev_summary.hip", "mdpp_discrete_eval.hpp")):
         assert unit in build.SOURCES and build.INCLUDED_SOURCES[unit] == [base]
         assert unit not in build.EXTRA_FLAGS                                           # the build flags are the default ones
 
