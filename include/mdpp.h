@@ -7,10 +7,12 @@
  * stream) and is asynchronous with respect to the host (image rollouts additionally fork to a side
  * stream owned by the handle and join back into the caller's stream before they return).  The library owns only its
  * per-env state and tables (freed by mdpp_destroy); nothing is allocated inside
- * mdpp_step / mdpp_step_n / mdpp_reset, so they can be captured into a HIP graph
- * (tests/test_gpu_parity.py::test_rollout_is_graph_capturable).  The handle's step counter
+ * mdpp_step / mdpp_step_n / mdpp_reset or the closed-loop launches (mdpp_step_n_policy / _learn / _eval and their
+ * _summary forms, mdpp_current_obs), so they can be captured into a HIP graph
+ * (tests/test_gpu_parity.py::test_rollout_is_graph_capturable, tests/test_gpu_graph_replay.py).  The handle's step counter
  * travels to the kernels by value: a replayed graph is exact for numpy-stream handles with
- * unit rewards; Philox keys and the key ring of non-unit rewards read the counter.  A handle is not
+ * unit rewards; Philox keys and the key ring of non-unit rewards read the counter -- such handles, and every
+ * closed-loop launch, replay exactly in capture mode (the section "HIP graphs" below).  A handle is not
  * thread-safe.  Every function returns 0 on success or a negative MDPP_E* code and
  * never throws; mdpp_last_error() gives the message.
  *
@@ -429,7 +431,8 @@ int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream);
  *   handle created with transition_noise[i] and reward_noise[i] and everything else equal.
  * Errors: MDPP_ESTATE for a handle mdpp_set_learner refuses or one created without the key, MDPP_EINVAL for a value out of
  * range, NaN, or more than MDPP_MAX_NOISE_LEVELS distinct transition levels (nothing changed; the reason: mdpp_last_error).
- * The arrays are copied into buffers of the handle, ordered on `stream`.  While levels are set mdpp_step and mdpp_step_n
+ * The arrays are copied into buffers of the handle, ordered on `stream` (the call also allocates the learner's per-env
+ * parameter arrays when absent: a launch with levels takes the PE form, and no launch allocates).  While levels are set mdpp_step and mdpp_step_n
  * return MDPP_ESTATE ("per-env noise levels: learner and evaluation launches only; clear_noise_levels() first"); mdpp_reset is
  * unaffected.  mdpp_get_noise_levels writes the values in force (the creation values while nothing was set) to HOST float64
  * [N] arrays (NULL: not asked for).  mdpp_clear_noise_levels returns to the creation values and the launches the handle made
@@ -466,7 +469,7 @@ int mdpp_set_state_continuous(mdpp_env *h, const float *derivs_host, const float
 int mdpp_get_line_history(mdpp_env *h, float *hist_host);
 int mdpp_set_line_history(mdpp_env *h, const float *hist_host);
 
-/* HIP graphs of single steps (RLToyVectorEnv.step_graph).  mdpp_step hands the handle's step counter to its
+/* HIP graphs.  Single steps first (RLToyVectorEnv.step_graph).  mdpp_step hands the handle's step counter to its
  * launch by value (ring head = counter mod delay for delay lines kept in memory; Philox keys), so a captured
  * launch replays with the counter it was captured with.
  * mdpp_graph_replay_exact: 1 when a graph of K captured mdpp_step launches replays exactly for this handle
@@ -484,6 +487,34 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *                mdpp_tick(h, K, NULL).
  * Launches made in capture mode add the device word that mdpp_graph_set_tick_offset writes to the step counter they
  * were captured with (ring head of a delay line in memory, Philox keys), first thing in the kernel. */
+/* Fused and closed-loop launches in a graph (tests/test_gpu_graph_replay.py pins what follows, bit for bit against an eager
+ * twin).  The protocol above holds for ANY launch of K steps in all -- mdpp_step_n, mdpp_step_n_policy, mdpp_step_n_learn,
+ * mdpp_step_n_eval, the _summary forms, and calls that go out as several launches (image batches on the handle's side stream,
+ * the pieces of a very long call): capture in capture mode, mdpp_tick(h, -K, NULL), and per replay the offset, the graph,
+ * mdpp_tick(h, K, NULL).  Every step, rollout and closed-loop kernel reads the counter through the device word: the Philox
+ * keys, the alignment of the launch inside a four-tick Philox block, the blocks it spans, the head of a delay line in memory.
+ * Any number of eager launches of any kind may run between two replays; the offset need not be a multiple of 4 or of the delay.
+ *   A CLOSED-LOOP launch replays exactly ONLY in capture mode, whatever the handle's RNG mode: the agent's streams (ids 14 - 17)
+ *   are Philox streams keyed by the counter on every handle, so a by-value capture would repeat the same exploration words at
+ *   every replay.  (Greedy evaluation draws none of them; it still needs capture mode for a Philox handle or a delay line in memory.)
+ *   mdpp_graph_replay_exact speaks of mdpp_step launches only.
+ *   BEFORE a capture make one eager launch of the same form on the same handle (same entry point, K, kernel options, agent,
+ *   per-env parameters or noise levels in force): what a form's first launch sets up -- a kernel's dynamic-LDS attribute, the
+ *   fill of the per-env parameter arrays with the uniform values, an image handle's pipeline -- then happens outside the
+ *   capture.  No entry point named above allocates, synchronises or copies from the host; the setters (mdpp_set_policy,
+ *   mdpp_set_learner*, mdpp_set_noise_levels, ...) may do all three and are not for a capture.
+ *   What a captured launch carries BY VALUE (a replay uses what was in force at capture; change it and capture again): K and
+ *   the caller's buffers, the kernel and its form (kernel options, the learner's algorithm, uniform or per-env parameters,
+ *   levels or none), the policy's and the learner's seeds, the UNIFORM alpha, gamma and epsilon (mdpp_set_learner_rates /
+ *   mdpp_set_learner_gamma after the capture do not reach a replay; an eager launch uses them), the NUMBER of noise levels and
+ *   where their cdfs are staged.
+ *   What it READS from the handle's buffers at replay (replace it between replays, on the replay's stream): the actions
+ *   tensor of mdpp_step_n, the policy's thresholds (mdpp_set_policy with the same seed), the Q-tables (mdpp_set_q), the per-env
+ *   alpha / gamma / epsilon arrays (mdpp_set_learner_params: the way to change rates under a graph), the per-env noise
+ *   levels' values (mdpp_set_noise_levels with the same number of distinct transition levels), the caller's five summary
+ *   arrays (they accumulate across replays), the env's state record, streams and tables.
+ *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
+ *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);
 int mdpp_graph_set_tick_offset(mdpp_env *h, int64_t offset, void *stream);
 int mdpp_tick(mdpp_env *h, int64_t advance, uint64_t *tick_out);

@@ -1555,6 +1555,10 @@ extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise
     if (!h->d_nl_M) HIPCHK(h, hipMalloc(&h->d_nl_M, MDPP_MAX_NOISE_LEVELS * sizeof(uint64_t)));
     // (the cdfs of the most levels there can be: a later call with more levels replaces no buffer a queued launch reads)
     if (!h->d_nl_cdf) HIPCHK(h, hipMalloc(&h->d_nl_cdf, (size_t)MDPP_MAX_NOISE_LEVELS * S * S * sizeof(double)));
+    // (the learner's per-env parameter arrays: a launch with levels takes the PE form and fills them while all three
+    //  parameters are uniform -- allocated here when absent, as in mdpp_set_learner_params, so that no launch entry point does)
+    for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
     HIPCHK(h, hipMemcpyAsync(h->d_nl_level, level.data(), N, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->d_nl_sigma, rn.data(), N * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(h->d_nl_T, T.data(), T.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));

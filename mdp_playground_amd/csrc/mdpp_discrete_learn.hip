@@ -46,11 +46,11 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
     const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
     if (h->nl_on && !h->learn_pe) {
         // per-env noise levels run the PE form: while all three parameters are uniform their arrays are filled here, and
-        // again when a value has changed since (the scalar setters do not mark them while nothing is per-env)
+        // again when a value has changed since (the scalar setters do not mark them while nothing is per-env).  The arrays
+        // themselves are mdpp_set_noise_levels': a launch entry point allocates nothing (it may be under a graph capture)
         const bool fresh = h->nl_fill_valid && h->nl_fill_alpha == h->learn_alpha && h->nl_fill_gamma == h->learn_gamma && h->nl_fill_E == h->learn_E;
         if (!fresh && !io.name_out) {
-            for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
-                if (!*d && hipMalloc(d, (size_t)h->cfg.num_envs * 4u) != hipSuccess) { h->err = "mdpp_step_n_learn: hipMalloc of the per-env parameter arrays failed"; return MDPP_EHIP; }
+            if (!h->d_learn_alpha || !h->d_learn_gamma || !h->d_learn_E) { h->err = "mdpp_step_n_learn: the per-env parameter arrays are missing (mdpp_set_noise_levels allocates them)"; return MDPP_ESTATE; }
             h->learn_pe_stale = 7u;
         }
     } else {
