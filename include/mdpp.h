@@ -647,6 +647,12 @@ int mdpp_post_step(mdpp_post *h, const void *obs_in_dev, const double *reward_in
                    void *obs_out_dev, double *reward_out_dev, void *stream);
 int mdpp_post_step_n(mdpp_post *h, int K, const void *obs_in_dev, const double *reward_in_dev, const uint8_t *done_dev,
                      void *obs_out_dev, double *reward_out_dev, void *stream);
+/* What mdpp_post_step_n(h, K, ...) would launch, as mdpp_kernel_name (nothing is launched; the string lives in the handle):
+ * "k_post_step<PHILOX=.,RING=.,DC=.>" (RING 2: the reward FIFO in registers, its delay the constant DC; 1: in LDS; 0: in
+ * HBM, or no delay), and for image handles " + " and the picture kernel, which mdpp_post_reset launches too:
+ * "k_post_image_lds<LDS=bytes,PER_CU=workgroups>" (dynamic LDS per workgroup, workgroups per CU of its grid) or
+ * "k_post_image" (the general form). */
+const char *mdpp_post_kernel_name(mdpp_post *h, int K);
 
 /* Episode statistics of a block of per-step outputs (what RLlib reports per training iteration and the reference's
  * callbacks write to the stats CSV, config_processor.py:275-407; mdp_playground_amd/stats_csv.py EpisodeStats): for

@@ -41,6 +41,7 @@ EXPORTS = [
     "mdpp_get_episode_stats", "mdpp_get_line_history", "mdpp_set_line_history",
     "mdpp_post_create", "mdpp_post_destroy", "mdpp_post_last_error", "mdpp_post_seed_streams", "mdpp_post_get_streams",
     "mdpp_post_get_reward_buffer", "mdpp_post_reset", "mdpp_post_actions", "mdpp_post_step", "mdpp_post_step_n",
+    "mdpp_post_kernel_name",
     "mdpp_episode_stats", "mdpp_probe_hbm", "mdpp_probe_launch",
     "mdpp_peer_create", "mdpp_peer_handle", "mdpp_peer_open", "mdpp_peer_push", "mdpp_peer_fence", "mdpp_peer_wait", "mdpp_peer_buffer",
     "mdpp_peer_status", "mdpp_peer_last_error", "mdpp_peer_destroy",
@@ -200,6 +201,8 @@ def load():
     L.mdpp_post_get_streams.argtypes = [vp, vp]
     L.mdpp_post_get_reward_buffer.argtypes = [vp, vp]
     L.mdpp_post_reset.argtypes = [vp] * 5
+    L.mdpp_post_kernel_name.argtypes = [vp, i32]
+    L.mdpp_post_kernel_name.restype = C.c_char_p
     L.mdpp_post_actions.argtypes = [vp] * 4
     L.mdpp_post_step.argtypes = [vp] * 7
     L.mdpp_post_step_n.argtypes = [vp, i32] + [vp] * 6

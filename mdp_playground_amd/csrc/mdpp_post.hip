@@ -33,6 +33,7 @@ struct mdpp_post {
     int num_cus;
     size_t shift_cap;           // image placements held by d_shift (K * N of the largest call so far)
     bool seeded;
+    char kname[kNameLen];       // mdpp_post_kernel_name()
 };
 
 static std::string g_post_create_err;
@@ -409,24 +410,49 @@ int ensure_place(mdpp_post *h, size_t count) {
     return MDPP_OK;
 }
 
-int launch_post_image(mdpp_post *h, const PostArgs &a, long M, const void *in, void *out, hipStream_t s) {
+// name != nullptr: a dry run -- the name of the picture kernel this call would launch is appended to `name` (kNameLen
+// bytes in all) and nothing is launched
+int launch_post_image(mdpp_post *h, const PostArgs &a, long M, const void *in, void *out, hipStream_t s, char *name = nullptr) {
+    const size_t nlen = name ? strlen(name) : 0;
     if (h->d_xyc) {
         const size_t lds = ((size_t)a.W * ((((a.H * a.C + 3) / 4 + 2) | 1) * 4) + 15) & ~(size_t)15;
+        const int per_cu = lds > 40 * 1024 ? 2 : lds > 24 * 1024 ? 4 : 6;
+        if (name) { snprintf(name + nlen, kNameLen - nlen, "k_post_image_lds<LDS=%zu,PER_CU=%d>", lds, per_cu); return MDPP_OK; }
         static size_t allowed = 48 * 1024;
         if (lds > allowed) {
             (void)hipFuncSetAttribute((const void *)k_post_image_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             allowed = lds;
         }
-        const long resident = (long)h->num_cus * (lds > 40 * 1024 ? 2 : lds > 24 * 1024 ? 4 : 6);
+        const long resident = (long)h->num_cus * per_cu;
         hipLaunchKernelGGL(k_post_image_lds, dim3((unsigned)(M < resident ? M : resident)), dim3(kBlock), lds, s, a, M, a.place,
                            (const uint32_t *)h->d_xyc, (const uint8_t *)in, (uint8_t *)out);
     } else {
+        if (name) { snprintf(name + nlen, kNameLen - nlen, "k_post_image"); return MDPP_OK; }
         const long dwords = (long)(a.W + 2 * a.pad) * (a.H + 2 * a.pad) * a.C / 4;
         const long blocks = (M * dwords + kBlock - 1) / kBlock;
         hipLaunchKernelGGL(k_post_image, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kBlock), 0, s, a, M, a.place,
                            (const uint8_t *)in, (uint8_t *)out);
     }
     return MDPP_OK;
+}
+
+// K fused steps of every instance.  name != nullptr: a dry run, as launch_post_image
+void launch_post_step(const PostArgs &a, int K, const void *obs_in, const double *reward_in, const uint8_t *done, void *obs_out,
+                      double *reward_out, hipStream_t s, char *name = nullptr) {
+    const int grid = (a.N + kBlock - 1) / kBlock;
+    const int ring = a.delay >= 1 && a.delay <= kPostRegDelay ? 2 : (a.delay >= 1 && a.delay <= kPostLdsDelay ? 1 : 0);
+    // (the register FIFO takes its delay as a compile-time constant, DC)
+    with_bools([&](auto PH) {
+        auto go = [&](auto RING, auto DC) {
+            if (name) { snprintf(name, kNameLen, "k_post_step<PHILOX=%d,RING=%d,DC=%d>", (int)PH(), (int)RING(), (int)DC()); return; }
+            hipLaunchKernelGGL((k_post_step<PH(), RING(), DC()>), dim3(grid), dim3(kBlock), 0, s, a, K, obs_in, reward_in, done, obs_out,
+                               reward_out);
+        };
+        using std::integral_constant;
+        if (ring == 2) with_value<1, 2, 3, 4, 5, 6, 7, 8>(a.delay, [&](auto DC) { go(integral_constant<int, 2>{}, DC); });
+        else if (ring == 1) go(integral_constant<int, 1>{}, integral_constant<int, 0>{});
+        else go(integral_constant<int, 0>{}, integral_constant<int, 0>{});
+    }, a.philox != 0);
 }
 
 int post_ready(mdpp_post *h, const char *what) {
@@ -633,23 +659,26 @@ extern "C" int mdpp_post_step_n(mdpp_post *h, int K, const void *obs_in_dev, con
     hipStream_t s = (hipStream_t)stream;
     if (h->cfg.image) { rc = ensure_place(h, (size_t)K * h->cfg.num_envs); if (rc) return rc; }
     PostArgs a = make_args(h);
-    const int grid = (a.N + kBlock - 1) / kBlock;
-    const int ring = a.delay >= 1 && a.delay <= kPostRegDelay ? 2 : (a.delay >= 1 && a.delay <= kPostLdsDelay ? 1 : 0);
-    // (the register FIFO takes its delay as a compile-time constant, DC)
-    with_bools([&](auto PH) {
-        auto go = [&](auto RING, auto DC) {
-            hipLaunchKernelGGL((k_post_step<PH(), RING(), DC()>), dim3(grid), dim3(kBlock), 0, s, a, K, obs_in_dev, reward_in_dev, done_dev, obs_out_dev,
-                               reward_out_dev);
-        };
-        using std::integral_constant;
-        if (ring == 2) with_value<1, 2, 3, 4, 5, 6, 7, 8>(a.delay, [&](auto DC) { go(integral_constant<int, 2>{}, DC); });
-        else if (ring == 1) go(integral_constant<int, 1>{}, integral_constant<int, 0>{});
-        else go(integral_constant<int, 0>{}, integral_constant<int, 0>{});
-    }, a.philox != 0);
+    launch_post_step(a, K, obs_in_dev, reward_in_dev, done_dev, obs_out_dev, reward_out_dev, s);
     if (h->cfg.image) launch_post_image(h, a, (long)K * a.N, obs_in_dev, obs_out_dev, s);
     PHIP(h, hipGetLastError());
     h->tick += (uint64_t)K;
     return MDPP_OK;
+}
+
+extern "C" const char *mdpp_post_kernel_name(mdpp_post *h, int K) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1) return h->kname;
+    // (dry runs of the launchers mdpp_post_step_n uses: they write the names and launch nothing)
+    const PostArgs a = make_args(h);
+    launch_post_step(a, K, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->kname);
+    if (h->cfg.image) {
+        const size_t n = strlen(h->kname);
+        snprintf(h->kname + n, kNameLen - n, " + ");
+        (void)launch_post_image(h, a, (long)K * a.N, nullptr, nullptr, nullptr, h->kname);
+    }
+    return h->kname;
 }
 
 extern "C" int mdpp_post_step(mdpp_post *h, const void *obs_in_dev, const double *reward_in_dev, const uint8_t *done_dev,

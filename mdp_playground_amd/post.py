@@ -202,6 +202,12 @@ class VectorPostProcessor:
                                                C.c_void_p(r_out.data_ptr()), self._stream()), "mdpp_post_step_n")
         return obs_out, r_out
 
+    def kernel_name(self, K=1):
+        """The kernels step() launches for K fused steps, e.g. "k_post_step<PHILOX=0,RING=2,DC=3>"; image handles:
+        " + " and the picture kernel, which reset() launches too ("k_post_image_lds<LDS=21840,PER_CU=6>": dynamic LDS
+        bytes per workgroup and workgroups per CU, or "k_post_image").  Launches nothing."""
+        return self._lib.mdpp_post_kernel_name(self._h, int(K)).decode()
+
     def close(self):
         if self._h is not None:
             torch.cuda.synchronize(self.device)

@@ -993,6 +993,11 @@ void ora_p_set_philox(ora_post *e, uint64_t seed, uint64_t env_id, uint64_t tick
     e->philox = 1; e->ph_seed = seed; e->ph_env = env_id; e->tick = tick; e->reset_tick = reset_tick;
     e->action_tick = tick;
 }
+void ora_p_set_counters(ora_post *e, uint64_t tick, uint64_t reset_tick, uint64_t action_tick) {
+    e->tick = tick; e->reset_tick = reset_tick; e->action_tick = action_tick;
+}
+void ora_p_clear_ring(ora_post *e) { for (int i = 0; i < e->delay; i++) e->ring[i] = 0.0; e->ring_n = e->delay; }
+void ora_p_get_ring(const ora_post *e, double *ring) { memcpy(ring, e->ring, sizeof(double) * (size_t)e->delay); }
 
 /* get_transformed_image, :523-618 (only "shift" does anything upstream; square RGB images) */
 static void post_image(ora_post *e, const uint8_t *in, uint8_t *out) {

@@ -108,6 +108,9 @@ def lib():
         L.ora_p_set_rng.argtypes = [vp, vp]
         L.ora_p_get_rng.argtypes = [vp, vp]
         L.ora_p_set_philox.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]
+        L.ora_p_set_counters.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
+        L.ora_p_get_ring.argtypes = [vp, vp]
+        L.ora_p_clear_ring.argtypes = [vp]
         L.ora_p_reset.argtypes = [vp, vp, vp]
         L.ora_p_action.argtypes = [vp, i32]
         L.ora_p_action.restype = i32
@@ -168,6 +171,7 @@ class PostOracle:
         self.shape = tuple(image_shape) if self.image else None
         H, W, Cc = self.shape if self.image else (0, 0, 0)
         self.pad = int(image_padding)
+        self.delay = int(delay)
         self.h = lib().ora_p_create(int(self.cont), int(n_actions), self.obs_dim, int(self.obs_dtype == np.float64),
                                     int(delay), int(transition_noise is not None), float(transition_noise or 0.0),
                                     int(reward_noise is not None), float(reward_noise or 0.0), float(reward_scale),
@@ -190,6 +194,20 @@ class PostOracle:
 
     def set_philox(self, seed, env_id, tick=0, reset_tick=0):
         lib().ora_p_set_philox(self.h, int(seed), int(env_id), int(tick), int(reset_tick))
+
+    def set_counters(self, tick, reset_tick, action_tick):
+        """The Philox counters alone (set_philox also puts action_tick at tick)."""
+        lib().ora_p_set_counters(self.h, int(tick), int(reset_tick), int(action_tick))
+
+    def clear_ring(self):
+        """The buffer refilled with zeros, nothing drawn: what a batched caller with autoreset=True gets on a done step."""
+        lib().ora_p_clear_ring(self.h)
+
+    def ring(self):
+        """self.reward_buffer, [0] pays out next."""
+        r = np.zeros(self.delay, np.float64)
+        lib().ora_p_get_ring(self.h, _p(r))
+        return r
 
     def _img_out(self):
         H, W, Cc = self.shape

@@ -342,10 +342,9 @@ def test_post_random_configurations_vs_oracle(k):
     else:
         args = dict(n_actions=p["n_actions"])
         okw.update(n_actions=p["n_actions"])
-    try:
-        post = VectorPostProcessor(N, rng=rng, autoreset=True, env_id_offset=500, **args, **cfg)
-    except Exception as e:                       # (a combination the library refuses at creation: say so, do not pass silently)
-        pytest.skip(f"refused at creation: {type(e).__name__}: {str(e)[:100]}")
+    # (none of _post_fuzz's combinations is among mdpp_post_create's documented refusals -- delay > 128, an odd or non-square picture,
+    #  a canvas that is no multiple of 4 bytes, shift without padding, noise outside [0, 1]: a refusal here is a failure, not a skip)
+    post = VectorPostProcessor(N, rng=rng, autoreset=True, env_id_offset=500, **args, **cfg)
     dev = post.device
     base_rew = r.integers(-8, 9, size=(2, K, N)) / 4.0
     base_done = r.random((2, K, N)) < p["p_done"]

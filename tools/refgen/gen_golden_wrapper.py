@@ -117,6 +117,14 @@ CASES = {
                                     image_padding=6, image_sh_quant=2, transition_noise=0.1)),
     "w_img_centre": dict(kind="image", T=20, seeds=3, done_every=7, env=dict(obs_shape=(12, 12, 3)),
                          config=dict(state_space_type="discrete", image_transforms="flip", image_padding=4)),
+    # the reference's own picture size: 84 x 84 x 3 on the default image_padding of 20 (a 124 x 124 canvas), and on
+    # image_padding 1 (canvas rows of 86 * 3 = 258 bytes, no multiple of 4; the shift is drawn and is always 0)
+    "w_img_84": dict(kind="image", T=6, seeds=2, done_every=4, env=dict(obs_shape=(84, 84, 3)),
+                     config=dict(state_space_type="discrete", delay=1, transition_noise=0.1, reward_noise=0.125,
+                                 image_transforms="shift", image_sh_quant=4)),
+    "w_img_84_pad1": dict(kind="image", T=6, seeds=2, done_every=4, env=dict(obs_shape=(84, 84, 3)),
+                          config=dict(state_space_type="discrete", delay=1, transition_noise=0.1, reward_noise=0.125,
+                                      image_transforms="shift", image_padding=1)),
 }
 
 
