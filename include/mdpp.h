@@ -101,7 +101,8 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
        MDPP_OPT_NO_LEARN_LDS = 1u << 18,   /* k_discrete_learn_rollout: the Q-tables stay in global memory (QLDS=0) */
        MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19, /* mdpp_step_n_policy and mdpp_step_n_learn go out in launches of at most 5 steps
                                               (the hand-over between the pieces of a very long call, at a size a test can run) */
-       MDPP_OPT_NO_NLEV_LDS = 1u << 20 };  /* per-env noise levels (mdpp_set_noise_levels): the per-level cdfs stay in global memory */
+       MDPP_OPT_NO_NLEV_LDS = 1u << 20,    /* per-env noise levels (mdpp_set_noise_levels): the per-level cdfs stay in global memory */
+       MDPP_OPT_NO_PM_LDS = 1u << 21 };    /* one MDP per env (mdpp_learner_per_env_mdp): the envs' tables stay in global memory (PM=1) */
 
 /* transition-noise levels one handle serves at a time (mdpp_set_noise_levels) */
 #define MDPP_MAX_NOISE_LEVELS 16
@@ -383,6 +384,30 @@ const char *mdpp_learn_kernel_name(mdpp_env *h, int K);
 int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream);
 int mdpp_set_learner_gamma(mdpp_env *h, float gamma);
 
+/* One MDP per env for the learner and evaluation launches.  mdpp_learner_per_env_mdp(h, on) sets a flag of the handle, off at
+ * creation.  With the flag on, a handle with cfg.num_tables == cfg.num_envs (each env its own P, terminal states, rewardable
+ * sequences and start distribution) is served by mdpp_set_learner, mdpp_step_n_learn, mdpp_step_n_eval, both _summary calls,
+ * mdpp_get_q / mdpp_set_q, mdpp_set_learner_params / _rates / _gamma and the kernel-name dry runs: the "one shared MDP" rule
+ * above is dropped and so is "within 64 KiB of LDS", which is about a shared MDP staged per workgroup; every other rule holds.
+ * Env i steps bit for bit as env i of an identical handle given the same actions through mdpp_step_n, and agent i is the
+ * learner above on table set i: sel, target, update, SARSA's carry, the reset call, summaries and evaluation hold word for
+ * word; the Philox streams are keyed by cfg.env_id_offset + i as ever.
+ * The launch is the kernel's PM form, always with PE=1 (uniform parameters travel as arrays of equal entries; mdpp_set_learner
+ * allocates them on such a handle).  Where the tables live is a placement the host makes per launch, never a refusal: the
+ * kernel's name ends ",PM=2>" when each lane's table set is staged into LDS (dword w of lane l at byte (256 w + l) 4: bank =
+ * lane) and ",PM=1>" when lane i reads set i in global memory; QLDS says the same of the Q-tables.  Tried in this order, as
+ * far as the device grants the LDS: Q and the MDPs, Q alone, the MDPs alone, neither (the MDPs are candidates while a
+ * workgroup's 256 table sets take at most 64 KiB, the Q-tables at most 160 KiB).  MDPP_OPT_NO_PM_LDS forces PM=1,
+ * MDPP_OPT_NO_LEARN_LDS QLDS=0.  The transition-noise cdf and the ziggurat tables stay shared.
+ * On a handle with one shared MDP, or one that is not discrete, the call is accepted and changes nothing.  Turning the flag
+ * off (on a handle it was on for) clears the learner.  Whatever the flag: mdpp_set_policy and mdpp_step_n_policy refuse one
+ * MDP per env ("need one shared MDP"), and mdpp_set_noise_levels on a flagged handle with one MDP per env returns
+ * MDPP_EUNSUPPORTED ("per-env noise levels on one MDP per env: not built").  Without the flag such a handle is refused by
+ * every learner entry point as before, message included.
+ * Under a graph capture the form (PM and QLDS) is fixed at capture like PE; the tables are read from the handle's buffers at
+ * replay. */
+int mdpp_learner_per_env_mdp(mdpp_env *h, int on);
+
 /* Greedy evaluation of the learner's tables: mdpp_step_n_eval runs K steps in which env i in state s takes
  *   one table:  a = the lowest j maximising Q[s][j] (scanned from j = 0 with a strict >),
  *   double Q:   a = the lowest j maximising QA[s][j] + QB[s][j] (one float32 addition per j) -- the greedy branch of sel above,
@@ -505,9 +530,9 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   mdpp_set_learner*, mdpp_set_noise_levels, ...) may do all three and are not for a capture.
  *   What a captured launch carries BY VALUE (a replay uses what was in force at capture; change it and capture again): K and
  *   the caller's buffers, the kernel and its form (kernel options, the learner's algorithm, uniform or per-env parameters,
- *   levels or none), the policy's and the learner's seeds, the UNIFORM alpha, gamma and epsilon (mdpp_set_learner_rates /
- *   mdpp_set_learner_gamma after the capture do not reach a replay; an eager launch uses them), the NUMBER of noise levels and
- *   where their cdfs are staged.
+ *   levels or none, one MDP per env and where its tables are placed), the policy's and the learner's seeds, the UNIFORM
+ *   alpha, gamma and epsilon (mdpp_set_learner_rates / mdpp_set_learner_gamma after the capture do not reach a replay; an
+ *   eager launch uses them), the NUMBER of noise levels and where their cdfs are staged.
  *   What it READS from the handle's buffers at replay (replace it between replays, on the replay's stream): the actions
  *   tensor of mdpp_step_n, the policy's thresholds (mdpp_set_policy with the same seed), the Q-tables (mdpp_set_q), the per-env
  *   alpha / gamma / epsilon arrays (mdpp_set_learner_params: the way to change rates under a graph), the per-env noise

@@ -121,6 +121,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_learn_q = h->d_learn_carry = nullptr; h->learn_seed = 0; h->learn_E = 0; h->learn_alpha = h->learn_gamma = 0.0f;
     h->learn_algo = MDPP_LEARN_Q_LEARNING; h->learn_ready = false;
     h->learn_q_tables = 0; h->d_learn_alpha = h->d_learn_gamma = h->d_learn_E = nullptr; h->learn_pe = h->learn_pe_stale = 0;
+    h->learn_pm = false;
     h->nl_on = false; h->nl_levels = 0; h->nl_fill_valid = false; h->nl_fill_alpha = h->nl_fill_gamma = 0.0f; h->nl_fill_E = 0;
     h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
@@ -1418,6 +1419,11 @@ extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma,
         h->learn_q_tables = tables;
     }
     if (!h->d_learn_carry) HIPCHK(h, hipMalloc(&h->d_learn_carry, N * sizeof(int32_t)));
+    // (one MDP per env: the launch takes the PE form and fills the parameter arrays while all three are uniform -- allocated
+    //  here, as in mdpp_set_noise_levels, so that no launch entry point does)
+    if (h->learn_pm)
+        for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
+            if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
     // (on the caller's stream: behind the rollouts already queued there, ahead of the next one)
     h->learn_algo = algo;        // (the copy below goes by the algorithm's number of tables)
     if (q_init_dev) {
@@ -1431,6 +1437,15 @@ extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma,
     h->learn_pe = h->learn_pe_stale = 0;                         // all three uniform
     h->nl_fill_valid = false;
     h->learn_ready = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_learner_per_env_mdp(mdpp_env *h, int on) {
+    if (!h) return MDPP_EINVAL;
+    // (a shared MDP, or no discrete handle: accepted, nothing changes)
+    if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
+    if (h->learn_pm && !on) h->learn_ready = false;      // (as mdpp_clear_learner: the buffers stay)
+    h->learn_pm = on != 0;
     return MDPP_OK;
 }
 
@@ -1498,6 +1513,7 @@ extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise
     if (!h) return MDPP_EINVAL;
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: " + why);
+    if (h->cfg.num_tables != 1) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_noise_levels: per-env noise levels on one MDP per env: not built");
     const mdpp_config &c = h->cfg;
     if (transition_noise && !c.has_transition_noise)
         return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: transition_noise: the handle was created without the key (it needs transition_noise > 0: the space streams and the NOISE kernels)");

@@ -44,6 +44,18 @@
 // staged in LDS behind the MDP's tables (from lds + a.lds_bytes, nl.lds_bytes of them; the agent's LDS moves behind) when
 // the host found room, else read in global memory.  The handle's own cdf (a.noise_cdf / a.lds_noise) is not staged.
 // A compile-time choice like SUMMARY: the NLEV = false instantiations are the code they were.
+//
+// PM (one MDP per env, mdpp_learner_per_env_mdp; NLEV = false only): 0 is the shared MDP above.  PM = 1: lane i reads table
+// set i of a.P / is_term / init_cdf / rbits / rtable in global memory, with k_discrete_step's strides.  PM = 2: the lane stages
+// its own set once per launch into LDS, laid out as the learners lay out Q: dword w of lane tid at byte (w 256 + tid) 4, w
+// counted in the handle's own carve (a.lds_P / 4 ..., a.lds_noise / 4 dwords per lane).  Bank = lane: no conflict whatever
+// (s, a) each lane holds -- a per-lane slot of the carve's own stride (216 B at 8 x 8: 54 dwords, 54 l mod 32 reaches 16
+// banks) would make every dependent read 2-way conflicted.  P, the terminal flags and the reward bits are bytes taken out of
+// their dword, a cdf entry or a reward two dwords.  Tail lanes of the last workgroup stage table set N - 1.  The transition
+// noise's cdf and the ziggurat tables stay shared: the cdf lies behind the slots (PM = 2) or at the start of LDS (PM = 1),
+// the agent's LDS behind it (closed_agent_lds_offset).  There is no queue of start states (fast_ok needs shared tables).
+// A compile-time choice, so that every table pointer has one provenance (ds_read or global_load, never flat); the PM = 0
+// instantiations are the code they were.
 #pragma once
 #include "mdpp_internal.hpp"
 #include "mdpp_rng.hpp"
@@ -73,8 +85,52 @@ __device__ __forceinline__ ZigLds closed_loop_zig_lds() {
     return ZigLds{s_ki, s_wi, s_fi};
 }
 
+// PM = 2: this lane's column of the workgroup's MDP slots, as the step reads it
+struct ClosedSlots {
+    const uint32_t *w;          // dword 0 of this lane: dword k at w[k 256]
+    uint32_t oP, oterm, orew, oinit;    // the carve in dwords
+    __device__ __forceinline__ uint32_t byte_of(uint32_t o, uint32_t k) const { return (w[(o + (k >> 2)) * kBlock] >> ((k & 3u) * 8u)) & 0xFFu; }
+    __device__ __forceinline__ double double_of(uint32_t o, uint32_t k) const {
+        return __hiloint2double((int)w[(o + 2u * k + 1u) * kBlock], (int)w[(o + 2u * k) * kBlock]);
+    }
+    __device__ __forceinline__ uint32_t next(uint32_t k) const { return byte_of(oP, k); }
+    __device__ __forceinline__ bool terminal(uint32_t s) const { return byte_of(oterm, s) != 0u; }
+    __device__ __forceinline__ uint32_t reward_byte(uint32_t k) const { return byte_of(orew, k); }
+    __device__ __forceinline__ double reward(uint32_t k) const { return double_of(orew, k); }
+    __device__ __forceinline__ int start(int S, double u) const {       // searchsorted_right on the lane's cdf
+        int c = 0;
+        for (int j = 0; j < S; j++) c += (double_of(oinit, (uint32_t)j) <= u) ? 1 : 0;
+        return c;
+    }
+};
+// PM = 2: n bytes / n doubles of src into dword o onwards of the lane whose dword 0 is w
+__device__ __forceinline__ void closed_stage_bytes(uint32_t *w, uint32_t o, const uint8_t *src, uint32_t n) {
+    for (uint32_t k = 0; k < n; k += 4u) {
+        uint32_t v = 0;
+        for (uint32_t b = 0; b < 4u && k + b < n; b++) v |= (uint32_t)src[k + b] << (8u * b);
+        w[(o + (k >> 2)) * kBlock] = v;
+    }
+}
+__device__ __forceinline__ void closed_stage_doubles(uint32_t *w, uint32_t o, const double *src, uint32_t n) {
+    for (uint32_t k = 0; k < n; k++) {
+        const double v = src[k];
+        w[(o + 2u * k) * kBlock] = (uint32_t)__double2loint(v);
+        w[(o + 2u * k + 1u) * kBlock] = (uint32_t)__double2hiint(v);
+    }
+}
+// Where the shared transition-noise cdf lies in a PM kernel's dynamic LDS, and where the agent's LDS starts behind it
+// (PM = 0: a.lds_noise and a.lds_bytes, the handle's own carve)
+template <int PM>
+__host__ __device__ __forceinline__ uint32_t closed_noise_lds_offset(const DiscreteArgs &a) {
+    return PM == 2 ? (uint32_t)kBlock * a.lds_noise : PM == 1 ? 0u : a.lds_noise;
+}
+template <int PM>
+__host__ __device__ __forceinline__ uint32_t closed_agent_lds_offset(const DiscreteArgs &a) {
+    return PM == 0 ? a.lds_bytes : closed_noise_lds_offset<PM>(a) + (a.lds_bytes - a.lds_noise);
+}
+
 // (a is the kernel's by-value argument, taken by const reference: see tick_now in mdpp_internal.hpp for what a write costs)
-template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, bool NLEV = false, class Agent>
+template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, bool NLEV = false, int PM = 0, class Agent>
 __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K, const bool obs64, int32_t *actions,
                                                     void *__restrict__ obs, float *__restrict__ reward,
                                                     uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
@@ -82,6 +138,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
                                                     const EpisodeSummaryArgs &sm = EpisodeSummaryArgs{},
                                                     const NoiseLevelArgs &nl = NoiseLevelArgs{}) {
     static_assert(NOISE || !NLEV, "per-env noise levels are levels of a NOISE kernel");
+    static_assert(PM == 0 || !NLEV, "per-env noise levels on one MDP per env: not built");
     const uint64_t ptick0 = tick_now(a);               // the step counter at this launch (through the device-side offset of a graph replay)
     const uint32_t rhead0 = ring_head_now(a, ptick0);  // ... and the head of a delay line kept in memory
     const int tid = threadIdx.x;
@@ -89,18 +146,29 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     const int S = a.S, A = a.A, L = a.L;
     const uint32_t N = (uint32_t)a.N;
     // stage the shared MDP (and the noise categoricals), then what the agent keeps in LDS
-    for (uint32_t k = tid; k < (uint32_t)S * (uint32_t)A; k += kBlock) lds[a.lds_P + k] = a.P[k];
-    for (int k = tid; k < S; k += kBlock) {
-        lds[a.lds_term + k] = a.is_term[k];
-        ((double *)(lds + a.lds_init))[k] = a.init_cdf[k];
+    if constexpr (PM == 0) {
+        for (uint32_t k = tid; k < (uint32_t)S * (uint32_t)A; k += kBlock) lds[a.lds_P + k] = a.P[k];
+        for (int k = tid; k < S; k += kBlock) {
+            lds[a.lds_term + k] = a.is_term[k];
+            ((double *)(lds + a.lds_init))[k] = a.init_cdf[k];
+        }
+        if (UNIT)
+            for (uint32_t k = tid; k < a.rbits_stride; k += kBlock) lds[a.lds_rew + k] = a.rbits[k];
+        else
+            for (uint32_t k = tid; k < a.nkeys; k += kBlock) ((double *)(lds + a.lds_rew))[k] = a.rtable[k];
     }
-    if (UNIT)
-        for (uint32_t k = tid; k < a.rbits_stride; k += kBlock) lds[a.lds_rew + k] = a.rbits[k];
-    else
-        for (uint32_t k = tid; k < a.nkeys; k += kBlock) ((double *)(lds + a.lds_rew))[k] = a.rtable[k];
+    if constexpr (PM == 2) {         // ... or this lane's own MDP into its column of the slots (tail lanes: the last env's)
+        uint32_t *const w = (uint32_t *)lds + tid;
+        const size_t ti = (size_t)(i < N ? i : N - 1u);
+        closed_stage_bytes(w, a.lds_P / 4u, a.P + ti * (size_t)(S * A), (uint32_t)(S * A));
+        closed_stage_bytes(w, a.lds_term / 4u, a.is_term + ti * (size_t)S, (uint32_t)S);
+        closed_stage_doubles(w, a.lds_init / 4u, a.init_cdf + ti * (size_t)S, (uint32_t)S);
+        if (UNIT) closed_stage_bytes(w, a.lds_rew / 4u, a.rbits + ti * (size_t)a.rbits_stride, a.rbits_stride);
+        else closed_stage_doubles(w, a.lds_rew / 4u, a.rtable + ti * (size_t)a.nkeys, a.nkeys);
+    }
     const bool pn_lds = !NLEV && NOISE && a.has_p_noise && a.noise_in_lds;
     if (pn_lds)
-        for (int k = tid; k < S * S; k += kBlock) ((double *)(lds + a.lds_noise))[k] = a.noise_cdf[k];
+        for (int k = tid; k < S * S; k += kBlock) ((double *)(lds + (PM == 0 ? a.lds_noise : closed_noise_lds_offset<PM>(a))))[k] = a.noise_cdf[k];
     if constexpr (NLEV) {
         if (!PHILOX && a.has_p_noise && nl.lds_bytes != 0u)
             for (uint32_t k = tid; k < nl.levels * (uint32_t)(S * S); k += kBlock) ((double *)(lds + a.lds_bytes))[k] = nl.cdf[k];
@@ -108,9 +176,14 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     agent.stage(tid);
     __syncthreads();
     if (i >= N) return;
-    const uint8_t *const tP = lds + a.lds_P, *const tterm = lds + a.lds_term, *const trbits = lds + a.lds_rew;
-    const double *const trtable = (const double *)(lds + a.lds_rew), *const tinit = (const double *)(lds + a.lds_init);
-    const double *const tnoise = (const double *)(lds + a.lds_noise);
+    // the tables: in LDS (PM = 0), this lane's set in global memory (PM = 1); PM = 2 reads its slots through ts instead
+    const uint8_t *const tP = PM == 1 ? a.P + (size_t)i * (size_t)(S * A) : lds + a.lds_P;
+    const uint8_t *const tterm = PM == 1 ? a.is_term + (size_t)i * (size_t)S : lds + a.lds_term;
+    const uint8_t *const trbits = PM == 1 ? a.rbits + (size_t)i * (size_t)a.rbits_stride : lds + a.lds_rew;
+    const double *const trtable = PM == 1 ? a.rtable + (size_t)i * (size_t)a.nkeys : (const double *)(lds + a.lds_rew);
+    const double *const tinit = PM == 1 ? a.init_cdf + (size_t)i * (size_t)S : (const double *)(lds + a.lds_init);
+    const double *const tnoise = (const double *)(lds + (PM == 0 ? a.lds_noise : closed_noise_lds_offset<PM>(a)));
+    const ClosedSlots ts{(const uint32_t *)lds + tid, a.lds_P / 4u, a.lds_term / 4u, a.lds_rew / 4u, a.lds_init / 4u};
     const uint64_t genv = (uint64_t)(a.env_id_offset + (int64_t)i);
     // NLEV: this lane's sigma, its level's (T, M) and where its level's cdfs start (in doubles)
     double lane_sigma = 0.0;
@@ -134,7 +207,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     const uint4 st = a.state[i];
     // fast_ok handles: word 1 is the queue of start states {24 bits of 4-bit entries, next one lowest; count in bits 24-26},
     // and history bytes 4-7 do not exist (L <= 3: never read)
-    const bool queued = a.fast_ok != 0;
+    const bool queued = PM == 0 && a.fast_ok != 0;
     uint64_t hist = ((uint64_t)(queued ? 0xFFFFFFFFu : st.y) << 32) | st.x;      // newest state in byte 0, 0xFF = NaN
     uint32_t qv = st.y & 0x00FFFFFFu, qc = (st.y >> 24) & 7u;
     uint32_t steps = st.z, ringbits = st.w;
@@ -182,14 +255,17 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
 
     // reset(): the first state of the next episode (:2255: one uniform, searchsorted(cdf, u, 'right'))
     auto start_state = [&](uint64_t ptick) -> uint32_t {
-        if (PHILOX)          // one word of the start-state stream per tick (mdpp_rng.hpp)
-            return (uint32_t)searchsorted_right(tinit, S, philox_start_uniform(philox_start_m31(a.philox_seed, genv, ptick, kPhiloxStartStream)));
+        if (PHILOX) {        // one word of the start-state stream per tick (mdpp_rng.hpp)
+            if constexpr (PM == 2) return (uint32_t)ts.start(S, philox_start_uniform(philox_start_m31(a.philox_seed, genv, ptick, kPhiloxStartStream)));
+            else return (uint32_t)searchsorted_right(tinit, S, philox_start_uniform(philox_start_m31(a.philox_seed, genv, ptick, kPhiloxStartStream)));
+        }
         if (queued && qc != 0) {                        // the next draws of the stream, made ahead by another kernel
             const uint32_t s0 = qv & 0xFu;
             qv >>= 4; qc -= 1;
             return s0;
         }
-        return (uint32_t)searchsorted_right(tinit, S, np_random(env_pcg));
+        if constexpr (PM == 2) return (uint32_t)ts.start(S, np_random(env_pcg));
+        else return (uint32_t)searchsorted_right(tinit, S, np_random(env_pcg));
     };
     auto episode_start = [&](uint32_t s0) {
         hist = 0xFFFFFFFFFFFFFF00ULL | (uint64_t)s0;
@@ -217,7 +293,9 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
             pending = false;
             continue;
         }
-        uint32_t nxt = tP[cur * (uint32_t)A + action];                              // D1
+        uint32_t nxt;
+        if constexpr (PM == 2) nxt = ts.next(cur * (uint32_t)A + action);
+        else nxt = tP[cur * (uint32_t)A + action];                              // D1
         if (NOISE && a.has_p_noise) {                                               // D2
             // (Philox streams: one word of the tick decides "noisy" and which other state; numpy streams: the state space's own
             //  generator and the categorical's cdf, as in the reference)
@@ -244,11 +322,14 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
         }
         // custom reward matrix: R(s, a) of this transition, whatever s' (noise included) was (:1259-1267)
         if (!UNIT && a.rew_sa) key = cur * (uint32_t)A + action;
-        const bool done = tterm[nxt] != 0;                                          // D7
+        bool done;
+        if constexpr (PM == 2) done = ts.terminal(nxt);
+        else done = tterm[nxt] != 0;                                          // D7
         float rout;
         if (UNIT) {
             uint32_t bit = 0;
-            if (key != kNoKey) bit = (trbits[key >> 3] >> (key & 7u)) & 1u;
+            if constexpr (PM == 2) { if (key != kNoKey) bit = (ts.reward_byte(key >> 3) >> (key & 7u)) & 1u; }
+            else if (key != kNoKey) bit = (trbits[key >> 3] >> (key & 7u)) & 1u;
             if (a.delay > 0) {                                                      // D5 (shift register)
                 const uint32_t out = (ringbits >> (a.delay - 1)) & 1u;
                 ringbits = (ringbits << 1) | bit;
@@ -272,7 +353,9 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
                 *slot = key;
                 key = out;
             }
-            double r = (key != kNoKey) ? trtable[key] : 0.0;
+            double r;
+            if constexpr (PM == 2) r = (key != kNoKey) ? ts.reward(key) : 0.0;
+            else r = (key != kNoKey) ? trtable[key] : 0.0;
             if (phase != 0) r = 0.0;                                                // D6
             if (NOISE && a.has_r_noise) r += reward_noise(ptick);
             r *= a.scale;
@@ -322,8 +405,11 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
 constexpr size_t kZigLdsBytes = 3u * 256u * 8u;        // a NOISE kernel's static LDS: the ziggurat tables
 
 // Why this handle has no closed-loop launch ("<noun> rollouts ..."), or empty: the kernel serves it.  agent_lds: the LDS
-// the agent needs whatever the launch (bytes), tables: what has to fit, for the message
-inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool serves_noise, uint64_t agent_lds, const char *tables) {
+// the agent needs whatever the launch (bytes), tables: what has to fit, for the message.  per_env_mdp: the agent has kernels
+// for one MDP per env (PM), which a handle flagged by mdpp_learner_per_env_mdp runs: its tables are placed per launch
+// (closed_agent_lds_pm), so the LDS rule -- a shared MDP staged per workgroup -- does not apply to it
+inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool serves_noise, uint64_t agent_lds, const char *tables,
+                                       bool per_env_mdp = false) {
     const mdpp_config &c = h->cfg;
     const DiscreteArgs &a = h->dargs;
     const char *why = nullptr;
@@ -331,13 +417,13 @@ inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool
     if (c.kind != MDPP_KIND_DISCRETE) why = "serve discrete envs only (this handle is continuous or a grid)";
     else if (c.image) why = "do not serve image observations";
     else if (c.irrelevant) why = "do not serve an irrelevant sub-space (irrelevant_features)";
-    else if (c.num_tables != 1) why = "need one shared MDP (this handle has one MDP per env: seeds=[...])";
+    else if (c.num_tables != 1 && !(per_env_mdp && h->learn_pm)) why = "need one shared MDP (this handle has one MDP per env: seeds=[...])";
     else if (c.S > 255) why = "need at most 255 states (state_space_size)";
     else if (c.L > 7) why = "need sequence_length <= 7";
     else if (!serves_noise && c.has_transition_noise) why = "do not serve a transition_noise key";
     else if (!serves_noise && c.has_reward_noise) why = "do not serve a reward_noise key";
     else if (c.episode_stats) why = "do not keep episode_stats";
-    else if (!a.rew_in_lds || (uint64_t)a.lds_bytes + agent_lds + (noise ? kZigLdsBytes : 0u) > 64u * 1024u)
+    else if (c.num_tables == 1 && (!a.rew_in_lds || (uint64_t)a.lds_bytes + agent_lds + (noise ? kZigLdsBytes : 0u) > 64u * 1024u))
         return std::string(noun) + " rollouts need " + tables + " within 64 KiB of LDS";
     return why ? std::string(noun) + " rollouts " + why : std::string();
 }
@@ -362,6 +448,24 @@ inline void closed_agent_lds(const mdpp_env *h, size_t q_lds, Granted &&granted,
     if (q_ok && c_ok && granted(true, (size_t)a.lds_bytes + cdf + q_lds)) qlds = clds = true;
     else if (q_ok && granted(true, (size_t)a.lds_bytes + q_lds)) qlds = true;
     else if (c_ok && granted(false, (size_t)a.lds_bytes + cdf)) clds = true;
+}
+// ... on a handle with one MDP per env (PM kernels; it has no noise levels): where the agent's tables and the envs' MDP slots
+// (kBlock a.lds_noise bytes: the carve up to the shared noise cdf, per lane) go, in the same order -- both in LDS (PM = 2 with
+// the agent's tables), the agent's alone, the slots alone, neither (PM = 1: the MDPs are read in global memory).  The shared
+// noise cdf (a.lds_bytes - a.lds_noise bytes) is in every sum.  The slots are candidates up to 64 KiB per workgroup (256 B
+// per lane): the bound closed_loop_refusal puts on a shared MDP's staged tables, here a placement -- 20 x 20 (608 B per lane)
+// reads its MDPs in global memory.  granted(q, slots, bytes) as above.
+inline size_t closed_pm_slots_lds_bytes(const mdpp_env *h) { return (size_t)kBlock * (size_t)h->dargs.lds_noise; }
+template <class Granted>
+inline void closed_agent_lds_pm(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &mlds) {
+    const DiscreteArgs &a = h->dargs;
+    const size_t fixed = (size_t)(a.lds_bytes - a.lds_noise), slots = closed_pm_slots_lds_bytes(h);
+    const bool m_ok = a.rew_in_lds && !(h->opts & MDPP_OPT_NO_PM_LDS) && slots <= 64u * 1024u;
+    const bool q_ok = q_lds != 0 && !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u;
+    qlds = mlds = false;
+    if (q_ok && m_ok && granted(true, true, fixed + slots + q_lds)) qlds = mlds = true;
+    else if (q_ok && granted(true, false, fixed + q_lds)) qlds = true;
+    else if (m_ok && granted(false, true, fixed + slots)) mlds = true;
 }
 inline NoiseLevelArgs noise_level_args(const mdpp_env *h, uint32_t cdf_lds) {
     return NoiseLevelArgs{(const uint8_t *)h->d_nl_level, (const double *)h->d_nl_sigma, (const double *)h->d_nl_cdf,

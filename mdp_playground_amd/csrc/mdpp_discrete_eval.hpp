@@ -18,10 +18,14 @@
 // step.  NLEV = 1 (per-env noise levels, mdpp_set_noise_levels) is the same agent around the NLEV form of the step, NOISE = 1
 // always; the per-level cdfs, when staged, lie between the MDP's tables and the Q-tables in LDS.
 //
-// launch_eval_form<SUMMARY, NLEV> launches one form.  Each of the four is instantiated in a translation unit of its own, so
-// that they compile in parallel: mdpp_discrete_eval.hip holds the plain rollout form and the dispatcher,
-// mdpp_discrete_eval_{summary,nlev,nlev_summary}.hip one explicit instantiation each; every other unit sees the `extern
-// template` below.
+// PM = 1 / 2 (one MDP per env, mdpp_learner_per_env_mdp) is the same agent around the PM form of the step, NLEV = 0 always; the
+// Q-tables lie behind the envs' MDP slots and the shared noise cdf in LDS (closed_agent_lds_offset).
+//
+// launch_eval_form<SUMMARY, NLEV> launches one form, launch_eval_form_pm<SUMMARY> the PM = 1 and PM = 2 kernels of one form on a
+// handle with one MDP per env.  Each of the six is instantiated in a translation unit of its own, so that they compile in
+// parallel: mdpp_discrete_eval.hip holds the plain rollout form and the dispatcher,
+// mdpp_discrete_eval_{summary,nlev,nlev_summary,pm,pm_summary}.hip one explicit instantiation each; every other unit sees the
+// `extern template` below.
 #pragma once
 #include "mdpp_discrete_closed.hpp"
 
@@ -71,39 +75,43 @@ struct EvalAgent {
     __device__ __forceinline__ void finish(uint32_t) {}
 };
 
-template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool DOUBLE, bool NLEV = false>
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool DOUBLE, bool NLEV = false, int PM = 0>
 __global__ __launch_bounds__(kBlock) void k_discrete_eval_rollout(DiscreteArgs a, std::conditional_t<NLEV, EvalArgsNL, EvalArgs> p, int K,
                                                                   void *__restrict__ obs,
                                                                   float *__restrict__ reward,
                                                                   uint8_t *__restrict__ term,
                                                                   uint8_t *__restrict__ trunc) {
     static_assert(!NLEV || NOISE, "per-env noise levels are levels of a NOISE step");
+    static_assert(PM == 0 || !NLEV, "one MDP per env runs without per-env noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
-    unsigned char *q_lds = lds + a.lds_bytes;           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    unsigned char *q_lds = lds + closed_agent_lds_offset<PM>(a);    // the agent's LDS: behind the MDP's tables and the per-level cdfs
     if constexpr (NLEV) q_lds += p.nl.lds_bytes;
     EvalAgent<QLDS, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
     if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, false, NLEV>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent, EpisodeSummaryArgs{}, p.nl);
+    else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, false, false, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
     else closed_loop_rollout<PHILOX, NOISE, UNIT>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
 }
 
 // ... keeping episode summaries instead of writing the [K][N] arrays
-template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool DOUBLE, bool NLEV = false>
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool DOUBLE, bool NLEV = false, int PM = 0>
 __global__ __launch_bounds__(kBlock) void k_discrete_eval_summary(DiscreteArgs a, std::conditional_t<NLEV, EvalArgsNL, EvalArgs> p, int K, EpisodeSummaryArgs sm) {
     static_assert(!NLEV || NOISE, "per-env noise levels are levels of a NOISE step");
+    static_assert(PM == 0 || !NLEV, "one MDP per env runs without per-env noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
-    unsigned char *q_lds = lds + a.lds_bytes;           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    unsigned char *q_lds = lds + closed_agent_lds_offset<PM>(a);    // the agent's LDS: behind the MDP's tables and the per-level cdfs
     if constexpr (NLEV) q_lds += p.nl.lds_bytes;
     EvalAgent<QLDS, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
     if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
+    else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
     else closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
 
-template <bool SUMMARY, bool PH, bool NZ, bool UNIT, bool QL, bool DOUBLE, bool NLEV>
+template <bool SUMMARY, bool PH, bool NZ, bool UNIT, bool QL, bool DOUBLE, bool NLEV, int PM = 0>
 constexpr auto eval_kernel() {
-    if constexpr (SUMMARY) return k_discrete_eval_summary<PH, NZ, UNIT, QL, DOUBLE, NLEV>;
-    else return k_discrete_eval_rollout<PH, NZ, UNIT, QL, DOUBLE, NLEV>;
+    if constexpr (SUMMARY) return k_discrete_eval_summary<PH, NZ, UNIT, QL, DOUBLE, NLEV, PM>;
+    else return k_discrete_eval_rollout<PH, NZ, UNIT, QL, DOUBLE, NLEV, PM>;
 }
 
 // K evaluation steps of one form (NLEV: of a handle with per-env noise levels -- NOISE = 1 whatever its keys)
@@ -139,10 +147,44 @@ int launch_eval_form(mdpp_env *h, const DiscreteIO &io) {
     return rc;
 }
 
-// the forms built <SUMMARY, NLEV>, each defined (an explicit instantiation) in the translation unit named
+// K evaluation steps of one form on a handle with one MDP per env (mdpp_learner_per_env_mdp): the PM = 1 and PM = 2 kernels
+template <bool SUMMARY>
+int launch_eval_form_pm(mdpp_env *h, const DiscreteIO &io) {
+    const DiscreteArgs &a = h->dargs;
+    const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
+    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (dbl ? 2u : 1u);
+    int rc = MDPP_OK;
+    // (the queue of start states drawn ahead needs shared tables: the PM kernels do not carry it)
+    if (a.fast_ok || a.shared_tables) { h->err = "mdpp_step_n_eval: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
+    with_bools([&](auto PH, auto NZ, auto UNIT, auto DB) {
+        // the placement, as for the learners
+        bool qlds = false, mlds = false;
+        closed_agent_lds_pm(h, q_lds, [&](bool q, bool m, size_t bytes) {
+            const void *k = nullptr;
+            with_bools([&](auto QL, auto ML) { k = (const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), false, ML() ? 2 : 1>(); }, q, m);
+            return dynamic_lds_ok(k, bytes);
+        }, qlds, mlds);
+        with_bools([&](auto QL, auto ML) {
+            constexpr int PM = ML() ? 2 : 1;
+            char name[kNameLen];
+            snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,DOUBLE=%d,PM=%d>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
+                     PH(), NZ(), UNIT(), QL(), DB(), PM);
+            rc = launch_closed_loop<SUMMARY>(h, io, eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), false, PM>(),
+                                             (size_t)closed_agent_lds_offset<PM>(a) + (QL() ? q_lds : 0u), true, name, [&](int, int, int32_t *actions) {
+                return EvalArgs{(const float *)h->d_learn_q, actions};
+            });
+        }, qlds, mlds);
+    }, a.philox != 0, a.has_p_noise || a.has_r_noise, a.unit_rewards != 0, dbl);
+    return rc;
+}
+
+// the forms built <SUMMARY, NLEV> and, with one MDP per env, <SUMMARY>, each defined (an explicit instantiation) in the
+// translation unit named
 extern template int launch_eval_form<false, false>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_eval.hip
 extern template int launch_eval_form<true, false>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_eval_summary.hip
 extern template int launch_eval_form<false, true>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_eval_nlev.hip
 extern template int launch_eval_form<true, true>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_eval_nlev_summary.hip
+extern template int launch_eval_form_pm<false>(mdpp_env *, const DiscreteIO &);         // mdpp_discrete_eval_pm.hip
+extern template int launch_eval_form_pm<true>(mdpp_env *, const DiscreteIO &);          // mdpp_discrete_eval_pm_summary.hip
 
 } // namespace mdpp

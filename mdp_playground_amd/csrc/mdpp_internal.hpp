@@ -338,6 +338,9 @@ struct mdpp_env {
     int32_t learn_q_tables;
     void *d_learn_alpha, *d_learn_gamma, *d_learn_E;
     uint32_t learn_pe, learn_pe_stale;
+    // mdpp_learner_per_env_mdp: the learner and evaluation launches serve this handle's one MDP per env (their PM forms; only
+    // ever set on a discrete handle with num_tables == num_envs != 1)
+    bool learn_pm;
     // Per-env noise levels (mdpp_set_noise_levels; mdpp_discrete_closed.hpp NoiseLevelArgs): nl_on: the learner and evaluation
     // launches take their NLEV form and every other step launch is refused.  Device: the level byte and the sigma of every
     // env, the per-level cdfs [levels][S][S] and (T, M) pairs; host: the values in force, for mdpp_get_noise_levels.
@@ -556,7 +559,7 @@ std::string discrete_learn_refusal(const mdpp_env *h);
 int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io);
 int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t s);
 // (the learner's forms -- per-env hyper-parameters, double Q-learning, episode summaries with io.summary, per-env noise
-// levels -- are instantiations of mdpp_discrete_learn.hpp's launch_learn_form, one translation unit each
+// levels, one MDP per env -- are instantiations of mdpp_discrete_learn.hpp's launch_learn_form, one translation unit each
 // (mdpp_discrete_learn_*.hip); launch_discrete_learn picks the handle's)
 // io.K steps of greedy evaluation of the learner's tables (mdpp_discrete_eval.hip; the forms with io.summary or per-env noise
 // levels: mdpp_discrete_eval.hpp's launch_eval_form, in mdpp_discrete_eval_{summary,nlev,nlev_summary}.hip)

@@ -95,6 +95,7 @@ class RLToyVectorEnv:
         self._learn_q_init = None             # the tensor last handed to set_learner / set_q, kept until its copy has been made
         self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
+        self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
                 raise ValueError("num_envs != len(seeds)")
@@ -768,30 +769,52 @@ class RLToyVectorEnv:
         rc = self._lib.mdpp_set_learner_params(self._h, capi.nptr(alpha), capi.nptr(gamma), capi.nptr(epsilon), self._stream())
         self._closed_call(rc, "mdpp_set_learner_params")
 
-    def set_learner(self, algo="q_learning", *, alpha=None, gamma=None, epsilon=None, seed=0, q=None):
+    def set_learner(self, algo="q_learning", *, alpha=None, gamma=None, epsilon=None, seed=0, q=None, per_env_mdp=False):
         """The handle's tabular TD learner for rollout_learn(): one independent agent PER ENV, ``algo`` "q_learning", "sarsa" or
         "double_q", float32 ``alpha`` in (0, 1], ``gamma`` and ``epsilon`` in [0, 1] -- each a scalar (uniform) or a 1-D array of
         num_envs entries (numpy, or a torch tensor on any device; env i of THIS handle learns with entry i), ``seed`` the 64-bit
         key of the learner's own Philox streams, ``q`` the initial tables (float32 [N, S, A] on the device, [N, 2, S, A] -- A
         then B -- for "double_q"; zeros when None).  ``set_learner(None)`` clears the learner.  Handles the kernel does not
-        serve raise NotImplementedError with the reason (include/mdpp.h: the rule)."""
+        serve raise NotImplementedError with the reason (include/mdpp.h: the rule).
+        ``per_env_mdp=True`` on a handle built with ``seeds=[...]`` or ``mdps=[...]``: every agent learns on its OWN env's
+        MDP -- a seed sweep in one launch; rollout_learn, rollout_eval, their summary= forms, get_q / set_q
+        and set_learner_rates then serve the handle, set_policy and set_noise_levels still refuse it.  Without it such a
+        handle is refused as ever -- also while a per_env_mdp learner is in force: that refused call leaves learner and tables as
+        they are (``set_learner(None)`` is how to drop them).  A call the library refuses leaves the opt-in as it was.
+        ValueError on a handle with one shared MDP; ``set_learner(None)`` clears it too."""
         if algo is None:
             capi.check(self._lib, self._h, self._lib.mdpp_clear_learner(self._h), "mdpp_clear_learner")
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_per_env_mdp(self._h, 0), "mdpp_learner_per_env_mdp")
             self._learn_rates = None
+            self._learn_pm = False
             return
         if alpha is None or gamma is None or epsilon is None:
             raise ValueError("set_learner: alpha, gamma and epsilon are required")
         policy_mod.check_learner_params(algo, alpha, gamma, epsilon, self.num_envs)
         arrays = [policy_mod.learner_param_array(n, v, self.num_envs) for n, v in (("alpha", alpha), ("gamma", gamma), ("epsilon", epsilon))]
+        if per_env_mdp and not self._per_env:
+            raise ValueError("set_learner: per_env_mdp=True needs one MDP per env (seeds=[...] or mdps=[...]); this handle has one shared MDP")
         self._learn_check_kind()
         if q is not None:
             q = self._learn_q_arg(q, "set_learner", algo)
+        if self._learn_pm and not per_env_mdp:
+            # (the call without the opt-in, refused as on a handle that never had it -- before the handle is touched)
+            raise NotImplementedError("mdpp_set_learner: learner rollouts need one shared MDP (this handle has one MDP per env: "
+                                      "seeds=[...]); the per_env_mdp=True learner in force stays as it is")
+        if per_env_mdp and not self._learn_pm:
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_per_env_mdp(self._h, 1), "mdpp_learner_per_env_mdp")
         # (a per-env parameter's scalar slot: any valid value -- the kernel's PE form does not read it)
         scalars = [float(v) if a is None else float(a[0]) for v, a in zip((alpha, gamma, epsilon), arrays)]
         code = dict(capi.LEARN_ALGOS, double_q=capi.MDPP_LEARN_DOUBLE_Q)[algo]
         rc = self._lib.mdpp_set_learner(self._h, code, *scalars, C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                         C.c_void_p(q.data_ptr()) if q is not None else None, self._stream())
+        if rc == capi.EUNSUPPORTED and per_env_mdp and not self._learn_pm:
+            # (refused for another reason: the opt-in goes back to what it was.  Read the reason first: the flag call keeps it)
+            msg = self._lib.mdpp_last_error(self._h)
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_per_env_mdp(self._h, 0), "mdpp_learner_per_env_mdp")
+            raise NotImplementedError(msg.decode() if msg else "mdpp_set_learner: unsupported")
         self._closed_call(rc, "mdpp_set_learner")
+        self._learn_pm = bool(per_env_mdp)
         self._learn_q_init = q           # (kept until the copy queued on the stream has certainly been made)
         self._learn_rates = [scalars[0], scalars[2]]
         self._learn_algo = algo
@@ -886,7 +909,7 @@ class RLToyVectorEnv:
     def learn_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
         launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning; NLEV=1: per-env
-        noise levels, set_noise_levels); empty for a handle it does not serve."""
+        noise levels, set_noise_levels; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory); empty for a handle it does not serve."""
         if self.kind != "discrete":
             return ""
         name = self._lib.mdpp_learn_kernel_name(self._h, int(K))
@@ -924,7 +947,7 @@ class RLToyVectorEnv:
         if all(a is None for a in arrays.values()):
             return
         rc = self._lib.mdpp_set_noise_levels(self._h, capi.nptr(arrays["transition_noise"]), capi.nptr(arrays["reward_noise"]), self._stream())
-        if rc == -4:                         # MDPP_ESTATE: a handle the learner kernels do not serve
+        if rc in (-4, capi.EUNSUPPORTED):    # MDPP_ESTATE: a handle the learner kernels do not serve; ... or one MDP per env
             msg = self._lib.mdpp_last_error(self._h)
             raise NotImplementedError(msg.decode() if msg else "mdpp_set_noise_levels: unsupported")
         capi.check(self._lib, self._h, rc, "mdpp_set_noise_levels")

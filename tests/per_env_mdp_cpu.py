@@ -1,0 +1,126 @@
+"""The closed loop on the CPU with ONE MDP PER ENV (RLToyVectorEnv(seeds=[...]).set_learner(..., per_env_mdp=True)): env i is
+the oracle env of mdp.build_mdp({**cfg, "seed": seeds[i]}) on the Philox streams of global id off + i, driven step by step by
+the learner's restatement tests/learner_sweep_ref.py -- tests/closed_loop_cpu.py's loop, which builds one MDP for all envs,
+with the envs made one by one.  It predicts a whole Philox launch without a GPU and shows on the CPU that the conditions the
+GPU test asserts about itself can be met.  Shared by tests/test_per_env_mdp_host.py and tests/test_gpu_per_env_mdp.py.
+
+The common set-up of both files is here too: N = 320 envs (one full workgroup and 64 lanes of a second), seeds 100 ... 419,
+env_id_offset 1000, K = 37 steps, two launches in a row."""
+import numpy as np
+
+import learner_sweep_ref as ref
+from closed_loop_cpu import make_oracles
+
+N, K, LAUNCHES = 320, 37, 2
+SEEDS = list(range(100, 100 + N))
+OFF = 1000
+PHILOX_SEED = 77
+SEED = (7 << 32) + 4321           # the learner's key, beyond 32 bits
+ALPHA, GAMMA, EPS = 0.3, 0.9, 0.25
+ALGOS = ("q_learning", "sarsa", "double_q")
+
+_D = dict(state_space_type="discrete", action_space_type="discrete")
+_S8 = dict(_D, state_space_size=8, action_space_size=8, delay=0, sequence_length=1)
+# (no "seed" key: the handle's seeds=[...] give it, env by env)
+CASES = {
+    "s8": (_S8, {}),
+    "s8_noise": (dict(_S8, transition_noise=0.1, reward_noise=0.5), {}),
+    "cfg2": (dict(_D, state_space_size=8, action_space_size=8, delay=4, sequence_length=3), {}),
+    "rdist_delay3": (dict(_D, state_space_size=8, action_space_size=8, delay=3, sequence_length=2, reward_dist=[0.5, 1.0]), {}),
+    "s20": (dict(_D, state_space_size=20, action_space_size=20, delay=0, sequence_length=1), {}),
+}
+# what the host test pins and the GPU test re-asserts on the device's result: (envs with non-zero Q in all, ... in each
+# workgroup's lanes, envs that terminate at least once), measured with exactly this set-up and identical for the three
+# algorithms: s8 309 (245 + 64), s8_noise 320 (256 + 64), cfg2 73 (57 + 16), rdist_delay3 187 (144 + 43), s20 319 (256 + 63);
+# every env terminates within the 74 steps but one of s20's
+FLOORS = {"s8": (280, 32, N), "s8_noise": (280, 32, N), "cfg2": (48, 8, N), "rdist_delay3": (120, 8, N), "s20": (280, 32, 300)}
+
+_mdps = {}
+
+
+def build_mdps(cfg, seeds=SEEDS):
+    """mdp.build_mdp({**cfg, "seed": s}) for every seed (kept: a case's MDPs are built once per session)"""
+    from mdp_playground_amd import mdp as mdp_mod
+    key = (repr(sorted(cfg.items(), key=lambda kv: kv[0])), tuple(seeds))
+    if key not in _mdps:
+        _mdps[key] = [mdp_mod.build_mdp({**cfg, "seed": s}) for s in seeds]
+    return _mdps[key]
+
+
+class PerEnvP:
+    """The P argument of learner_sweep_ref.run / learner_ref.run for one MDP per env: P[s, a] with s, a int [n] is
+    P_i[s_i, a_i]"""
+
+    def __init__(self, mdps):
+        self.P = np.stack([np.asarray(m.P) for m in mdps])
+
+    def __getitem__(self, key):
+        s, a = key
+        return self.P[np.arange(self.P.shape[0]), s, a]
+
+
+def closed_loop(cfg, kw, algo, alpha, gamma, epsilon, seeds=SEEDS, q0=None, *, seed=SEED, K=K, launches=LAUNCHES,
+                philox_seed=PHILOX_SEED, off=OFF):
+    """closed_loop_cpu.closed_loop (its arguments, its three results) with env i on the MDP of seeds[i]"""
+    mdps = build_mdps(cfg, seeds)
+    n, m = len(mdps), mdps[0]
+    autoreset, max_steps = kw.get("autoreset", ref.SAME_STEP), kw.get("max_episode_steps", 0)
+    envs = [make_oracles(mi, 1, philox_seed, off + i)[0] for i, mi in enumerate(mdps)]
+    s = np.array([o.reset() for o in envs], np.int64)
+    al, ga, E = ref.per_env(n, alpha, gamma, epsilon)
+    Q = (np.zeros((n, 2, m.S, m.A) if algo == "double_q" else (n, m.S, m.A), np.float32) if q0 is None else q0.copy())
+    pending, steps = np.zeros(n, bool), np.zeros(n, np.int64)
+    info = ref.new_info(n)
+    total = launches * K
+    w = {st: ref.tick_words(seed, off, 0, total + 1, n, st) for st in (ref.EXPLORE_STREAM, ref.ACTION_STREAM, ref.UPDATE_STREAM)}
+    have_carry, carry = np.zeros(n, bool), np.zeros(n, np.int64)
+    traj = {k: np.zeros((total, n), dt) for k, dt in (("actions", np.int64), ("obs", np.int64), ("reward", np.float32), ("terminated", bool),
+                                                       ("truncated", bool), ("reset_call", bool))}
+    traj["obs0"] = s.copy()
+    for t in range(total):
+        live = ~pending
+        if t % K == 0:
+            have_carry[:] = False                        # (a launch's first step selects afresh)
+        fresh, _ = ref.select(algo, Q, s, w[ref.EXPLORE_STREAM][t], w[ref.ACTION_STREAM][t], E, info, ~have_carry)
+        a = np.where(have_carry, carry, fresh)
+        info["carried"] += int(have_carry.sum())
+        info["carried_differs"] += int((have_carry & (carry != fresh)).sum())
+        s2, r, te = s.copy(), np.zeros(n, np.float32), np.zeros(n, bool)
+        for i in np.flatnonzero(live):
+            o, rr, d = envs[i].step(int(a[i]))
+            s2[i], r[i], te[i] = o, np.float32(rr), d
+        steps[live] += 1
+        tr = live & (max_steps > 0) & (steps >= max_steps)
+        a2 = ref.select(algo, Q, s2, w[ref.EXPLORE_STREAM][t + 1], w[ref.ACTION_STREAM][t + 1], E)[0] if algo == "sarsa" else None
+        ref.update(algo, Q, s, a, r, s2, te, live, al, ga, w[ref.UPDATE_STREAM][t], a2, info)
+        cut = live & ~te & tr & (autoreset != ref.DISABLED)
+        have_carry = live & (algo == "sarsa") & ~te & ~cut
+        carry = a2 if a2 is not None else carry
+        ended = live & (te | tr)
+        for i in np.flatnonzero(pending | (ended & (autoreset == ref.SAME_STEP))):
+            if pending[i]:
+                # a next-step reset call takes a tick of its own: the start state is the one of tick t and the env's next step
+                # is tick t + 1 (the oracle's in-step reset draws at its tick - 1 and leaves the tick alone; one explicit
+                # reset() has been made)
+                envs[i].set_philox(philox_seed, off + i, t + 1, 1)
+            s2[i] = envs[i].reset(explicit=False)
+            steps[i] = 0
+        for k, v in (("actions", a), ("obs", s2), ("reward", r), ("terminated", te), ("truncated", tr), ("reset_call", pending)):
+            traj[k][t] = v
+        pending = ended & (autoreset == ref.NEXT_STEP)
+        s = s2
+    return info, Q, traj
+
+
+def nonzero_envs(Q):
+    """bool [n]: the envs whose tables are not all zero"""
+    return (np.asarray(Q) != 0).any(axis=tuple(range(1, np.asarray(Q).ndim)))
+
+
+def check_floors(case, Q, terminated, what=""):
+    """the conditions of FLOORS on a result (Q [n, ...], terminated bool [steps, n]); returns the counts"""
+    total, per_wg, term_floor = FLOORS[case]
+    nz = nonzero_envs(Q)
+    counts = (int(nz.sum()), int(nz[:256].sum()), int(nz[256:].sum()), int(np.asarray(terminated).any(axis=0).sum()))
+    assert counts[0] >= total and counts[1] >= per_wg and counts[2] >= per_wg and counts[3] >= term_floor, (what, case, counts)
+    return counts
