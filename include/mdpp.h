@@ -102,7 +102,9 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
        MDPP_OPT_LEARN_SHORT_PIECES = 1u << 19, /* mdpp_step_n_policy and mdpp_step_n_learn go out in launches of at most 5 steps
                                               (the hand-over between the pieces of a very long call, at a size a test can run) */
        MDPP_OPT_NO_NLEV_LDS = 1u << 20,    /* per-env noise levels (mdpp_set_noise_levels): the per-level cdfs stay in global memory */
-       MDPP_OPT_NO_PM_LDS = 1u << 21 };    /* one MDP per env (mdpp_learner_per_env_mdp): the envs' tables stay in global memory (PM=1) */
+       MDPP_OPT_NO_PM_LDS = 1u << 21,      /* one MDP per env (mdpp_learner_per_env_mdp): the envs' tables stay in global memory (PM=1) */
+       MDPP_OPT_NO_PM_NLEV_LDS = 1u << 22 }; /* per-env noise levels on one MDP per env (mdpp_noise_levels_per_env_mdp): the per-level cdfs stay
+                                              in global memory in the PM kernels (MDPP_OPT_NO_NLEV_LDS keeps its meaning for a shared MDP) */
 
 /* transition-noise levels one handle serves at a time (mdpp_set_noise_levels) */
 #define MDPP_MAX_NOISE_LEVELS 16
@@ -402,8 +404,8 @@ int mdpp_set_learner_gamma(mdpp_env *h, float gamma);
  * On a handle with one shared MDP, or one that is not discrete, the call is accepted and changes nothing.  Turning the flag
  * off (on a handle it was on for) clears the learner.  Whatever the flag: mdpp_set_policy and mdpp_step_n_policy refuse one
  * MDP per env ("need one shared MDP"), and mdpp_set_noise_levels on a flagged handle with one MDP per env returns
- * MDPP_EUNSUPPORTED ("per-env noise levels on one MDP per env: not built").  Without the flag such a handle is refused by
- * every learner entry point as before, message included.
+ * MDPP_EUNSUPPORTED ("per-env noise levels on one MDP per env: not built") unless mdpp_noise_levels_per_env_mdp (below) has
+ * opted in.  Without the flag such a handle is refused by every learner entry point as before, message included.
  * Under a graph capture the form (PM and QLDS) is fixed at capture like PE; the tables are read from the handle's buffers at
  * replay. */
 int mdpp_learner_per_env_mdp(mdpp_env *h, int on);
@@ -465,6 +467,26 @@ int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream);
 int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream);
 int mdpp_get_noise_levels(mdpp_env *h, double *transition_noise_out, double *reward_noise_out);
 int mdpp_clear_noise_levels(mdpp_env *h);
+
+/* Per-env noise levels on one MDP per env: a noise x seed sweep in one launch.  mdpp_noise_levels_per_env_mdp(h, on) sets a
+ * second flag of the handle, off at creation.  With it off, mdpp_set_noise_levels on a handle with cfg.num_tables != 1 returns
+ * exactly what it returned before the flag existed (MDPP_ESTATE "need one shared MDP" without mdpp_learner_per_env_mdp,
+ * MDPP_EUNSUPPORTED "... not built" with it).  With it on AND mdpp_learner_per_env_mdp on, mdpp_set_noise_levels proceeds: every
+ * rule of the section above holds word for word (the values, the level bytes, sigma, (T, M), the limit of
+ * MDPP_MAX_NOISE_LEVELS, the errors), and env i behaves bit for bit (outputs, Q-tables, state record, env and space streams,
+ * status, step counter) like env i of a handle with the same table sets, created uniformly with transition_noise[i] and
+ * reward_noise[i], that runs the per-env-MDP learner.  The per-level cdfs depend on S and p only: they stay one
+ * [levels][S][S] table shared by the envs' MDPs.
+ * The launch is the kernel's NLEV form with PM != 0; its name ends ",NLEV=1,PM=1>" or ",NLEV=1,PM=2>".  Placement per launch,
+ * never a refusal: the Q-tables (at most 160 KiB, not under MDPP_OPT_NO_LEARN_LDS), the envs' MDP slots (at most 64 KiB, not
+ * under MDPP_OPT_NO_PM_LDS) and the per-level cdfs (at most 32 KiB, numpy streams with the transition key only, not under
+ * MDPP_OPT_NO_PM_NLEV_LDS) go to LDS in the first of these subsets the device grants: {Q, slots, cdfs}, {Q, slots}, {Q, cdfs},
+ * {Q}, {slots, cdfs}, {slots}, {cdfs}, {}.  The handle's own shared cdf is not staged; the per-level cdfs lie in its place
+ * (behind the slots for PM=2, at the start of dynamic LDS for PM=1), the Q-tables behind them.
+ * On a handle with one shared MDP, or one that is not discrete, the call is accepted and changes nothing.  Turning this flag
+ * off, or mdpp_learner_per_env_mdp off, on a handle with one MDP per env also clears the levels (mdpp_clear_noise_levels) and
+ * this flag.  mdpp_step, mdpp_step_n and mdpp_set_policy refuse as in the two sections above. */
+int mdpp_noise_levels_per_env_mdp(mdpp_env *h, int on);
 
 /* Per-env internal state <-> host (synchronous; checkpoint / set_augmented_state).
  * Discrete: hist int32[N][L+1] (-1 = NaN slot), steps int32[N], ring double[N][delay].
@@ -530,14 +552,17 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   mdpp_set_learner*, mdpp_set_noise_levels, ...) may do all three and are not for a capture.
  *   What a captured launch carries BY VALUE (a replay uses what was in force at capture; change it and capture again): K and
  *   the caller's buffers, the kernel and its form (kernel options, the learner's algorithm, uniform or per-env parameters,
- *   levels or none, one MDP per env and where its tables are placed), the policy's and the learner's seeds, the UNIFORM
+ *   levels or none, one MDP per env and where its tables are placed -- PM, QLDS and NLEV are fixed at capture), the policy's
+ *   and the learner's seeds, the UNIFORM
  *   alpha, gamma and epsilon (mdpp_set_learner_rates / mdpp_set_learner_gamma after the capture do not reach a replay; an
  *   eager launch uses them), the NUMBER of noise levels and where their cdfs are staged.
  *   What it READS from the handle's buffers at replay (replace it between replays, on the replay's stream): the actions
  *   tensor of mdpp_step_n, the policy's thresholds (mdpp_set_policy with the same seed), the Q-tables (mdpp_set_q), the per-env
  *   alpha / gamma / epsilon arrays (mdpp_set_learner_params: the way to change rates under a graph), the per-env noise
  *   levels' values (mdpp_set_noise_levels with the same number of distinct transition levels), the caller's five summary
- *   arrays (they accumulate across replays), the env's state record, streams and tables.
+ *   arrays (they accumulate across replays), the env's state record, streams and tables.  Per-env noise levels on one MDP
+ *   per env (mdpp_noise_levels_per_env_mdp) are no exception: the level bytes, sigma, the per-level cdfs and (T, M) and every
+ *   env's table set are read from the handle's buffers at replay.
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

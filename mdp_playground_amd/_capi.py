@@ -23,7 +23,8 @@ OPTIONS = {"NO_PIPE": 1 << 0, "NO_HELPER": 1 << 1, "NO_PARK": 1 << 2, "NO_CFAST"
            "NO_QUIET_NOISE": 1 << 5, "NO_DUO": 1 << 6, "NO_TRIO": 1 << 7, "NO_GFAST": 1 << 8,
            "NO_GFAST_NOISE": 1 << 9, "NO_IMGFAST": 1 << 10, "NO_IMG_OVERLAP": 1 << 11, "NO_PHILOX_FAST": 1 << 12, "NO_LEAN": 1 << 13,
            "NO_IMG_NEARTAB": 1 << 14, "NO_STEP1": 1 << 15, "NO_SIGMA0": 1 << 16, "NO_QUIET_SF": 1 << 17,
-           "NO_LEARN_LDS": 1 << 18, "LEARN_SHORT_PIECES": 1 << 19, "NO_NLEV_LDS": 1 << 20, "NO_PM_LDS": 1 << 21}
+           "NO_LEARN_LDS": 1 << 18, "LEARN_SHORT_PIECES": 1 << 19, "NO_NLEV_LDS": 1 << 20, "NO_PM_LDS": 1 << 21,
+           "NO_PM_NLEV_LDS": 1 << 22}
 MAX_NOISE_LEVELS = 16                              # MDPP_MAX_NOISE_LEVELS
 LEARN_ALGOS = {"q_learning": 0, "sarsa": 1}        # MDPP_LEARN_*: the one-table algorithms
 MDPP_LEARN_DOUBLE_Q = 2                            # "double_q": two tables per env
@@ -51,6 +52,7 @@ EXPORTS = [
     "mdpp_learn_kernel_name", "mdpp_set_learner_params", "mdpp_set_learner_gamma",
     "mdpp_step_n_eval", "mdpp_eval_kernel_name", "mdpp_step_n_learn_summary", "mdpp_step_n_eval_summary", "mdpp_current_obs",
     "mdpp_set_noise_levels", "mdpp_get_noise_levels", "mdpp_clear_noise_levels", "mdpp_learner_per_env_mdp",
+    "mdpp_noise_levels_per_env_mdp",
 ]
 
 
@@ -183,6 +185,7 @@ def load():
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]
     L.mdpp_learner_per_env_mdp.argtypes = [vp, i32]
+    L.mdpp_noise_levels_per_env_mdp.argtypes = [vp, i32]
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

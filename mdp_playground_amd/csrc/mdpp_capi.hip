@@ -122,7 +122,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->learn_algo = MDPP_LEARN_Q_LEARNING; h->learn_ready = false;
     h->learn_q_tables = 0; h->d_learn_alpha = h->d_learn_gamma = h->d_learn_E = nullptr; h->learn_pe = h->learn_pe_stale = 0;
     h->learn_pm = false;
-    h->nl_on = false; h->nl_levels = 0; h->nl_fill_valid = false; h->nl_fill_alpha = h->nl_fill_gamma = 0.0f; h->nl_fill_E = 0;
+    h->nl_on = false; h->nl_pm = false; h->nl_levels = 0; h->nl_fill_valid = false; h->nl_fill_alpha = h->nl_fill_gamma = 0.0f; h->nl_fill_E = 0;
     h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
@@ -1444,8 +1444,21 @@ extern "C" int mdpp_learner_per_env_mdp(mdpp_env *h, int on) {
     if (!h) return MDPP_EINVAL;
     // (a shared MDP, or no discrete handle: accepted, nothing changes)
     if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
-    if (h->learn_pm && !on) h->learn_ready = false;      // (as mdpp_clear_learner: the buffers stay)
+    if (h->learn_pm && !on) {
+        h->learn_ready = false;                          // (as mdpp_clear_learner: the buffers stay)
+        if (h->nl_pm) h->nl_on = false;                  // ... and levels given on one MDP per env go with the learner that ran them
+        h->nl_pm = false;
+    }
     h->learn_pm = on != 0;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_noise_levels_per_env_mdp(mdpp_env *h, int on) {
+    if (!h) return MDPP_EINVAL;
+    // (a shared MDP, or no discrete handle: accepted, nothing changes)
+    if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
+    if (h->nl_pm && !on) h->nl_on = false;               // (as mdpp_clear_noise_levels: the buffers stay)
+    h->nl_pm = on != 0;
     return MDPP_OK;
 }
 
@@ -1513,7 +1526,7 @@ extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise
     if (!h) return MDPP_EINVAL;
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: " + why);
-    if (h->cfg.num_tables != 1) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_noise_levels: per-env noise levels on one MDP per env: not built");
+    if (h->cfg.num_tables != 1 && !(h->nl_pm && h->learn_pm)) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_noise_levels: per-env noise levels on one MDP per env: not built");
     const mdpp_config &c = h->cfg;
     if (transition_noise && !c.has_transition_noise)
         return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: transition_noise: the handle was created without the key (it needs transition_noise > 0: the space streams and the NOISE kernels)");

@@ -45,7 +45,7 @@
 // the host found room, else read in global memory.  The handle's own cdf (a.noise_cdf / a.lds_noise) is not staged.
 // A compile-time choice like SUMMARY: the NLEV = false instantiations are the code they were.
 //
-// PM (one MDP per env, mdpp_learner_per_env_mdp; NLEV = false only): 0 is the shared MDP above.  PM = 1: lane i reads table
+// PM (one MDP per env, mdpp_learner_per_env_mdp): 0 is the shared MDP above.  PM = 1: lane i reads table
 // set i of a.P / is_term / init_cdf / rbits / rtable in global memory, with k_discrete_step's strides.  PM = 2: the lane stages
 // its own set once per launch into LDS, laid out as the learners lay out Q: dword w of lane tid at byte (w 256 + tid) 4, w
 // counted in the handle's own carve (a.lds_P / 4 ..., a.lds_noise / 4 dwords per lane).  Bank = lane: no conflict whatever
@@ -56,6 +56,13 @@
 // the agent's LDS behind it (closed_agent_lds_offset).  There is no queue of start states (fast_ok needs shared tables).
 // A compile-time choice, so that every table pointer has one provenance (ds_read or global_load, never flat); the PM = 0
 // instantiations are the code they were.
+//
+// NLEV with PM != 0 (mdpp_noise_levels_per_env_mdp: a noise x seed sweep in one launch): both of the above at once.  The
+// per-level cdfs depend on S and p only, so they stay ONE [levels][S][S] table shared by the envs' MDPs; they take the place
+// of the handle's own cdf, which is not staged: at closed_noise_lds_offset<PM> (behind the slots for PM = 2, at the start of
+// dynamic LDS for PM = 1), nl.lds_bytes of them, the agent's LDS behind (closed_agent_lds_offset with nl.lds_bytes).  The
+// workgroup stages the cdfs co-operatively and every lane its slots (tail lanes: set N - 1) BEFORE the barrier and the
+// `i >= N` return; the level byte, sigma and (T, M) are loaded after it, so no tail lane reads level[i] beyond N.
 #pragma once
 #include "mdpp_internal.hpp"
 #include "mdpp_rng.hpp"
@@ -128,6 +135,16 @@ template <int PM>
 __host__ __device__ __forceinline__ uint32_t closed_agent_lds_offset(const DiscreteArgs &a) {
     return PM == 0 ? a.lds_bytes : closed_noise_lds_offset<PM>(a) + (a.lds_bytes - a.lds_noise);
 }
+// ... in an NLEV kernel, whose per-level cdfs (nl_lds bytes; 0: they are read in global memory) lie where the shared cdf
+// would: behind the whole carve (PM = 0: the shared cdf keeps its room, unstaged), in its place (PM != 0)
+template <int PM>
+__host__ __device__ __forceinline__ uint32_t closed_nlev_lds_offset(const DiscreteArgs &a) {
+    return PM == 0 ? a.lds_bytes : closed_noise_lds_offset<PM>(a);
+}
+template <int PM>
+__host__ __device__ __forceinline__ uint32_t closed_agent_lds_offset(const DiscreteArgs &a, uint32_t nl_lds) {
+    return closed_nlev_lds_offset<PM>(a) + nl_lds;
+}
 
 // (a is the kernel's by-value argument, taken by const reference: see tick_now in mdpp_internal.hpp for what a write costs)
 template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, bool NLEV = false, int PM = 0, class Agent>
@@ -138,7 +155,6 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
                                                     const EpisodeSummaryArgs &sm = EpisodeSummaryArgs{},
                                                     const NoiseLevelArgs &nl = NoiseLevelArgs{}) {
     static_assert(NOISE || !NLEV, "per-env noise levels are levels of a NOISE kernel");
-    static_assert(PM == 0 || !NLEV, "per-env noise levels on one MDP per env: not built");
     const uint64_t ptick0 = tick_now(a);               // the step counter at this launch (through the device-side offset of a graph replay)
     const uint32_t rhead0 = ring_head_now(a, ptick0);  // ... and the head of a delay line kept in memory
     const int tid = threadIdx.x;
@@ -171,7 +187,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
         for (int k = tid; k < S * S; k += kBlock) ((double *)(lds + (PM == 0 ? a.lds_noise : closed_noise_lds_offset<PM>(a))))[k] = a.noise_cdf[k];
     if constexpr (NLEV) {
         if (!PHILOX && a.has_p_noise && nl.lds_bytes != 0u)
-            for (uint32_t k = tid; k < nl.levels * (uint32_t)(S * S); k += kBlock) ((double *)(lds + a.lds_bytes))[k] = nl.cdf[k];
+            for (uint32_t k = tid; k < nl.levels * (uint32_t)(S * S); k += kBlock) ((double *)(lds + closed_nlev_lds_offset<PM>(a)))[k] = nl.cdf[k];
     }
     agent.stage(tid);
     __syncthreads();
@@ -304,7 +320,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
                 else if (lane_T != 0u) {            // (a lane of level 0 makes no draw: its space stream does not move)
                     const double u = np_random(sp_pcg);
                     const uint32_t row = lane_cdf + nxt * (uint32_t)S;
-                    if (nl.lds_bytes != 0u) nxt = (uint32_t)searchsorted_right((const double *)(lds + a.lds_bytes) + row, S, u);
+                    if (nl.lds_bytes != 0u) nxt = (uint32_t)searchsorted_right((const double *)(lds + closed_nlev_lds_offset<PM>(a)) + row, S, u);
                     else nxt = (uint32_t)searchsorted_right(nl.cdf + row, S, u);
                 }
             }
@@ -466,6 +482,26 @@ inline void closed_agent_lds_pm(const mdpp_env *h, size_t q_lds, Granted &&grant
     if (q_ok && m_ok && granted(true, true, fixed + slots + q_lds)) qlds = mlds = true;
     else if (q_ok && granted(true, false, fixed + q_lds)) qlds = true;
     else if (m_ok && granted(false, true, fixed + slots)) mlds = true;
+}
+// ... on such a handle with per-env noise levels (mdpp_noise_levels_per_env_mdp; the NLEV kernels with PM != 0): three
+// candidates, ranked by what leaving each in global memory was measured to cost -- the agent's tables (+49-56 %), the MDP
+// slots (+17-26 %), the per-level cdfs (+15-18 %) -- so the subsets are tried in the order {Q, slots, cdfs}, {Q, slots},
+// {Q, cdfs}, {Q}, {slots, cdfs}, {slots}, {cdfs}, {}.  Each candidate keeps its bound and its option from the two rules above;
+// the cdfs' option here is MDPP_OPT_NO_PM_NLEV_LDS.  The handle's own shared cdf is not staged by these kernels and is in
+// no sum.  granted(q, slots, cdfs, bytes) as above.
+template <class Granted>
+inline void closed_agent_lds_pm_nlev(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &mlds, bool &clds) {
+    const DiscreteArgs &a = h->dargs;
+    const size_t slots = closed_pm_slots_lds_bytes(h), cdf = noise_levels_cdf_lds_bytes(h);
+    const bool q_ok = q_lds != 0 && !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u;
+    const bool m_ok = a.rew_in_lds && !(h->opts & MDPP_OPT_NO_PM_LDS) && slots <= 64u * 1024u;
+    const bool c_ok = !a.philox && a.has_p_noise && cdf <= 32u * 1024u && !(h->opts & MDPP_OPT_NO_PM_NLEV_LDS);
+    qlds = mlds = clds = false;
+    for (unsigned drop = 0; drop < 8u; drop++) {        // bit 2: without Q, bit 1: without the slots, bit 0: without the cdfs
+        const bool q = !(drop & 4u), m = !(drop & 2u), c = !(drop & 1u);
+        if ((q && !q_ok) || (m && !m_ok) || (c && !c_ok)) continue;
+        if (drop == 7u || granted(q, m, c, (q ? q_lds : 0u) + (m ? slots : 0u) + (c ? cdf : 0u))) { qlds = q; mlds = m; clds = c; return; }
+    }
 }
 inline NoiseLevelArgs noise_level_args(const mdpp_env *h, uint32_t cdf_lds) {
     return NoiseLevelArgs{(const uint8_t *)h->d_nl_level, (const double *)h->d_nl_sigma, (const double *)h->d_nl_cdf,

@@ -11,7 +11,7 @@ int launch_discrete_eval(mdpp_env *h, const DiscreteIO &io) {
     if (!why.empty()) { h->err = "mdpp_step_n_eval: " + why; return MDPP_EUNSUPPORTED; }
     int rc = MDPP_OK;
     if (h->learn_pm && h->cfg.num_tables != 1) {                 // one MDP per env: the PM kernels
-        with_bools([&](auto SM) { rc = launch_eval_form_pm<SM()>(h, io); }, io.summary != nullptr);
+        with_bools([&](auto SM, auto NL) { rc = launch_eval_form_pm<SM(), NL()>(h, io); }, io.summary != nullptr, h->nl_on);
         return rc;
     }
     with_bools([&](auto SM, auto NL) { rc = launch_eval_form<SM(), NL()>(h, io); }, io.summary != nullptr, h->nl_on);

@@ -18,14 +18,15 @@
 // step.  NLEV = 1 (per-env noise levels, mdpp_set_noise_levels) is the same agent around the NLEV form of the step, NOISE = 1
 // always; the per-level cdfs, when staged, lie between the MDP's tables and the Q-tables in LDS.
 //
-// PM = 1 / 2 (one MDP per env, mdpp_learner_per_env_mdp) is the same agent around the PM form of the step, NLEV = 0 always; the
-// Q-tables lie behind the envs' MDP slots and the shared noise cdf in LDS (closed_agent_lds_offset).
+// PM = 1 / 2 (one MDP per env, mdpp_learner_per_env_mdp) is the same agent around the PM form of the step; the Q-tables lie
+// behind the envs' MDP slots and the shared noise cdf in LDS (closed_agent_lds_offset) -- with NLEV = 1
+// (mdpp_noise_levels_per_env_mdp) behind the per-level cdfs, which take the shared cdf's place.
 //
-// launch_eval_form<SUMMARY, NLEV> launches one form, launch_eval_form_pm<SUMMARY> the PM = 1 and PM = 2 kernels of one form on a
-// handle with one MDP per env.  Each of the six is instantiated in a translation unit of its own, so that they compile in
-// parallel: mdpp_discrete_eval.hip holds the plain rollout form and the dispatcher,
-// mdpp_discrete_eval_{summary,nlev,nlev_summary,pm,pm_summary}.hip one explicit instantiation each; every other unit sees the
-// `extern template` below.
+// launch_eval_form<SUMMARY, NLEV> launches one form, launch_eval_form_pm<SUMMARY, NLEV> the PM = 1 and PM = 2 kernels of one
+// form on a handle with one MDP per env.  Each of the eight is instantiated in a translation unit of its own, so that they
+// compile in parallel: mdpp_discrete_eval.hip holds the plain rollout form and the dispatcher,
+// mdpp_discrete_eval_{summary,nlev,nlev_summary,pm,pm_summary,pm_nlev,pm_nlev_summary}.hip one explicit instantiation each;
+// every other unit sees the `extern template` below.
 #pragma once
 #include "mdpp_discrete_closed.hpp"
 
@@ -82,13 +83,16 @@ __global__ __launch_bounds__(kBlock) void k_discrete_eval_rollout(DiscreteArgs a
                                                                   uint8_t *__restrict__ term,
                                                                   uint8_t *__restrict__ trunc) {
     static_assert(!NLEV || NOISE, "per-env noise levels are levels of a NOISE step");
-    static_assert(PM == 0 || !NLEV, "one MDP per env runs without per-env noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
-    unsigned char *q_lds = lds + closed_agent_lds_offset<PM>(a);    // the agent's LDS: behind the MDP's tables and the per-level cdfs
-    if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    if constexpr (NLEV && PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else {
+        q_lds = lds + closed_agent_lds_offset<PM>(a);
+        if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    }
     EvalAgent<QLDS, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
-    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, false, NLEV>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent, EpisodeSummaryArgs{}, p.nl);
+    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, false, NLEV, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent, EpisodeSummaryArgs{}, p.nl);
     else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, false, false, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
     else closed_loop_rollout<PHILOX, NOISE, UNIT>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
 }
@@ -97,13 +101,16 @@ __global__ __launch_bounds__(kBlock) void k_discrete_eval_rollout(DiscreteArgs a
 template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool DOUBLE, bool NLEV = false, int PM = 0>
 __global__ __launch_bounds__(kBlock) void k_discrete_eval_summary(DiscreteArgs a, std::conditional_t<NLEV, EvalArgsNL, EvalArgs> p, int K, EpisodeSummaryArgs sm) {
     static_assert(!NLEV || NOISE, "per-env noise levels are levels of a NOISE step");
-    static_assert(PM == 0 || !NLEV, "one MDP per env runs without per-env noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
-    unsigned char *q_lds = lds + closed_agent_lds_offset<PM>(a);    // the agent's LDS: behind the MDP's tables and the per-level cdfs
-    if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    if constexpr (NLEV && PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else {
+        q_lds = lds + closed_agent_lds_offset<PM>(a);
+        if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    }
     EvalAgent<QLDS, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
-    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
+    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
     else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
     else closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
@@ -147,8 +154,9 @@ int launch_eval_form(mdpp_env *h, const DiscreteIO &io) {
     return rc;
 }
 
-// K evaluation steps of one form on a handle with one MDP per env (mdpp_learner_per_env_mdp): the PM = 1 and PM = 2 kernels
-template <bool SUMMARY>
+// K evaluation steps of one form on a handle with one MDP per env (mdpp_learner_per_env_mdp): the PM = 1 and PM = 2 kernels;
+// NLEV: with per-env noise levels (mdpp_noise_levels_per_env_mdp)
+template <bool SUMMARY, bool NLEV>
 int launch_eval_form_pm(mdpp_env *h, const DiscreteIO &io) {
     const DiscreteArgs &a = h->dargs;
     const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
@@ -157,34 +165,49 @@ int launch_eval_form_pm(mdpp_env *h, const DiscreteIO &io) {
     // (the queue of start states drawn ahead needs shared tables: the PM kernels do not carry it)
     if (a.fast_ok || a.shared_tables) { h->err = "mdpp_step_n_eval: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
     with_bools([&](auto PH, auto NZ, auto UNIT, auto DB) {
-        // the placement, as for the learners
-        bool qlds = false, mlds = false;
-        closed_agent_lds_pm(h, q_lds, [&](bool q, bool m, size_t bytes) {
-            const void *k = nullptr;
-            with_bools([&](auto QL, auto ML) { k = (const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), false, ML() ? 2 : 1>(); }, q, m);
-            return dynamic_lds_ok(k, bytes);
-        }, qlds, mlds);
-        with_bools([&](auto QL, auto ML) {
-            constexpr int PM = ML() ? 2 : 1;
-            char name[kNameLen];
-            snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,DOUBLE=%d,PM=%d>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
-                     PH(), NZ(), UNIT(), QL(), DB(), PM);
-            rc = launch_closed_loop<SUMMARY>(h, io, eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), false, PM>(),
-                                             (size_t)closed_agent_lds_offset<PM>(a) + (QL() ? q_lds : 0u), true, name, [&](int, int, int32_t *actions) {
-                return EvalArgs{(const float *)h->d_learn_q, actions};
-            });
-        }, qlds, mlds);
-    }, a.philox != 0, a.has_p_noise || a.has_r_noise, a.unit_rewards != 0, dbl);
+        if constexpr (!NLEV || NZ()) {
+            // the placement, as for the learners
+            bool qlds = false, mlds = false, clds = false;
+            if constexpr (NLEV)
+                closed_agent_lds_pm_nlev(h, q_lds, [&](bool q, bool m, bool, size_t bytes) {
+                    const void *k = nullptr;
+                    with_bools([&](auto QL, auto ML) { k = (const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), true, ML() ? 2 : 1>(); }, q, m);
+                    return dynamic_lds_ok(k, bytes);
+                }, qlds, mlds, clds);
+            else
+                closed_agent_lds_pm(h, q_lds, [&](bool q, bool m, size_t bytes) {
+                    const void *k = nullptr;
+                    with_bools([&](auto QL, auto ML) { k = (const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), false, ML() ? 2 : 1>(); }, q, m);
+                    return dynamic_lds_ok(k, bytes);
+                }, qlds, mlds);
+            const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
+            with_bools([&](auto QL, auto ML) {
+                constexpr int PM = ML() ? 2 : 1;
+                char name[kNameLen];
+                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,DOUBLE=%d%s,PM=%d>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
+                         PH(), NZ(), UNIT(), QL(), DB(), NLEV ? ",NLEV=1" : "", PM);
+                const size_t agent_at = NLEV ? (size_t)closed_agent_lds_offset<PM>(a, cdf_lds) : (size_t)closed_agent_lds_offset<PM>(a);
+                rc = launch_closed_loop<SUMMARY>(h, io, eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), NLEV, PM>(),
+                                                 agent_at + (QL() ? q_lds : 0u), true, name, [&](int, int, int32_t *actions) {
+                    const EvalArgs base{(const float *)h->d_learn_q, actions};
+                    if constexpr (NLEV) return EvalArgsNL{base, noise_level_args(h, cdf_lds)};
+                    else return base;
+                });
+            }, qlds, mlds);
+        }
+    }, a.philox != 0, NLEV || a.has_p_noise || a.has_r_noise, a.unit_rewards != 0, dbl);
     return rc;
 }
 
-// the forms built <SUMMARY, NLEV> and, with one MDP per env, <SUMMARY>, each defined (an explicit instantiation) in the
+// the forms built <SUMMARY, NLEV> and, with one MDP per env, <SUMMARY, NLEV>, each defined (an explicit instantiation) in the
 // translation unit named
 extern template int launch_eval_form<false, false>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_eval.hip
 extern template int launch_eval_form<true, false>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_eval_summary.hip
 extern template int launch_eval_form<false, true>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_eval_nlev.hip
 extern template int launch_eval_form<true, true>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_eval_nlev_summary.hip
-extern template int launch_eval_form_pm<false>(mdpp_env *, const DiscreteIO &);         // mdpp_discrete_eval_pm.hip
-extern template int launch_eval_form_pm<true>(mdpp_env *, const DiscreteIO &);          // mdpp_discrete_eval_pm_summary.hip
+extern template int launch_eval_form_pm<false, false>(mdpp_env *, const DiscreteIO &);  // mdpp_discrete_eval_pm.hip
+extern template int launch_eval_form_pm<true, false>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_eval_pm_summary.hip
+extern template int launch_eval_form_pm<false, true>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_eval_pm_nlev.hip
+extern template int launch_eval_form_pm<true, true>(mdpp_env *, const DiscreteIO &);    // mdpp_discrete_eval_pm_nlev_summary.hip
 
 } // namespace mdpp

@@ -2,4 +2,4 @@
 // kernels): greedy evaluation -- in a translation unit of its own so that the forms compile in parallel.
 #include "mdpp_discrete_eval.hpp"
 
-template int mdpp::launch_eval_form_pm<false>(mdpp_env *, const mdpp::DiscreteIO &);
+template int mdpp::launch_eval_form_pm<false, false>(mdpp_env *, const mdpp::DiscreteIO &);

@@ -3,4 +3,4 @@
 // parallel.
 #include "mdpp_discrete_eval.hpp"
 
-template int mdpp::launch_eval_form_pm<true>(mdpp_env *, const mdpp::DiscreteIO &);
+template int mdpp::launch_eval_form_pm<true, false>(mdpp_env *, const mdpp::DiscreteIO &);

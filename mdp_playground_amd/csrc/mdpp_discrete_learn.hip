@@ -75,7 +75,7 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
     }
     int rc = MDPP_OK;
     if (pm) {
-        with_bools([&](auto DB, auto SM) { rc = launch_learn_form_pm<DB(), SM()>(h, io); }, dbl, io.summary != nullptr);
+        with_bools([&](auto DB, auto SM, auto NL) { rc = launch_learn_form_pm<DB(), SM(), NL()>(h, io); }, dbl, io.summary != nullptr, h->nl_on);
         return rc;
     }
     with_bools([&](auto PE, auto DB, auto SM, auto NL) {

@@ -42,11 +42,12 @@
 // between the MDP's tables and the Q-tables in LDS.
 //
 // PM = 1 / 2 (one MDP per env, mdpp_learner_per_env_mdp) is the PE learner around the step's PM form (mdpp_discrete_closed.hpp:
-// the lane's own tables in global memory / staged in LDS slots), NLEV = 0 always; the Q-tables lie behind the slots and the
-// shared noise cdf in LDS (closed_agent_lds_offset).  The host picks PM and QLDS per launch (closed_agent_lds_pm).
+// the lane's own tables in global memory / staged in LDS slots); the Q-tables lie behind the slots and the shared noise cdf
+// in LDS (closed_agent_lds_offset).  The host picks PM and QLDS per launch (closed_agent_lds_pm).  With NLEV = 1
+// (mdpp_noise_levels_per_env_mdp) the per-level cdfs take the shared cdf's place (closed_agent_lds_pm_nlev).
 //
-// launch_learn_form<PE, DOUBLE, SUMMARY, NLEV> launches one form, launch_learn_form_pm<DOUBLE, SUMMARY> the PM = 1 and PM = 2
-// kernels of one form on a handle with one MDP per env.  Each of the sixteen forms built is instantiated in a translation
+// launch_learn_form<PE, DOUBLE, SUMMARY, NLEV> launches one form, launch_learn_form_pm<DOUBLE, SUMMARY, NLEV> the PM = 1 and PM = 2
+// kernels of one form on a handle with one MDP per env.  Each of the twenty forms built is instantiated in a translation
 // unit of its own, so that they compile in parallel: mdpp_discrete_learn.hip holds the uniform rollout form and the
 // dispatcher, mdpp_discrete_learn_*.hip one explicit instantiation each; every other unit sees the `extern template` below.
 #pragma once
@@ -235,13 +236,17 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs 
                                                                    uint8_t *__restrict__ term,
                                                                    uint8_t *__restrict__ trunc) {
     static_assert(!NLEV || (NOISE && PE), "per-env noise levels run the PE learner around a NOISE step");
-    static_assert(PM == 0 || (PE && !NLEV), "one MDP per env runs the PE learner, without per-env noise levels");
+    static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
-    unsigned char *q_lds = lds + closed_agent_lds_offset<PM>(a);    // the agent's LDS: behind the MDP's tables and the per-level cdfs
-    if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    if constexpr (NLEV && PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else {
+        q_lds = lds + closed_agent_lds_offset<PM>(a);
+        if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    }
     LearnAgent<QLDS, PE, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
-    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, false, NLEV>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent, EpisodeSummaryArgs{}, p.nl);
+    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, false, NLEV, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent, EpisodeSummaryArgs{}, p.nl);
     else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, false, false, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
     else closed_loop_rollout<PHILOX, NOISE, UNIT>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
 }
@@ -250,13 +255,17 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs 
 template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false, bool NLEV = false, int PM = 0>
 __global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs a, LearnArgsOf<PE, NLEV> p, int K, EpisodeSummaryArgs sm) {
     static_assert(!NLEV || (NOISE && PE), "per-env noise levels run the PE learner around a NOISE step");
-    static_assert(PM == 0 || (PE && !NLEV), "one MDP per env runs the PE learner, without per-env noise levels");
+    static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
-    unsigned char *q_lds = lds + closed_agent_lds_offset<PM>(a);    // the agent's LDS: behind the MDP's tables and the per-level cdfs
-    if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    if constexpr (NLEV && PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else {
+        q_lds = lds + closed_agent_lds_offset<PM>(a);
+        if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    }
     LearnAgent<QLDS, PE, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
-    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
+    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
     else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
     else closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
@@ -305,8 +314,9 @@ int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
 }
 
 // K learning steps of one form on a handle with one MDP per env (mdpp_learner_per_env_mdp): the PE learner's PM = 1 and
-// PM = 2 kernels, without per-env noise levels
-template <bool DOUBLE, bool SUMMARY>
+// PM = 2 kernels.  NLEV: with per-env noise levels (mdpp_noise_levels_per_env_mdp) -- NOISE = 1 whatever the handle's keys,
+// the per-level cdfs in the shared cdf's place (closed_agent_lds_pm_nlev)
+template <bool DOUBLE, bool SUMMARY, bool NLEV>
 int launch_learn_form_pm(mdpp_env *h, const DiscreteIO &io) {
     constexpr bool PE = true;
     const DiscreteArgs &a = h->dargs;
@@ -315,30 +325,43 @@ int launch_learn_form_pm(mdpp_env *h, const DiscreteIO &io) {
     // (the queue of start states drawn ahead needs shared tables: the PM kernels do not carry it)
     if (a.fast_ok || a.shared_tables) { h->err = "mdpp_step_n_learn: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
     with_bools([&](auto PH, auto NZ, auto UNIT) {
-        // the placement: the Q-tables and the envs' MDP slots in LDS as far as the device grants them
-        bool qlds = false, mlds = false;
-        closed_agent_lds_pm(h, q_lds, [&](bool q, bool m, size_t bytes) {
-            const void *k = nullptr;
-            with_bools([&](auto QL, auto ML) { k = (const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, false, ML() ? 2 : 1>(); }, q, m);
-            return dynamic_lds_ok(k, bytes);
-        }, qlds, mlds);
-        with_bools([&](auto QL, auto ML) {
-            constexpr int PM = ML() ? 2 : 1;
-            char name[kNameLen];
-            snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,PE=1%s,PM=%d>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
-                     PH(), NZ(), UNIT(), QL(), DOUBLE ? ",DOUBLE=1" : "", PM);
-            rc = launch_closed_loop<SUMMARY>(h, io, learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, false, PM>(),
-                                             (size_t)closed_agent_lds_offset<PM>(a) + (QL() ? q_lds : 0u), true, name, [&](int k0, int kc, int32_t *actions) {
-                const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
-                                     h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
-                return LearnArgsPE{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E};
-            });
-        }, qlds, mlds);
-    }, a.philox != 0, a.has_p_noise || a.has_r_noise, a.unit_rewards != 0);
+        if constexpr (!NLEV || NZ()) {
+            // the placement: the Q-tables, the envs' MDP slots and the per-level cdfs in LDS as far as the device grants them
+            bool qlds = false, mlds = false, clds = false;
+            if constexpr (NLEV)
+                closed_agent_lds_pm_nlev(h, q_lds, [&](bool q, bool m, bool, size_t bytes) {
+                    const void *k = nullptr;
+                    with_bools([&](auto QL, auto ML) { k = (const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, true, ML() ? 2 : 1>(); }, q, m);
+                    return dynamic_lds_ok(k, bytes);
+                }, qlds, mlds, clds);
+            else
+                closed_agent_lds_pm(h, q_lds, [&](bool q, bool m, size_t bytes) {
+                    const void *k = nullptr;
+                    with_bools([&](auto QL, auto ML) { k = (const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, false, ML() ? 2 : 1>(); }, q, m);
+                    return dynamic_lds_ok(k, bytes);
+                }, qlds, mlds);
+            const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
+            with_bools([&](auto QL, auto ML) {
+                constexpr int PM = ML() ? 2 : 1;
+                char name[kNameLen];
+                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,PE=1%s%s,PM=%d>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
+                         PH(), NZ(), UNIT(), QL(), DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", PM);
+                const size_t agent_at = NLEV ? (size_t)closed_agent_lds_offset<PM>(a, cdf_lds) : (size_t)closed_agent_lds_offset<PM>(a);
+                rc = launch_closed_loop<SUMMARY>(h, io, learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, NLEV, PM>(),
+                                                 agent_at + (QL() ? q_lds : 0u), true, name, [&](int k0, int kc, int32_t *actions) {
+                    const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
+                                         h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
+                    const LearnArgsPE pe{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E};
+                    if constexpr (NLEV) return LearnArgsNL{pe, noise_level_args(h, cdf_lds)};
+                    else return pe;
+                });
+            }, qlds, mlds);
+        }
+    }, a.philox != 0, NLEV || a.has_p_noise || a.has_r_noise, a.unit_rewards != 0);
     return rc;
 }
 
-// the forms built <PE, DOUBLE, SUMMARY, NLEV> and, with one MDP per env, <DOUBLE, SUMMARY>, each defined (an explicit
+// the forms built <PE, DOUBLE, SUMMARY, NLEV> and, with one MDP per env, <DOUBLE, SUMMARY, NLEV>, each defined (an explicit
 // instantiation) in the translation unit named
 extern template int launch_learn_form<false, false, false, false>(mdpp_env *, const DiscreteIO &);  // mdpp_discrete_learn.hip
 extern template int launch_learn_form<true, false, false, false>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_learn_pe.hip
@@ -352,9 +375,13 @@ extern template int launch_learn_form<true, false, false, true>(mdpp_env *, cons
 extern template int launch_learn_form<true, true, false, true>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_learn_double_pe_nlev.hip
 extern template int launch_learn_form<true, false, true, true>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_learn_pe_nlev_summary.hip
 extern template int launch_learn_form<true, true, true, true>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_learn_double_pe_nlev_summary.hip
-extern template int launch_learn_form_pm<false, false>(mdpp_env *, const DiscreteIO &);             // mdpp_discrete_learn_pe_pm.hip
-extern template int launch_learn_form_pm<true, false>(mdpp_env *, const DiscreteIO &);              // mdpp_discrete_learn_double_pe_pm.hip
-extern template int launch_learn_form_pm<false, true>(mdpp_env *, const DiscreteIO &);              // mdpp_discrete_learn_pe_pm_summary.hip
-extern template int launch_learn_form_pm<true, true>(mdpp_env *, const DiscreteIO &);               // mdpp_discrete_learn_double_pe_pm_summary.hip
+extern template int launch_learn_form_pm<false, false, false>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_learn_pe_pm.hip
+extern template int launch_learn_form_pm<true, false, false>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_double_pe_pm.hip
+extern template int launch_learn_form_pm<false, true, false>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_pe_pm_summary.hip
+extern template int launch_learn_form_pm<true, true, false>(mdpp_env *, const DiscreteIO &);        // mdpp_discrete_learn_double_pe_pm_summary.hip
+extern template int launch_learn_form_pm<false, false, true>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_pe_pm_nlev.hip
+extern template int launch_learn_form_pm<true, false, true>(mdpp_env *, const DiscreteIO &);        // mdpp_discrete_learn_double_pe_pm_nlev.hip
+extern template int launch_learn_form_pm<false, true, true>(mdpp_env *, const DiscreteIO &);        // mdpp_discrete_learn_pe_pm_nlev_summary.hip
+extern template int launch_learn_form_pm<true, true, true>(mdpp_env *, const DiscreteIO &);         // mdpp_discrete_learn_double_pe_pm_nlev_summary.hip
 
 } // namespace mdpp

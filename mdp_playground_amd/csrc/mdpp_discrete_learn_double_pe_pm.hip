@@ -3,4 +3,4 @@
 // compile in parallel.
 #include "mdpp_discrete_learn.hpp"
 
-template int mdpp::launch_learn_form_pm<true, false>(mdpp_env *, const mdpp::DiscreteIO &);
+template int mdpp::launch_learn_form_pm<true, false, false>(mdpp_env *, const mdpp::DiscreteIO &);

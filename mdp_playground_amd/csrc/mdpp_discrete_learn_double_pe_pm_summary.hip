@@ -3,4 +3,4 @@
 // own so that the forms compile in parallel.
 #include "mdpp_discrete_learn.hpp"
 
-template int mdpp::launch_learn_form_pm<true, true>(mdpp_env *, const mdpp::DiscreteIO &);
+template int mdpp::launch_learn_form_pm<true, true, false>(mdpp_env *, const mdpp::DiscreteIO &);

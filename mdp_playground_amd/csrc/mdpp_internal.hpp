@@ -345,7 +345,9 @@ struct mdpp_env {
     // launches take their NLEV form and every other step launch is refused.  Device: the level byte and the sigma of every
     // env, the per-level cdfs [levels][S][S] and (T, M) pairs; host: the values in force, for mdpp_get_noise_levels.
     // nl_fill_*: the uniform alpha / gamma / E the learner's per-env arrays were last filled with for an NLEV launch.
-    bool nl_on;
+    // nl_pm: mdpp_noise_levels_per_env_mdp -- levels are accepted on a handle with one MDP per env whose learn_pm is on (the
+    // NLEV kernels with PM != 0; only ever set on a discrete handle with num_tables != 1)
+    bool nl_on, nl_pm;
     int32_t nl_levels;
     void *d_nl_level, *d_nl_sigma, *d_nl_cdf, *d_nl_T, *d_nl_M;
     std::vector<double> nl_tn, nl_rn;

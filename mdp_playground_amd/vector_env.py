@@ -96,6 +96,7 @@ class RLToyVectorEnv:
         self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
         self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
+        self._nl_pm = False                   # set_noise_levels(per_env_mdp=True) is in force (the handle's second flag is on)
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
                 raise ValueError("num_envs != len(seeds)")
@@ -787,6 +788,7 @@ class RLToyVectorEnv:
             capi.check(self._lib, self._h, self._lib.mdpp_learner_per_env_mdp(self._h, 0), "mdpp_learner_per_env_mdp")
             self._learn_rates = None
             self._learn_pm = False
+            self._drop_noise_levels_per_env_mdp()
             return
         if alpha is None or gamma is None or epsilon is None:
             raise ValueError("set_learner: alpha, gamma and epsilon are required")
@@ -909,7 +911,9 @@ class RLToyVectorEnv:
     def learn_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
         launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning; NLEV=1: per-env
-        noise levels, set_noise_levels; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory); empty for a handle it does not serve."""
+        noise levels, set_noise_levels; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
+        per-env noise levels on one MDP per env, set_noise_levels(..., per_env_mdp=True) -- the arguments come in template order,
+        "...,PE=1[,DOUBLE=1],NLEV=1,PM=1|2>"); empty for a handle it does not serve."""
         if self.kind != "discrete":
             return ""
         name = self._lib.mdpp_learn_kernel_name(self._h, int(K))
@@ -922,7 +926,13 @@ class RLToyVectorEnv:
         if self._noise_levels_set:
             raise capi.MdppError(self._NOISE_LEVELS_ONLY)
 
-    def set_noise_levels(self, transition_noise=None, reward_noise=None):
+    def _drop_noise_levels_per_env_mdp(self):
+        # (the library has dropped the levels and the opt-in with the learner's per-env-MDP flag)
+        if self._nl_pm:
+            self._nl_pm = False
+            self._noise_levels_set = False
+
+    def set_noise_levels(self, transition_noise=None, reward_noise=None, per_env_mdp=False):
         """Per-env noise levels for rollout_learn / rollout_eval (and their summary= forms): env i of THIS handle (its local
         index, like the per-env learner parameters: a sharded run gives each shard its slice) steps with
         ``transition_noise[i]`` in [0, 1] -- at most 16 distinct values per handle -- and ``reward_noise[i]`` finite and >= 0,
@@ -932,7 +942,15 @@ class RLToyVectorEnv:
         config (any value), ``transition_noise`` > 0.  A noise sweep then runs as ONE launch.  ValueError for a
         bad array or a key the handle lacks, before any device work.  While levels are set step(), rollout() and step_graph()
         raise; reset() is unaffected.  Levels are configuration, not state: get_augmented_state / set_augmented_state and
-        checkpoints neither carry nor disturb them -- set them again on a restored handle."""
+        checkpoints neither carry nor disturb them -- set them again on a restored handle.
+        ``per_env_mdp=True`` on a handle built with ``seeds=[...]`` or ``mdps=[...]`` whose learner was set with
+        ``per_env_mdp=True``: the levels are accepted on one MDP per env -- a noise x seed sweep in ONE launch (DESIGN.md 3.18);
+        env i behaves bit for bit like env i of such a handle created uniformly at its two values.  Without it that handle is
+        refused as ever; the opt-in stays until clear_noise_levels(), ``set_learner(None)`` or a call without it.  ValueError
+        on a handle with one shared MDP; a one-MDP-per-env handle without the per_env_mdp learner raises the learner's
+        refusal."""
+        if per_env_mdp and not self._per_env:
+            raise ValueError("set_noise_levels: per_env_mdp=True needs one MDP per env (seeds=[...] or mdps=[...]); this handle has one shared MDP")
         arrays = {}
         for key, v in (("transition_noise", transition_noise), ("reward_noise", reward_noise)):
             arrays[key] = policy_mod.noise_level_array(key, v, self.num_envs)
@@ -946,11 +964,26 @@ class RLToyVectorEnv:
                                  (key, " (it needs transition_noise > 0)" if key == "transition_noise" else ""))
         if all(a is None for a in arrays.values()):
             return
+        want_pm = bool(per_env_mdp) and self._per_env
+        if self._nl_pm and not want_pm:
+            # (the call without the opt-in, refused as on a handle that never had it -- before the handle is touched)
+            raise NotImplementedError("mdpp_set_noise_levels: per-env noise levels on one MDP per env: not built; the per_env_mdp=True "
+                                      "levels in force stay as they are")
+        flipped = want_pm and not self._nl_pm
+        if flipped:
+            capi.check(self._lib, self._h, self._lib.mdpp_noise_levels_per_env_mdp(self._h, 1), "mdpp_noise_levels_per_env_mdp")
         rc = self._lib.mdpp_set_noise_levels(self._h, capi.nptr(arrays["transition_noise"]), capi.nptr(arrays["reward_noise"]), self._stream())
         if rc in (-4, capi.EUNSUPPORTED):    # MDPP_ESTATE: a handle the learner kernels do not serve; ... or one MDP per env
             msg = self._lib.mdpp_last_error(self._h)
+            if flipped:                      # (the opt-in goes back to what it was.  The reason was read first: the flag call keeps it)
+                capi.check(self._lib, self._h, self._lib.mdpp_noise_levels_per_env_mdp(self._h, int(self._nl_pm)), "mdpp_noise_levels_per_env_mdp")
             raise NotImplementedError(msg.decode() if msg else "mdpp_set_noise_levels: unsupported")
+        if rc != 0 and flipped:
+            msg = self._lib.mdpp_last_error(self._h)
+            capi.check(self._lib, self._h, self._lib.mdpp_noise_levels_per_env_mdp(self._h, int(self._nl_pm)), "mdpp_noise_levels_per_env_mdp")
+            raise capi.MdppError("mdpp_set_noise_levels failed (%d): %s" % (rc, msg.decode() if msg else ""))
         capi.check(self._lib, self._h, rc, "mdpp_set_noise_levels")
+        self._nl_pm = want_pm
         self._noise_levels_set = True
 
     def noise_levels(self):
@@ -964,6 +997,9 @@ class RLToyVectorEnv:
     def clear_noise_levels(self):
         """Back to the creation values of both keys: the handle launches the kernels it launched before set_noise_levels."""
         capi.check(self._lib, self._h, self._lib.mdpp_clear_noise_levels(self._h), "mdpp_clear_noise_levels")
+        if self._nl_pm:
+            capi.check(self._lib, self._h, self._lib.mdpp_noise_levels_per_env_mdp(self._h, 0), "mdpp_noise_levels_per_env_mdp")
+            self._nl_pm = False
         self._noise_levels_set = False
 
     def rollout_kernel_name(self, K):
