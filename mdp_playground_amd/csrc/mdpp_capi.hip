@@ -388,7 +388,12 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
             const bool next_ok = cfg->autoreset != MDPP_AUTORESET_NEXT_STEP || cfg->rng_mode != MDPP_RNG_NUMPY_PCG64 ||
                                  (!cfg->has_p_noise && !cfg->has_reward_noise);
             // (the fused kernels test the hypercubes in an unrolled loop of MDPP_MAX_BOXES: more than that -> general kernel)
-            a.fast_ok = (a.rel_prefix && !cfg->image && !line && !cfg->target_f64 && next_ok && cfg->n_boxes <= MDPP_MAX_BOXES &&
+            // (the fused kernels skip the action penalty at weight 0 when a wave's actions were all admitted: alw * ||a|| is +0 then --
+            //  unless the box admits actions whose squares sum beyond float32 (the default box admits +-inf): 0 * inf = NaN, which the
+            //  reference pays (:1943).  D * amax^2 stays below FLT_MAX for amax <= 1e18 at every D built; beyond it such a handle
+            //  goes to the general kernel, which always computes the penalty.  DESIGN.md §3.19)
+            const bool pen_ok = a.alw32 != 0.0f || a.amax32 <= 1.0e18f;
+            a.fast_ok = (a.rel_prefix && !cfg->image && !line && !cfg->target_f64 && next_ok && cfg->n_boxes <= MDPP_MAX_BOXES && pen_ok &&
                          (a.bounded || isfinite(cfg->action_space_max))) ? 1u : 0u;
             a.image_quirk = cfg->image ? 1 : 0;
         }

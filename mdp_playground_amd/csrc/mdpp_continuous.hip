@@ -707,8 +707,14 @@ __global__ __launch_bounds__(kBlock) void k_continuous_step(ContinuousArgs a, in
         const bool in_box = (a.n_boxes > 0) && c_in_box<DMAX>(a, rel);
         steps += 1;
         // ---- C6
+        // :1858: no reward while coordinate 0 of the state this step left is NaN -- the reference's test for "the history does
+        // not reach back that far" also fires on a NaN STATE, which unbounded boxes allow (inf, then -inf; np.clip keeps it).
+        // The reward stays the Python float 0.0, the action penalty is not subtracted.  (move_to_a_point)
+        const bool nan_gate = !a.line_L && cur[0] != cur[0];
         CRew r;
-        if (a.line_L) {
+        if (nan_gate) {
+            r.v = 0.0; r.is32 = false;
+        } else if (a.line_L) {
             // gate (:1856): the state sequence_length transitions back must exist
             c_line_put<DMAX>(a, i, steps, rel, lds_line);
             r.v = 0.0;
@@ -731,7 +737,7 @@ __global__ __launch_bounds__(kBlock) void k_continuous_step(ContinuousArgs a, in
         } else {
             r.v = within ? 1.0 : 0.0;
         }
-        if (!a.line_L) {
+        if (!a.line_L && !nan_gate) {
             double acc = 0.0;
 #pragma unroll
             for (int d = 0; d < DMAX; d++)
@@ -749,7 +755,7 @@ __global__ __launch_bounds__(kBlock) void k_continuous_step(ContinuousArgs a, in
         } else if (a.delay > 0) {
             uint32_t *slot = a.ring + (size_t)(tick % (uint32_t)a.delay) * N + i;
             uint32_t bits = *slot;
-            *slot = __float_as_uint((float)r.v);
+            *slot = r.is32 ? __float_as_uint((float)r.v) : kRingPyZero;       // (the Python float 0.0 of the NaN gate keeps its type)
             if (bits == kRingPyZero) { r.v = 0.0; r.is32 = false; }
             else { r.v = (double)__uint_as_float(bits); r.is32 = true; }
         }

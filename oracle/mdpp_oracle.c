@@ -676,11 +676,17 @@ void ora_c_step(ora_continuous *e, const float *a, float *obs, double *reward,
     e->steps += 1; /* :2058 */
     /* C6: :1912-1945 */
     rew_t r;
+    /* :1858: no reward while coordinate 0 of the state this step left is NaN (the reference's test for "the history
+     * does not reach back that far" also fires on a NaN STATE, which unbounded boxes allow: inf, then -inf).  The
+     * reward stays the Python float 0.0 and the action penalty is not subtracted.  move_to_a_point only. */
+    const int nan_gate = !e->line_L && isnan(e->cur[0]);
     if (e->line_L) {
         /* :1864-1910; gate :1856: the state delay+sequence_length transitions back must exist */
         line_push(e, nxt);
         r.v = (e->steps >= e->line_L) ? line_reward(e) : 0.0;
         r.is32 = 0;
+    } else if (nan_gate) {
+        r.v = 0.0; r.is32 = 0;
     } else if (e->make_denser && e->target64) {
         r.v = -dist_new64;                       /* np.float64 (:1926) */
         r.v = r.v + norm64_rel(e, e->cur);       /* :1929 */
@@ -690,7 +696,7 @@ void ora_c_step(ora_continuous *e, const float *a, float *obs, double *reward,
     } else {
         r.v = within ? 1.0 : 0.0;
     }
-    if (!e->line_L) {
+    if (!e->line_L && !nan_gate) {
         float pen = e->alw32 * norm32(a, D);     /* Python float * np.float32 -> np.float32 */
         if (e->make_denser && e->target64) { r.v = r.v - (double)pen; r.is32 = 0; }   /* np.float64 - np.float32 */
         else { r.v = (double)((float)r.v - pen); r.is32 = 1; }
