@@ -29,7 +29,8 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_generate.hip"]
 HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdpp_pcg64_limbs.inc", "np_ziggurat_tables.inc",
            os.path.join("..", "..", "include", "mdpp.h")]
-INCLUDED_SOURCES = {"mdpp_discrete_wide.hip": ["mdpp_discrete.hip"], "mdpp_discrete_long.hip": ["mdpp_discrete.hip"], "mdpp_discrete_lean_next.hip": ["mdpp_discrete_lean.hip"], "mdpp_discrete_lean_noise.hip": ["mdpp_discrete_lean.hip"], "mdpp_discrete_lean_npnoise.hip": ["mdpp_discrete_lean.hip"],
+_LEAN_DEPS = ["mdpp_discrete_lean.hip", "mdpp_discrete_lean_e.inc"]      # (the kernel and its E role, included into its body)
+INCLUDED_SOURCES = {"mdpp_discrete_lean.hip": ["mdpp_discrete_lean_e.inc"], "mdpp_discrete_wide.hip": ["mdpp_discrete.hip"], "mdpp_discrete_long.hip": ["mdpp_discrete.hip"], "mdpp_discrete_lean_next.hip": _LEAN_DEPS, "mdpp_discrete_lean_noise.hip": _LEAN_DEPS, "mdpp_discrete_lean_npnoise.hip": _LEAN_DEPS,
                     "mdpp_continuous_line8.hip": ["mdpp_continuous.hip"], "mdpp_continuous_step1.hip": ["mdpp_continuous_fast.hip"], "mdpp_discrete_quiet_nu.hip": ["mdpp_discrete_quiet.hip"],   # a .hip that #includes another one
                     # ... or a header of its own
                     **{u: ["mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith("mdpp_discrete_learn")},

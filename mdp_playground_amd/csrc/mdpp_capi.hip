@@ -57,7 +57,7 @@ static void free_all(mdpp_env *h) {
                     h->d_P1, h->d_init_cdf1, h->d_noise_cdf1, h->d_irr_state,
                     h->d_img_tpl, h->d_img_tplp, h->d_img_clsx, h->d_img_clsy, h->d_img_rot, h->d_img_state_out,
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
-                    h->d_img_near, h->d_s1_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
+                    h->d_img_near, h->d_s1_blob, h->d_lean_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
                     h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E,
                     h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M};
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -116,6 +116,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_img_tpl = h->d_img_tplp = h->d_img_clsx = h->d_img_clsy = h->d_img_rot = nullptr;
     h->d_img_near = nullptr;
     h->d_s1_blob = nullptr;
+    h->d_lean_blob = nullptr;
     memset(&h->s1args, 0, sizeof(h->s1args));
     h->d_policy_thr = nullptr; h->policy_seed = 0; h->policy_ready = false;
     h->d_learn_q = h->d_learn_carry = nullptr; h->learn_seed = 0; h->learn_E = 0; h->learn_alpha = h->learn_gamma = 0.0f;
@@ -478,6 +479,24 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
 
 static inline bool t_fits53(uint64_t t) { return t <= (1ULL << 53) - 1; }
 
+// k_discrete_rollout_lean's tables (DiscreteArgs::lean_blob), built on the device from the tables just uploaded: called
+// wherever a handle's P, reward bits, terminal states, rho_0, reward values or irrelevant tables are set, never from a
+// rollout entry point (a launch captured into a HIP graph must not allocate or launch extras).  Only a handle that
+// lean_launch can take gets one (its shape conditions, mdpp_discrete_lean.hip); every other keeps the null pointer.
+static int lean_tables_build(mdpp_env *h) {
+    DiscreteArgs &a = h->dargs;
+    const mdpp_config &c = h->cfg;
+    a.lean_blob = nullptr;
+    const bool lean_shape = a.shape_ok || a.shape_ok_irr || a.lean_next_ok || a.shape_ok_noise || a.shape_ok_noise_np;
+    if (!lean_shape || !h->tables_ready || (c.irrelevant && !h->irr_ready)) return MDPP_OK;
+    if (c.S > 8 || c.A > 16 || c.L > 3 || c.every_n > 64 || (c.irrelevant && (c.S_irr > 8 || c.A_irr > 16))) return MDPP_OK;
+    if (!h->d_lean_blob) HIPCHK(h, hipMalloc(&h->d_lean_blob, (size_t)mdpp::kLeanTabUnits * 16));
+    HIPCHK(h, mdpp::launch_lean_build_tables(a, h->d_lean_blob, nullptr));      // (the stream of the uploads' hipMemcpy)
+    HIPCHK(h, hipStreamSynchronize(nullptr));
+    a.lean_blob = (const uint4 *)h->d_lean_blob;
+    return MDPP_OK;
+}
+
 // What the kernels' dispatch derives from a discrete handle's tables: DiscreteArgs' fast-path constants and the one-launch
 // step's blob.  Shared by the host upload and the device generator (mdpp_generate_discrete), so that a handle selects the
 // same kernels whichever built its tables.  P / rtable / rbits are read for single-table handles only (every specialised
@@ -670,7 +689,7 @@ static int discrete_derived(mdpp_env *h, const uint8_t *P, const double *rtable,
         }
     }
     h->tables_ready = true;
-    return MDPP_OK;
+    return lean_tables_build(h);
 }
 
 extern "C" int mdpp_upload_discrete_tables(mdpp_env *h, const uint8_t *P, const double *rtable,
@@ -848,7 +867,7 @@ extern "C" int mdpp_upload_discrete_irrelevant(mdpp_env *h, const uint8_t *P1, c
     if (h->cfg.has_transition_noise)
         HIPCHK(h, hipMemcpy(h->d_noise_cdf1, noise_cdf1, S1 * S1 * sizeof(double), hipMemcpyHostToDevice));
     h->irr_ready = true;
-    return MDPP_OK;
+    return lean_tables_build(h);
 }
 
 extern "C" int mdpp_upload_image_disc(mdpp_env *h, const uint8_t *disc) {

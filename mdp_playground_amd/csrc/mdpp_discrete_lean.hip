@@ -53,6 +53,14 @@
 //     walks positions: reads meta[p], meta[p + 1], meta[p + 2] (fetched one step ahead), copies x[p] into the step's
 //     record for O1, and moves on by the draw's words (+ 1 if the episode ended); H runs up to 16 positions ahead of the
 //     position E publishes and un-draws what E did not reach at the end of the launch.
+// Set-up (profiles/lean_fixed_cost.txt): the tables that depend on the MDP alone -- reward-bit table, action columns, rho_0
+// thresholds, reward values, the irrelevant sub-space's two -- are built ONCE per table upload by k_lean_build_tables into a
+// blob of the handle (DiscreteArgs::lean_blob), and a launch copies it into LDS, 16 bytes per O / H lane, behind one barrier;
+// the E lanes issue their state word and the actions of their first kAhead + 1 chunks before that set-up, so the launch's
+// first HBM round trip runs under it (the E role's text is mdpp_discrete_lean_e.inc, included into the kernel's body).  NOT
+// the numpy-noise unit (MDPP_LEAN_TU_NOISE == 2): it keeps the tables it builds per launch, one set-up for all four roles and
+// the E role last -- in the new arrangement cfg2 + both noises lost 14 us per launch and ten of its instantiations reserved
+// a private segment they had not had (profiles/lean_fixed_cost.txt section 5).
 // What the measurements said (profiles/archive/r02_ablation_lean_kernel.txt): with the default cache policy
 // the time was set by the stores, whoever issued them (147 us per 512-step launch of 65 536 envs with
 // one, two or three storing waves per SIMD); marked nt they cost 10 us on top of the 95 us the
@@ -177,6 +185,79 @@ __device__ __forceinline__ void chunk_normals(uint64_t seed, uint64_t genv, uint
 } // namespace lean
 using namespace lean;
 
+#if !MDPP_LEAN_TU_NEXT && !MDPP_LEAN_TU_NOISE
+// The tables k_discrete_rollout_lean keeps in LDS depend on the MDP alone: built here once per upload (mdpp_capi.hip
+// lean_tables_build) into the handle's blob, in the layout of kLeanTab* (mdpp_internal.hpp), and copied by every workgroup
+// of every launch.  One workgroup of the rollout kernel's size; what it does not write stays zero.
+__global__ __launch_bounds__(kRoles * kBlock) void k_lean_build_tables(DiscreteArgs a, uint4 *__restrict__ blob) {
+    __shared__ __align__(16) uint4 lds_tab[kLeanTabUnits];
+    __shared__ __align__(16) uint32_t lds_R[128];             // 4096 reward bits by key (staging for lds_V)
+    uint32_t *const lds_V = (uint32_t *)&lds_tab[kLeanTabV];
+    uint2 *const lds_col = (uint2 *)&lds_tab[kLeanTabCol], *const lds_col1 = (uint2 *)&lds_tab[kLeanTabCol1];
+    uint64_t *const lds_T = (uint64_t *)&lds_tab[kLeanTabT], *const lds_T1 = (uint64_t *)&lds_tab[kLeanTabT1];
+    float *const lds_rsel = (float *)&lds_tab[kLeanTabRsel];
+    const int tid = threadIdx.x;
+    if (tid < (int)kLeanTabUnits) lds_tab[tid] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    const uint32_t S = (uint32_t)a.S, L = (uint32_t)a.L;
+    if (tid < 16) {
+        uint64_t cs = 0;
+        if (tid < a.A)
+            for (uint32_t s = 0; s < S; s++) {
+                const uint32_t nx = a.P[s * a.A + tid] & 7u;
+                cs |= (uint64_t)(nx | 8u | ((uint32_t)((a.term_mask >> nx) & 1ULL) << 7)) << (8 * s);
+            }
+        lds_col[tid] = make_uint2((uint32_t)cs, (uint32_t)(cs >> 32));
+        if (tid < 8) lds_T[tid] = a.init_thr[tid];
+        if (a.irr) {                                            // (:2028-2035, :2063-2082, reset :2259-2264)
+            uint64_t c1 = 0;
+            if (tid < a.A1)
+                for (int s1 = 0; s1 < a.S1; s1++) c1 |= (uint64_t)(a.P1[s1 * a.A1 + tid] & 7u) << (8 * s1);
+            lds_col1[tid] = make_uint2((uint32_t)c1, (uint32_t)(c1 >> 32));
+            if (tid < 8) lds_T1[tid] = tid < a.S1 ? (uint64_t)ceil(a.init_cdf1[tid] * 9007199254740992.0) : ~0ULL;
+        }
+    }
+    // only pay steps hand out the bit (:1975-1976); row 0 alone is what an instantiation without every-n reads
+    for (int k = tid; k < 4 * a.every_n; k += kRoles * kBlock) lds_rsel[k] = a.rsel[k < 4 ? k : (k & 1)];
+    for (uint32_t k = tid; k < 128; k += kRoles * kBlock) {
+        uint32_t wd = 0;
+        for (int b = 0; b < 4; b++) {
+            uint32_t byte = 4 * k + b;
+            if (byte < a.rbits_stride) wd |= (uint32_t)a.rbits[byte] << (8 * b);
+        }
+        lds_R[k] = wd;
+    }
+    __syncthreads();
+    {   // lds_V: dword d holds indices 32 d .. 32 d + 31; nibble j of an index = (d * 32 + b) >> 4 j.
+        // Non-zero only where nibbles 0..L all carry bit 3: nibbles 1..L are fixed by d.
+        uint32_t dmask = 0;
+        for (uint32_t j = 1; j <= L; j++) dmask |= 1u << (4 * j - 2);
+        for (uint32_t d = tid; d < 2048; d += kRoles * kBlock) {
+            uint32_t wd = 0;
+            if ((d & dmask) == dmask) {
+                for (uint32_t b = 8; b < 32; b++) {
+                    if (!(b & 8u)) continue;
+                    const uint32_t idx = d * 32u + b;
+                    uint32_t key = 0, pw = 1;
+                    for (uint32_t j = 0; j < L; j++) { key += ((idx >> (4 * j)) & 7u) * pw; pw *= S; }
+                    if (key < a.nkeys) wd |= ((lds_R[key >> 5] >> (key & 31u)) & 1u) << b;
+                }
+            }
+            lds_V[d] = wd;
+        }
+    }
+    __syncthreads();
+    if (tid < (int)kLeanTabUnits) blob[tid] = lds_tab[tid];
+}
+
+hipError_t launch_lean_build_tables(const DiscreteArgs &a, void *blob, hipStream_t s) {
+    static_assert(kLeanTabUnits <= (uint32_t)(kRoles * kBlock) && kLeanTabUnits - (kLeanTabRsel - kLeanTabCol1) <= (uint32_t)((kRoles - 1) * kBlock),
+                  "one unit per thread: the builder's, and the rollout kernel's copy by its O and H lanes");
+    hipLaunchKernelGGL(k_lean_build_tables, dim3(1), dim3(kRoles * kBlock), 0, s, a, (uint4 *)blob);
+    return hipGetLastError();
+}
+#endif
+
 template <bool OBS64, bool DELAY, bool HASMAX, bool EVN, bool PHILOX, bool IRR, bool NEXT, int NZ = 0>
 __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(DiscreteArgs a, int K,
                                                                       const int32_t *__restrict__ actions,
@@ -204,11 +285,24 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     //  236 -> 233-238 us, nothing -- the H / E position pipeline bounds this form, not its stores)
     constexpr int KD = NRN ? kDepthNp : kDepth;                       // E->O ring depth in steps
     __shared__ __align__(16) uint32_t lds_rec[3][KD][kBlock];
+#if MDPP_LEAN_TU_NOISE == 2       // (numpy noise keeps the tables it builds itself: see the set-up)
     __shared__ __align__(16) uint32_t lds_V[2048];            // reward bit & NaN gate, by the 4 low nibbles
     __shared__ __align__(16) uint2 lds_col[16];               // action a, byte s: P[s][a] | 8 | is_term[P[s][a]] << 7
     __shared__ __align__(16) uint32_t lds_R[128];             // 4096 reward bits by key (staging for lds_V)
     __shared__ __align__(16) uint64_t lds_T[8];               // rho_0 thresholds
     __shared__ __align__(16) float lds_rsel[EVN ? 4 * 64 : 4]; // reward by (steps to pay step, bit, terminated)
+#else
+    // The MDP's tables: a copy of the handle's blob (DiscreteArgs::lean_blob, built once per upload by k_lean_build_tables
+    // below), 16 bytes per thread.  Without an irrelevant sub-space its two tables are left out, without reward_every_n_steps
+    // all but the first row of the reward values.
+    constexpr uint32_t kTabSkip = IRR ? 0u : kLeanTabRsel - kLeanTabCol1;     // blob units the LDS copy leaves out
+    constexpr uint32_t kTabUnits = kLeanTabRsel - kTabSkip + (EVN ? kLeanTabUnits - kLeanTabRsel : 1u);
+    __shared__ __align__(16) uint4 lds_tab[kTabUnits];
+    uint32_t *const lds_V = (uint32_t *)&lds_tab[kLeanTabV];          // reward bit & NaN gate, by the 4 low nibbles
+    uint2 *const lds_col = (uint2 *)&lds_tab[kLeanTabCol];            // action a, byte s: P[s][a] | 8 | is_term[P[s][a]] << 7
+    uint64_t *const lds_T = (uint64_t *)&lds_tab[kLeanTabT];          // rho_0 thresholds
+    float *const lds_rsel = (float *)&lds_tab[kLeanTabRsel - kTabSkip];   // reward by (steps to pay step, bit, terminated)
+#endif
     __shared__ __align__(16) uint64_t lds_ring[kBlock];       // H -> E: {8 nibbles, #pushed}
     __shared__ uint32_t lds_head[kBlock];                     // E -> H: #popped
     __shared__ uint32_t lds_prod[kBlock / 64];                // steps published by E wave w
@@ -230,8 +324,13 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     __shared__ __align__(16) uint32_t lds_rprod[kBlock / 64], lds_rcons[kBlock / 64];   // chunks staged by O1 wave w / stored by O2 wave w
     typedef typename std::conditional<IRR, uint64_t, uint32_t>::type S0Word;   // a nibble per tick; with an irrelevant sub-space two
     __shared__ __align__(16) S0Word lds_s0[PHILOX ? kHChunks : 1][kBlock];     // Philox: H -> E, the chunk's 8 start states
+#if MDPP_LEAN_TU_NOISE == 2
     __shared__ __align__(16) uint2 lds_col1[IRR ? 16 : 1];    // irrelevant sub-space: action a1, byte s1: P1[s1][a1]
     __shared__ __align__(16) uint64_t lds_T1[IRR ? 8 : 1];    // its rho_0 thresholds
+#else
+    uint2 *const lds_col1 = (uint2 *)&lds_tab[IRR ? kLeanTabCol1 : kLeanTabCol];    // irrelevant sub-space: action a1, byte s1: P1[s1][a1]
+    uint64_t *const lds_T1 = (uint64_t *)&lds_tab[IRR ? kLeanTabT1 : kLeanTabT];    // its rho_0 thresholds
+#endif
     __shared__ uint32_t lds_hprod[kBlock / 64];               // Philox: chunks published by H wave w
     __shared__ uint32_t lds_pprod[kBlock / 64];               // Philox transition noise made by the O2 wave: chunks published
     // Wave priorities (s_setprio).  numpy streams: the serial recurrence (E) first, the H wave's PCG64 draws are filler work.
@@ -274,6 +373,11 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     const int role = tid / kBlock;                  // 0 = E, 1 = O1, 2 = O2, 3 = H
     const int l = tid & (kBlock - 1);               // env slot inside the block
     const int w = l >> 6;
+#if MDPP_LEAN_TU_NOISE == 2
+    // Numpy noise: this unit keeps the parent arrangement whole -- its own tables built in the kernel, one set-up for all four
+    // roles, the E role last.  Its E lanes' share of the form's own tables (lds_sstab, lds_pntab, lds_kw, lds_fi) has global loads
+    // of its own, so early action loads would gain nothing, and any other order of this form's blocks changed what the compiler
+    // reserves for its scalar spills and cost cfg2 + both noises 14 us per launch (profiles/lean_fixed_cost.txt section 5).
     const uint32_t S = (uint32_t)a.S, L = (uint32_t)a.L;
     if (tid < 16) {
         uint64_t cs = 0;
@@ -381,6 +485,82 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
     constexpr int kMinLanes = MDPP_LEAN_HMIN;       // H draws for the whole wave once this many lanes have room (or one runs low)
     uint32_t status = 0;
 
+#else
+    // Workgroup b runs on XCD b % 8 (round-robin dispatch).  Give every XCD one contiguous eighth of the
+    // envs, so that what its L2 writes back per output row is one contiguous range, not every eighth
+    // 256-env piece of it.
+    const uint32_t eblk = ((gridDim.x & 7u) == 0u) ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const uint32_t i = eblk * kBlock + l;
+    const uint32_t N = (uint32_t)a.N;
+    const bool rows = ROWS2 && (N % (uint32_t)kBlock) == 0u;       // (every wave of every block is there)
+    const uint32_t blk0 = eblk * kBlock, ln = (uint32_t)l & 63u;
+    const uint32_t ws = (uint32_t)__builtin_amdgcn_readfirstlane(w);
+    // min over the four waves' counters (two 64-bit LDS reads)
+    auto min4 = [&](const uint32_t *p) -> uint32_t {
+        const uint64_t x = __hip_atomic_load((const uint64_t *)p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint64_t y = __hip_atomic_load((const uint64_t *)p + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return min(min((uint32_t)x, (uint32_t)(x >> 32)), min((uint32_t)y, (uint32_t)(y >> 32)));
+    };
+    const uint32_t A = (uint32_t)a.A;
+    constexpr int kMinLanes = MDPP_LEAN_HMIN;       // H draws for the whole wave once this many lanes have room (or one runs low)
+    uint32_t status = 0;
+
+    const uint32_t total = (uint32_t)K * N;
+    typedef typename std::conditional<IRR, uint2, int>::type Act;      // (action, irrelevant action)
+    // the set-up every lane has a share of: rings and counters, and the noise forms' tables
+    auto setup_shared = [&]() __attribute__((always_inline)) {
+        if (tid < kBlock) { lds_ring[tid] = 0; lds_head[tid] = 0; if (NRN) { lds_hhead[tid] = 0; lds_epos[tid] = 0; } }
+        if (NRN || NPN) {
+            for (uint32_t k = tid; k < 2048u; k += kRoles * kBlock) {
+                const uint64_t lo = (uint64_t)k << 53, hi = lo + ((1ULL << 53) - 1ULL);       // the bucket's words
+                uint32_t c0 = 0, c1 = 0;
+                for (int j = 0; j < 8; j++) {
+                    const uint64_t t = a.init_thr[j] > (1ULL << 53) - 1ULL ? ~0ULL : a.init_thr[j] << 11;
+                    c0 += (t <= lo) ? 1u : 0u; c1 += (t <= hi) ? 1u : 0u;
+                }
+                lds_sstab[k] = (uint8_t)(c0 == c1 ? c0 : 0xFFu);
+            }
+        }
+        if (NPN) {
+            for (uint32_t k = tid; k < 4096u; k += kRoles * kBlock) {
+                const uint64_t lo = (uint64_t)k << 52, hi = lo + ((1ULL << 52) - 1ULL);
+                uint32_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+                for (int j = 0; j < 7; j++) { a0 += (a.pn_TL[j] <= lo) ? 1u : 0u; a1 += (a.pn_TL[j] <= hi) ? 1u : 0u; }
+                for (int j = 0; j < 8; j++) { b0 += (a.pn_TU[j] <= lo) ? 1u : 0u; b1 += (a.pn_TU[j] <= hi) ? 1u : 0u; }
+                lds_pntab[k] = (uint8_t)((a0 == a1 && b0 == b1) ? (a0 | (b0 << 4)) : 0xFFu);
+            }
+        }
+        if (NRN)
+            for (int k = tid; k < 256; k += kRoles * kBlock) { lds_kw[k] = make_ulonglong2(d_zig_ki[k], (unsigned long long)(__double_as_longlong(d_zig_wi[k]) + (52LL << 52)));   /* {ki, W = wi 2^52} */ lds_fi[k] = d_zig_fi[k]; }
+        if (tid < kBlock / 64) { lds_prod[tid] = 0; lds_cons[tid][0] = 0; lds_cons[tid][1] = 0; lds_hprod[tid] = 0; lds_pprod[tid] = 0; lds_rprod[tid] = 0; lds_rcons[tid] = 0; }
+        if (tid == 0) lds_done = 0;
+    };
+
+    // =============================================================== E: state recurrence (mdpp_discrete_lean_e.inc)
+    // The E lanes go first and alone: before the set-up they fetch their state word and the actions of the first
+    // kAhead + 1 chunks, whose way from HBM then runs under the table copy of the other lanes and the barrier -- they take no
+    // part in the copy, so nothing they wait for lies behind those loads.  (A lane past N of a ragged block reads what the
+    // last env reads; it leaves after the barrier.)
+    if (role == 0) {
+#include "mdpp_discrete_lean_e.inc"
+        return;
+    }
+
+    // =============================================================== the other roles' set-up
+    // the tables: thread kBlock + c copies unit c (the E lanes, tid < kBlock, have their first loads to issue instead)
+    if (tid >= kBlock && (uint32_t)(tid - kBlock) < kTabUnits) {
+        const uint32_t c = (uint32_t)(tid - kBlock);
+        lds_tab[c] = a.lean_blob[c < kLeanTabCol1 ? c : c + kTabSkip];
+    }
+    setup_shared();
+    // (the episode step count at launch, for the O1 lane's every-n phase: read BEFORE the barrier -- the E lane
+    //  writes the word back at the end of the launch, and with K <= kDepth it could get there before O1 starts)
+    uint32_t steps_at_launch = 0;
+    if (EVN && role == 1 && i < N) steps_at_launch = ((const uint32_t *)&a.state[i])[2] & 0x7FFFFFFFu;
+    __syncthreads();                                // these waves' one barrier (the E waves run theirs: mdpp_discrete_lean_e.inc)
+    if (i >= N) return;                             // ragged last block: its spare lanes leave (as above)
+
+#endif
     // =============================================================== H: start-state producer
     if (role == 3) {
         if (!ar && !PN && !NRN) return;
@@ -665,7 +845,9 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
         return;
     }
 
+#if MDPP_LEAN_TU_NOISE == 2
     const uint32_t total = (uint32_t)K * N;
+#endif
     const int nchunks = (K + kChunk - 1) / kChunk;
 
     // =============================================================== O1: reward path
@@ -923,326 +1105,10 @@ __global__ __launch_bounds__(kRoles * kBlock) void k_discrete_rollout_lean(Discr
         return;
     }
 
+#if MDPP_LEAN_TU_NOISE == 2
     // =============================================================== E: state recurrence
-    __builtin_amdgcn_s_setprio(kPrioE);   // the serial recurrence is the critical path; H is filler work
-    // hist: bytes newest first, 0xFF = NaN  ->  nibbles newest first, bit 3 = is a state
-    uint32_t k2, qv, cnt, steps0, last_reset = 0, badq[2] = {0u, 0u};
-    bool pend = false;                              // next-step mode: the episode ended on the previous step
-    {
-        uint4 st = a.state[i];
-        k2 = 0;
-        for (int j = 3; j >= 0; j--) {
-            const uint32_t b = (st.x >> (8 * j)) & 0xFFu;
-            k2 = (k2 << 4) | (b == 0xFFu ? 0u : ((b & 7u) | 8u));
-        }
-        const bool own_q = !PHILOX && !IRR && !nextmode && NZ == 0;   // word 1 of the state is this kernel's draw queue (fast_ok handles)
-        const uint32_t qc = own_q ? (st.y >> 24) & 7u : 0u;
-        qv = own_q ? (st.y & 0x00777777u) | (0x00888888u & ((1u << (4u * qc)) - 1u)) : 0u;
-        steps0 = st.z & 0x7FFFFFFFu;
-        pend = nextmode && (st.z >> 31) != 0u;
-        const uint32_t ms = (uint32_t)a.max_steps;
-        cnt = HASMAX ? (0x10000u - ms) + (steps0 < ms ? steps0 : ms) : 0u;
-    }
-    const uint32_t c0 = HASMAX ? 0x10000u - (uint32_t)a.max_steps : 0u;
-    auto r_act = __builtin_amdgcn_make_buffer_rsrc((void *)actions, 0, total * 4u * (uint32_t)kEN, kPRsrc);
-    const uint32_t v4 = i * 4u * (uint32_t)kEN;
-    uint32_t head_local = 0;
-    S0Word s0c = 0;
-    uint32_t sel = (k2 & 7u) | kSelPad;
-    uint32_t c1 = IRR ? (a.irr_state[i] & 7u) : 0u;                 // the irrelevant part of curr_state
-    const uint32_t A1 = IRR ? (uint32_t)a.A1 : 1u;
-
-    uint32_t pnc = 0, pnc_hi = 0;                   // PN: this chunk's transition-noise nibbles (numpy streams: bytes a | b << 4)
-    // NRN: the env stream by position (header).  ep = position of the next draw; (m0, m1, m2, xv) = meta[ep .. ep + 2], x[ep],
-    // fetched at the end of the previous step; hh = positions H has made, as last read
-    uint32_t ep = 0, hh = 0, m0 = 0, m1 = 0, m2 = 0;
-    double xv = 0.0;
-    auto ensure = [&](uint32_t upto) __attribute__((always_inline)) {       // positions < upto are made
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(upto > hh) != 0, 0)) {
-            uint32_t spins = 0;
-            hh = __hip_atomic_load(&lds_hhead[l], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            while (__builtin_amdgcn_ballot_w64(upto > hh) != 0) {
-                __hip_atomic_store(&lds_epos[l], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);    // (H's window follows E)
-                __builtin_amdgcn_s_sleep(1);
-                hh = __hip_atomic_load(&lds_hhead[l], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (++spins > kSpinLimit) { status |= kStatusInternal; hh = upto; break; }
-            }
-        }
-    };
-    auto fetch = [&]() __attribute__((always_inline)) {
-        ensure(ep + 3u);
-        m0 = lds_meta[ep & (uint32_t)(kXR - 1)][l];
-        m1 = lds_meta[(ep + 1u) & (uint32_t)(kXR - 1)][l];
-        m2 = lds_meta[(ep + 2u) & (uint32_t)(kXR - 1)][l];
-        if constexpr (NRX) xv = lds_x[ep & (uint32_t)(kXR - 1)][l];
-    };
-    if constexpr (NRN) fetch();
-    // PN: byte s of {enc_lo, enc_hi} = s | 8 | is_terminal[s] << 7, the column byte of a re-drawn state
-    uint32_t enc_lo = 0, enc_hi = 0;
-    if constexpr (PN) {
-        uint64_t enc = 0;
-        for (uint32_t s_ = 0; s_ < 8u; s_++) enc |= (uint64_t)(s_ | 8u | ((uint32_t)((a.term_mask >> s_) & 1ULL) << 7)) << (8 * s_);
-        enc_lo = (uint32_t)enc; enc_hi = (uint32_t)(enc >> 32);
-    }
-    auto pull = [&](int c) {
-        if (!ar && !PN) return;                     // (no resets: nothing is drawn, the H lanes have left)
-        if (NPN && c >= 0) {                        // this chunk's transition-noise bytes, made by the H wave from the space stream
-            uint32_t spins = 0;
-            while (wg_load_acq(&lds_hprod[w]) < (uint32_t)(c + 1)) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
-            }
-            pnc = lds_pn2[c % kHChunksNp][0][l];
-            pnc_hi = lds_pn2[c % kHChunksNp][1][l];
-        }
-        if constexpr (NRN) return;                  // (start states come with the positions)
-        if (!PHILOX && !ar) return;
-        if constexpr (PHILOX) {                     // this chunk's start states, made by the H wave
-            uint32_t spins = 0;
-            while (wg_load_acq(&lds_hprod[w]) < (uint32_t)(c + 1)) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
-            }
-            s0c = lds_s0[c % kHChunks][l];
-            if constexpr (PN) {
-                spins = 0;
-                while (wg_load_acq(&lds_pprod[w]) < (uint32_t)(c + 1)) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
-                }
-                pnc = lds_pn[c % kHChunks][l];
-            }
-            return;
-        }
-        const uint64_t rt = __hip_atomic_load(&lds_ring[l], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const uint32_t vals = (uint32_t)rt, tail = (uint32_t)(rt >> 32);
-        const uint32_t qc = (uint32_t)__builtin_popcount(qv & 0x88888888u);
-        const uint32_t avail = tail - head_local, room = kQueueCap - qc;       // (IRR: both even, entries are nibble pairs)
-        const uint32_t take = avail < room ? avail : room;
-        const uint32_t rot = __builtin_amdgcn_alignbit(vals, vals, (head_local & 7u) * 4u);
-        const uint32_t m = (1u << (4u * take)) - 1u;
-        qv |= (rot & m) << (4u * qc);
-        head_local += take;
-        __hip_atomic_store(&lds_head[l], head_local, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-    typedef typename std::conditional<IRR, uint2, int>::type Act;      // (action, irrelevant action)
-    typedef typename std::conditional<IRR, uint4, uint2>::type Col;    // their columns
-    auto column = [&](Act act, uint32_t &badm, int u) -> Col {
-        int action;
-        if constexpr (IRR) action = (int)act.x; else action = act;
-        uint32_t ua = (uint32_t)action;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(ua >= A) != 0, 0)) {
-            ua = (uint32_t)(action + ((action >> 31) & (int)A));
-            const bool bad = ua >= A;
-            // (next-step mode: an action the reset call ignores is not an error; decided at the step)
-            if (nextmode) badm |= bad ? (1u << u) : 0u; else status |= bad ? (uint32_t)MDPP_STATUS_BAD_ACTION : 0u;
-            ua = bad ? 0u : ua;
-        }
-        if constexpr (IRR) {
-            const int action1 = (int)act.y;
-            uint32_t ub = (uint32_t)action1;
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64(ub >= A1) != 0, 0)) {
-                ub = (uint32_t)(action1 + ((action1 >> 31) & (int)A1));
-                const bool bad = ub >= A1;
-                if (nextmode) badm |= bad ? (1u << u) : 0u; else status |= bad ? (uint32_t)MDPP_STATUS_BAD_ACTION : 0u;
-                ub = bad ? 0u : ub;
-            }
-            const uint2 ca = lds_col[ua], cb = lds_col1[ub];
-            return make_uint4(ca.x, ca.y, cb.x, cb.y);
-        } else {
-            return lds_col[ua];
-        }
-    };
-    auto stepE = [&](const Col &col, int k, uint32_t badbit) {
-        uint32_t entry = __builtin_amdgcn_perm(col.y, col.x, sel);                    // D1: P[cur][a] | 8 | terminal << 7
-        if constexpr (PN && PHILOX) {                                                 // D2 (:1604-1622), philox_pnoise_*
-            const uint32_t nib = (pnc >> (4 * (k % kChunk))) & 0xFu, j = nib & 7u, nx = entry & 7u;
-            const uint32_t ns = nib > 7u ? j + (j >= nx ? 1u : 0u) : nx;
-            entry = __builtin_amdgcn_perm(enc_hi, enc_lo, ns | kSelPad);
-        }
-        if constexpr (NPN) {                                                          // ... on the space stream's word: min(a, n) + max(b - n, 0)
-            const uint32_t by = (((k % kChunk) < 4 ? pnc : pnc_hi) >> (8 * (k & 3))) & 0xFFu, nx = entry & 7u;
-            const uint32_t ns = min(by & 15u, nx) + (uint32_t)max((int)(by >> 4) - (int)nx, 0);
-            entry = __builtin_amdgcn_perm(enc_hi, enc_lo, ns | kSelPad);
-        }
-        const uint32_t k2n = (k2 << 4) | entry;       // (bit 7 of the sum is set anyway: the nibble below was a state)
-        bool need = entry > 0x7Fu;                                                    // D7: is_terminal[next]
-        uint32_t rc = entry;                          // (O1 / O2 take bit 7 out)
-        if (HASMAX) {
-            cnt += 1;
-            need = need || cnt >= 0x10000u;
-            rc = __builtin_amdgcn_perm(cnt, entry, 0x0c060c00u);                       // byte 0 the entry, byte 2 truncated
-        }
-        need = need && ar;
-        uint32_t rec_a = k2n;
-        if (nextmode) {
-            const bool ended = need && !pend;
-            need = pend;                                         // reset now: this call is reset() (:2250-2278) ...
-            rc = pend ? 0u : rc;                                 // ... which returns no flags,
-            rec_a = pend ? 0u : k2n;                             // no reward (history word 0: O1 sees a reset, pays 0.0)
-            status |= (badbit != 0u && !pend) ? (uint32_t)MDPP_STATUS_BAD_ACTION : 0u;
-            pend = ended;
-        }
-        uint32_t s0v = PHILOX ? (uint32_t)(s0c >> (kEN * 4 * (k % kChunk))) & (IRR ? 0xFFu : 0xFu) : qv & (IRR ? 0xFFu : 0xFu);
-        if constexpr (NRN) {
-            // this step's draws on the env stream: the normal that starts at position ep, then -- if the episode ended -- one word
-            uint32_t kind = (m0 >> 3) & 3u;
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64(kind >= 2u) != 0, 0)) {
-                uint32_t guard = 0;
-                while (__builtin_amdgcn_ballot_w64(kind == 2u) != 0) {          // wedge point rejected: the draw starts over two words on
-                    const bool red = kind == 2u;
-                    ep += red ? 2u : 0u;
-                    uint32_t o0 = m0, o1 = m1, o2 = m2;
-                    double ox = xv;
-                    fetch();
-                    if (!red) { m0 = o0; m1 = o1; m2 = o2; xv = ox; }
-                    kind = (m0 >> 3) & 3u;
-                    if (++guard > 64u) { status |= kStatusInternal; break; }
-                }
-            }
-            uint32_t cntw = kind == 0u ? 1u : 2u, ssm = kind == 0u ? m1 : m2;
-            // tail: its words are counted in the high byte, the start state of the word behind them is in bits 5-7
-            if (kind == 3u) { cntw = m0 >> 8; ssm = m0 >> 5; }
-            if constexpr (NRX) lds_rx[k % KD][l] = xv;
-            s0v = (ssm & 7u) | 8u;
-            ep += cntw + (need ? 1u : 0u);
-            __hip_atomic_store(&lds_epos[l], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (H's window follows E)
-            fetch();
-        }
-        if (!PHILOX && !NRN && __builtin_expect(__builtin_amdgcn_ballot_w64(need && s0v == 0u) != 0, 0)) {
-            uint32_t spins = 0;
-            while (__builtin_amdgcn_ballot_w64(need && (qv & 0xFu) == 0u) != 0) {
-                pull(-1);                                        // (the queue only: not the chunk's noise bytes)
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > kSpinLimit) { status |= kStatusInternal; qv |= 8u; break; }
-            }
-            s0v = qv & (IRR ? 0xFFu : 0xFu);
-        }
-        if constexpr (IRR) {                                     // the irrelevant sub-space steps on its own table
-            const uint32_t n1 = __builtin_amdgcn_perm(col.w, col.z, c1 | kSelPad);
-            c1 = need ? ((s0v >> 4) & 7u) : n1;
-            rc |= c1 << 8;                                       // byte 1: the irrelevant observation
-            s0v &= 0xFu;
-        }
-        k2 = need ? s0v : k2n;
-        if (!PHILOX && !NRN) qv = need ? (qv >> (4 * kEN)) : qv;
-        if (HASMAX) cnt = need ? c0 : cnt;
-        else last_reset = need ? (uint32_t)(k + 1) : last_reset;
-        sel = (k2 & 7u) | kSelPad;
-        lds_rec[0][k % KD][l] = rec_a;
-        lds_rec[1][k % KD][l] = k2;
-        lds_rec[2][k % KD][l] = rc;
-    };
-
-    auto load_act = [&](int k) -> Act {
-        const uint32_t kk = (uint32_t)min(k, K - 1);
-        if constexpr (IRR) {
-            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r_act, v4, kk * N * 8u, MDPP_LEAN_LD_AUX);
-            return make_uint2(v.x, v.y);
-        } else {
-            return __builtin_amdgcn_raw_buffer_load_b32(r_act, v4, kk * N * 4u, MDPP_LEAN_LD_AUX);
-        }
-    };
-    // Actions are fetched kAhead chunks ahead of their use, columns one chunk ahead.  The buffers rotate
-    // by NAME (the chunk loop is unrolled kAhead times): copying a register whose load is still in
-    // flight makes the wave wait for it, which would put one HBM latency into every chunk.
-    constexpr int kAh = IRR ? 2 : kAhead;      // (action pairs: half the depth, for registers)
-    static_assert(kAh % 2 == 0, "the column double buffer alternates with the chunk index");
-    Act actq[kAh][kChunk];       // slot (m - 1) % kAhead holds the actions of chunk m
-    Col colq[2][kChunk];            // slot m & 1 holds the columns of chunk m
-#pragma unroll
-    for (int u = 0; u < kChunk; u++) colq[0][u] = column(load_act(u), badq[0], u);
-#pragma unroll
-    for (int q = 0; q < kAh; q++)
-#pragma unroll
-        for (int u = 0; u < kChunk; u++) actq[q][u] = load_act((q + 1) * kChunk + u);
-
-    const int nfull = K / kChunk;   // full chunks; a ragged tail (K % kChunk steps) follows the loop
-    auto wait_room = [&](int kend) {                // do not run more than kDepth steps ahead of the O wave
-        if (kend > KD) {
-            const uint32_t must = (uint32_t)(kend - KD);
-            uint32_t spins = 0;
-            for (;;) {
-                const uint64_t cc = __hip_atomic_load((const uint64_t *)&lds_cons[w][0], __ATOMIC_ACQUIRE,
-                                                      __HIP_MEMORY_SCOPE_WORKGROUP);
-                uint32_t have = min((uint32_t)cc, (uint32_t)(cc >> 32));
-                if (rows) {                         // whole-row stores: every O2 wave reads this wave's records
-#pragma unroll
-                    for (int j = 0; j < kBlock / 64; j++) have = min(have, wg_load_acq(&lds_cons[j][1]));
-                }
-                if (have >= must) break;
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > kSpinLimit) { status |= kStatusInternal; break; }
-            }
-        }
-    };
-    // one full chunk: slot j's actions -> next chunk's columns, (re)fill slot j, step, publish
-    auto chunkE = [&](int c, int j, bool refill) {
-        const int kbase = c * kChunk;
-        badq[(j + 1) & 1] = 0u;
-#pragma unroll
-        for (int u = 0; u < kChunk; u++) colq[(j + 1) & 1][u] = column(actq[j][u], badq[(j + 1) & 1], u);
-        if (refill) {
-#pragma unroll
-            for (int u = 0; u < kChunk; u++) actq[j][u] = load_act(kbase + (kAh + 1) * kChunk + u);
-        }
-        wait_room(kbase + kChunk);
-        pull(c);
-#pragma unroll
-        for (int u = 0; u < kChunk; u++) stepE(colq[j & 1][u], kbase + u, (badq[j & 1] >> u) & 1u);
-        if (NRN) __hip_atomic_store(&lds_epos[l], ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if ((l & 63) == 0) wg_store_rel(&lds_prod[w], (uint32_t)(kbase + kChunk));
-    };
-    // (single-exit loop body, no global load in an inner loop: the compiler then counts its vmcnt waits
-    //  exactly, vmcnt(8 (kAhead - 1) + ...), instead of waiting for every load in flight)
-    const int ngrp = nfull / kAh;
-    for (int g = 0; g < ngrp; g++) {
-#pragma unroll
-        for (int j = 0; j < kAh; j++) chunkE(g * kAh + j, j, true);
-    }
-#pragma unroll
-    for (int j = 0; j < kAh - 1; j++)
-        if (ngrp * kAh + j < nfull) chunkE(ngrp * kAh + j, j, false);
-    if (K % kChunk) {               // (no global load inside the loop above: its waits stay counted, not vmcnt(0))
-        const int kbase = nfull * kChunk;
-        Act ta[kChunk];
-#pragma unroll
-        for (int u = 0; u < kChunk; u++) ta[u] = load_act(kbase + u);
-        wait_room(kbase + kChunk);
-        pull(nfull);
-#pragma unroll
-        for (int u = 0; u < kChunk; u++)
-            if (kbase + u < K) {
-                uint32_t bm = 0;
-                const Col cc = column(ta[u], bm, 0);
-                stepE(cc, kbase + u, bm);
-            }
-        if ((l & 63) == 0) wg_store_rel(&lds_prod[w], (uint32_t)K);
-    }
-
-    // back to the handle's state words: hist bytes, queue nibbles + count, episode steps
-    uint32_t hist = 0;
-    for (int j = 3; j >= 0; j--) {
-        const uint32_t nb = (k2 >> (4 * j)) & 0xFu;
-        hist = (hist << 8) | ((nb & 8u) ? (nb & 7u) : 0xFFu);
-    }
-    const uint32_t qc = (uint32_t)__builtin_popcount(qv & 0x00888888u);
-    const bool own_q = !PHILOX && !IRR && !nextmode && NZ == 0;
-    if (NRN) __hip_atomic_store(&lds_epos[l], ep, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // (H un-draws what lies beyond)
-    if (!own_q && !PHILOX && !NRN) {
-        // word 1 of the state is not a queue for these handles: what sits in the register queue goes back to the H
-        // lane (it un-draws everything not taken)
-        __hip_atomic_store(&lds_head[l], head_local - qc, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    if (IRR) a.irr_state[i] = c1;                   // the irrelevant state has its own array
-    uint32_t steps;
-    if (HASMAX) steps = cnt - c0;
-    else steps = last_reset ? (uint32_t)K - last_reset : steps0 + (uint32_t)K;
-    uint32_t *st = (uint32_t *)&a.state[i];
-    st[0] = hist; st[2] = steps | (pend ? 0x80000000u : 0u);        // word 3 (delay line) belongs to the O1 lane
-    if (own_q) st[1] = (qv & 0x00777777u) | (qc << 24);   // (other handles: word 1 is older history, unused at L <= 3)
-    if ((l & 63) == 0) __hip_atomic_fetch_add(&lds_done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (status) atomicOr(&a.status[i], status);
+#include "mdpp_discrete_lean_e.inc"
+#endif
 }
 
 // This unit's instantiations; nz: the noise bits (1 transition, 2 reward; 0 outside the two noise units).
@@ -1251,6 +1117,7 @@ static bool lean_launch(const DiscreteArgs &a, const DiscreteIO &io, const int n
     constexpr bool kNext = MDPP_LEAN_TU_NEXT;
     const int K = io.K;
     const bool ph = a.philox != 0, irr = a.irr != 0;
+    if (!a.lean_blob) return false;        // (no tables: not a handle for this kernel, mdpp_capi.hip lean_tables_build)
     if (io.final_obs) return false;        // (rollouts of K >= 32 steps never ask for final observations: mdpp_step does, K = 1)
     const bool shape = a.autoreset == MDPP_AUTORESET_NEXT_STEP ? a.lean_next_ok != 0
                        : (nz && !ph) ? a.shape_ok_noise_np != 0

@@ -124,7 +124,16 @@ struct DiscreteArgs {
     uint64_t init_thr[16];      // ceil(init_cdf[j] * 2^53): cdf[j] <= u  <=>  init_thr[j] <= (r >> 11)
     float rsel[4];              // reward for {paid*2 + terminal}, formed in float64 like :1987-1990,:2107
     uint64_t minv_lo, minv_hi;  // inverse of the PCG64 LCG multiplier mod 2^128 (un-drawing)
+    // k_discrete_rollout_lean's LDS tables as one device blob (layout: kLeanTab* below), built once per upload by
+    // k_lean_build_tables; nullptr: the handle is not one the lean launcher takes
+    const uint4 *lean_blob;
 };
+
+// The lean rollout kernel's MDP tables, in 16-byte units of the blob (mdpp_discrete_lean.hip): the reward-bit table, the action
+// columns, the rho_0 thresholds, the same two of the irrelevant sub-space, the reward values by (steps to the pay step, bit,
+// terminated).  An instantiation without an irrelevant sub-space leaves units [kLeanTabCol1, kLeanTabRsel) out of its LDS copy.
+constexpr uint32_t kLeanTabV = 0, kLeanTabCol = 512, kLeanTabT = 520, kLeanTabCol1 = 524, kLeanTabT1 = 532, kLeanTabRsel = 536,
+                   kLeanTabUnits = 600;
 
 // ---- discrete, one launch = one step (mdpp_discrete_step1.hip): everything the kernel reads, nothing else -- built once at
 // mdpp_upload_discrete_tables (the caller's buffers are filled in per launch)
@@ -318,6 +327,7 @@ struct mdpp_env {
     mdpp::DiscreteArgs dargs;
     mdpp::Step1Args s1args;     // k_discrete_step1's argument block (blob == nullptr: the shape does not qualify)
     void *d_s1_blob;
+    void *d_lean_blob;          // DiscreteArgs::lean_blob (kLeanTabUnits * 16 bytes)
     // the tabular policy of closed-loop rollouts (mdpp_set_policy): thresholds uint32 [S][A] on the device, the seed of its stream
     void *d_policy_thr;
     uint64_t policy_seed;
@@ -545,6 +555,8 @@ bool launch_discrete_step1(const DiscreteArgs &d, const Step1Args &proto, const 
 bool launch_discrete_quiet(const DiscreteArgs &a, const DiscreteIO &io);
 bool launch_discrete_pipe(const DiscreteArgs &a, const DiscreteIO &io);
 bool launch_discrete_lean(const DiscreteArgs &a, const DiscreteIO &io);
+// the tables of `a` as the lean kernel's LDS image, into blob (kLeanTabUnits * 16 bytes); a.lean_blob itself is not read
+hipError_t launch_lean_build_tables(const DiscreteArgs &a, void *blob, hipStream_t s);
 bool launch_continuous_fast(const ContinuousArgs &a, const ContinuousIO &io);
 bool launch_continuous_step1(const ContinuousArgs &a, const ContinuousIO &io);
 bool launch_continuous_line(const ContinuousArgs &a, const ContinuousIO &io);
