@@ -108,6 +108,7 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
 
 /* transition-noise levels one handle serves at a time (mdpp_set_noise_levels) */
 #define MDPP_MAX_NOISE_LEVELS 16
+#define MDPP_MAX_SCHEDULE_ENTRIES (1 << 22) /* R M of one table of mdpp_set_learner_schedule */
 
 /* the tabular learner's algorithm (mdpp_set_learner); 2 is double Q-learning: two tables per env */
 enum { MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1, MDPP_LEARN_DOUBLE_Q = 2 };
@@ -348,7 +349,8 @@ const char *mdpp_policy_kernel_name(mdpp_env *h, int K);
  * RNG mode, with or without the transition- and reward-noise keys.  Anything else: MDPP_EUNSUPPORTED with the reason in
  * mdpp_last_error, from mdpp_set_learner already.
  * mdpp_set_learner (re)starts the learner: Q = q_init_dev ([N][S][A], device; copied on `stream`) or zeros.
- * mdpp_set_learner_rates changes alpha and epsilon only (no device work: a host-side decay schedule costs nothing).
+ * mdpp_set_learner_rates changes alpha and epsilon only (no device work); the new values hold from the next launch on, for
+ * every env alike -- rates that follow each env's own episode count are mdpp_set_learner_schedule's (Schedules, below).
  * mdpp_get_q / mdpp_set_q: device pointers, float32 [N][S][A], ordered on `stream`.  Without a learner: MDPP_ESTATE, as
  * mdpp_step_n_learn.  mdpp_learn_kernel_name: as mdpp_kernel_name, for that launch (QLDS=1: the tables are staged in LDS). */
 int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma, float epsilon, uint64_t seed, const float *q_init_dev,
@@ -385,6 +387,42 @@ const char *mdpp_learn_kernel_name(mdpp_env *h, int K);
  * in LDS beside the MDP's. */
 int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream);
 int mdpp_set_learner_gamma(mdpp_env *h, float gamma);
+
+/* Schedules: per-EPISODE epsilon and / or alpha.  A handle with a learner may carry one schedule: an epsilon table (float32 in
+ * [0, 1]), an alpha table (float32 in (0, 1]) or both, each [R][M] with 1 <= M and R M <= MDPP_MAX_SCHEDULE_ENTRIES; a row index
+ * row[i] in [0, R) per env (the handle's LOCAL index i, like the per-env parameters); and a counter ep[i], int32, in a buffer
+ * of the handle -- zero when the schedule is set.  The epsilon table becomes thresholds on the host by the rule above:
+ * T[r][e] = ceil((double)epsilon[r][e] 2^31).
+ * In a learning launch (mdpp_step_n_learn, mdpp_step_n_learn_summary) env i starts with e = min(ep[i], M - 1),
+ * E = T[row[i]][e] if epsilon is scheduled (else its own E, uniform or per-env), alpha = A[row[i]][e] if alpha is scheduled
+ * (else its own).  Every selection made in a step -- the action, and sarsa's a' = sel(s', t + 1) inside its target -- uses the E
+ * in force at the step's start, the update the alpha in force then.  AFTER the update of a step that is not the reset call
+ * of a next-step-autoreset env: terminated or truncated moves ep[i] by one and E and alpha are looked up again -- exactly the
+ * rule by which the summary's `episodes` moves.  The counter is stored when the launch ends.  So: with autoreset disabled
+ * truncated stays set past max_episode_steps and the counter moves at every step, as `episodes` does; a sarsa action carried
+ * over an episode's end was chosen under the old E; a reset call selects with the current E, writes the action, ignores it
+ * and counts nothing; past M - 1 the last entry holds.  Behaviour of ep[i] beyond 2^31 - 1 is unspecified.
+ * Everything else above holds word for word (stream ids 15 - 17, the twin property, pieces, QLDS).  mdpp_step_n_eval and its
+ * summary form read neither table and do not move the counter.
+ * mdpp_set_learner_schedule takes HOST pointers: epsilon and alpha [R][M] or NULL (one at least), row [N] or NULL when R == 1.
+ * It validates (MDPP_EINVAL: nothing changed), forms the thresholds, copies on `stream` and zeroes the counters.  Without a
+ * learner: MDPP_ESTATE.  On a handle with per-env noise levels in force or with mdpp_learner_per_env_mdp on:
+ * MDPP_EUNSUPPORTED, "... an epsilon/alpha schedule with per-env noise levels / one MDP per env: not built", nothing changed;
+ * while a schedule is in force mdpp_set_noise_levels and turning mdpp_learner_per_env_mdp on are refused with the same
+ * reason, and what is in force stays.  mdpp_clear_learner_schedule drops it (the scheduled parameter is again what
+ * mdpp_set_learner / _rates / _params made it); so do mdpp_set_learner and mdpp_clear_learner.  While epsilon is scheduled,
+ * mdpp_set_learner_params with an epsilon and mdpp_set_learner_rates (which always carries one) are refused: MDPP_ESTATE,
+ * the reason names mdpp_clear_learner_schedule; likewise alpha while alpha is scheduled.
+ * mdpp_get_learner_episodes / mdpp_set_learner_episodes: the counters, int32 [N] DEVICE pointers, ordered on `stream`;
+ * dev_in NULL zeroes them (the schedule starts again).  Without a schedule: MDPP_ESTATE.
+ * The launch is the kernel's SCHED form, always with PE=1 (the name gains ",SCHED=1", last): the lane looks its values up at
+ * the launch's start and at each of its episode ends, one dword load per scheduled table.
+ * Under a graph: which tables are scheduled and M are carried by value; the tables, the rows and the counters are read from
+ * the handle's buffers at replay, so a captured launch continues the schedule where the last launch left it, like Q. */
+int mdpp_set_learner_schedule(mdpp_env *h, const float *epsilon, const float *alpha, int R, int M, const int32_t *row, void *stream);
+int mdpp_clear_learner_schedule(mdpp_env *h);
+int mdpp_get_learner_episodes(mdpp_env *h, int32_t *dev_out, void *stream);
+int mdpp_set_learner_episodes(mdpp_env *h, const int32_t *dev_in, void *stream);
 
 /* One MDP per env for the learner and evaluation launches.  mdpp_learner_per_env_mdp(h, on) sets a flag of the handle, off at
  * creation.  With the flag on, a handle with cfg.num_tables == cfg.num_envs (each env its own P, terminal states, rewardable
@@ -562,7 +600,9 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   levels' values (mdpp_set_noise_levels with the same number of distinct transition levels), the caller's five summary
  *   arrays (they accumulate across replays), the env's state record, streams and tables.  Per-env noise levels on one MDP
  *   per env (mdpp_noise_levels_per_env_mdp) are no exception: the level bytes, sigma, the per-level cdfs and (T, M) and every
- *   env's table set are read from the handle's buffers at replay.
+ *   env's table set are read from the handle's buffers at replay.  A schedule (mdpp_set_learner_schedule): which tables are
+ *   scheduled and M go by value; the tables, the rows and the episode counters are read -- and the counters written -- at
+ *   replay (mdpp_set_learner_schedule with the same tables given and the same M, or mdpp_set_learner_episodes, between replays).
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

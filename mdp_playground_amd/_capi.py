@@ -26,6 +26,8 @@ OPTIONS = {"NO_PIPE": 1 << 0, "NO_HELPER": 1 << 1, "NO_PARK": 1 << 2, "NO_CFAST"
            "NO_LEARN_LDS": 1 << 18, "LEARN_SHORT_PIECES": 1 << 19, "NO_NLEV_LDS": 1 << 20, "NO_PM_LDS": 1 << 21,
            "NO_PM_NLEV_LDS": 1 << 22}
 MAX_NOISE_LEVELS = 16                              # MDPP_MAX_NOISE_LEVELS
+MAX_SCHEDULE_ENTRIES = 1 << 22                     # MDPP_MAX_SCHEDULE_ENTRIES
+ESTATE = -4               # MDPP_ESTATE
 LEARN_ALGOS = {"q_learning": 0, "sarsa": 1}        # MDPP_LEARN_*: the one-table algorithms
 MDPP_LEARN_DOUBLE_Q = 2                            # "double_q": two tables per env
 
@@ -53,6 +55,7 @@ EXPORTS = [
     "mdpp_step_n_eval", "mdpp_eval_kernel_name", "mdpp_step_n_learn_summary", "mdpp_step_n_eval_summary", "mdpp_current_obs",
     "mdpp_set_noise_levels", "mdpp_get_noise_levels", "mdpp_clear_noise_levels", "mdpp_learner_per_env_mdp",
     "mdpp_noise_levels_per_env_mdp",
+    "mdpp_set_learner_schedule", "mdpp_clear_learner_schedule", "mdpp_get_learner_episodes", "mdpp_set_learner_episodes",
 ]
 
 
@@ -186,6 +189,10 @@ def load():
     L.mdpp_clear_noise_levels.argtypes = [vp]
     L.mdpp_learner_per_env_mdp.argtypes = [vp, i32]
     L.mdpp_noise_levels_per_env_mdp.argtypes = [vp, i32]
+    L.mdpp_set_learner_schedule.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    L.mdpp_clear_learner_schedule.argtypes = [vp]
+    L.mdpp_get_learner_episodes.argtypes = [vp, vp, vp]
+    L.mdpp_set_learner_episodes.argtypes = [vp, vp, vp]
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

@@ -58,7 +58,7 @@ static void free_all(mdpp_env *h) {
                     h->d_img_tpl, h->d_img_tplp, h->d_img_clsx, h->d_img_clsy, h->d_img_rot, h->d_img_state_out,
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
                     h->d_img_near, h->d_s1_blob, h->d_lean_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
-                    h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E,
+                    h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E, h->d_sched_E, h->d_sched_alpha, h->d_sched_row, h->d_sched_ep,
                     h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
@@ -125,6 +125,8 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->learn_pm = false;
     h->nl_on = false; h->nl_pm = false; h->nl_levels = 0; h->nl_fill_valid = false; h->nl_fill_alpha = h->nl_fill_gamma = 0.0f; h->nl_fill_E = 0;
     h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
+    h->sched_on = h->sched_eps = h->sched_alpha = false; h->sched_R = h->sched_M = 0; h->sched_cap = 0;
+    h->d_sched_E = h->d_sched_alpha = h->d_sched_row = h->d_sched_ep = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
     h->d_hist_hi = nullptr;
@@ -1418,6 +1420,12 @@ extern "C" const char *mdpp_policy_kernel_name(mdpp_env *h, int K) {
 }
 
 // ---- ... of in-kernel tabular TD learners (mdpp_discrete_learn.hip) ----
+// what a handle that would need SCHED on the NLEV or PM forms is told
+static const char *const kSchedNotBuilt = "an epsilon/alpha schedule with per-env noise levels / one MDP per env: not built";
+static std::string sched_owns(const char *fn, const char *what) {
+    return std::string(fn) + ": " + what + " follows the schedule in force (mdpp_set_learner_schedule); mdpp_clear_learner_schedule first";
+}
+
 static bool learner_rates_ok(float alpha, float epsilon) {
     return alpha > 0.0f && alpha <= 1.0f && epsilon >= 0.0f && epsilon <= 1.0f;      // (NaN fails both)
 }
@@ -1460,6 +1468,7 @@ extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma,
     h->learn_E = (uint32_t)ceil((double)epsilon * 2147483648.0);
     h->learn_pe = h->learn_pe_stale = 0;                         // all three uniform
     h->nl_fill_valid = false;
+    h->sched_on = false;         // (a new learner starts without a schedule: the next one zeroes the counters)
     h->learn_ready = true;
     return MDPP_OK;
 }
@@ -1468,6 +1477,7 @@ extern "C" int mdpp_learner_per_env_mdp(mdpp_env *h, int on) {
     if (!h) return MDPP_EINVAL;
     // (a shared MDP, or no discrete handle: accepted, nothing changes)
     if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
+    if (on && h->sched_on) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kSchedNotBuilt);
     if (h->learn_pm && !on) {
         h->learn_ready = false;                          // (as mdpp_clear_learner: the buffers stay)
         if (h->nl_pm) h->nl_on = false;                  // ... and levels given on one MDP per env go with the learner that ran them
@@ -1489,6 +1499,7 @@ extern "C" int mdpp_noise_levels_per_env_mdp(mdpp_env *h, int on) {
 extern "C" int mdpp_clear_learner(mdpp_env *h) {
     if (!h) return MDPP_EINVAL;
     h->learn_ready = false;      // (the buffers stay: a launch queued earlier may still use them)
+    h->sched_on = false;
     return MDPP_OK;
 }
 
@@ -1496,6 +1507,8 @@ extern "C" int mdpp_set_learner_rates(mdpp_env *h, float alpha, float epsilon) {
     if (!h) return MDPP_EINVAL;
     if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_set_learner_rates: no learner set (mdpp_set_learner)");
     if (!learner_rates_ok(alpha, epsilon)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_rates: need alpha in (0, 1] and epsilon in [0, 1]");
+    // (the call carries both parameters, and a schedule in force owns one of them at least)
+    if (h->sched_on) return fail(h, MDPP_ESTATE, sched_owns("mdpp_set_learner_rates", h->sched_eps ? "epsilon" : "alpha"));
     h->learn_alpha = alpha;
     h->learn_E = (uint32_t)ceil((double)epsilon * 2147483648.0);
     // alpha and epsilon are uniform again; while gamma stays per-env the next launch fills their arrays with these values
@@ -1524,6 +1537,8 @@ extern "C" int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const fl
         if (epsilon && !(epsilon[i] >= 0.0f && epsilon[i] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_params: need every epsilon in [0, 1]");
     }
     if (!alpha && !gamma && !epsilon) return MDPP_OK;
+    if (h->sched_on && epsilon && h->sched_eps) return fail(h, MDPP_ESTATE, sched_owns("mdpp_set_learner_params", "epsilon"));
+    if (h->sched_on && alpha && h->sched_alpha) return fail(h, MDPP_ESTATE, sched_owns("mdpp_set_learner_params", "alpha"));
     HIPCHK(h, hipSetDevice(h->device));
     for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
         if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
@@ -1545,11 +1560,91 @@ extern "C" int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const fl
     return MDPP_OK;
 }
 
+// ---- per-episode epsilon / alpha schedules of the learning launches (mdpp_discrete_learn.hpp: SCHED) ----
+extern "C" int mdpp_set_learner_schedule(mdpp_env *h, const float *epsilon, const float *alpha, int R, int M, const int32_t *row, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_set_learner_schedule: no learner set (mdpp_set_learner)");
+    if (h->nl_on || h->learn_pm) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_learner_schedule: ") + kSchedNotBuilt);
+    if (!epsilon && !alpha) return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: need an epsilon table, an alpha table or both");
+    if (R < 1 || M < 1 || (uint64_t)R * (uint64_t)M > (uint64_t)MDPP_MAX_SCHEDULE_ENTRIES)
+        return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: need R >= 1, M >= 1 and R M <= 2^22");
+    if (!row && R != 1) return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: R > 1 needs row, the row index of every env");
+    const size_t N = (size_t)h->cfg.num_envs, RM = (size_t)R * (size_t)M;
+    for (size_t k = 0; k < RM; k++) {                            // (NaN fails every comparison)
+        if (epsilon && !(epsilon[k] >= 0.0f && epsilon[k] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: need every epsilon in [0, 1]");
+        if (alpha && !(alpha[k] > 0.0f && alpha[k] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: need every alpha in (0, 1]");
+    }
+    for (size_t i = 0; row && i < N; i++)
+        if (row[i] < 0 || row[i] >= R) return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: need every row index in [0, R)");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->sched_cap < RM) {                                     // (hipFree waits for the launches that still read them)
+        for (void **d : {&h->d_sched_E, &h->d_sched_alpha})
+            if (*d) { HIPCHK(h, hipFree(*d)); *d = nullptr; }
+        h->sched_cap = 0;
+        h->sched_on = false;
+    }
+    for (void **d : {&h->d_sched_E, &h->d_sched_alpha})
+        if (!*d) HIPCHK(h, hipMalloc(d, RM * 4u));
+    h->sched_cap = h->sched_cap < RM ? RM : h->sched_cap;
+    for (void **d : {&h->d_sched_row, &h->d_sched_ep})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
+    // (the launch takes the PE form and fills the parameter arrays while all three are uniform -- allocated here, as in
+    //  mdpp_set_noise_levels, so that no launch entry point does)
+    for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
+    // (host to device from the caller's pageable memory: the runtime has read the source when the call returns)
+    if (alpha) HIPCHK(h, hipMemcpyAsync(h->d_sched_alpha, alpha, RM * 4u, hipMemcpyHostToDevice, s));
+    if (row) HIPCHK(h, hipMemcpyAsync(h->d_sched_row, row, N * 4u, hipMemcpyHostToDevice, s));
+    else HIPCHK(h, hipMemsetAsync(h->d_sched_row, 0, N * 4u, s));
+    HIPCHK(h, hipMemsetAsync(h->d_sched_ep, 0, N * 4u, s));
+    if (epsilon) {
+        std::vector<uint32_t> T(RM);
+        for (size_t k = 0; k < RM; k++) T[k] = (uint32_t)ceil((double)epsilon[k] * 2147483648.0);
+        HIPCHK(h, hipMemcpyAsync(h->d_sched_E, T.data(), RM * 4u, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipStreamSynchronize(s));                      // (T is this call's own: gone at return)
+    }
+    h->sched_eps = epsilon != nullptr; h->sched_alpha = alpha != nullptr;
+    h->sched_R = R; h->sched_M = M;
+    h->sched_on = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_learner_schedule(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->sched_on = false;         // (the buffers stay: a launch queued earlier may still read them)
+    return MDPP_OK;
+}
+
+static int sched_counters_ready(mdpp_env *h, const char *what) {
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_learner)");
+    if (!h->sched_on) return fail(h, MDPP_ESTATE, std::string(what) + ": no schedule set (mdpp_set_learner_schedule)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_get_learner_episodes(mdpp_env *h, int32_t *dev_out, void *stream) {
+    if (!h || !dev_out) return MDPP_EINVAL;
+    if (int rc = sched_counters_ready(h, "mdpp_get_learner_episodes")) return rc;
+    HIPCHK(h, hipMemcpyAsync(dev_out, h->d_sched_ep, (size_t)h->cfg.num_envs * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_learner_episodes(mdpp_env *h, const int32_t *dev_in, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (int rc = sched_counters_ready(h, "mdpp_set_learner_episodes")) return rc;
+    const size_t bytes = (size_t)h->cfg.num_envs * 4u;
+    if (dev_in) HIPCHK(h, hipMemcpyAsync(h->d_sched_ep, dev_in, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else HIPCHK(h, hipMemsetAsync(h->d_sched_ep, 0, bytes, (hipStream_t)stream));
+    return MDPP_OK;
+}
+
 // ---- per-env noise levels of the learner and evaluation launches (mdpp_discrete_closed.hpp: NLEV) ----
 extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream) {
     if (!h) return MDPP_EINVAL;
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: " + why);
+    if (h->sched_on) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_noise_levels: ") + kSchedNotBuilt + "; mdpp_clear_learner_schedule first");
     if (h->cfg.num_tables != 1 && !(h->nl_pm && h->learn_pm)) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_noise_levels: per-env noise levels on one MDP per env: not built");
     const mdpp_config &c = h->cfg;
     if (transition_noise && !c.has_transition_noise)

@@ -27,6 +27,8 @@
 //   act(cur, ptick)            the action of this step; also called on a reset call, from the state in the record
 //   learn(cur, action, nxt, reward, done, truncated_with_reset, ptick)
 //                              after the reward is formed, before a same-step reset: nxt is the true next state
+//   episode_end(ended)         after every step that is not a reset call, where the summary rule below is applied: ended =
+//                              terminated or truncated (empty but for the scheduled learner, mdpp_discrete_learn.hpp SCHED)
 //   finish(i)                  per lane, after the last step
 //
 // SUMMARY = true (mdpp_step_n_learn_summary / mdpp_step_n_eval_summary): the same K steps with no [K][N] output.  The lane
@@ -390,6 +392,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
             episode_start(out_state);
         }
         put_obs(out_state, so);
+        agent.episode_end(done || truncated);
         if constexpr (SUMMARY) {
             ep_ret += (double)rout;
             ep_len += 1;

@@ -45,20 +45,20 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
     if (!why.empty()) { h->err = "mdpp_step_n_learn: " + why; return MDPP_EUNSUPPORTED; }
     const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
     const bool pm = h->learn_pm && h->cfg.num_tables != 1;       // one MDP per env: the PM kernels
-    if ((h->nl_on || pm) && !h->learn_pe) {
-        // per-env noise levels and one MDP per env run the PE form: while all three parameters are uniform their arrays are
+    if ((h->nl_on || pm || h->sched_on) && !h->learn_pe) {
+        // per-env noise levels, one MDP per env and a per-episode schedule run the PE form: while all three parameters are uniform their arrays are
         // filled here, and again when a value has changed since (the scalar setters do not mark them while nothing is per-env).
         // The arrays themselves are mdpp_set_noise_levels' (mdpp_set_learner's with one MDP per env): a launch entry point
         // allocates nothing (it may be under a graph capture)
         const bool fresh = h->nl_fill_valid && h->nl_fill_alpha == h->learn_alpha && h->nl_fill_gamma == h->learn_gamma && h->nl_fill_E == h->learn_E;
         if (!fresh && !io.name_out) {
-            if (!h->d_learn_alpha || !h->d_learn_gamma || !h->d_learn_E) { h->err = "mdpp_step_n_learn: the per-env parameter arrays are missing (mdpp_set_noise_levels / mdpp_set_learner allocate them)"; return MDPP_ESTATE; }
+            if (!h->d_learn_alpha || !h->d_learn_gamma || !h->d_learn_E) { h->err = "mdpp_step_n_learn: the per-env parameter arrays are missing (mdpp_set_noise_levels / mdpp_set_learner / mdpp_set_learner_schedule allocate them)"; return MDPP_ESTATE; }
             h->learn_pe_stale = 7u;
         }
     } else {
         h->nl_fill_valid = false;
     }
-    const bool pe = h->learn_pe || h->nl_on || pm;
+    const bool pe = h->learn_pe || h->nl_on || pm || h->sched_on;
     if (pe && h->learn_pe_stale && !io.name_out) {
         const uint32_t N = (uint32_t)h->cfg.num_envs, grid = (N + kBlock - 1) / kBlock;
         uint32_t abits, gbits;
@@ -76,6 +76,10 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
     int rc = MDPP_OK;
     if (pm) {
         with_bools([&](auto DB, auto SM, auto NL) { rc = launch_learn_form_pm<DB(), SM(), NL()>(h, io); }, dbl, io.summary != nullptr, h->nl_on);
+        return rc;
+    }
+    if (h->sched_on) {           // (mdpp_set_learner_schedule refuses levels and one MDP per env: the shared-MDP PE form with the tables)
+        with_bools([&](auto DB, auto SM) { rc = launch_learn_form<true, DB(), SM(), false, true>(h, io); }, dbl, io.summary != nullptr);
         return rc;
     }
     with_bools([&](auto PE, auto DB, auto SM, auto NL) {

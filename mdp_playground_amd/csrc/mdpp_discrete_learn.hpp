@@ -46,8 +46,17 @@
 // in LDS (closed_agent_lds_offset).  The host picks PM and QLDS per launch (closed_agent_lds_pm).  With NLEV = 1
 // (mdpp_noise_levels_per_env_mdp) the per-level cdfs take the shared cdf's place (closed_agent_lds_pm_nlev).
 //
-// launch_learn_form<PE, DOUBLE, SUMMARY, NLEV> launches one form, launch_learn_form_pm<DOUBLE, SUMMARY, NLEV> the PM = 1 and PM = 2
-// kernels of one form on a handle with one MDP per env.  Each of the twenty forms built is instantiated in a translation
+// SCHED = 1 (per-episode schedules, mdpp_set_learner_schedule) is the PE learner with E and / or alpha looked up in a table
+// by the env's own episode count: begin() loads the lane's row index and its counter ep and looks up entry min(ep, M - 1) of
+// its row -- one plain global dword load per scheduled table (the tables are small, L2-resident and read only here and at
+// episode ends; they have no LDS placement) -- into the registers the PE form keeps its parameters in.  closed_loop_rollout
+// calls episode_end(terminated or truncated) after every step that is not a reset call, where the summary's `episodes`
+// moves: the counter moves and both are looked up again, so the NEXT step selects and updates with them (sarsa's a' inside
+// this step's target was selected before, under the old E).  finish() stores the counter.  The agent alone knows of the
+// schedule: the step and the other agents (an empty episode_end) are the code they were.
+//
+// launch_learn_form<PE, DOUBLE, SUMMARY, NLEV, SCHED> launches one form, launch_learn_form_pm<DOUBLE, SUMMARY, NLEV> the PM = 1 and PM = 2
+// kernels of one form on a handle with one MDP per env.  Each of the twenty-four forms built is instantiated in a translation
 // unit of its own, so that they compile in parallel: mdpp_discrete_learn.hip holds the uniform rollout form and the
 // dispatcher, mdpp_discrete_learn_*.hip one explicit instantiation each; every other unit sees the `extern template` below.
 #pragma once
@@ -75,12 +84,22 @@ struct LearnArgsPE : LearnArgs {
 struct LearnArgsNL : LearnArgsPE {
     NoiseLevelArgs nl;
 };
-template <bool PE, bool NLEV>
-using LearnArgsOf = std::conditional_t<NLEV, LearnArgsNL, std::conditional_t<PE, LearnArgsPE, LearnArgs>>;
+// ... of the scheduled form: the PE parameters and the per-episode tables [R][M] (device; a NULL table: that parameter is not
+// scheduled and the lane keeps its PE value), the envs' rows and episode counters [N]
+struct LearnArgsSched : LearnArgsPE {
+    const uint32_t *sc_E;
+    const float *sc_alpha;
+    const int32_t *sc_row;
+    int32_t *sc_ep;
+    int32_t M;
+};
+template <bool PE, bool NLEV, bool SCHED = false>
+using LearnArgsOf = std::conditional_t<SCHED, LearnArgsSched, std::conditional_t<NLEV, LearnArgsNL, std::conditional_t<PE, LearnArgsPE, LearnArgs>>>;
 
-template <bool QLDS, bool PE, bool DOUBLE>
+template <bool QLDS, bool PE, bool DOUBLE, bool SCHED = false>
 struct LearnAgent {
-    const std::conditional_t<PE, LearnArgsPE, LearnArgs> &p;
+    static_assert(!SCHED || PE, "a schedule runs the PE learner");
+    const std::conditional_t<SCHED, LearnArgsSched, std::conditional_t<PE, LearnArgsPE, LearnArgs>> &p;
     float *q_lds;               // this lane's column of the workgroup's tables: entry e at q_lds[e 256]
     uint32_t A, SA, N;          // (DOUBLE: SA is ONE table's entries; B's entry e is SA + e)
     float *qg;                  // this lane's table in the buffer: entry e at qg[e N]
@@ -92,7 +111,19 @@ struct LearnAgent {
     uint64_t blk_cur;
     float pe_alpha, pe_gamma;   // PE: this lane's parameters
     uint32_t pe_E;
+    uint32_t sc_base;           // SCHED: row[i] M, where this lane's row starts in the tables
+    int32_t sc_ep;              // SCHED: this lane's episode counter
 
+    // SCHED: entry min(ep, M - 1) of the lane's row into the PE registers
+    __device__ __forceinline__ void sched_lookup() {
+        if constexpr (SCHED) {
+            // (compared unsigned: a negative counter, which only mdpp_set_learner_episodes could have put there, clamps too)
+            const uint32_t last = (uint32_t)(p.M - 1);
+            const uint32_t at = sc_base + ((uint32_t)sc_ep < last ? (uint32_t)sc_ep : last);
+            if (p.sc_E) pe_E = p.sc_E[at];                      // (wave-uniform: a table is there or not)
+            if (p.sc_alpha) pe_alpha = p.sc_alpha[at];
+        }
+    }
     __device__ __forceinline__ float alpha() const { if constexpr (PE) return pe_alpha; else return p.alpha; }
     __device__ __forceinline__ float gamma() const { if constexpr (PE) return pe_gamma; else return p.gamma; }
     __device__ __forceinline__ uint32_t E() const { if constexpr (PE) return pe_E; else return p.E; }
@@ -110,6 +141,11 @@ struct LearnAgent {
     __device__ __forceinline__ void begin(uint32_t i, uint64_t genv, uint64_t ptick0) {
         qg = p.q + i;
         if constexpr (PE) { pe_alpha = p.pe_alpha[i]; pe_gamma = p.pe_gamma[i]; pe_E = p.pe_E[i]; }
+        if constexpr (SCHED) {
+            sc_base = (uint32_t)p.sc_row[i] * (uint32_t)p.M;
+            sc_ep = p.sc_ep[i];
+            sched_lookup();
+        }
         if (QLDS)
             for (uint32_t e = 0; e < entries(); e++) q_lds[e * kBlock] = qg[(size_t)e * N];
         philox_start_block(p.seed, genv, ptick0 >> 2, kPhiloxLearnExploreStream, e_nxt);
@@ -220,7 +256,17 @@ struct LearnAgent {
         have_carry = sarsa && !done && !truncated_with_reset;
         carried = a2;
     }
+    // after a step that is not a reset call: the episode ended -- the schedule moves on for the next step
+    __device__ __forceinline__ void episode_end(bool ended) {
+        if constexpr (SCHED) {
+            if (ended) {
+                sc_ep += 1;
+                sched_lookup();
+            }
+        } else (void)ended;
+    }
     __device__ __forceinline__ void finish(uint32_t i) {
+        if constexpr (SCHED) p.sc_ep[i] = sc_ep;
         if (QLDS)
             for (uint32_t e = 0; e < entries(); e++) qg[(size_t)e * N] = q_lds[e * kBlock];
         if (p.carry_out) p.carry[i] = have_carry ? (int32_t)carried : -1;
@@ -229,14 +275,15 @@ struct LearnAgent {
 
 // (the step is called with or without the levels, not with empty ones: one call handed a NoiseLevelArgs{} of the kernel's own
 //  making reorders instructions in 34 of the forms without levels)
-template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false, bool NLEV = false, int PM = 0>
-__global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs a, LearnArgsOf<PE, NLEV> p, int K,
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false, bool NLEV = false, int PM = 0, bool SCHED = false>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs a, LearnArgsOf<PE, NLEV, SCHED> p, int K,
                                                                    void *__restrict__ obs,
                                                                    float *__restrict__ reward,
                                                                    uint8_t *__restrict__ term,
                                                                    uint8_t *__restrict__ trunc) {
     static_assert(!NLEV || (NOISE && PE), "per-env noise levels run the PE learner around a NOISE step");
     static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
+    static_assert(!SCHED || (PE && !NLEV && PM == 0), "a schedule runs the PE learner on a shared MDP without noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
     unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
@@ -245,17 +292,18 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs 
         q_lds = lds + closed_agent_lds_offset<PM>(a);
         if constexpr (NLEV) q_lds += p.nl.lds_bytes;
     }
-    LearnAgent<QLDS, PE, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    LearnAgent<QLDS, PE, DOUBLE, SCHED> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
     if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, false, NLEV, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent, EpisodeSummaryArgs{}, p.nl);
     else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, false, false, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
     else closed_loop_rollout<PHILOX, NOISE, UNIT>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent);
 }
 
 // ... keeping episode summaries instead of writing the [K][N] arrays (p.actions is unused)
-template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false, bool NLEV = false, int PM = 0>
-__global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs a, LearnArgsOf<PE, NLEV> p, int K, EpisodeSummaryArgs sm) {
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false, bool NLEV = false, int PM = 0, bool SCHED = false>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs a, LearnArgsOf<PE, NLEV, SCHED> p, int K, EpisodeSummaryArgs sm) {
     static_assert(!NLEV || (NOISE && PE), "per-env noise levels run the PE learner around a NOISE step");
     static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
+    static_assert(!SCHED || (PE && !NLEV && PM == 0), "a schedule runs the PE learner on a shared MDP without noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
     unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
@@ -264,23 +312,25 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs 
         q_lds = lds + closed_agent_lds_offset<PM>(a);
         if constexpr (NLEV) q_lds += p.nl.lds_bytes;
     }
-    LearnAgent<QLDS, PE, DOUBLE> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    LearnAgent<QLDS, PE, DOUBLE, SCHED> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
     if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
     else if constexpr (PM != 0) closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
     else closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
 
 // the kernel of one form: full output, or summaries
-template <bool SUMMARY, bool PH, bool NZ, bool UNIT, bool QL, bool PE, bool DOUBLE, bool NLEV, int PM = 0>
+template <bool SUMMARY, bool PH, bool NZ, bool UNIT, bool QL, bool PE, bool DOUBLE, bool NLEV, int PM = 0, bool SCHED = false>
 constexpr auto learn_kernel() {
-    if constexpr (SUMMARY) return k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM>;
-    else return k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM>;
+    if constexpr (SUMMARY) return k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
+    else return k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
 }
 
-// K learning steps of one form (NLEV: of a handle with per-env noise levels -- NOISE = 1 whatever its keys)
-template <bool PE, bool DOUBLE, bool SUMMARY, bool NLEV>
+// K learning steps of one form (NLEV: of a handle with per-env noise levels -- NOISE = 1 whatever its keys; SCHED: of a handle
+// with a per-episode schedule in force)
+template <bool PE, bool DOUBLE, bool SUMMARY, bool NLEV, bool SCHED = false>
 int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
     static_assert(!NLEV || PE, "per-env noise levels run the PE form");
+    static_assert(!SCHED || (PE && !NLEV), "a schedule runs the PE form, without noise levels");
     const DiscreteArgs &a = h->dargs;
     const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (DOUBLE ? 2u : 1u);
     int rc = MDPP_OK;
@@ -289,21 +339,24 @@ int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
             // the LDS forms when a workgroup's 256 tables (and the per-level cdfs) fit beside the MDP's (and the device grants it)
             bool qlds = false, clds = false;
             closed_agent_lds(h, q_lds, [&](bool q, size_t bytes) {
-                return q ? dynamic_lds_ok((const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), true, PE, DOUBLE, NLEV>(), bytes)
-                         : dynamic_lds_ok((const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), false, PE, DOUBLE, NLEV>(), bytes);
+                return q ? dynamic_lds_ok((const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), true, PE, DOUBLE, NLEV, 0, SCHED>(), bytes)
+                         : dynamic_lds_ok((const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), false, PE, DOUBLE, NLEV, 0, SCHED>(), bytes);
             }, qlds, clds);
             const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
             with_bools([&](auto QL) {
                 char name[kNameLen];
-                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s%s>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
-                         PH(), NZ(), UNIT(), QL(), PE ? ",PE=1" : "", DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "");
-                rc = launch_closed_loop<SUMMARY>(h, io, learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, NLEV>(),
+                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s%s%s>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
+                         PH(), NZ(), UNIT(), QL(), PE ? ",PE=1" : "", DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", SCHED ? ",SCHED=1" : "");
+                rc = launch_closed_loop<SUMMARY>(h, io, learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, NLEV, 0, SCHED>(),
                                                  (size_t)a.lds_bytes + cdf_lds + (QL() ? q_lds : 0u), qlds || clds, name, [&](int k0, int kc, int32_t *actions) {
                     const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
                                          h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
                     if constexpr (PE) {
                         const LearnArgsPE pe{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E};
                         if constexpr (NLEV) return LearnArgsNL{pe, noise_level_args(h, cdf_lds)};
+                        else if constexpr (SCHED)
+                            return LearnArgsSched{pe, h->sched_eps ? (const uint32_t *)h->d_sched_E : nullptr, h->sched_alpha ? (const float *)h->d_sched_alpha : nullptr,
+                                                  (const int32_t *)h->d_sched_row, (int32_t *)h->d_sched_ep, h->sched_M};
                         else return pe;
                     } else return base;
                 });
@@ -361,7 +414,7 @@ int launch_learn_form_pm(mdpp_env *h, const DiscreteIO &io) {
     return rc;
 }
 
-// the forms built <PE, DOUBLE, SUMMARY, NLEV> and, with one MDP per env, <DOUBLE, SUMMARY, NLEV>, each defined (an explicit
+// the forms built <PE, DOUBLE, SUMMARY, NLEV[, SCHED]> and, with one MDP per env, <DOUBLE, SUMMARY, NLEV>, each defined (an explicit
 // instantiation) in the translation unit named
 extern template int launch_learn_form<false, false, false, false>(mdpp_env *, const DiscreteIO &);  // mdpp_discrete_learn.hip
 extern template int launch_learn_form<true, false, false, false>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_learn_pe.hip
@@ -375,6 +428,10 @@ extern template int launch_learn_form<true, false, false, true>(mdpp_env *, cons
 extern template int launch_learn_form<true, true, false, true>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_learn_double_pe_nlev.hip
 extern template int launch_learn_form<true, false, true, true>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_learn_pe_nlev_summary.hip
 extern template int launch_learn_form<true, true, true, true>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_learn_double_pe_nlev_summary.hip
+extern template int launch_learn_form<true, false, false, false, true>(mdpp_env *, const DiscreteIO &);  // mdpp_discrete_learn_pe_sched.hip
+extern template int launch_learn_form<true, false, true, false, true>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_learn_pe_sched_summary.hip
+extern template int launch_learn_form<true, true, false, false, true>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_learn_double_pe_sched.hip
+extern template int launch_learn_form<true, true, true, false, true>(mdpp_env *, const DiscreteIO &);    // mdpp_discrete_learn_double_pe_sched_summary.hip
 extern template int launch_learn_form_pm<false, false, false>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_learn_pe_pm.hip
 extern template int launch_learn_form_pm<true, false, false>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_double_pe_pm.hip
 extern template int launch_learn_form_pm<false, true, false>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_pe_pm_summary.hip

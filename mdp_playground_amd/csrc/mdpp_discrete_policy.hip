@@ -69,6 +69,7 @@ struct PolicyAgent {
         return cnt < A - 1u ? cnt : A - 1u;
     }
     __device__ __forceinline__ void learn(uint32_t, uint32_t, uint32_t, float, bool, bool, uint64_t) {}
+    __device__ __forceinline__ void episode_end(bool) {}
     __device__ __forceinline__ void finish(uint32_t) {}
 };
 

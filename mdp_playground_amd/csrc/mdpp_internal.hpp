@@ -364,6 +364,14 @@ struct mdpp_env {
     bool nl_fill_valid;
     float nl_fill_alpha, nl_fill_gamma;
     uint32_t nl_fill_E;
+    // Per-episode schedules of the learner (mdpp_set_learner_schedule; mdpp_discrete_learn.hpp SCHED): sched_on: the learning
+    // launches take their SCHED form.  Device: the thresholds uint32 [R][M] and / or the alphas float32 [R][M] (sched_eps /
+    // sched_alpha: which table is in force), every env's row int32 [N] and episode counter int32 [N]; sched_cap: the entries
+    // the two table buffers were allocated for.  Like levels, a schedule makes the launch the PE form (nl_fill_*).
+    bool sched_on, sched_eps, sched_alpha;
+    int32_t sched_R, sched_M;
+    size_t sched_cap;
+    void *d_sched_E, *d_sched_alpha, *d_sched_row, *d_sched_ep;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };

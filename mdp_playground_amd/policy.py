@@ -21,13 +21,19 @@ Per-env noise levels (set_noise_levels) are validated and reduced here as the li
 float64 [N] array of one key, noise_levels_reduce the distinct transition levels and each env's level byte,
 noise_level_thresholds the Philox (T, M) pair of every level, noise_level_cdfs the [levels, S, S] table of the
 categoricals' cdfs.
+
+Per-episode schedules of the learners (set_learner_schedule): epsilon_decay makes one row of a table,
+learner_schedule_arrays validates the tables and the envs' row indices and returns what the library takes.
 """
 import numpy as np
 
 __all__ = ["policy_thresholds", "epsilon_threshold", "explore_action", "check_learner_params", "learner_param_array", "LEARN_ALGOS",
-           "noise_level_array", "noise_levels_reduce", "noise_level_thresholds", "noise_level_cdfs", "MAX_NOISE_LEVELS"]
+           "noise_level_array", "noise_levels_reduce", "noise_level_thresholds", "noise_level_cdfs", "MAX_NOISE_LEVELS",
+           "epsilon_decay", "learner_schedule_arrays", "MAX_SCHEDULE_ENTRIES", "DECAY_KINDS"]
 
 LEARN_ALGOS = ("q_learning", "sarsa", "double_q")
+MAX_SCHEDULE_ENTRIES = 1 << 22   # R M of one schedule table (MDPP_MAX_SCHEDULE_ENTRIES)
+DECAY_KINDS = ("linear", "log", "const")
 MAX_NOISE_LEVELS = 16        # distinct transition_noise values one handle serves at a time (MDPP_MAX_NOISE_LEVELS)
 
 
@@ -201,3 +207,77 @@ def noise_level_cdfs(levels, S):
             cdf /= cdf[-1]
             out[l, n] = cdf
     return out
+
+
+def epsilon_decay(kind, start, num_episodes, final=0.0):
+    """One row of a per-episode table (set_learner_schedule), float64 [num_episodes]: entry e is the value of episode e.  With
+    x = e / max(num_episodes - 1, 1):
+        "const":   start
+        "linear":  start + (final - start) x
+        "log":     start (final / start) ** x        (needs start > 0 and final > 0)
+    so the first entry is ``start`` and, for num_episodes > 1, the last is ``final``.  These are THIS project's definitions: the
+    reference's experiment files name the three kinds ("epsilon_decay": ["linear", "log", "const"]) and ship no tabular agent
+    that would define them.  The row serves epsilon and alpha alike; the table's range checks are learner_schedule_arrays'."""
+    if kind not in DECAY_KINDS:
+        raise ValueError(f"epsilon_decay: kind must be one of {DECAY_KINDS}, got {kind!r}")
+    m = int(num_episodes)
+    if m != num_episodes or m < 1:
+        raise ValueError(f"epsilon_decay: num_episodes must be a positive integer, got {num_episodes!r}")
+    start, final = float(start), float(final)
+    if not (np.isfinite(start) and np.isfinite(final)):
+        raise ValueError("epsilon_decay: start and final must be finite")
+    x = np.arange(m, dtype=np.float64) / np.float64(max(m - 1, 1))
+    if kind == "const":
+        return np.full(m, start, dtype=np.float64)
+    if kind == "linear":
+        return start + (final - start) * x
+    if not (start > 0.0 and final > 0.0):
+        raise ValueError(f"epsilon_decay: \"log\" needs start > 0 and final > 0, got start = {start!r}, final = {final!r}")
+    return start * (final / start) ** x
+
+
+def _schedule_table(name, v):
+    a = _to_numpy(v)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"a schedule's {name} table must hold numbers, got dtype {a.dtype}")
+    if a.ndim not in (1, 2):
+        raise ValueError(f"a schedule's {name} table must be [M] or [R, M], got shape {a.shape}")
+    a = np.ascontiguousarray(a.reshape(1, -1) if a.ndim == 1 else a, dtype=np.float32)
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"a schedule's {name} table needs at least one row and one entry, got shape {a.shape}")
+    if a.size > MAX_SCHEDULE_ENTRIES:
+        raise ValueError(f"a schedule's {name} table has {a.size} entries, at most 2^22 = {MAX_SCHEDULE_ENTRIES} are served")
+    ok = (a > 0.0) & (a <= 1.0) if name == "alpha" else (a >= 0.0) & (a <= 1.0)       # (NaN fails both)
+    if not np.all(ok):
+        r, e = (int(x) for x in np.argwhere(~ok)[0])
+        raise ValueError(f"a schedule's {name} must lie in {'(0, 1]' if name == 'alpha' else '[0, 1]'} as float32, got {a[r, e]!r} "
+                         f"at row {r}, episode {e}")
+    return a
+
+
+def learner_schedule_arrays(epsilon=None, alpha=None, row=None, num_envs=None):
+    """What set_learner_schedule hands the library, after every check: (epsilon, alpha, row, R, M) with the tables float32
+    [R, M] (None: that parameter is not scheduled) and row int32 [num_envs] (None when R == 1).  A table is [M] (one row) or
+    [R, M], numpy or a torch tensor on any device; epsilon lies in [0, 1], alpha -- as float32 -- in (0, 1]; NaN fails; at
+    least one table is given, two have the same shape, 1 <= M and R M <= 2^22.  ``row`` is an integer array of num_envs entries
+    in [0, R): the table row env i of THE HANDLE follows; required iff R > 1 (with R == 1 it may be given, all zeros).
+    ValueError otherwise."""
+    if epsilon is None and alpha is None:
+        raise ValueError("a schedule needs an epsilon table, an alpha table or both")
+    eps = None if epsilon is None else _schedule_table("epsilon", epsilon)
+    al = None if alpha is None else _schedule_table("alpha", alpha)
+    if eps is not None and al is not None and eps.shape != al.shape:
+        raise ValueError(f"a schedule's tables must have one shape, got epsilon {eps.shape} and alpha {al.shape}")
+    R, M = (eps if eps is not None else al).shape
+    if row is None:
+        if R > 1:
+            raise ValueError(f"a schedule of R = {R} rows needs row, the row index of every env")
+        return eps, al, None, R, M
+    r = _to_numpy(row)
+    if r.dtype == np.bool_ or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"a schedule's row must be an integer array, got dtype {r.dtype}")
+    if r.ndim != 1 or (num_envs is not None and r.shape[0] != int(num_envs)):
+        raise ValueError(f"a schedule's row must be 1-D with num_envs{'' if num_envs is None else ' = %d' % int(num_envs)} entries, got shape {r.shape}")
+    if r.size and (r.min() < 0 or r.max() >= R):
+        raise ValueError(f"a schedule's row indices must lie in [0, {R}), got {int(r.min() if r.min() < 0 else r.max())}")
+    return eps, al, (None if R == 1 else np.ascontiguousarray(r, dtype=np.int32)), R, M

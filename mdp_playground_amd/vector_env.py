@@ -96,6 +96,7 @@ class RLToyVectorEnv:
         self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
         self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
+        self._learn_sched = None              # set_learner_schedule's validated arrays while a schedule is in force
         self._nl_pm = False                   # set_noise_levels(per_env_mdp=True) is in force (the handle's second flag is on)
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
@@ -782,12 +783,14 @@ class RLToyVectorEnv:
         and set_learner_rates then serve the handle, set_policy and set_noise_levels still refuse it.  Without it such a
         handle is refused as ever -- also while a per_env_mdp learner is in force: that refused call leaves learner and tables as
         they are (``set_learner(None)`` is how to drop them).  A call the library refuses leaves the opt-in as it was.
-        ValueError on a handle with one shared MDP; ``set_learner(None)`` clears it too."""
+        ValueError on a handle with one shared MDP; ``set_learner(None)`` clears it too.
+        Every successful call, ``set_learner(None)`` included, also drops a schedule (set_learner_schedule) and its counters."""
         if algo is None:
             capi.check(self._lib, self._h, self._lib.mdpp_clear_learner(self._h), "mdpp_clear_learner")
             capi.check(self._lib, self._h, self._lib.mdpp_learner_per_env_mdp(self._h, 0), "mdpp_learner_per_env_mdp")
             self._learn_rates = None
             self._learn_pm = False
+            self._learn_sched = None
             self._drop_noise_levels_per_env_mdp()
             return
         if alpha is None or gamma is None or epsilon is None:
@@ -817,6 +820,7 @@ class RLToyVectorEnv:
             raise NotImplementedError(msg.decode() if msg else "mdpp_set_learner: unsupported")
         self._closed_call(rc, "mdpp_set_learner")
         self._learn_pm = bool(per_env_mdp)
+        self._learn_sched = None         # (mdpp_set_learner drops the schedule and its counters)
         self._learn_q_init = q           # (kept until the copy queued on the stream has certainly been made)
         self._learn_rates = [scalars[0], scalars[2]]
         self._learn_algo = algo
@@ -825,11 +829,24 @@ class RLToyVectorEnv:
 
     def set_learner_rates(self, alpha=None, epsilon=None, *, gamma=None):
         """New alpha, epsilon and / or gamma for the learner, each a scalar (uniform from now on) or a per-env array as in
-        set_learner (scalars: parameters only, no device work -- a decay schedule on the host costs nothing between launches;
-        arrays: one small copy on the current stream)."""
+        set_learner (scalars: parameters only, no device work; arrays: one small copy on the current stream).  A new value
+        holds from the next LAUNCH on, for every env alike: rates that follow each env's own episode count are
+        set_learner_schedule's.  While a schedule is in force the parameter it schedules is refused here (MdppError;
+        clear_learner_schedule() first) and what is in force stays; the other one and gamma are set as ever (a scalar for the
+        other one travels as an array of equal entries: the library's scalar call carries both parameters)."""
         policy_mod.check_learner_params(None, alpha, gamma, epsilon, self.num_envs)
         if self._learn_rates is None:
             raise capi.MdppError("set_learner_rates: no learner set (set_learner)")
+        if self._learn_sched is not None:
+            for n, v in (("alpha", alpha), ("epsilon", epsilon)):
+                if v is not None and self._learn_sched[n] is not None:
+                    raise capi.MdppError(f"set_learner_rates: {n} follows the schedule in force; clear_learner_schedule() "
+                                         "(mdpp_clear_learner_schedule) first")
+            # (mdpp_set_learner_rates carries both parameters and is refused under a schedule: the free one goes out as an array)
+            if alpha is not None and not policy_mod._is_array(alpha):
+                alpha = np.full(self.num_envs, alpha, np.float32)
+            if epsilon is not None and not policy_mod._is_array(epsilon):
+                epsilon = np.full(self.num_envs, epsilon, np.float32)
         given = {"alpha": alpha, "gamma": gamma, "epsilon": epsilon}
         arrays = {n: policy_mod.learner_param_array(n, v, self.num_envs) for n, v in given.items()}
         scalar = {n: v is not None and arrays[n] is None for n, v in given.items()}
@@ -848,6 +865,64 @@ class RLToyVectorEnv:
             self._closed_call(self._lib.mdpp_set_learner_gamma(self._h, float(gamma)), "mdpp_set_learner_gamma")
         self._learn_send_arrays(arrays["alpha"], arrays["gamma"], arrays["epsilon"])
 
+    # ------------------------------------------------------------------ per-episode epsilon / alpha schedules
+    def set_learner_schedule(self, epsilon=None, alpha=None, row=None):
+        """Per-EPISODE epsilon and / or alpha for rollout_learn.  ``epsilon`` and ``alpha`` are tables [M] or
+        [R, M] (numpy, or a torch tensor on any device; epsilon in [0, 1], alpha as float32 in (0, 1]; R M <= 2^22), ``row`` an
+        integer array [N] in [0, R) -- the table row env i of THIS handle follows (its local index, like the per-env
+        parameters); required iff R > 1.  The kernel keeps an int32 episode counter per env, zero after this call: the env
+        learns with entry min(counter, M - 1) of its row, and the counter moves, after the update, at every step that is
+        ``terminated or truncated`` and is not the reset call of a next-step-autoreset env -- the rule by which
+        summary.episodes moves -- so the envs of one launch each follow their own episode count.  Past M - 1 the last entry
+        holds.  A parameter without a table stays what set_learner / set_learner_rates made it.  policy.epsilon_decay makes
+        the rows "linear", "log" and "const".  rollout_eval reads no table and moves no counter.
+        ValueError (policy.learner_schedule_arrays) before any device work; MdppError without a learner;
+        NotImplementedError, nothing changed, on a handle with per-env noise levels or a per_env_mdp learner (not built).
+        set_learner drops the schedule; while it is in force set_noise_levels is refused.  Like noise levels the schedule is
+        configuration, and its counters are the learner's, not the env's: get_augmented_state / set_augmented_state carry
+        neither -- a checkpoint keeps learner_episodes() beside get_q() and gives both back (set_learner_episodes, set_q)."""
+        eps, al, rows, R, M = policy_mod.learner_schedule_arrays(epsilon, alpha, row, self.num_envs)
+        self._learn_check_kind()
+        rc = self._lib.mdpp_set_learner_schedule(self._h, capi.nptr(eps), capi.nptr(al), R, M, capi.nptr(rows), self._stream())
+        self._closed_call(rc, "mdpp_set_learner_schedule")
+        self._learn_sched = dict(epsilon=eps, alpha=al, row=rows)
+
+    def clear_learner_schedule(self):
+        """Drop the schedule: epsilon and alpha are again what set_learner / set_learner_rates made them (the scheduled
+        parameter's last uniform or per-env value).  The counters are zeroed by the next set_learner_schedule."""
+        capi.check(self._lib, self._h, self._lib.mdpp_clear_learner_schedule(self._h), "mdpp_clear_learner_schedule")
+        self._learn_sched = None
+
+    def learner_schedule(self):
+        """The schedule in force -- dict(epsilon=float32 [R, M] or None, alpha=likewise, row=int32 [N] or None), copies -- or
+        None."""
+        if self._learn_sched is None:
+            return None
+        return {k: None if v is None else v.copy() for k, v in self._learn_sched.items()}
+
+    def learner_episodes(self):
+        """The schedule's per-env episode counters, int32 [N] on the device; a copy, made on the current stream."""
+        self._learn_check_kind()
+        ep = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        self._closed_call(self._lib.mdpp_get_learner_episodes(self._h, C.c_void_p(ep.data_ptr()), self._stream()), "mdpp_get_learner_episodes")
+        return ep
+
+    def set_learner_episodes(self, x=None):
+        """Replace the schedule's counters: an integer array [N] of values >= 0 (numpy, or a torch tensor on any device), or
+        None for zeros -- the schedule starts again.  Copied on the current stream."""
+        self._learn_check_kind()
+        ep = None
+        if x is not None:
+            a = policy_mod._to_numpy(x)
+            if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or a.shape != (self.num_envs,):
+                raise ValueError(f"set_learner_episodes: need an integer array of shape ({self.num_envs},), got {a.dtype} {a.shape}")
+            if a.size and (a.min() < 0 or a.max() > 2 ** 31 - 1):
+                raise ValueError("set_learner_episodes: every counter must lie in [0, 2^31)")
+            ep = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        rc = self._lib.mdpp_set_learner_episodes(self._h, C.c_void_p(ep.data_ptr()) if ep is not None else None, self._stream())
+        self._closed_call(rc, "mdpp_set_learner_episodes")
+        self._learn_ep_init = ep         # (kept until the copy queued on the stream has certainly been made)
+
     def alloc_rollout_learn(self, K):
         """Output buffers of rollout_learn(K): alloc_rollout(K) and the actions, int32 [K, N]."""
         return self._alloc_rollout_closed(K)
@@ -856,7 +931,8 @@ class RLToyVectorEnv:
         """K steps of "select epsilon-greedily from the env's own Q, step, update that Q" in ONE kernel launch.  Returns (obs,
         reward, terminated, truncated, actions), each with a leading K axis; rollout(actions) on an identically built env
         returns the same first four, bit for bit.  SARSA carries its next action from step to step inside a call only: the
-        first step of every call selects afresh.
+        first step of every call selects afresh.  With a schedule (set_learner_schedule) every env selects and
+        updates with the epsilon / alpha of its own episode count, looked up again inside the launch at each episode end.
         ``summary`` (episode_summary()): the same K steps with the same effect on the env and the tables, but NO [K, N] array
         is written -- the kernel keeps the per-env episode numbers in ``summary`` and that object is returned."""
         self._learn_check_kind()
@@ -911,7 +987,7 @@ class RLToyVectorEnv:
     def learn_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
         launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning; NLEV=1: per-env
-        noise levels, set_noise_levels; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
+        noise levels, set_noise_levels; SCHED=1, always last: a per-episode schedule, set_learner_schedule; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
         per-env noise levels on one MDP per env, set_noise_levels(..., per_env_mdp=True) -- the arguments come in template order,
         "...,PE=1[,DOUBLE=1],NLEV=1,PM=1|2>"); empty for a handle it does not serve."""
         if self.kind != "discrete":
