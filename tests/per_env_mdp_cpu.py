@@ -39,11 +39,16 @@ _mdps = {}
 
 
 def build_mdps(cfg, seeds=SEEDS):
-    """mdp.build_mdp({**cfg, "seed": s}) for every seed (kept: a case's MDPs are built once per session)"""
+    """mdp.build_mdp({**cfg, "seed": s}) for every seed (kept: a case's MDPs are built once per session).  A config with a
+    "per_env_cfg" key -- an object called with a seed that returns further config keys, for envs that differ by more than the
+    seed: use_custom_mdp matrices (tests/closed_forms_shape_cases.py); its repr names it -- gives
+    mdp.build_mdp({**cfg, **cfg["per_env_cfg"](s), "seed": s}); such handles are made with mdps=[...]"""
     from mdp_playground_amd import mdp as mdp_mod
     key = (repr(sorted(cfg.items(), key=lambda kv: kv[0])), tuple(seeds))
     if key not in _mdps:
-        _mdps[key] = [mdp_mod.build_mdp({**cfg, "seed": s}) for s in seeds]
+        base = {k: v for k, v in cfg.items() if k != "per_env_cfg"}
+        more = cfg.get("per_env_cfg", lambda s: {})
+        _mdps[key] = [mdp_mod.build_mdp({**base, **more(s), "seed": s}) for s in seeds]
     return _mdps[key]
 
 
