@@ -1,7 +1,15 @@
 // The closed-loop step of a discrete env, stated once: K steps of "an agent picks a from the state the env is in, the env
-// steps, the agent sees the transition" in ONE launch.  k_discrete_policy_rollout (mdpp_discrete_policy.hip) and
-// k_discrete_learn_rollout (mdpp_discrete_learn.hip) are this body around their own Agent; so is the launcher and the rule
-// for which handles are served.
+// steps, the agent sees the transition" in ONE launch.  k_discrete_policy_rollout (mdpp_discrete_policy.hip), the learners'
+// kernels (mdpp_discrete_learn.hpp) and the greedy evaluation's (mdpp_discrete_eval.hpp) are this body, closed_loop_rollout,
+// around their own Agent; so is the launcher (launch_closed_loop) and the rule for which handles are served.
+//
+// What the learners and the evaluation share on the host -- both keep per-env Q-tables -- is here too, each stated once:
+//   closed_agent_lds       the placement: which of the Q-tables, the envs' MDP slots and the per-level cdfs go to LDS
+//   launch_closed_form     the launcher of one form: the step's compile-time facts, the placement, the kernel, its name, its LDS
+// A header of theirs holds the agent, the two __global__ kernels (the ziggurat LDS, where the agent's LDS starts, the agent,
+// the step), a form type for launch_closed_form and the entry templates its translation units instantiate.  The kernels'
+// bodies and the agents' table access are written out in each header: a shared body function, a shared table struct and a
+// shared "where the agent's LDS starts" each changed the instructions of kernels that exist.
 //
 // The step restates k_discrete_step (mdpp_discrete.hip) without its IRR branches and episode statistics, on the same lines
 // of the reference's mdp_playground/envs/rl_toy_env.py:
@@ -426,7 +434,7 @@ constexpr size_t kZigLdsBytes = 3u * 256u * 8u;        // a NOISE kernel's stati
 // Why this handle has no closed-loop launch ("<noun> rollouts ..."), or empty: the kernel serves it.  agent_lds: the LDS
 // the agent needs whatever the launch (bytes), tables: what has to fit, for the message.  per_env_mdp: the agent has kernels
 // for one MDP per env (PM), which a handle flagged by mdpp_learner_per_env_mdp runs: its tables are placed per launch
-// (closed_agent_lds_pm), so the LDS rule -- a shared MDP staged per workgroup -- does not apply to it
+// (closed_agent_lds), so the LDS rule -- a shared MDP staged per workgroup -- does not apply to it
 inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool serves_noise, uint64_t agent_lds, const char *tables,
                                        bool per_env_mdp = false) {
     const mdpp_config &c = h->cfg;
@@ -452,59 +460,39 @@ inline std::string closed_loop_refusal(const mdpp_env *h, const char *noun, bool
 inline uint32_t noise_levels_cdf_lds_bytes(const mdpp_env *h) {
     return ((uint32_t)h->nl_levels * (uint32_t)h->cfg.S * (uint32_t)h->cfg.S * 8u + 15u) & ~15u;
 }
-// The closed-loop agents' LDS placement: where the agent's tables (q_lds bytes; 0: it keeps none there, or may not) and, on a
-// handle with per-env noise levels, the per-level cdfs go: both in LDS, then the agent's alone, then the cdfs alone, then
-// neither -- the agent's tables are touched several times a step, a cdf row once.  Without levels the rule is its second line.
-// The cdfs are candidates under noise_in_lds's rule (at most 32 KiB; numpy streams with a transition_noise key only: the others
-// read no cdf).  granted(q, bytes): the device grants `bytes` of dynamic LDS to the kernel with (q) / without the agent's tables.
-template <class Granted>
-inline void closed_agent_lds(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &clds) {
-    const DiscreteArgs &a = h->dargs;
-    const size_t cdf = noise_levels_cdf_lds_bytes(h);
-    const bool c_ok = h->nl_on && !a.philox && a.has_p_noise && cdf <= 32u * 1024u && !(h->opts & MDPP_OPT_NO_NLEV_LDS);
-    const bool q_ok = q_lds != 0 && !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u;
-    qlds = clds = false;
-    if (q_ok && c_ok && granted(true, (size_t)a.lds_bytes + cdf + q_lds)) qlds = clds = true;
-    else if (q_ok && granted(true, (size_t)a.lds_bytes + q_lds)) qlds = true;
-    else if (c_ok && granted(false, (size_t)a.lds_bytes + cdf)) clds = true;
-}
-// ... on a handle with one MDP per env (PM kernels; it has no noise levels): where the agent's tables and the envs' MDP slots
-// (kBlock a.lds_noise bytes: the carve up to the shared noise cdf, per lane) go, in the same order -- both in LDS (PM = 2 with
-// the agent's tables), the agent's alone, the slots alone, neither (PM = 1: the MDPs are read in global memory).  The shared
-// noise cdf (a.lds_bytes - a.lds_noise bytes) is in every sum.  The slots are candidates up to 64 KiB per workgroup (256 B
-// per lane): the bound closed_loop_refusal puts on a shared MDP's staged tables, here a placement -- 20 x 20 (608 B per lane)
-// reads its MDPs in global memory.  granted(q, slots, bytes) as above.
+// The envs' MDP slots of a PM = 2 kernel as LDS bytes: the carve up to the shared noise cdf, per lane
 inline size_t closed_pm_slots_lds_bytes(const mdpp_env *h) { return (size_t)kBlock * (size_t)h->dargs.lds_noise; }
+// The closed-loop agents' LDS placement, the one rule of every learner and evaluation launch: which of the agent's Q-tables
+// (q_lds bytes), the envs' MDP slots and the per-level cdfs go to LDS, the rest being read in global memory.  The three are
+// ranked by what leaving each in global memory was measured to cost on one MDP per env with levels -- the Q-tables (+49-56 %:
+// touched several times a step), the slots (+17-26 %), the cdfs (+15-18 %: a row once a step) -- so the subsets are tried in
+// the order {Q, slots, cdfs}, {Q, slots}, {Q, cdfs}, {Q}, {slots, cdfs}, {slots}, {cdfs}, {}, and the first one granted is
+// taken; {} is taken without asking.  A subset with a candidate that does not exist or is not allowed is skipped:
+//   Q       q_lds != 0 (the agent keeps tables there), at most 160 KiB, not under MDPP_OPT_NO_LEARN_LDS
+//   slots   pm only (the handle runs the PM kernels: PM = 2 with them, PM = 1 reads the MDPs in global memory); rew_in_lds,
+//           at most 64 KiB per workgroup (256 B per lane) -- the bound closed_loop_refusal puts on a shared MDP's staged
+//           tables, here a placement: 20 x 20 (608 B per lane) reads its MDPs in global memory --, not under MDPP_OPT_NO_PM_LDS
+//   cdfs    a handle with per-env noise levels only, under noise_in_lds's rule (at most 32 KiB; numpy streams with a
+//           transition_noise key: the others read no cdf); not under MDPP_OPT_NO_NLEV_LDS (shared MDP) / MDPP_OPT_NO_PM_NLEV_LDS (pm)
+// granted(q, slots, cdfs, bytes): the device grants `bytes` of dynamic LDS to the kernel of that subset.  bytes: the chosen
+// candidates and what the kernel stages whatever the placement -- the handle's carve on a shared MDP (with levels its own cdf
+// keeps its room, unstaged), the shared noise cdf (a.lds_bytes - a.lds_noise) with pm, nothing with pm and levels (the per-level
+// cdfs take the shared cdf's place).
+struct ClosedLdsPlacement { bool q, slots, cdfs; };
 template <class Granted>
-inline void closed_agent_lds_pm(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &mlds) {
-    const DiscreteArgs &a = h->dargs;
-    const size_t fixed = (size_t)(a.lds_bytes - a.lds_noise), slots = closed_pm_slots_lds_bytes(h);
-    const bool m_ok = a.rew_in_lds && !(h->opts & MDPP_OPT_NO_PM_LDS) && slots <= 64u * 1024u;
-    const bool q_ok = q_lds != 0 && !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u;
-    qlds = mlds = false;
-    if (q_ok && m_ok && granted(true, true, fixed + slots + q_lds)) qlds = mlds = true;
-    else if (q_ok && granted(true, false, fixed + q_lds)) qlds = true;
-    else if (m_ok && granted(false, true, fixed + slots)) mlds = true;
-}
-// ... on such a handle with per-env noise levels (mdpp_noise_levels_per_env_mdp; the NLEV kernels with PM != 0): three
-// candidates, ranked by what leaving each in global memory was measured to cost -- the agent's tables (+49-56 %), the MDP
-// slots (+17-26 %), the per-level cdfs (+15-18 %) -- so the subsets are tried in the order {Q, slots, cdfs}, {Q, slots},
-// {Q, cdfs}, {Q}, {slots, cdfs}, {slots}, {cdfs}, {}.  Each candidate keeps its bound and its option from the two rules above;
-// the cdfs' option here is MDPP_OPT_NO_PM_NLEV_LDS.  The handle's own shared cdf is not staged by these kernels and is in
-// no sum.  granted(q, slots, cdfs, bytes) as above.
-template <class Granted>
-inline void closed_agent_lds_pm_nlev(const mdpp_env *h, size_t q_lds, Granted &&granted, bool &qlds, bool &mlds, bool &clds) {
+inline ClosedLdsPlacement closed_agent_lds(const mdpp_env *h, size_t q_lds, bool pm, Granted &&granted) {
     const DiscreteArgs &a = h->dargs;
     const size_t slots = closed_pm_slots_lds_bytes(h), cdf = noise_levels_cdf_lds_bytes(h);
-    const bool q_ok = q_lds != 0 && !(h->opts & MDPP_OPT_NO_LEARN_LDS) && q_lds <= 160u * 1024u;
-    const bool m_ok = a.rew_in_lds && !(h->opts & MDPP_OPT_NO_PM_LDS) && slots <= 64u * 1024u;
-    const bool c_ok = !a.philox && a.has_p_noise && cdf <= 32u * 1024u && !(h->opts & MDPP_OPT_NO_PM_NLEV_LDS);
-    qlds = mlds = clds = false;
-    for (unsigned drop = 0; drop < 8u; drop++) {        // bit 2: without Q, bit 1: without the slots, bit 0: without the cdfs
+    const size_t fixed = !pm ? (size_t)a.lds_bytes : h->nl_on ? 0u : (size_t)(a.lds_bytes - a.lds_noise);
+    const bool q_ok = q_lds != 0 && q_lds <= 160u * 1024u && !(h->opts & MDPP_OPT_NO_LEARN_LDS);
+    const bool m_ok = pm && a.rew_in_lds && slots <= 64u * 1024u && !(h->opts & MDPP_OPT_NO_PM_LDS);
+    const bool c_ok = h->nl_on && !a.philox && a.has_p_noise && cdf <= 32u * 1024u && !(h->opts & (pm ? MDPP_OPT_NO_PM_NLEV_LDS : MDPP_OPT_NO_NLEV_LDS));
+    for (unsigned drop = 0; drop < 7u; drop++) {        // bit 2: without Q, bit 1: without the slots, bit 0: without the cdfs
         const bool q = !(drop & 4u), m = !(drop & 2u), c = !(drop & 1u);
         if ((q && !q_ok) || (m && !m_ok) || (c && !c_ok)) continue;
-        if (drop == 7u || granted(q, m, c, (q ? q_lds : 0u) + (m ? slots : 0u) + (c ? cdf : 0u))) { qlds = q; mlds = m; clds = c; return; }
+        if (granted(q, m, c, fixed + (q ? q_lds : 0u) + (m ? slots : 0u) + (c ? cdf : 0u))) return {q, m, c};
     }
+    return {false, false, false};
 }
 inline NoiseLevelArgs noise_level_args(const mdpp_env *h, uint32_t cdf_lds) {
     return NoiseLevelArgs{(const uint8_t *)h->d_nl_level, (const double *)h->d_nl_sigma, (const double *)h->d_nl_cdf,
@@ -540,6 +528,47 @@ inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size
         return true;
     });
     return step_done(h, io.K, kernel.c_str());
+}
+
+// K steps of one form of an agent that keeps per-env Q-tables, the one launcher of the learners and the evaluation:
+// the step's compile-time facts from the handle, the placement (closed_agent_lds), the kernel of both, its name and its
+// dynamic LDS.  PMH: the handle has one MDP per env and runs the PM = 1 / PM = 2 kernels, else PM = 0.  A form F says
+//   F::SUMMARY, F::NLEV        the step's form (NLEV: of a handle with per-env noise levels -- NOISE = 1 whatever its keys)
+//   F::TABLES                  how many tables Q has (1, or 2 for double Q)
+//   F::kernel<PH, NZ, UNIT, QL, PM>()                      the __global__ function
+//   F::name(out, ph, nz, unit, ql, pm)                     its name with its template arguments, kNameLen bytes at most
+//   F::args(h, io, k0, kc, actions, cdf_lds)               the kernel's second argument for the piece [k0, k0 + kc) of io's
+//                                                          steps, with cdf_lds bytes of per-level cdfs staged in LDS
+template <class F, bool PMH>
+int launch_closed_form(mdpp_env *h, const DiscreteIO &io) {
+    const DiscreteArgs &a = h->dargs;
+    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * F::TABLES;
+    int rc = MDPP_OK;
+    with_bools([&](auto PH, auto NZ, auto UNIT) {
+        if constexpr (!F::NLEV || NZ()) {
+            const ClosedLdsPlacement at = closed_agent_lds(h, q_lds, PMH, [&](bool q, bool m, bool, size_t bytes) {
+                const void *k = nullptr;
+                with_bools([&](auto QL, auto ML) {
+                    if constexpr (PMH || !ML()) k = (const void *)F::template kernel<PH(), NZ(), UNIT(), QL(), PMH ? (ML() ? 2 : 1) : 0>();
+                }, q, m);
+                return dynamic_lds_ok(k, bytes);
+            });
+            const uint32_t cdf_lds = at.cdfs ? noise_levels_cdf_lds_bytes(h) : 0u;
+            with_bools([&](auto QL, auto ML) {
+                if constexpr (PMH || !ML()) {
+                    constexpr int PM = PMH ? (ML() ? 2 : 1) : 0;
+                    char name[kNameLen];
+                    F::name(name, PH(), NZ(), UNIT(), QL(), PM);
+                    const size_t agent_at = F::NLEV ? (size_t)closed_agent_lds_offset<PM>(a, cdf_lds) : (size_t)closed_agent_lds_offset<PM>(a);
+                    // (granted already unless the placement is {}, which was not asked about)
+                    rc = launch_closed_loop<F::SUMMARY>(h, io, F::template kernel<PH(), NZ(), UNIT(), QL(), PM>(), agent_at + (QL() ? q_lds : 0u),
+                                                        at.q || at.slots || at.cdfs, name,
+                                                        [&](int k0, int kc, int32_t *actions) { return F::args(h, io, k0, kc, actions, cdf_lds); });
+                }
+            }, at.q, at.slots);
+        }
+    }, a.philox != 0, F::NLEV || a.has_p_noise || a.has_r_noise, a.unit_rewards != 0);
+    return rc;
 }
 
 } // namespace mdpp

@@ -1,11 +1,13 @@
 // Greedy evaluation of the in-kernel learners' tables (mdpp_step_n_eval): K steps of "take the best action of the env's own Q,
 // step" in ONE launch, the tables read and never written.  The step is closed_loop_rollout (mdpp_discrete_closed.hpp) with its
-// NOISE branches; this file holds the agent, the kernels and the launcher of every form.
+// NOISE branches; the LDS placement (closed_agent_lds) and the launcher (launch_closed_form) are there too, shared with the
+// learners.  This file holds the agent, the two kernels around
+// it, and EvalForm: what launch_closed_form needs to know of an evaluation form -- its kernel, its name, its argument block.
 //
 // Env i in state s takes
 //   one table:  the lowest j maximising Q[s][j], scanned from j = 0 with a strict >
 //   DOUBLE = 1: the lowest j maximising QA[s][j] + QB[s][j], one float32 addition per j
-// -- the greedy branch of the learners' sel (mdpp_discrete_learn.hip).  There is no exploration, no target, no update and no
+// -- the greedy branch of the learners' sel (mdpp_discrete_learn.hpp).  There is no exploration, no target, no update and no
 // carry: the agent makes no Philox block (next_block is empty: no word of streams 15, 16, 17), loads no alpha, gamma or E (so
 // ONE form serves uniform and per-env handles), learn() is empty.  On the reset call of a next-step-autoreset env the action
 // is selected from the state in the record, written and ignored, as there.
@@ -23,7 +25,8 @@
 // (mdpp_noise_levels_per_env_mdp) behind the per-level cdfs, which take the shared cdf's place.
 //
 // launch_eval_form<SUMMARY, NLEV> launches one form, launch_eval_form_pm<SUMMARY, NLEV> the PM = 1 and PM = 2 kernels of one
-// form on a handle with one MDP per env.  Each of the eight is instantiated in a translation unit of its own, so that they
+// form on a handle with one MDP per env: each picks DOUBLE from the handle and calls launch_closed_form on that EvalForm.
+// Each of the eight is instantiated in a translation unit of its own, so that they
 // compile in parallel: mdpp_discrete_eval.hip holds the plain rollout form and the dispatcher,
 // mdpp_discrete_eval_{summary,nlev,nlev_summary,pm,pm_summary,pm_nlev,pm_nlev_summary}.hip one explicit instantiation each;
 // every other unit sees the `extern template` below.
@@ -83,7 +86,6 @@ __global__ __launch_bounds__(kBlock) void k_discrete_eval_rollout(DiscreteArgs a
                                                                   float *__restrict__ reward,
                                                                   uint8_t *__restrict__ term,
                                                                   uint8_t *__restrict__ trunc) {
-    static_assert(!NLEV || NOISE, "per-env noise levels are levels of a NOISE step");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
     unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
@@ -101,7 +103,6 @@ __global__ __launch_bounds__(kBlock) void k_discrete_eval_rollout(DiscreteArgs a
 // ... keeping episode summaries instead of writing the [K][N] arrays
 template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool DOUBLE, bool NLEV = false, int PM = 0>
 __global__ __launch_bounds__(kBlock) void k_discrete_eval_summary(DiscreteArgs a, std::conditional_t<NLEV, EvalArgsNL, EvalArgs> p, int K, EpisodeSummaryArgs sm) {
-    static_assert(!NLEV || NOISE, "per-env noise levels are levels of a NOISE step");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
     unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
@@ -116,42 +117,37 @@ __global__ __launch_bounds__(kBlock) void k_discrete_eval_summary(DiscreteArgs a
     else closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
 
-template <bool SUMMARY, bool PH, bool NZ, bool UNIT, bool QL, bool DOUBLE, bool NLEV, int PM = 0>
-constexpr auto eval_kernel() {
-    if constexpr (SUMMARY) return k_discrete_eval_summary<PH, NZ, UNIT, QL, DOUBLE, NLEV, PM>;
-    else return k_discrete_eval_rollout<PH, NZ, UNIT, QL, DOUBLE, NLEV, PM>;
-}
+// One form of the evaluation, as launch_closed_form (mdpp_discrete_closed.hpp) takes it
+template <bool DOUBLE, bool SUMMARY_, bool NLEV_>
+struct EvalForm {
+    static constexpr bool SUMMARY = SUMMARY_, NLEV = NLEV_;
+    static constexpr int TABLES = DOUBLE ? 2 : 1;
+    template <bool PH, bool NZ, bool UNIT, bool QL, int PM>
+    static constexpr auto kernel() {
+        if constexpr (SUMMARY) return k_discrete_eval_summary<PH, NZ, UNIT, QL, DOUBLE, NLEV, PM>;
+        else return k_discrete_eval_rollout<PH, NZ, UNIT, QL, DOUBLE, NLEV, PM>;
+    }
+    static void name(char *out, int ph, int nz, int unit, int ql, int pm) {
+        if (pm)
+            snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,DOUBLE=%d%s,PM=%d>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
+                     ph, nz, unit, ql, DOUBLE, NLEV ? ",NLEV=1" : "", pm);
+        else
+            snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,DOUBLE=%d%s>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
+                     ph, nz, unit, ql, DOUBLE, NLEV ? ",NLEV=1" : "");
+    }
+    static std::conditional_t<NLEV, EvalArgsNL, EvalArgs> args(const mdpp_env *h, const DiscreteIO &, int, int, int32_t *actions, uint32_t cdf_lds) {
+        const EvalArgs base{(const float *)h->d_learn_q, actions};
+        if constexpr (NLEV) return EvalArgsNL{base, noise_level_args(h, cdf_lds)};
+        else return base;
+    }
+};
 
-// K evaluation steps of one form (NLEV: of a handle with per-env noise levels -- NOISE = 1 whatever its keys)
+// K evaluation steps of one form (NLEV: of a handle with per-env noise levels); DOUBLE, how many tables the learner keeps, is
+// the handle's to say
 template <bool SUMMARY, bool NLEV>
 int launch_eval_form(mdpp_env *h, const DiscreteIO &io) {
-    const DiscreteArgs &a = h->dargs;
-    const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
-    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (dbl ? 2u : 1u);
     int rc = MDPP_OK;
-    with_bools([&](auto PH, auto NZ, auto UNIT, auto DB) {
-        if constexpr (!NLEV || NZ()) {
-            // the LDS forms when a workgroup's 256 tables (and the per-level cdfs) fit beside the MDP's (and the device grants it),
-            // as for the learners
-            bool qlds = false, clds = false;
-            closed_agent_lds(h, q_lds, [&](bool q, size_t bytes) {
-                return q ? dynamic_lds_ok((const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), true, DB(), NLEV>(), bytes)
-                         : dynamic_lds_ok((const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), false, DB(), NLEV>(), bytes);
-            }, qlds, clds);
-            const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
-            with_bools([&](auto QL) {
-                char name[kNameLen];
-                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,DOUBLE=%d%s>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
-                         PH(), NZ(), UNIT(), QL(), DB(), NLEV ? ",NLEV=1" : "");
-                rc = launch_closed_loop<SUMMARY>(h, io, eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), NLEV>(),
-                                                 (size_t)a.lds_bytes + cdf_lds + (QL() ? q_lds : 0u), qlds || clds, name, [&](int, int, int32_t *actions) {
-                    const EvalArgs base{(const float *)h->d_learn_q, actions};
-                    if constexpr (NLEV) return EvalArgsNL{base, noise_level_args(h, cdf_lds)};
-                    else return base;
-                });
-            }, qlds);
-        }
-    }, a.philox != 0, NLEV || a.has_p_noise || a.has_r_noise, a.unit_rewards != 0, dbl);
+    with_bools([&](auto DB) { rc = launch_closed_form<EvalForm<DB(), SUMMARY, NLEV>, false>(h, io); }, h->learn_algo == MDPP_LEARN_DOUBLE_Q);
     return rc;
 }
 
@@ -159,44 +155,10 @@ int launch_eval_form(mdpp_env *h, const DiscreteIO &io) {
 // NLEV: with per-env noise levels (mdpp_noise_levels_per_env_mdp)
 template <bool SUMMARY, bool NLEV>
 int launch_eval_form_pm(mdpp_env *h, const DiscreteIO &io) {
-    const DiscreteArgs &a = h->dargs;
-    const bool dbl = h->learn_algo == MDPP_LEARN_DOUBLE_Q;
-    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (dbl ? 2u : 1u);
-    int rc = MDPP_OK;
     // (the queue of start states drawn ahead needs shared tables: the PM kernels do not carry it)
-    if (a.fast_ok || a.shared_tables) { h->err = "mdpp_step_n_eval: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
-    with_bools([&](auto PH, auto NZ, auto UNIT, auto DB) {
-        if constexpr (!NLEV || NZ()) {
-            // the placement, as for the learners
-            bool qlds = false, mlds = false, clds = false;
-            if constexpr (NLEV)
-                closed_agent_lds_pm_nlev(h, q_lds, [&](bool q, bool m, bool, size_t bytes) {
-                    const void *k = nullptr;
-                    with_bools([&](auto QL, auto ML) { k = (const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), true, ML() ? 2 : 1>(); }, q, m);
-                    return dynamic_lds_ok(k, bytes);
-                }, qlds, mlds, clds);
-            else
-                closed_agent_lds_pm(h, q_lds, [&](bool q, bool m, size_t bytes) {
-                    const void *k = nullptr;
-                    with_bools([&](auto QL, auto ML) { k = (const void *)eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), false, ML() ? 2 : 1>(); }, q, m);
-                    return dynamic_lds_ok(k, bytes);
-                }, qlds, mlds);
-            const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
-            with_bools([&](auto QL, auto ML) {
-                constexpr int PM = ML() ? 2 : 1;
-                char name[kNameLen];
-                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,DOUBLE=%d%s,PM=%d>", SUMMARY ? "k_discrete_eval_summary" : "k_discrete_eval_rollout",
-                         PH(), NZ(), UNIT(), QL(), DB(), NLEV ? ",NLEV=1" : "", PM);
-                const size_t agent_at = NLEV ? (size_t)closed_agent_lds_offset<PM>(a, cdf_lds) : (size_t)closed_agent_lds_offset<PM>(a);
-                rc = launch_closed_loop<SUMMARY>(h, io, eval_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), DB(), NLEV, PM>(),
-                                                 agent_at + (QL() ? q_lds : 0u), true, name, [&](int, int, int32_t *actions) {
-                    const EvalArgs base{(const float *)h->d_learn_q, actions};
-                    if constexpr (NLEV) return EvalArgsNL{base, noise_level_args(h, cdf_lds)};
-                    else return base;
-                });
-            }, qlds, mlds);
-        }
-    }, a.philox != 0, NLEV || a.has_p_noise || a.has_r_noise, a.unit_rewards != 0, dbl);
+    if (h->dargs.fast_ok || h->dargs.shared_tables) { h->err = "mdpp_step_n_eval: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
+    int rc = MDPP_OK;
+    with_bools([&](auto DB) { rc = launch_closed_form<EvalForm<DB(), SUMMARY, NLEV>, true>(h, io); }, h->learn_algo == MDPP_LEARN_DOUBLE_Q);
     return rc;
 }
 

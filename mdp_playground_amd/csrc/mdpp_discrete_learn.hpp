@@ -1,6 +1,9 @@
 // In-kernel tabular TD learners: one Q-learning or SARSA agent per env instance, its Q-table beside the env state, K steps of
 // "select epsilon-greedily from the env's own Q, step, update that Q" in ONE launch (mdpp_step_n_learn).  The step itself is
-// closed_loop_rollout (mdpp_discrete_closed.hpp) WITH its NOISE branches; this file holds the agent.
+// closed_loop_rollout (mdpp_discrete_closed.hpp) WITH its NOISE branches.  That header also has what the learners share with
+// the greedy evaluation on the host: the LDS placement (closed_agent_lds) and the launcher (launch_closed_form).  This file
+// holds the agent (LearnAgent), the two kernels around it, and LearnForm: what launch_closed_form needs to know of a learner
+// form -- its kernel, its name, its argument block.
 //
 // The learner of env g = env_id_offset + i is (algo, alpha, gamma, E = ceil(epsilon 2^31), seed, Q float32 [S][A]).  At step counter
 // t in state s:
@@ -43,8 +46,8 @@
 //
 // PM = 1 / 2 (one MDP per env, mdpp_learner_per_env_mdp) is the PE learner around the step's PM form (mdpp_discrete_closed.hpp:
 // the lane's own tables in global memory / staged in LDS slots); the Q-tables lie behind the slots and the shared noise cdf
-// in LDS (closed_agent_lds_offset).  The host picks PM and QLDS per launch (closed_agent_lds_pm).  With NLEV = 1
-// (mdpp_noise_levels_per_env_mdp) the per-level cdfs take the shared cdf's place (closed_agent_lds_pm_nlev).
+// in LDS (closed_agent_lds_offset).  The host picks PM and QLDS per launch (closed_agent_lds).  With NLEV = 1
+// (mdpp_noise_levels_per_env_mdp) the per-level cdfs take the shared cdf's place.
 //
 // SCHED = 1 (per-episode schedules, mdpp_set_learner_schedule) is the PE learner with E and / or alpha looked up in a table
 // by the env's own episode count: begin() loads the lane's row index and its counter ep and looks up entry min(ep, M - 1) of
@@ -56,7 +59,8 @@
 // schedule: the step and the other agents (an empty episode_end) are the code they were.
 //
 // launch_learn_form<PE, DOUBLE, SUMMARY, NLEV, SCHED> launches one form, launch_learn_form_pm<DOUBLE, SUMMARY, NLEV> the PM = 1 and PM = 2
-// kernels of one form on a handle with one MDP per env.  Each of the twenty-four forms built is instantiated in a translation
+// kernels of one form on a handle with one MDP per env: launch_closed_form on the form's LearnForm, without and with one MDP
+// per env.  Each of the twenty-four forms built is instantiated in a translation
 // unit of its own, so that they compile in parallel: mdpp_discrete_learn.hip holds the uniform rollout form and the
 // dispatcher, mdpp_discrete_learn_*.hip one explicit instantiation each; every other unit sees the `extern template` below.
 #pragma once
@@ -281,9 +285,6 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs 
                                                                    float *__restrict__ reward,
                                                                    uint8_t *__restrict__ term,
                                                                    uint8_t *__restrict__ trunc) {
-    static_assert(!NLEV || (NOISE && PE), "per-env noise levels run the PE learner around a NOISE step");
-    static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
-    static_assert(!SCHED || (PE && !NLEV && PM == 0), "a schedule runs the PE learner on a shared MDP without noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
     unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
@@ -301,9 +302,6 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs 
 // ... keeping episode summaries instead of writing the [K][N] arrays (p.actions is unused)
 template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false, bool NLEV = false, int PM = 0, bool SCHED = false>
 __global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs a, LearnArgsOf<PE, NLEV, SCHED> p, int K, EpisodeSummaryArgs sm) {
-    static_assert(!NLEV || (NOISE && PE), "per-env noise levels run the PE learner around a NOISE step");
-    static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
-    static_assert(!SCHED || (PE && !NLEV && PM == 0), "a schedule runs the PE learner on a shared MDP without noise levels");
     extern __shared__ __align__(16) unsigned char lds[];
     const ZigLds zig = closed_loop_zig_lds<NOISE>();
     unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
@@ -318,100 +316,56 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs 
     else closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
 
-// the kernel of one form: full output, or summaries
-template <bool SUMMARY, bool PH, bool NZ, bool UNIT, bool QL, bool PE, bool DOUBLE, bool NLEV, int PM = 0, bool SCHED = false>
-constexpr auto learn_kernel() {
-    if constexpr (SUMMARY) return k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
-    else return k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
-}
+// One form of the learner, as launch_closed_form (mdpp_discrete_closed.hpp) takes it
+template <bool PE, bool DOUBLE, bool SUMMARY_, bool NLEV_, bool SCHED>
+struct LearnForm {
+    static constexpr bool SUMMARY = SUMMARY_, NLEV = NLEV_;
+    static constexpr int TABLES = DOUBLE ? 2 : 1;
+    // the kernel: full output, or summaries
+    template <bool PH, bool NZ, bool UNIT, bool QL, int PM>
+    static constexpr auto kernel() {
+        static_assert(!NLEV || (NZ && PE), "per-env noise levels run the PE learner around a NOISE step");
+        static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
+        static_assert(!SCHED || (PE && !NLEV && PM == 0), "a schedule runs the PE learner on a shared MDP without noise levels");
+        if constexpr (SUMMARY) return k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
+        else return k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
+    }
+    static void name(char *out, int ph, int nz, int unit, int ql, int pm) {
+        if (pm)
+            snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,PE=1%s%s,PM=%d>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
+                     ph, nz, unit, ql, DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", pm);
+        else
+            snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s%s%s>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
+                     ph, nz, unit, ql, PE ? ",PE=1" : "", DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", SCHED ? ",SCHED=1" : "");
+    }
+    static LearnArgsOf<PE, NLEV, SCHED> args(const mdpp_env *h, const DiscreteIO &io, int k0, int kc, int32_t *actions, uint32_t cdf_lds) {
+        const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
+                             h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
+        if constexpr (PE) {
+            const LearnArgsPE pe{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E};
+            if constexpr (NLEV) return LearnArgsNL{pe, noise_level_args(h, cdf_lds)};
+            else if constexpr (SCHED)
+                return LearnArgsSched{pe, h->sched_eps ? (const uint32_t *)h->d_sched_E : nullptr, h->sched_alpha ? (const float *)h->d_sched_alpha : nullptr,
+                                      (const int32_t *)h->d_sched_row, (int32_t *)h->d_sched_ep, h->sched_M};
+            else return pe;
+        } else return base;
+    }
+};
 
-// K learning steps of one form (NLEV: of a handle with per-env noise levels -- NOISE = 1 whatever its keys; SCHED: of a handle
-// with a per-episode schedule in force)
+// K learning steps of one form (NLEV: of a handle with per-env noise levels; SCHED: of a handle with a per-episode schedule
+// in force)
 template <bool PE, bool DOUBLE, bool SUMMARY, bool NLEV, bool SCHED = false>
 int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
-    static_assert(!NLEV || PE, "per-env noise levels run the PE form");
-    static_assert(!SCHED || (PE && !NLEV), "a schedule runs the PE form, without noise levels");
-    const DiscreteArgs &a = h->dargs;
-    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (DOUBLE ? 2u : 1u);
-    int rc = MDPP_OK;
-    with_bools([&](auto PH, auto NZ, auto UNIT) {
-        if constexpr (!NLEV || NZ()) {
-            // the LDS forms when a workgroup's 256 tables (and the per-level cdfs) fit beside the MDP's (and the device grants it)
-            bool qlds = false, clds = false;
-            closed_agent_lds(h, q_lds, [&](bool q, size_t bytes) {
-                return q ? dynamic_lds_ok((const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), true, PE, DOUBLE, NLEV, 0, SCHED>(), bytes)
-                         : dynamic_lds_ok((const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), false, PE, DOUBLE, NLEV, 0, SCHED>(), bytes);
-            }, qlds, clds);
-            const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
-            with_bools([&](auto QL) {
-                char name[kNameLen];
-                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s%s%s>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
-                         PH(), NZ(), UNIT(), QL(), PE ? ",PE=1" : "", DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", SCHED ? ",SCHED=1" : "");
-                rc = launch_closed_loop<SUMMARY>(h, io, learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, NLEV, 0, SCHED>(),
-                                                 (size_t)a.lds_bytes + cdf_lds + (QL() ? q_lds : 0u), qlds || clds, name, [&](int k0, int kc, int32_t *actions) {
-                    const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
-                                         h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
-                    if constexpr (PE) {
-                        const LearnArgsPE pe{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E};
-                        if constexpr (NLEV) return LearnArgsNL{pe, noise_level_args(h, cdf_lds)};
-                        else if constexpr (SCHED)
-                            return LearnArgsSched{pe, h->sched_eps ? (const uint32_t *)h->d_sched_E : nullptr, h->sched_alpha ? (const float *)h->d_sched_alpha : nullptr,
-                                                  (const int32_t *)h->d_sched_row, (int32_t *)h->d_sched_ep, h->sched_M};
-                        else return pe;
-                    } else return base;
-                });
-            }, qlds);
-        }
-    }, a.philox != 0, NLEV || a.has_p_noise || a.has_r_noise, a.unit_rewards != 0);
-    return rc;
+    return launch_closed_form<LearnForm<PE, DOUBLE, SUMMARY, NLEV, SCHED>, false>(h, io);
 }
 
 // K learning steps of one form on a handle with one MDP per env (mdpp_learner_per_env_mdp): the PE learner's PM = 1 and
-// PM = 2 kernels.  NLEV: with per-env noise levels (mdpp_noise_levels_per_env_mdp) -- NOISE = 1 whatever the handle's keys,
-// the per-level cdfs in the shared cdf's place (closed_agent_lds_pm_nlev)
+// PM = 2 kernels.  NLEV: with per-env noise levels (mdpp_noise_levels_per_env_mdp)
 template <bool DOUBLE, bool SUMMARY, bool NLEV>
 int launch_learn_form_pm(mdpp_env *h, const DiscreteIO &io) {
-    constexpr bool PE = true;
-    const DiscreteArgs &a = h->dargs;
-    const size_t q_lds = (size_t)kBlock * (size_t)a.S * (size_t)a.A * sizeof(float) * (DOUBLE ? 2u : 1u);
-    int rc = MDPP_OK;
     // (the queue of start states drawn ahead needs shared tables: the PM kernels do not carry it)
-    if (a.fast_ok || a.shared_tables) { h->err = "mdpp_step_n_learn: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
-    with_bools([&](auto PH, auto NZ, auto UNIT) {
-        if constexpr (!NLEV || NZ()) {
-            // the placement: the Q-tables, the envs' MDP slots and the per-level cdfs in LDS as far as the device grants them
-            bool qlds = false, mlds = false, clds = false;
-            if constexpr (NLEV)
-                closed_agent_lds_pm_nlev(h, q_lds, [&](bool q, bool m, bool, size_t bytes) {
-                    const void *k = nullptr;
-                    with_bools([&](auto QL, auto ML) { k = (const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, true, ML() ? 2 : 1>(); }, q, m);
-                    return dynamic_lds_ok(k, bytes);
-                }, qlds, mlds, clds);
-            else
-                closed_agent_lds_pm(h, q_lds, [&](bool q, bool m, size_t bytes) {
-                    const void *k = nullptr;
-                    with_bools([&](auto QL, auto ML) { k = (const void *)learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, false, ML() ? 2 : 1>(); }, q, m);
-                    return dynamic_lds_ok(k, bytes);
-                }, qlds, mlds);
-            const uint32_t cdf_lds = clds ? noise_levels_cdf_lds_bytes(h) : 0u;
-            with_bools([&](auto QL, auto ML) {
-                constexpr int PM = ML() ? 2 : 1;
-                char name[kNameLen];
-                snprintf(name, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,PE=1%s%s,PM=%d>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
-                         PH(), NZ(), UNIT(), QL(), DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", PM);
-                const size_t agent_at = NLEV ? (size_t)closed_agent_lds_offset<PM>(a, cdf_lds) : (size_t)closed_agent_lds_offset<PM>(a);
-                rc = launch_closed_loop<SUMMARY>(h, io, learn_kernel<SUMMARY, PH(), NZ(), UNIT(), QL(), PE, DOUBLE, NLEV, PM>(),
-                                                 agent_at + (QL() ? q_lds : 0u), true, name, [&](int k0, int kc, int32_t *actions) {
-                    const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
-                                         h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
-                    const LearnArgsPE pe{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E};
-                    if constexpr (NLEV) return LearnArgsNL{pe, noise_level_args(h, cdf_lds)};
-                    else return pe;
-                });
-            }, qlds, mlds);
-        }
-    }, a.philox != 0, NLEV || a.has_p_noise || a.has_r_noise, a.unit_rewards != 0);
-    return rc;
+    if (h->dargs.fast_ok || h->dargs.shared_tables) { h->err = "mdpp_step_n_learn: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
+    return launch_closed_form<LearnForm<true, DOUBLE, SUMMARY, NLEV, false>, true>(h, io);
 }
 
 // the forms built <PE, DOUBLE, SUMMARY, NLEV[, SCHED]> and, with one MDP per env, <DOUBLE, SUMMARY, NLEV>, each defined (an explicit

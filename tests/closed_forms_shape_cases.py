@@ -196,8 +196,8 @@ def sched_honest(case, algo, kind, info, ep, row):
     lsc.honest(_SCHED_ALIAS.get(case, "s20"), algo, kind, sched_m(case, kind), info, ep, row)
 
 
-# ---- the LDS placements, restated from the carve numbers (include/mdpp.h; closed_agent_lds, closed_agent_lds_pm and
-# closed_agent_lds_pm_nlev of mdpp_discrete_closed.hpp)
+# ---- the LDS placements, restated from the carve numbers (include/mdpp.h; closed_agent_lds of
+# mdpp_discrete_closed.hpp, on a shared MDP and on one MDP per env, without and with levels)
 ZIG_BYTES = 3 * 256 * 8              # a NOISE kernel's static LDS; 24 bytes otherwise (closed_loop_shape_cases.static_lds)
 Q_BOUND, SLOT_BOUND, CDF_BOUND = 160 * 1024, 64 * 1024, 32 * 1024
 

@@ -152,7 +152,7 @@ LDS_BYTES, ZIG_BYTES = 160 * 1024, 6144      # a workgroup's LDS on gfx950; the 
 
 
 def placement(cfg, algo, rng, *options, levels=5):
-    """(QLDS, PM, cdfs staged, dynamic LDS bytes) by the rule of include/mdpp.h (closed_agent_lds_pm_nlev) restated: the
+    """(QLDS, PM, cdfs staged, dynamic LDS bytes) by the rule of include/mdpp.h (closed_agent_lds on one MDP per env with levels) restated: the
     Q-tables (at most 160 KiB, not under NO_LEARN_LDS), the MDP slots (at most 64 KiB, not under NO_PM_LDS) and the per-level
     cdfs (at most 32 KiB, numpy streams only, not under NO_PM_NLEV_LDS) go to LDS in the first of the subsets {Q, slots, cdfs},
     {Q, slots}, {Q, cdfs}, {Q}, {slots, cdfs}, {slots}, {cdfs}, {} that fits beside the 6 KiB of ziggurat tables.  A lane's slot
