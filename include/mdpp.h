@@ -418,11 +418,27 @@ int mdpp_set_learner_gamma(mdpp_env *h, float gamma);
  * The launch is the kernel's SCHED form, always with PE=1 (the name gains ",SCHED=1", last): the lane looks its values up at
  * the launch's start and at each of its episode ends, one dword load per scheduled table.
  * Under a graph: which tables are scheduled and M are carried by value; the tables, the rows and the counters are read from
- * the handle's buffers at replay, so a captured launch continues the schedule where the last launch left it, like Q. */
+ * the handle's buffers at replay, so a captured launch continues the schedule where the last launch left it, like Q.
+ * Schedules together with per-env noise levels and / or one MDP per env: mdpp_learner_schedule_sweep(h, on) sets a flag of the
+ * handle, off at creation.  With it off every call above returns exactly what it returns without the flag, the three "not
+ * built" refusals included.  With it on those three refusals do not fire: mdpp_set_learner_schedule is accepted with levels
+ * in force and / or mdpp_learner_per_env_mdp on, and while such a schedule is in force mdpp_set_noise_levels and turning
+ * mdpp_learner_per_env_mdp on are accepted too (mdpp_noise_levels_per_env_mdp keeps its own rule).  The launch is then the
+ * learner of that handle -- its step, stream ids 15 - 17, the level bytes, an env of transition_noise 0 making no
+ * transition draw, every env's own tables, the LDS placements of the sections below -- with E and alpha taken from
+ * (row[i], ep[i]) exactly as above: looked up at the launch's start, the counter moved and both looked up again after the
+ * update of every step that ends an episode and is not a reset call, the clamp at M - 1, sarsa's a' chosen under the old E,
+ * the counter stored when the launch ends.  The kernel's name gains ",SCHED=1" after everything else
+ * ("...,PE=1[,DOUBLE=1][,NLEV=1][,PM=1|2],SCHED=1>"); the schedule has no LDS placement and changes none.  mdpp_step_n_eval and
+ * its summary form read no table and move no counter.  Turning the flag off while a schedule is in force together with
+ * levels or one MDP per env drops the schedule as mdpp_clear_learner_schedule does; otherwise turning it off changes nothing.
+ * mdpp_set_learner and mdpp_clear_learner drop the schedule and leave the flag; turning mdpp_learner_per_env_mdp off drops the
+ * learner and its schedule.  On a handle that is not discrete the call is accepted and changes nothing. */
 int mdpp_set_learner_schedule(mdpp_env *h, const float *epsilon, const float *alpha, int R, int M, const int32_t *row, void *stream);
 int mdpp_clear_learner_schedule(mdpp_env *h);
 int mdpp_get_learner_episodes(mdpp_env *h, int32_t *dev_out, void *stream);
 int mdpp_set_learner_episodes(mdpp_env *h, const int32_t *dev_in, void *stream);
+int mdpp_learner_schedule_sweep(mdpp_env *h, int on);
 
 /* One MDP per env for the learner and evaluation launches.  mdpp_learner_per_env_mdp(h, on) sets a flag of the handle, off at
  * creation.  With the flag on, a handle with cfg.num_tables == cfg.num_envs (each env its own P, terminal states, rewardable

@@ -56,6 +56,7 @@ EXPORTS = [
     "mdpp_set_noise_levels", "mdpp_get_noise_levels", "mdpp_clear_noise_levels", "mdpp_learner_per_env_mdp",
     "mdpp_noise_levels_per_env_mdp",
     "mdpp_set_learner_schedule", "mdpp_clear_learner_schedule", "mdpp_get_learner_episodes", "mdpp_set_learner_episodes",
+    "mdpp_learner_schedule_sweep",
 ]
 
 
@@ -193,6 +194,7 @@ def load():
     L.mdpp_clear_learner_schedule.argtypes = [vp]
     L.mdpp_get_learner_episodes.argtypes = [vp, vp, vp]
     L.mdpp_set_learner_episodes.argtypes = [vp, vp, vp]
+    L.mdpp_learner_schedule_sweep.argtypes = [vp, i32]
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

@@ -26,6 +26,11 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_discrete_learn_double_pe_pm_nlev_summary.hip", "mdpp_discrete_eval_pm_nlev.hip", "mdpp_discrete_eval_pm_nlev_summary.hip",
            "mdpp_discrete_learn_pe_sched.hip", "mdpp_discrete_learn_pe_sched_summary.hip", "mdpp_discrete_learn_double_pe_sched.hip",
            "mdpp_discrete_learn_double_pe_sched_summary.hip",
+           "mdpp_discrete_learn_pe_nlev_sched.hip", "mdpp_discrete_learn_pe_nlev_sched_summary.hip", "mdpp_discrete_learn_double_pe_nlev_sched.hip",
+           "mdpp_discrete_learn_double_pe_nlev_sched_summary.hip", "mdpp_discrete_learn_pe_pm_sched.hip", "mdpp_discrete_learn_pe_pm_sched_summary.hip",
+           "mdpp_discrete_learn_double_pe_pm_sched.hip", "mdpp_discrete_learn_double_pe_pm_sched_summary.hip",
+           "mdpp_discrete_learn_pe_pm_nlev_sched.hip", "mdpp_discrete_learn_pe_pm_nlev_sched_summary.hip",
+           "mdpp_discrete_learn_double_pe_pm_nlev_sched.hip", "mdpp_discrete_learn_double_pe_pm_nlev_sched_summary.hip",
            "mdpp_continuous.hip", "mdpp_continuous_line8.hip",
            "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
            "mdpp_generate.hip"]

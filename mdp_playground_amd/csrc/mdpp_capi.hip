@@ -125,7 +125,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->learn_pm = false;
     h->nl_on = false; h->nl_pm = false; h->nl_levels = 0; h->nl_fill_valid = false; h->nl_fill_alpha = h->nl_fill_gamma = 0.0f; h->nl_fill_E = 0;
     h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
-    h->sched_on = h->sched_eps = h->sched_alpha = false; h->sched_R = h->sched_M = 0; h->sched_cap = 0;
+    h->sched_on = h->sched_eps = h->sched_alpha = h->sched_sweep = false; h->sched_R = h->sched_M = 0; h->sched_cap = 0;
     h->d_sched_E = h->d_sched_alpha = h->d_sched_row = h->d_sched_ep = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
@@ -1420,7 +1420,7 @@ extern "C" const char *mdpp_policy_kernel_name(mdpp_env *h, int K) {
 }
 
 // ---- ... of in-kernel tabular TD learners (mdpp_discrete_learn.hip) ----
-// what a handle that would need SCHED on the NLEV or PM forms is told
+// what a handle that would need SCHED on the NLEV or PM forms is told while mdpp_learner_schedule_sweep is off
 static const char *const kSchedNotBuilt = "an epsilon/alpha schedule with per-env noise levels / one MDP per env: not built";
 static std::string sched_owns(const char *fn, const char *what) {
     return std::string(fn) + ": " + what + " follows the schedule in force (mdpp_set_learner_schedule); mdpp_clear_learner_schedule first";
@@ -1477,9 +1477,10 @@ extern "C" int mdpp_learner_per_env_mdp(mdpp_env *h, int on) {
     if (!h) return MDPP_EINVAL;
     // (a shared MDP, or no discrete handle: accepted, nothing changes)
     if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
-    if (on && h->sched_on) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kSchedNotBuilt);
+    if (on && h->sched_on && !h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kSchedNotBuilt);
     if (h->learn_pm && !on) {
-        h->learn_ready = false;                          // (as mdpp_clear_learner: the buffers stay)
+        h->learn_ready = false;                          // (as mdpp_clear_learner: the buffers stay, the schedule goes)
+        h->sched_on = false;
         if (h->nl_pm) h->nl_on = false;                  // ... and levels given on one MDP per env go with the learner that ran them
         h->nl_pm = false;
     }
@@ -1564,7 +1565,7 @@ extern "C" int mdpp_set_learner_params(mdpp_env *h, const float *alpha, const fl
 extern "C" int mdpp_set_learner_schedule(mdpp_env *h, const float *epsilon, const float *alpha, int R, int M, const int32_t *row, void *stream) {
     if (!h) return MDPP_EINVAL;
     if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_set_learner_schedule: no learner set (mdpp_set_learner)");
-    if (h->nl_on || h->learn_pm) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_learner_schedule: ") + kSchedNotBuilt);
+    if ((h->nl_on || h->learn_pm) && !h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_learner_schedule: ") + kSchedNotBuilt);
     if (!epsilon && !alpha) return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: need an epsilon table, an alpha table or both");
     if (R < 1 || M < 1 || (uint64_t)R * (uint64_t)M > (uint64_t)MDPP_MAX_SCHEDULE_ENTRIES)
         return fail(h, MDPP_EINVAL, "mdpp_set_learner_schedule: need R >= 1, M >= 1 and R M <= 2^22");
@@ -1616,6 +1617,15 @@ extern "C" int mdpp_clear_learner_schedule(mdpp_env *h) {
     return MDPP_OK;
 }
 
+extern "C" int mdpp_learner_schedule_sweep(mdpp_env *h, int on) {
+    if (!h) return MDPP_EINVAL;
+    if (h->cfg.kind != MDPP_KIND_DISCRETE) return MDPP_OK;       // (no discrete handle: accepted, nothing changes)
+    // (off: a schedule that runs with levels or one MDP per env goes, as by mdpp_clear_learner_schedule; any other stays)
+    if (h->sched_sweep && !on && h->sched_on && (h->nl_on || h->learn_pm)) h->sched_on = false;
+    h->sched_sweep = on != 0;
+    return MDPP_OK;
+}
+
 static int sched_counters_ready(mdpp_env *h, const char *what) {
     if (!h->learn_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_learner)");
     if (!h->sched_on) return fail(h, MDPP_ESTATE, std::string(what) + ": no schedule set (mdpp_set_learner_schedule)");
@@ -1644,7 +1654,7 @@ extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise
     if (!h) return MDPP_EINVAL;
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: " + why);
-    if (h->sched_on) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_noise_levels: ") + kSchedNotBuilt + "; mdpp_clear_learner_schedule first");
+    if (h->sched_on && !h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_noise_levels: ") + kSchedNotBuilt + "; mdpp_clear_learner_schedule first");
     if (h->cfg.num_tables != 1 && !(h->nl_pm && h->learn_pm)) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_noise_levels: per-env noise levels on one MDP per env: not built");
     const mdpp_config &c = h->cfg;
     if (transition_noise && !c.has_transition_noise)

@@ -75,11 +75,11 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
     }
     int rc = MDPP_OK;
     if (pm) {
-        with_bools([&](auto DB, auto SM, auto NL) { rc = launch_learn_form_pm<DB(), SM(), NL()>(h, io); }, dbl, io.summary != nullptr, h->nl_on);
+        with_bools([&](auto DB, auto SM, auto NL, auto SC) { rc = launch_learn_form_pm<DB(), SM(), NL(), SC()>(h, io); }, dbl, io.summary != nullptr, h->nl_on, h->sched_on);
         return rc;
     }
-    if (h->sched_on) {           // (mdpp_set_learner_schedule refuses levels and one MDP per env: the shared-MDP PE form with the tables)
-        with_bools([&](auto DB, auto SM) { rc = launch_learn_form<true, DB(), SM(), false, true>(h, io); }, dbl, io.summary != nullptr);
+    if (h->sched_on) {           // (the PE form with the tables, on a shared MDP; with levels only under mdpp_learner_schedule_sweep, which mdpp_set_learner_schedule and mdpp_set_noise_levels see to)
+        with_bools([&](auto DB, auto SM, auto NL) { rc = launch_learn_form<true, DB(), SM(), NL(), true>(h, io); }, dbl, io.summary != nullptr, h->nl_on);
         return rc;
     }
     with_bools([&](auto PE, auto DB, auto SM, auto NL) {

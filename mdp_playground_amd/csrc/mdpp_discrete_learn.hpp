@@ -49,7 +49,9 @@
 // in LDS (closed_agent_lds_offset).  The host picks PM and QLDS per launch (closed_agent_lds).  With NLEV = 1
 // (mdpp_noise_levels_per_env_mdp) the per-level cdfs take the shared cdf's place.
 //
-// SCHED = 1 (per-episode schedules, mdpp_set_learner_schedule) is the PE learner with E and / or alpha looked up in a table
+// SCHED = 1 (per-episode schedules, mdpp_set_learner_schedule; with NLEV = 1 and / or PM != 0 under
+// mdpp_learner_schedule_sweep: the agent below around that step, nothing else changes -- the schedule has no LDS placement
+// and with levels the kernels are the overloads that take LearnArgsNLSched, the levels behind the schedule) is the PE learner with E and / or alpha looked up in a table
 // by the env's own episode count: begin() loads the lane's row index and its counter ep and looks up entry min(ep, M - 1) of
 // its row -- one plain global dword load per scheduled table (the tables are small, L2-resident and read only here and at
 // episode ends; they have no LDS placement) -- into the registers the PE form keeps its parameters in.  closed_loop_rollout
@@ -58,9 +60,9 @@
 // this step's target was selected before, under the old E).  finish() stores the counter.  The agent alone knows of the
 // schedule: the step and the other agents (an empty episode_end) are the code they were.
 //
-// launch_learn_form<PE, DOUBLE, SUMMARY, NLEV, SCHED> launches one form, launch_learn_form_pm<DOUBLE, SUMMARY, NLEV> the PM = 1 and PM = 2
+// launch_learn_form<PE, DOUBLE, SUMMARY, NLEV, SCHED> launches one form, launch_learn_form_pm<DOUBLE, SUMMARY, NLEV, SCHED> the PM = 1 and PM = 2
 // kernels of one form on a handle with one MDP per env: launch_closed_form on the form's LearnForm, without and with one MDP
-// per env.  Each of the twenty-four forms built is instantiated in a translation
+// per env.  Each of the thirty-six forms built is instantiated in a translation
 // unit of its own, so that they compile in parallel: mdpp_discrete_learn.hip holds the uniform rollout form and the
 // dispatcher, mdpp_discrete_learn_*.hip one explicit instantiation each; every other unit sees the `extern template` below.
 #pragma once
@@ -99,6 +101,13 @@ struct LearnArgsSched : LearnArgsPE {
 };
 template <bool PE, bool NLEV, bool SCHED = false>
 using LearnArgsOf = std::conditional_t<SCHED, LearnArgsSched, std::conditional_t<NLEV, LearnArgsNL, std::conditional_t<PE, LearnArgsPE, LearnArgs>>>;
+// ... of the scheduled form on a handle with per-env noise levels: the schedule and the levels.  A struct of its own behind
+// LearnArgsSched, which the agent reads through a reference to that base, and NOT a branch of LearnArgsOf: that alias is
+// spelled out in the mangled name of every learner kernel, and LearnArgsNL and LearnArgsSched keep their layouts, so the
+// kernels without one of the two keep their symbols and their code.  The kernels that take it are overloads of the two below.
+struct LearnArgsNLSched : LearnArgsSched {
+    NoiseLevelArgs nl;
+};
 
 template <bool QLDS, bool PE, bool DOUBLE, bool SCHED = false>
 struct LearnAgent {
@@ -316,37 +325,70 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs 
     else closed_loop_rollout<PHILOX, NOISE, UNIT, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
 
+// NLEV = 1 with SCHED = 1: the same two kernels taking LearnArgsNLSched (overloads: the template arguments are the same, the
+// second parameter tells them apart; LearnForm::kernel picks by it).  Their bodies are the NLEV branches of the ones above
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE, bool DOUBLE, bool NLEV, int PM, bool SCHED>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_rollout(DiscreteArgs a, LearnArgsNLSched p, int K,
+                                                                   void *__restrict__ obs,
+                                                                   float *__restrict__ reward,
+                                                                   uint8_t *__restrict__ term,
+                                                                   uint8_t *__restrict__ trunc) {
+    static_assert(PE && NLEV && SCHED && NOISE, "the argument block of a schedule with per-env noise levels");
+    extern __shared__ __align__(16) unsigned char lds[];
+    const ZigLds zig = closed_loop_zig_lds<NOISE>();
+    unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    if constexpr (PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else q_lds = lds + closed_agent_lds_offset<PM>(a) + p.nl.lds_bytes;
+    LearnAgent<QLDS, PE, DOUBLE, SCHED> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, NOISE, UNIT, false, NLEV, PM>(a, K, !a.obs_i32, p.actions, obs, reward, term, trunc, lds, zig, agent, EpisodeSummaryArgs{}, p.nl);
+}
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE, bool DOUBLE, bool NLEV, int PM, bool SCHED>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs a, LearnArgsNLSched p, int K, EpisodeSummaryArgs sm) {
+    static_assert(PE && NLEV && SCHED && NOISE, "the argument block of a schedule with per-env noise levels");
+    extern __shared__ __align__(16) unsigned char lds[];
+    const ZigLds zig = closed_loop_zig_lds<NOISE>();
+    unsigned char *q_lds;                                           // the agent's LDS: behind the MDP's tables and the per-level cdfs
+    if constexpr (PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else q_lds = lds + closed_agent_lds_offset<PM>(a) + p.nl.lds_bytes;
+    LearnAgent<QLDS, PE, DOUBLE, SCHED> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
+}
+
 // One form of the learner, as launch_closed_form (mdpp_discrete_closed.hpp) takes it
 template <bool PE, bool DOUBLE, bool SUMMARY_, bool NLEV_, bool SCHED>
 struct LearnForm {
     static constexpr bool SUMMARY = SUMMARY_, NLEV = NLEV_;
     static constexpr int TABLES = DOUBLE ? 2 : 1;
+    using Args = std::conditional_t<NLEV_ && SCHED, LearnArgsNLSched, LearnArgsOf<PE, NLEV_, SCHED>>;      // the kernel's second parameter
     // the kernel: full output, or summaries
     template <bool PH, bool NZ, bool UNIT, bool QL, int PM>
     static constexpr auto kernel() {
         static_assert(!NLEV || (NZ && PE), "per-env noise levels run the PE learner around a NOISE step");
         static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
-        static_assert(!SCHED || (PE && !NLEV && PM == 0), "a schedule runs the PE learner on a shared MDP without noise levels");
-        if constexpr (SUMMARY) return k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
-        else return k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>;
+        static_assert(!SCHED || PE, "a schedule runs the PE learner");
+        // (the cast picks the overload by its second parameter)
+        if constexpr (SUMMARY) return static_cast<void (*)(DiscreteArgs, Args, int, EpisodeSummaryArgs)>(k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>);
+        else return static_cast<void (*)(DiscreteArgs, Args, int, void *, float *, uint8_t *, uint8_t *)>(k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>);
     }
     static void name(char *out, int ph, int nz, int unit, int ql, int pm) {
         if (pm)
-            snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,PE=1%s%s,PM=%d>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
-                     ph, nz, unit, ql, DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", pm);
+            snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d,PE=1%s%s,PM=%d%s>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
+                     ph, nz, unit, ql, DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", pm, SCHED ? ",SCHED=1" : "");
         else
             snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s%s%s>", SUMMARY ? "k_discrete_learn_summary" : "k_discrete_learn_rollout",
                      ph, nz, unit, ql, PE ? ",PE=1" : "", DOUBLE ? ",DOUBLE=1" : "", NLEV ? ",NLEV=1" : "", SCHED ? ",SCHED=1" : "");
     }
-    static LearnArgsOf<PE, NLEV, SCHED> args(const mdpp_env *h, const DiscreteIO &io, int k0, int kc, int32_t *actions, uint32_t cdf_lds) {
+    static Args args(const mdpp_env *h, const DiscreteIO &io, int k0, int kc, int32_t *actions, uint32_t cdf_lds) {
         const LearnArgs base{(float *)h->d_learn_q, (int32_t *)h->d_learn_carry, actions, h->learn_seed, h->learn_E,
                              h->learn_alpha, h->learn_gamma, h->learn_algo, k0 > 0 ? 1 : 0, k0 + kc < io.K ? 1 : 0};
         if constexpr (PE) {
             const LearnArgsPE pe{base, (const float *)h->d_learn_alpha, (const float *)h->d_learn_gamma, (const uint32_t *)h->d_learn_E};
-            if constexpr (NLEV) return LearnArgsNL{pe, noise_level_args(h, cdf_lds)};
-            else if constexpr (SCHED)
-                return LearnArgsSched{pe, h->sched_eps ? (const uint32_t *)h->d_sched_E : nullptr, h->sched_alpha ? (const float *)h->d_sched_alpha : nullptr,
-                                      (const int32_t *)h->d_sched_row, (int32_t *)h->d_sched_ep, h->sched_M};
+            if constexpr (SCHED) {
+                const LearnArgsSched sc{pe, h->sched_eps ? (const uint32_t *)h->d_sched_E : nullptr, h->sched_alpha ? (const float *)h->d_sched_alpha : nullptr,
+                                        (const int32_t *)h->d_sched_row, (int32_t *)h->d_sched_ep, h->sched_M};
+                if constexpr (NLEV) return LearnArgsNLSched{sc, noise_level_args(h, cdf_lds)};
+                else return sc;
+            } else if constexpr (NLEV) return LearnArgsNL{pe, noise_level_args(h, cdf_lds)};
             else return pe;
         } else return base;
     }
@@ -360,15 +402,16 @@ int launch_learn_form(mdpp_env *h, const DiscreteIO &io) {
 }
 
 // K learning steps of one form on a handle with one MDP per env (mdpp_learner_per_env_mdp): the PE learner's PM = 1 and
-// PM = 2 kernels.  NLEV: with per-env noise levels (mdpp_noise_levels_per_env_mdp)
-template <bool DOUBLE, bool SUMMARY, bool NLEV>
+// PM = 2 kernels.  NLEV: with per-env noise levels (mdpp_noise_levels_per_env_mdp); SCHED: with a per-episode schedule in
+// force (mdpp_learner_schedule_sweep)
+template <bool DOUBLE, bool SUMMARY, bool NLEV, bool SCHED = false>
 int launch_learn_form_pm(mdpp_env *h, const DiscreteIO &io) {
     // (the queue of start states drawn ahead needs shared tables: the PM kernels do not carry it)
     if (h->dargs.fast_ok || h->dargs.shared_tables) { h->err = "mdpp_step_n_learn: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
-    return launch_closed_form<LearnForm<true, DOUBLE, SUMMARY, NLEV, false>, true>(h, io);
+    return launch_closed_form<LearnForm<true, DOUBLE, SUMMARY, NLEV, SCHED>, true>(h, io);
 }
 
-// the forms built <PE, DOUBLE, SUMMARY, NLEV[, SCHED]> and, with one MDP per env, <DOUBLE, SUMMARY, NLEV>, each defined (an explicit
+// the forms built <PE, DOUBLE, SUMMARY, NLEV[, SCHED]> and, with one MDP per env, <DOUBLE, SUMMARY, NLEV[, SCHED]>, each defined (an explicit
 // instantiation) in the translation unit named
 extern template int launch_learn_form<false, false, false, false>(mdpp_env *, const DiscreteIO &);  // mdpp_discrete_learn.hip
 extern template int launch_learn_form<true, false, false, false>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_learn_pe.hip
@@ -394,5 +437,17 @@ extern template int launch_learn_form_pm<false, false, true>(mdpp_env *, const D
 extern template int launch_learn_form_pm<true, false, true>(mdpp_env *, const DiscreteIO &);        // mdpp_discrete_learn_double_pe_pm_nlev.hip
 extern template int launch_learn_form_pm<false, true, true>(mdpp_env *, const DiscreteIO &);        // mdpp_discrete_learn_pe_pm_nlev_summary.hip
 extern template int launch_learn_form_pm<true, true, true>(mdpp_env *, const DiscreteIO &);         // mdpp_discrete_learn_double_pe_pm_nlev_summary.hip
+extern template int launch_learn_form<true, false, false, true, true>(mdpp_env *, const DiscreteIO &);   // mdpp_discrete_learn_pe_nlev_sched.hip
+extern template int launch_learn_form<true, false, true, true, true>(mdpp_env *, const DiscreteIO &);    // mdpp_discrete_learn_pe_nlev_sched_summary.hip
+extern template int launch_learn_form<true, true, false, true, true>(mdpp_env *, const DiscreteIO &);    // mdpp_discrete_learn_double_pe_nlev_sched.hip
+extern template int launch_learn_form<true, true, true, true, true>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_learn_double_pe_nlev_sched_summary.hip
+extern template int launch_learn_form_pm<false, false, false, true>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_learn_pe_pm_sched.hip
+extern template int launch_learn_form_pm<true, false, false, true>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_learn_double_pe_pm_sched.hip
+extern template int launch_learn_form_pm<false, true, false, true>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_learn_pe_pm_sched_summary.hip
+extern template int launch_learn_form_pm<true, true, false, true>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_double_pe_pm_sched_summary.hip
+extern template int launch_learn_form_pm<false, false, true, true>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_learn_pe_pm_nlev_sched.hip
+extern template int launch_learn_form_pm<true, false, true, true>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_double_pe_pm_nlev_sched.hip
+extern template int launch_learn_form_pm<false, true, true, true>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_learn_pe_pm_nlev_sched_summary.hip
+extern template int launch_learn_form_pm<true, true, true, true>(mdpp_env *, const DiscreteIO &);        // mdpp_discrete_learn_double_pe_pm_nlev_sched_summary.hip
 
 } // namespace mdpp

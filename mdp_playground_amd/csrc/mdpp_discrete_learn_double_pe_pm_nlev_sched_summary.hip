@@ -1,0 +1,6 @@
+// The learner form <DOUBLE = 1, SUMMARY = 1, NLEV = 1, SCHED = 1> on one MDP per env (mdpp_discrete_learn.hpp: launch_learn_form_pm, the
+// PM = 1 and PM = 2 kernels): double Q-learning with a per-episode epsilon / alpha schedule on a handle with per-env noise levels, keeping episode summaries -- in a
+// translation unit of its own so that the forms compile in parallel.
+#include "mdpp_discrete_learn.hpp"
+
+template int mdpp::launch_learn_form_pm<true, true, true, true>(mdpp_env *, const mdpp::DiscreteIO &);

@@ -368,7 +368,9 @@ struct mdpp_env {
     // launches take their SCHED form.  Device: the thresholds uint32 [R][M] and / or the alphas float32 [R][M] (sched_eps /
     // sched_alpha: which table is in force), every env's row int32 [N] and episode counter int32 [N]; sched_cap: the entries
     // the two table buffers were allocated for.  Like levels, a schedule makes the launch the PE form (nl_fill_*).
-    bool sched_on, sched_eps, sched_alpha;
+    // sched_sweep: mdpp_learner_schedule_sweep -- a schedule is accepted together with per-env noise levels and / or learn_pm
+    // (the SCHED kernels with NLEV = 1 and / or PM != 0; only ever set on a discrete handle)
+    bool sched_on, sched_eps, sched_alpha, sched_sweep;
     int32_t sched_R, sched_M;
     size_t sched_cap;
     void *d_sched_E, *d_sched_alpha, *d_sched_row, *d_sched_ep;

@@ -98,6 +98,7 @@ class RLToyVectorEnv:
         self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
         self._learn_sched = None              # set_learner_schedule's validated arrays while a schedule is in force
         self._nl_pm = False                   # set_noise_levels(per_env_mdp=True) is in force (the handle's second flag is on)
+        self._sched_sweep = False             # set_learner_schedule(sweep=True) has turned the handle's mdpp_learner_schedule_sweep flag on
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
                 raise ValueError("num_envs != len(seeds)")
@@ -866,7 +867,7 @@ class RLToyVectorEnv:
         self._learn_send_arrays(arrays["alpha"], arrays["gamma"], arrays["epsilon"])
 
     # ------------------------------------------------------------------ per-episode epsilon / alpha schedules
-    def set_learner_schedule(self, epsilon=None, alpha=None, row=None):
+    def set_learner_schedule(self, epsilon=None, alpha=None, row=None, sweep=False):
         """Per-EPISODE epsilon and / or alpha for rollout_learn.  ``epsilon`` and ``alpha`` are tables [M] or
         [R, M] (numpy, or a torch tensor on any device; epsilon in [0, 1], alpha as float32 in (0, 1]; R M <= 2^22), ``row`` an
         integer array [N] in [0, R) -- the table row env i of THIS handle follows (its local index, like the per-env
@@ -877,20 +878,50 @@ class RLToyVectorEnv:
         holds.  A parameter without a table stays what set_learner / set_learner_rates made it.  policy.epsilon_decay makes
         the rows "linear", "log" and "const".  rollout_eval reads no table and moves no counter.
         ValueError (policy.learner_schedule_arrays) before any device work; MdppError without a learner;
-        NotImplementedError, nothing changed, on a handle with per-env noise levels or a per_env_mdp learner (not built).
-        set_learner drops the schedule; while it is in force set_noise_levels is refused.  Like noise levels the schedule is
+        NotImplementedError, nothing changed, on a handle with per-env noise levels or a per_env_mdp learner (not built)
+        unless ``sweep=True``.  set_learner drops the schedule; while it is in force set_noise_levels is refused, again
+        unless the schedule was set with ``sweep=True``.
+        ``sweep=True``: the schedule is also served on a handle with per-env noise levels
+        (set_noise_levels), with a per_env_mdp learner, or with both -- the same learner, step and placements as without a
+        schedule, with E and alpha taken from (row[i], counter[i]) by the rules above -- so an agent with a decay schedule
+        trains over noise levels x seeds in ONE launch.  Schedule and levels may be given in either order; on a plain
+        shared-MDP handle without levels ``sweep=True`` changes nothing.  The opt-in stays until clear_learner_schedule().
+        While a sweep schedule is in force together with levels or a per_env_mdp learner, a call without ``sweep=True`` is
+        refused (NotImplementedError) and what is in force stays; a call the library refuses leaves the opt-in as it was.
+        Like noise levels the schedule is
         configuration, and its counters are the learner's, not the env's: get_augmented_state / set_augmented_state carry
         neither -- a checkpoint keeps learner_episodes() beside get_q() and gives both back (set_learner_episodes, set_q)."""
         eps, al, rows, R, M = policy_mod.learner_schedule_arrays(epsilon, alpha, row, self.num_envs)
         self._learn_check_kind()
+        sweep = bool(sweep)
+        if self._sched_sweep and not sweep and self._learn_sched is not None and (self._noise_levels_set or self._learn_pm):
+            # (the call without the opt-in, refused as on a handle that never had it -- before the handle is touched)
+            raise NotImplementedError("mdpp_set_learner_schedule: an epsilon/alpha schedule with per-env noise levels / one MDP per env: "
+                                      "not built; the sweep=True schedule in force stays as it is")
+        was = self._sched_sweep
+        if sweep != was:
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_schedule_sweep(self._h, int(sweep)), "mdpp_learner_schedule_sweep")
+            self._sched_sweep = sweep
         rc = self._lib.mdpp_set_learner_schedule(self._h, capi.nptr(eps), capi.nptr(al), R, M, capi.nptr(rows), self._stream())
+        if rc != 0 and sweep and not was:
+            # (the opt-in goes back to what it was.  Read the reason first: the flag call keeps it)
+            msg = self._lib.mdpp_last_error(self._h)
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_schedule_sweep(self._h, 0), "mdpp_learner_schedule_sweep")
+            self._sched_sweep = False
+            if rc == capi.EUNSUPPORTED:
+                raise NotImplementedError(msg.decode() if msg else "mdpp_set_learner_schedule: unsupported")
+            raise capi.MdppError("mdpp_set_learner_schedule failed (%d): %s" % (rc, msg.decode() if msg else ""))
         self._closed_call(rc, "mdpp_set_learner_schedule")
         self._learn_sched = dict(epsilon=eps, alpha=al, row=rows)
 
     def clear_learner_schedule(self):
         """Drop the schedule: epsilon and alpha are again what set_learner / set_learner_rates made them (the scheduled
-        parameter's last uniform or per-env value).  The counters are zeroed by the next set_learner_schedule."""
+        parameter's last uniform or per-env value).  The counters are zeroed by the next set_learner_schedule.  The
+        ``sweep=True`` opt-in of set_learner_schedule goes with it."""
         capi.check(self._lib, self._h, self._lib.mdpp_clear_learner_schedule(self._h), "mdpp_clear_learner_schedule")
+        if self._sched_sweep:
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_schedule_sweep(self._h, 0), "mdpp_learner_schedule_sweep")
+            self._sched_sweep = False
         self._learn_sched = None
 
     def learner_schedule(self):
@@ -989,7 +1020,8 @@ class RLToyVectorEnv:
         launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning; NLEV=1: per-env
         noise levels, set_noise_levels; SCHED=1, always last: a per-episode schedule, set_learner_schedule; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
         per-env noise levels on one MDP per env, set_noise_levels(..., per_env_mdp=True) -- the arguments come in template order,
-        "...,PE=1[,DOUBLE=1],NLEV=1,PM=1|2>"); empty for a handle it does not serve."""
+        "...,PE=1[,DOUBLE=1],NLEV=1,PM=1|2>", and a set_learner_schedule(..., sweep=True) schedule on any of these appends
+        ",SCHED=1" after everything else: "...,NLEV=1,PM=2,SCHED=1>"); empty for a handle it does not serve."""
         if self.kind != "discrete":
             return ""
         name = self._lib.mdpp_learn_kernel_name(self._h, int(K))
@@ -1024,7 +1056,9 @@ class RLToyVectorEnv:
         env i behaves bit for bit like env i of such a handle created uniformly at its two values.  Without it that handle is
         refused as ever; the opt-in stays until clear_noise_levels(), ``set_learner(None)`` or a call without it.  ValueError
         on a handle with one shared MDP; a one-MDP-per-env handle without the per_env_mdp learner raises the learner's
-        refusal."""
+        refusal.  While a schedule (set_learner_schedule) is in force the call is refused (NotImplementedError, nothing
+        changed) unless the schedule was set with ``sweep=True``: then the levels are accepted and the launch is the
+        scheduled learner on them."""
         if per_env_mdp and not self._per_env:
             raise ValueError("set_noise_levels: per_env_mdp=True needs one MDP per env (seeds=[...] or mdps=[...]); this handle has one shared MDP")
         arrays = {}
