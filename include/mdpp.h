@@ -486,6 +486,28 @@ int mdpp_learner_per_env_mdp(mdpp_env *h, int on);
  * A reset call changes nothing.  The launch loads the five values before its first step and stores them after its last:
  * the caller zeroes them (all five at an episode boundary it makes itself, mdpp_reset; the three sums when it has read
  * them).  Nothing of them is kept in the handle.  Without [K][N] arrays a call is one launch whatever K.
+ *   The episode log: mdpp_step_n_learn_log is mdpp_step_n_learn_summary with three more arrays of the
+ * caller and a capacity M >= 1 -- log_count int32 [N], the number of episodes this log has seen finish for env i (it goes on
+ * counting past M); log_ret float64 [M][N] and log_len int32 [M][N], episode-major: entry [m][i] is the return and the length
+ * of the m-th episode of env i that finished under this log.  Where the rule above finds terminated or truncated, BEFORE ret
+ * and len are zeroed:
+ *   if (count < M) { log_ret[count][i] = ret;  log_len[count][i] = len; }   (the values just added to return_sum / length_sum)
+ *   count += 1;
+ * ret is the float64 value added to return_sum.  Nothing else changes: the five summary values, env, streams, step counter,
+ * tables, schedule counters and the kernel name the library reports are those of the same launch without a log (the launch
+ * itself runs the form's k_discrete_learn_summary_log kernel, so that a launch WITHOUT a log runs the code it always ran).
+ * There is no log for mdpp_step_n_eval_summary: a greedy evaluation ends episodes at nearly every step, and its log launch
+ * did not beat the full-output launch; run the evaluation with full output where its episodes are wanted.  The lane loads log_count[i]
+ * where it loads its five values and stores it where it stores them (no atomics); entries the launch does not write keep what
+ * they held; a reset call writes nothing; the log never reads `episodes`, so zeroing the three sums does not disturb it.
+ * Two consequences, both exact: a log and a summary zeroed together, the sums never zeroed in between, have
+ * log_count == episodes and length_sum[i] == the sum of log_len[0 .. min(count, M) - 1][i] wherever count <= M; and the
+ * left-to-right float64 sum of log_ret[0 .. count[i] - 1][i] equals return_sum[i] bit for bit for every env with
+ * count[i] <= M.  Episode-major so that lanes of a wave finishing their m-th episode at one step store adjacent entries, and
+ * "the mean over envs of episode m" is a contiguous row.  Served handles, forms and refusals are mdpp_step_n_learn_summary's, with the
+ * same text; a null log pointer, M < 1 or M * num_envs > 2^31 - 1 is MDPP_EINVAL with a message, before any device work.
+ * Nothing of a log is kept in the handle; after mdpp_reset the caller zeroes the five summary arrays (which hold the running
+ * episode), the log's finished episodes stay valid.
  * mdpp_current_obs writes the observation each env shows now (what the last step or reset returned for it), taken from the
  * state record, to obs_dev [N] in the handle's observation type, ordered on `stream`: what a caller needs after a launch
  * that wrote no observations.  Served: the handles of mdpp_step_n_learn. */
@@ -496,6 +518,9 @@ int mdpp_step_n_learn_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_
                               double *return_sum_dev, int32_t *length_sum_dev, void *stream);
 int mdpp_step_n_eval_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
                              double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+int mdpp_step_n_learn_log(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                          double *return_sum_dev, int32_t *length_sum_dev,
+                          int32_t *log_count_dev, double *log_ret_dev, int32_t *log_len_dev, int M, void *stream);
 int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream);
 
 /* Per-env noise levels for the learner and evaluation launches.  A handle mdpp_set_learner serves may give each env its own
@@ -619,6 +644,8 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   env's table set are read from the handle's buffers at replay.  A schedule (mdpp_set_learner_schedule): which tables are
  *   scheduled and M go by value; the tables, the rows and the episode counters are read -- and the counters written -- at
  *   replay (mdpp_set_learner_schedule with the same tables given and the same M, or mdpp_set_learner_episodes, between replays).
+ *   An episode log (mdpp_step_n_learn_log): the three log pointers and M go by value; log_count is read and written at replay and
+ *   log_ret / log_len are written, so a log accumulates across replays like the five summary arrays.
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

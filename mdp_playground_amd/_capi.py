@@ -57,6 +57,7 @@ EXPORTS = [
     "mdpp_noise_levels_per_env_mdp",
     "mdpp_set_learner_schedule", "mdpp_clear_learner_schedule", "mdpp_get_learner_episodes", "mdpp_set_learner_episodes",
     "mdpp_learner_schedule_sweep",
+    "mdpp_step_n_learn_log",
 ]
 
 
@@ -184,6 +185,7 @@ def load():
     L.mdpp_eval_kernel_name.restype = C.c_char_p
     L.mdpp_step_n_learn_summary.argtypes = [vp, i32] + [vp] * 6
     L.mdpp_step_n_eval_summary.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_step_n_learn_log.argtypes = [vp, i32] + [vp] * 8 + [i32, vp]
     L.mdpp_current_obs.argtypes = [vp, vp, vp]
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]

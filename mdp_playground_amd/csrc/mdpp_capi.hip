@@ -1786,18 +1786,25 @@ extern "C" const char *mdpp_eval_kernel_name(mdpp_env *h, int K) {
 }
 
 // the checks of step_n_closed for a launch that keeps the caller's five [N] summary arrays and writes nothing else
-static int step_n_summary(mdpp_env *h, const char *what, int (*launch)(mdpp_env *, const DiscreteIO &), int K, double *ret,
-                          int32_t *len, int32_t *episodes, double *return_sum, int32_t *length_sum, void *stream) {
+// sm: the five arrays and, for a _log call (log), the episode log's three and its capacity in sm.log_cap -- M as the caller
+// gave it, checked here; a _summary call leaves them null and 0
+static int step_n_summary(mdpp_env *h, const char *what, int (*launch)(mdpp_env *, const DiscreteIO &), int K, const EpisodeSummaryArgs &sm,
+                          bool log, int M, void *stream) {
     if (!h) return MDPP_EINVAL;
     if (K < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": K < 1");
-    if (!ret || !len || !episodes || !return_sum || !length_sum) return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    if (!sm.ret || !sm.len || !sm.episodes || !sm.return_sum || !sm.length_sum) return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    if (log) {
+        if (!sm.log_count || !sm.log_ret || !sm.log_len) return fail(h, MDPP_EINVAL, std::string(what) + ": null log buffer");
+        if (M < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": M < 1");
+        if ((long long)M * (long long)h->cfg.num_envs > (long long)INT32_MAX)
+            return fail(h, MDPP_EINVAL, std::string(what) + ": M * num_envs > 2^31 - 1");
+    }
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
     if (!h->learn_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_learner)");
     int rc = check_ready(h, what);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    const EpisodeSummaryArgs sm{ret, len, episodes, return_sum, length_sum};
     DiscreteIO io{};
     io.K = K; io.s = (hipStream_t)stream; io.summary = &sm;
     return launch(h, io);
@@ -1805,12 +1812,22 @@ static int step_n_summary(mdpp_env *h, const char *what, int (*launch)(mdpp_env 
 
 extern "C" int mdpp_step_n_learn_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
                                          double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
-    return step_n_summary(h, "mdpp_step_n_learn_summary", launch_discrete_learn, K, ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, stream);
+    return step_n_summary(h, "mdpp_step_n_learn_summary", launch_discrete_learn, K,
+                          EpisodeSummaryArgs{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u}, false, 0, stream);
 }
 
 extern "C" int mdpp_step_n_eval_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
                                         double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
-    return step_n_summary(h, "mdpp_step_n_eval_summary", launch_discrete_eval, K, ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, stream);
+    return step_n_summary(h, "mdpp_step_n_eval_summary", launch_discrete_eval, K,
+                          EpisodeSummaryArgs{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u}, false, 0, stream);
+}
+
+extern "C" int mdpp_step_n_learn_log(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                     double *return_sum_dev, int32_t *length_sum_dev, int32_t *log_count_dev,
+                                     double *log_ret_dev, int32_t *log_len_dev, int M, void *stream) {
+    return step_n_summary(h, "mdpp_step_n_learn_log", launch_discrete_learn, K,
+                          EpisodeSummaryArgs{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, log_count_dev, log_ret_dev, log_len_dev,
+                                             M > 0 ? (uint32_t)M : 0u}, true, M, stream);
 }
 
 extern "C" int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream) {

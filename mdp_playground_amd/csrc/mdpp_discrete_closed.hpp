@@ -44,6 +44,16 @@
 //   ret += (double)reward;  len += 1;  terminated or truncated: episodes += 1, return_sum += ret, length_sum += len, ret = len = 0
 // and stores them after finish().  The five output pointers are unused (null).  A compile-time choice: the SUMMARY = false
 // instantiations are the code they were.
+// An episode log (sm.log_cap = M != 0, a run-time field: no kernel is added or renamed for it): the lane loads count[i] with
+// its five values and, where the rule finds terminated or truncated, before ret and len are zeroed,
+//   count < M: log_ret[count][i] = ret, log_len[count][i] = len;  count += 1
+// -- the values just added to return_sum / length_sum; the element index count N + i is kept in 64 bits and moved on by N per
+// episode (the host keeps M N below 2^31); the stores are non-temporal, like the [K][N] outputs' (MDPP_ST_NT) -- and stores
+// count[i] with the five.  No atomics: env i's column is this lane's alone.  Rows the launch does not reach are not touched.
+// LOG = true is the body of the learner's k_discrete_learn_summary_log kernels (mdpp_discrete_learn.hpp), which the launcher
+// takes when sm.log_cap != 0; the summary kernels themselves are LOG = false, the code they were.  (As a run-time branch in the
+// summary kernels' step loop the log cost the launches WITHOUT one 3-6 %, executed or not: the loops are latency-bound and any
+// addition moved their schedule.  Two copies of the loop inside one kernel still shared its register allocation.)
 //
 // NLEV = true (per-env noise levels, mdpp_set_noise_levels; with NOISE only): env i has its own reward-noise sigma and its own
 // transition-noise level.  After the `i >= N` return the lane loads its level byte, its sigma and its level's Philox
@@ -157,7 +167,7 @@ __host__ __device__ __forceinline__ uint32_t closed_agent_lds_offset(const Discr
 }
 
 // (a is the kernel's by-value argument, taken by const reference: see tick_now in mdpp_internal.hpp for what a write costs)
-template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, bool NLEV = false, int PM = 0, class Agent>
+template <bool PHILOX, bool NOISE, bool UNIT, bool SUMMARY = false, bool NLEV = false, int PM = 0, bool LOG = false, class Agent>
 __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K, const bool obs64, int32_t *actions,
                                                     void *__restrict__ obs, float *__restrict__ reward,
                                                     uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
@@ -165,6 +175,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
                                                     const EpisodeSummaryArgs &sm = EpisodeSummaryArgs{},
                                                     const NoiseLevelArgs &nl = NoiseLevelArgs{}) {
     static_assert(NOISE || !NLEV, "per-env noise levels are levels of a NOISE kernel");
+    static_assert(SUMMARY || !LOG, "the episode log is kept by the summary form");
     const uint64_t ptick0 = tick_now(a);               // the step counter at this launch (through the device-side offset of a graph replay)
     const uint32_t rhead0 = ring_head_now(a, ptick0);  // ... and the head of a delay line kept in memory
     const int tid = threadIdx.x;
@@ -225,9 +236,15 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     agent.begin(i, genv, ptick0);
     double ep_ret = 0.0, ep_return_sum = 0.0;           // SUMMARY: this env's five values
     int32_t ep_len = 0, ep_count = 0, ep_length_sum = 0;
+    uint32_t ep_logged = 0;                             // LOG: the episodes the log has seen this env finish ...
+    uint64_t log_at = 0;                                // ... and the element ep_logged N + i of its next row
     if constexpr (SUMMARY) {
         ep_ret = sm.ret[i]; ep_len = sm.len[i];
         ep_count = sm.episodes[i]; ep_return_sum = sm.return_sum[i]; ep_length_sum = sm.length_sum[i];
+        if constexpr (LOG) {
+            ep_logged = (uint32_t)sm.log_count[i];
+            log_at = (uint64_t)ep_logged * (uint64_t)N + (uint64_t)i;
+        }
     }
 
     const uint4 st = a.state[i];
@@ -405,6 +422,14 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
             ep_ret += (double)rout;
             ep_len += 1;
             if (done || truncated) {
+                if constexpr (LOG) {        // the episode log: row ep_logged of the episode-major [log_cap][N] arrays, while there is one
+                    if (ep_logged < sm.log_cap) {
+                        __builtin_nontemporal_store(ep_ret, sm.log_ret + log_at);
+                        __builtin_nontemporal_store(ep_len, sm.log_len + log_at);
+                    }
+                    ep_logged += 1;
+                    log_at += (uint64_t)N;
+                }
                 ep_count += 1;
                 ep_return_sum += ep_ret;
                 ep_length_sum += ep_len;
@@ -421,6 +446,7 @@ __device__ __forceinline__ void closed_loop_rollout(const DiscreteArgs &a, int K
     if constexpr (SUMMARY) {
         sm.ret[i] = ep_ret; sm.len[i] = ep_len;
         sm.episodes[i] = ep_count; sm.return_sum[i] = ep_return_sum; sm.length_sum[i] = ep_length_sum;
+        if constexpr (LOG) sm.log_count[i] = (int32_t)ep_logged;
     }
     a.state[i] = make_uint4((uint32_t)hist, queued ? (qv | (qc << 24)) : (uint32_t)(hist >> 32),
                             steps | (pending ? 0x80000000u : 0u), ringbits);
@@ -533,6 +559,7 @@ inline int launch_closed_loop(mdpp_env *h, const DiscreteIO &io, Kern kern, size
 // K steps of one form of an agent that keeps per-env Q-tables, the one launcher of the learners and the evaluation:
 // the step's compile-time facts from the handle, the placement (closed_agent_lds), the kernel of both, its name and its
 // dynamic LDS.  PMH: the handle has one MDP per env and runs the PM = 1 / PM = 2 kernels, else PM = 0.  A form F says
+//   F::LOG                     the form has _log kernels, F::kernel_log<...>(), launched when io.summary carries an episode log
 //   F::SUMMARY, F::NLEV        the step's form (NLEV: of a handle with per-env noise levels -- NOISE = 1 whatever its keys)
 //   F::TABLES                  how many tables Q has (1, or 2 for double Q)
 //   F::kernel<PH, NZ, UNIT, QL, PM>()                      the __global__ function
@@ -561,9 +588,17 @@ int launch_closed_form(mdpp_env *h, const DiscreteIO &io) {
                     F::name(name, PH(), NZ(), UNIT(), QL(), PM);
                     const size_t agent_at = F::NLEV ? (size_t)closed_agent_lds_offset<PM>(a, cdf_lds) : (size_t)closed_agent_lds_offset<PM>(a);
                     // (granted already unless the placement is {}, which was not asked about)
-                    rc = launch_closed_loop<F::SUMMARY>(h, io, F::template kernel<PH(), NZ(), UNIT(), QL(), PM>(), agent_at + (QL() ? q_lds : 0u),
-                                                        at.q || at.slots || at.cdfs, name,
-                                                        [&](int k0, int kc, int32_t *actions) { return F::args(h, io, k0, kc, actions, cdf_lds); });
+                    const auto args = [&](int k0, int kc, int32_t *actions) { return F::args(h, io, k0, kc, actions, cdf_lds); };
+                    bool with_log = false;
+                    if constexpr (F::SUMMARY && F::LOG) with_log = io.summary && io.summary->log_cap != 0u;
+                    if constexpr (F::SUMMARY && F::LOG) {
+                        // with an episode log: the form's _log kernel -- same placement, same LDS, same reported name; asked about
+                        // its LDS itself (the placement asked the summary kernel)
+                        if (with_log) rc = launch_closed_loop<true>(h, io, F::template kernel_log<PH(), NZ(), UNIT(), QL(), PM>(), agent_at + (QL() ? q_lds : 0u), false, name, args);
+                    }
+                    if (!with_log)
+                        rc = launch_closed_loop<F::SUMMARY>(h, io, F::template kernel<PH(), NZ(), UNIT(), QL(), PM>(), agent_at + (QL() ? q_lds : 0u),
+                                                            at.q || at.slots || at.cdfs, name, args);
                 }
             }, at.q, at.slots);
         }

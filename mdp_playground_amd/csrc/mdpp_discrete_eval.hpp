@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void k_discrete_eval_summary(DiscreteArgs a
 // One form of the evaluation, as launch_closed_form (mdpp_discrete_closed.hpp) takes it
 template <bool DOUBLE, bool SUMMARY_, bool NLEV_>
 struct EvalForm {
-    static constexpr bool SUMMARY = SUMMARY_, NLEV = NLEV_;
+    static constexpr bool SUMMARY = SUMMARY_, NLEV = NLEV_, LOG = false;     // (no episode log under evaluation: DESIGN.md 3.24)
     static constexpr int TABLES = DOUBLE ? 2 : 1;
     template <bool PH, bool NZ, bool UNIT, bool QL, int PM>
     static constexpr auto kernel() {

@@ -354,10 +354,38 @@ __global__ __launch_bounds__(kBlock) void k_discrete_learn_summary(DiscreteArgs 
     closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
 }
 
+// ... and keeping an episode log beside them (mdpp_step_n_learn_log: sm.log_cap != 0).  Kernels of their own, so that the
+// summary kernels above stay the code they were: the same bodies around closed_loop_rollout<..., LOG = true>
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE = false, bool DOUBLE = false, bool NLEV = false, int PM = 0, bool SCHED = false>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_summary_log(DiscreteArgs a, LearnArgsOf<PE, NLEV, SCHED> p, int K, EpisodeSummaryArgs sm) {
+    extern __shared__ __align__(16) unsigned char lds[];
+    const ZigLds zig = closed_loop_zig_lds<NOISE>();
+    unsigned char *q_lds;
+    if constexpr (NLEV && PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else {
+        q_lds = lds + closed_agent_lds_offset<PM>(a);
+        if constexpr (NLEV) q_lds += p.nl.lds_bytes;
+    }
+    LearnAgent<QLDS, PE, DOUBLE, SCHED> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    if constexpr (NLEV) closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV, PM, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
+    else closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, PM, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
+}
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE, bool DOUBLE, bool NLEV, int PM, bool SCHED>
+__global__ __launch_bounds__(kBlock) void k_discrete_learn_summary_log(DiscreteArgs a, LearnArgsNLSched p, int K, EpisodeSummaryArgs sm) {
+    static_assert(PE && NLEV && SCHED && NOISE, "the argument block of a schedule with per-env noise levels");
+    extern __shared__ __align__(16) unsigned char lds[];
+    const ZigLds zig = closed_loop_zig_lds<NOISE>();
+    unsigned char *q_lds;
+    if constexpr (PM != 0) q_lds = lds + closed_agent_lds_offset<PM>(a, p.nl.lds_bytes);
+    else q_lds = lds + closed_agent_lds_offset<PM>(a) + p.nl.lds_bytes;
+    LearnAgent<QLDS, PE, DOUBLE, SCHED> agent{p, (float *)q_lds + threadIdx.x, (uint32_t)a.A, (uint32_t)a.S * (uint32_t)a.A, (uint32_t)a.N};
+    closed_loop_rollout<PHILOX, NOISE, UNIT, true, NLEV, PM, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm, p.nl);
+}
+
 // One form of the learner, as launch_closed_form (mdpp_discrete_closed.hpp) takes it
 template <bool PE, bool DOUBLE, bool SUMMARY_, bool NLEV_, bool SCHED>
 struct LearnForm {
-    static constexpr bool SUMMARY = SUMMARY_, NLEV = NLEV_;
+    static constexpr bool SUMMARY = SUMMARY_, NLEV = NLEV_, LOG = SUMMARY_;
     static constexpr int TABLES = DOUBLE ? 2 : 1;
     using Args = std::conditional_t<NLEV_ && SCHED, LearnArgsNLSched, LearnArgsOf<PE, NLEV_, SCHED>>;      // the kernel's second parameter
     // the kernel: full output, or summaries
@@ -369,6 +397,12 @@ struct LearnForm {
         // (the cast picks the overload by its second parameter)
         if constexpr (SUMMARY) return static_cast<void (*)(DiscreteArgs, Args, int, EpisodeSummaryArgs)>(k_discrete_learn_summary<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>);
         else return static_cast<void (*)(DiscreteArgs, Args, int, void *, float *, uint8_t *, uint8_t *)>(k_discrete_learn_rollout<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>);
+    }
+    // ... the summary form's kernel that keeps an episode log too
+    template <bool PH, bool NZ, bool UNIT, bool QL, int PM>
+    static constexpr auto kernel_log() {
+        static_assert(SUMMARY, "the episode log is kept by the summary form");
+        return static_cast<void (*)(DiscreteArgs, Args, int, EpisodeSummaryArgs)>(k_discrete_learn_summary_log<PH, NZ, UNIT, QL, PE, DOUBLE, NLEV, PM, SCHED>);
     }
     static void name(char *out, int ph, int nz, int unit, int ql, int pm) {
         if (pm)

@@ -467,12 +467,18 @@ template <int... Vs, class F> inline bool with_value(int v, F &&f) {
 constexpr int kNameLen = 192;
 // The episode summaries of a closed-loop launch that writes no [K][N] array (mdpp_step_n_learn_summary /
 // mdpp_step_n_eval_summary): the caller's five [N] arrays on the device -- the running episode's return and length, the
-// finished episodes' count and the sums of their returns and lengths
+// finished episodes' count and the sums of their returns and lengths.  With an episode log (mdpp_step_n_learn_log /
+// mdpp_step_n_eval_log; log_cap == 0: none, the other three are not read) the caller's count [N] and the episode-major
+// [log_cap][N] returns and lengths of the episodes that finished under it (include/mdpp.h "Episode summaries")
 struct EpisodeSummaryArgs {
     double *ret;
     int32_t *len, *episodes;
     double *return_sum;
     int32_t *length_sum;
+    int32_t *log_count;         // (no default member initialisers: with them EpisodeSummaryArgs{} is built field by field, and
+    double *log_ret;            //  the kernels that take it as an unused default argument came out with other registers)
+    int32_t *log_len;
+    uint32_t log_cap;
 };
 template <class Act, class Obs>
 struct StepIO {

@@ -29,7 +29,7 @@ import torch
 from . import _capi as capi
 from . import mdp as mdp_mod
 from . import policy as policy_mod
-from .summary import EpisodeSummary
+from .summary import EpisodeLog, EpisodeSummary
 from .spaces import BatchedSpace, BoxSpace, DiscreteSpace, ImageSpace, TupleSpace
 
 _OBS_FROM_STATE = object()    # _obs_src after a launch that wrote no observations: take them from the state record
@@ -713,12 +713,21 @@ class RLToyVectorEnv:
         self._obs_src = obs[K - 1]        # (a view: reset(mask=...) shows it for the envs it leaves alone)
         return obs, rew, term.view(torch.bool), trunc.view(torch.bool), act
 
-    def _rollout_summary(self, step_n, what, K, summary):
-        """K closed-loop steps that keep ``summary`` and write no [K, N] array (mdpp_step_n_learn_summary / _eval_summary)."""
+    def _rollout_summary(self, step_n, what, K, summary, log=None):
+        """K closed-loop steps through the entry point step_n, named ``what``, that keep ``summary`` and write no [K, N] array:
+        mdpp_step_n_learn_summary / _eval_summary, or with ``log`` mdpp_step_n_learn_log, which keeps the episode log too
+        (the caller picks the pair)."""
         if not isinstance(summary, EpisodeSummary):
             raise ValueError(f"{what}: summary must be an EpisodeSummary (env.episode_summary())")
         summary.check(self.num_envs, self.device, what)
-        rc = step_n(self._h, K, *(C.c_void_p(t.data_ptr()) for t in summary.tensors()), self._stream())
+        if log is None:
+            rc = step_n(self._h, K, *(C.c_void_p(t.data_ptr()) for t in summary.tensors()), self._stream())
+        else:
+            if not isinstance(log, EpisodeLog):
+                raise ValueError(f"{what}: log must be an EpisodeLog (env.episode_log(max_episodes))")
+            log.check(self.num_envs, self.device, what)
+            rc = step_n(self._h, K, *(C.c_void_p(t.data_ptr()) for t in summary.tensors() + log.tensors()),
+                        log.max_episodes, self._stream())
         self._closed_call(rc, what)
         self._obs_src = _OBS_FROM_STATE
         return summary
@@ -728,6 +737,12 @@ class RLToyVectorEnv:
         length_sum -- for rollout_learn(K, summary=) / rollout_eval(K, summary=); pop() reads and zeroes the finished episodes'
         three, clear() zeroes all five (call it after reset(): the handle knows nothing of the object)."""
         return EpisodeSummary(self.num_envs, self.device)
+
+    def episode_log(self, max_episodes):
+        """A new EpisodeLog for this handle (summary.py): count [N], ret and len [max_episodes, N], zeroed device tensors, for
+        rollout_learn(K, summary=, log=) -- the return and length of every episode each env
+        finishes, by the env's own episode index; curve() is the learning curve.  Nothing of it lives in the handle."""
+        return EpisodeLog(self.num_envs, max_episodes, self.device)
 
     def alloc_rollout_policy(self, K):
         """Output buffers of rollout_policy(K): alloc_rollout(K) and the actions, int32 [K, N]."""
@@ -958,18 +973,24 @@ class RLToyVectorEnv:
         """Output buffers of rollout_learn(K): alloc_rollout(K) and the actions, int32 [K, N]."""
         return self._alloc_rollout_closed(K)
 
-    def rollout_learn(self, K, out=None, *, summary=None):
+    def rollout_learn(self, K, out=None, *, summary=None, log=None):
         """K steps of "select epsilon-greedily from the env's own Q, step, update that Q" in ONE kernel launch.  Returns (obs,
         reward, terminated, truncated, actions), each with a leading K axis; rollout(actions) on an identically built env
         returns the same first four, bit for bit.  SARSA carries its next action from step to step inside a call only: the
         first step of every call selects afresh.  With a schedule (set_learner_schedule) every env selects and
         updates with the epsilon / alpha of its own episode count, looked up again inside the launch at each episode end.
         ``summary`` (episode_summary()): the same K steps with the same effect on the env and the tables, but NO [K, N] array
-        is written -- the kernel keeps the per-env episode numbers in ``summary`` and that object is returned."""
+        is written -- the kernel keeps the per-env episode numbers in ``summary`` and that object is returned.
+        ``log`` (episode_log(M), with ``summary`` only): the same launch also writes the return and length of every episode that
+        ends into the log, at the env's own episode index; ``summary`` is still what is returned."""
         self._learn_check_kind()
+        if log is not None and (summary is None or out is not None):
+            raise ValueError("rollout_learn: log goes with summary (and without out)")
         if summary is not None:
             if out is not None:
                 raise ValueError("rollout_learn: give out or summary, not both")
+            if log is not None:
+                return self._rollout_summary(self._lib.mdpp_step_n_learn_log, "mdpp_step_n_learn_log", int(K), summary, log)
             return self._rollout_summary(self._lib.mdpp_step_n_learn_summary, "mdpp_step_n_learn_summary", int(K), summary)
         return self._rollout_closed(self._lib.mdpp_step_n_learn, "mdpp_step_n_learn", int(K), out)
 
@@ -982,7 +1003,7 @@ class RLToyVectorEnv:
         maximises its own Q[s] (QA[s] + QB[s] for "double_q").  No exploration and no update: the tables stay bit for bit what
         they were, the learner's Philox streams are not consumed, alpha, gamma and epsilon are not read.  Needs a learner
         (set_learner, any algorithm).  Returns (obs, reward, terminated, truncated, actions) like rollout_learn; with
-        ``summary`` the episode numbers instead, as there.  The steps are steps of THIS env: to evaluate on a separate one,
+        ``summary`` the episode numbers instead, as there (an episode log is kept by rollout_learn only: DESIGN.md 3.24).  The steps are steps of THIS env: to evaluate on a separate one,
         build a second handle and give it the tables -- set_learner(..., q=train.get_q()) or set_q(train.get_q())."""
         self._learn_check_kind()
         if summary is not None:
