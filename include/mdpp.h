@@ -103,8 +103,9 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
                                               (the hand-over between the pieces of a very long call, at a size a test can run) */
        MDPP_OPT_NO_NLEV_LDS = 1u << 20,    /* per-env noise levels (mdpp_set_noise_levels): the per-level cdfs stay in global memory */
        MDPP_OPT_NO_PM_LDS = 1u << 21,      /* one MDP per env (mdpp_learner_per_env_mdp): the envs' tables stay in global memory (PM=1) */
-       MDPP_OPT_NO_PM_NLEV_LDS = 1u << 22 }; /* per-env noise levels on one MDP per env (mdpp_noise_levels_per_env_mdp): the per-level cdfs stay
+       MDPP_OPT_NO_PM_NLEV_LDS = 1u << 22,   /* per-env noise levels on one MDP per env (mdpp_noise_levels_per_env_mdp): the per-level cdfs stay
                                               in global memory in the PM kernels (MDPP_OPT_NO_NLEV_LDS keeps its meaning for a shared MDP) */
+       MDPP_OPT_NO_LINEAR_LDS = 1u << 23 };  /* k_continuous_linear_rollout / _summary: the linear policies' parameters stay in global memory (PLDS=0) */
 
 /* transition-noise levels one handle serves at a time (mdpp_set_noise_levels) */
 #define MDPP_MAX_NOISE_LEVELS 16
@@ -510,7 +511,8 @@ int mdpp_learner_per_env_mdp(mdpp_env *h, int on);
  * episode), the log's finished episodes stay valid.
  * mdpp_current_obs writes the observation each env shows now (what the last step or reset returned for it), taken from the
  * state record, to obs_dev [N] in the handle's observation type, ordered on `stream`: what a caller needs after a launch
- * that wrote no observations.  Served: the handles of mdpp_step_n_learn. */
+ * that wrote no observations.  Served: the handles of mdpp_step_n_learn; and a continuous handle that has a linear policy
+ * (mdpp_set_linear_policy): the state in every env's record as float32 [N][D]. */
 int mdpp_step_n_eval(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
                      uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
 const char *mdpp_eval_kernel_name(mdpp_env *h, int K);
@@ -522,6 +524,41 @@ int mdpp_step_n_learn_log(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev,
                           double *return_sum_dev, int32_t *length_sum_dev,
                           int32_t *log_count_dev, double *log_ret_dev, int32_t *log_len_dev, int M, void *stream);
 int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream);
+
+/* Linear policies: closed-loop CONTINUOUS rollouts.  The handle holds float32 parameters theta, one set shared by every env
+ * ([D][D + 1]) or one per env ([N][D][D + 1]; per_env != 0): theta[.., r, c] for c < D is W[r][c], theta[.., r, D] is b[r]
+ * (D = state_space_dim = action_space_dim).  At every step of a launch env i forms its action from o = the state in its
+ * record -- the last observation returned for it; after a same-step reset the new episode's first state; on the reset call
+ * of a next-step-autoreset env the ended episode's last state --:
+ *   for r = 0 .. D-1:  acc = b[r];  for c = 0 .. D-1 in that order: acc = acc + W[r][c] * o[c]
+ *                      a[r] = acc < -amax ? -amax : (acc > amax ? amax : acc),   amax = (float)action_space_max
+ * every product and every sum rounded to float32, no fused multiply-add; a NaN acc stays NaN.  The step is mdpp_step_n's with
+ * that action: a NaN component fails the admission test, the env stays and gets MDPP_STATUS_BAD_ACTION.  On the reset call of
+ * a next-step-autoreset env the action is formed, written and ignored.  The policy reads no stream: mdpp_step_n on an
+ * identically built handle, fed the actions mdpp_step_n_linear wrote, writes the same observations, rewards and flags and
+ * leaves the same state, streams, status words and step counter, bit for bit.
+ * Served: continuous handles with reward_function move_to_a_point, state_space_dim <= 12 and transition_dynamics_order <= 2,
+ * no image observations and no episode_stats; every other field of the config as mdpp_step_n serves it.  Anything else is
+ * MDPP_EUNSUPPORTED with the reason, from mdpp_set_linear_policy on.  Without a policy the launches return MDPP_ESTATE
+ * ("no linear policy set").
+ * mdpp_set_linear_policy copies theta_dev (DEVICE pointer, the caller's layout above) into the handle's entry-major buffer on
+ * `stream`; mdpp_get_linear_policy writes it back in the layout it was given in.  mdpp_clear_linear_policy forgets it.
+ * mdpp_step_n_linear: K steps in ONE launch; actions_out_dev float32 [K][N][D] receives the actions taken, the other four as
+ * mdpp_step_n.  mdpp_step_n_linear_summary: the same K steps with no [K][N] output, keeping the caller's five [N] arrays by
+ * the rule of "Episode summaries" above (reward: the float32 the full-output launch writes).
+ * Kernels: k_continuous_linear_rollout / k_continuous_linear_summary<D,ORDER,PHILOX,NOISE,PLDS> (D, ORDER: the padded shape).
+ * PLDS=1: every lane stages its D (D + 1) parameters once per launch in dynamic LDS (256 D (D + 1) 4 bytes per workgroup) and
+ * reads them there at every step -- taken when the device grants that beside the kernel's static LDS; PLDS=0: they are read
+ * from the buffer at every step (MDPP_OPT_NO_LINEAR_LDS forces it).  mdpp_linear_kernel_name: as mdpp_kernel_name, for the
+ * launch of mdpp_step_n_linear (summary == 0) or mdpp_step_n_linear_summary; nothing is launched. */
+int mdpp_set_linear_policy(mdpp_env *h, const float *theta_dev, int per_env, void *stream);
+int mdpp_get_linear_policy(mdpp_env *h, float *theta_dev, void *stream);
+int mdpp_clear_linear_policy(mdpp_env *h);
+int mdpp_step_n_linear(mdpp_env *h, int K, float *actions_out_dev, float *obs_dev, float *reward_dev,
+                       uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+int mdpp_step_n_linear_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                               double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+const char *mdpp_linear_kernel_name(mdpp_env *h, int K, int summary);
 
 /* Per-env noise levels for the learner and evaluation launches.  A handle mdpp_set_learner serves may give each env its own
  * reward-noise sigma and its own transition-noise probability; mdpp_step_n_learn, mdpp_step_n_eval and their _summary forms
@@ -646,6 +683,9 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   replay (mdpp_set_learner_schedule with the same tables given and the same M, or mdpp_set_learner_episodes, between replays).
  *   An episode log (mdpp_step_n_learn_log): the three log pointers and M go by value; log_count is read and written at replay and
  *   log_ret / log_len are written, so a log accumulates across replays like the five summary arrays.
+ *   A linear policy (mdpp_step_n_linear / mdpp_step_n_linear_summary): shared or per-env parameters and their placement (PLDS)
+ *   go by value; the parameter buffer is READ at replay (mdpp_set_linear_policy with the same per_env between replays, on the
+ *   replay's stream).  The policy reads no stream, so only a Philox handle or a delay line in memory needs capture mode.
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

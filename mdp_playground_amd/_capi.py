@@ -24,7 +24,7 @@ OPTIONS = {"NO_PIPE": 1 << 0, "NO_HELPER": 1 << 1, "NO_PARK": 1 << 2, "NO_CFAST"
            "NO_GFAST_NOISE": 1 << 9, "NO_IMGFAST": 1 << 10, "NO_IMG_OVERLAP": 1 << 11, "NO_PHILOX_FAST": 1 << 12, "NO_LEAN": 1 << 13,
            "NO_IMG_NEARTAB": 1 << 14, "NO_STEP1": 1 << 15, "NO_SIGMA0": 1 << 16, "NO_QUIET_SF": 1 << 17,
            "NO_LEARN_LDS": 1 << 18, "LEARN_SHORT_PIECES": 1 << 19, "NO_NLEV_LDS": 1 << 20, "NO_PM_LDS": 1 << 21,
-           "NO_PM_NLEV_LDS": 1 << 22}
+           "NO_PM_NLEV_LDS": 1 << 22, "NO_LINEAR_LDS": 1 << 23}
 MAX_NOISE_LEVELS = 16                              # MDPP_MAX_NOISE_LEVELS
 MAX_SCHEDULE_ENTRIES = 1 << 22                     # MDPP_MAX_SCHEDULE_ENTRIES
 ESTATE = -4               # MDPP_ESTATE
@@ -58,6 +58,8 @@ EXPORTS = [
     "mdpp_set_learner_schedule", "mdpp_clear_learner_schedule", "mdpp_get_learner_episodes", "mdpp_set_learner_episodes",
     "mdpp_learner_schedule_sweep",
     "mdpp_step_n_learn_log",
+    "mdpp_set_linear_policy", "mdpp_get_linear_policy", "mdpp_clear_linear_policy", "mdpp_step_n_linear",
+    "mdpp_step_n_linear_summary", "mdpp_linear_kernel_name",
 ]
 
 
@@ -187,6 +189,13 @@ def load():
     L.mdpp_step_n_eval_summary.argtypes = [vp, i32] + [vp] * 6
     L.mdpp_step_n_learn_log.argtypes = [vp, i32] + [vp] * 8 + [i32, vp]
     L.mdpp_current_obs.argtypes = [vp, vp, vp]
+    L.mdpp_set_linear_policy.argtypes = [vp, vp, i32, vp]
+    L.mdpp_get_linear_policy.argtypes = [vp, vp, vp]
+    L.mdpp_clear_linear_policy.argtypes = [vp]
+    L.mdpp_step_n_linear.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_step_n_linear_summary.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_linear_kernel_name.argtypes = [vp, i32, i32]
+    L.mdpp_linear_kernel_name.restype = C.c_char_p
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]

@@ -59,7 +59,7 @@ static void free_all(mdpp_env *h) {
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
                     h->d_img_near, h->d_s1_blob, h->d_lean_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
                     h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E, h->d_sched_E, h->d_sched_alpha, h->d_sched_row, h->d_sched_ep,
-                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M};
+                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -127,6 +127,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
     h->sched_on = h->sched_eps = h->sched_alpha = h->sched_sweep = false; h->sched_R = h->sched_M = 0; h->sched_cap = 0;
     h->d_sched_E = h->d_sched_alpha = h->d_sched_row = h->d_sched_ep = nullptr;
+    h->d_lin_theta = nullptr; h->lin_per_env = h->lin_ready = false;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
     h->d_hist_hi = nullptr;
@@ -1836,7 +1837,87 @@ extern "C" int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream) {
     int rc = check_ready(h, "mdpp_current_obs");
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
+    // a continuous handle under a linear policy: the state in the record, [N][D] (every other continuous handle is refused below)
+    if (h->cfg.kind == MDPP_KIND_CONTINUOUS && h->lin_ready && continuous_linear_refusal(h).empty())
+        return launch_continuous_current_obs(h, (float *)obs_dev, (hipStream_t)stream);
     return launch_discrete_current_obs(h, obs_dev, (hipStream_t)stream);
+}
+
+// ---- closed-loop CONTINUOUS rollouts under a linear policy per env (mdpp_continuous_linear.hip) ----
+extern "C" int mdpp_set_linear_policy(mdpp_env *h, const float *theta_dev, int per_env, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!theta_dev) return fail(h, MDPP_EINVAL, "mdpp_set_linear_policy: null parameters");
+    const std::string why = continuous_linear_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_linear_policy: " + why);
+    HIPCHK(h, hipSetDevice(h->device));
+    // (one allocation for the larger layout: a launch queued earlier may still read the buffer when the layout changes)
+    const size_t E = (size_t)h->cfg.D * (size_t)(h->cfg.D + 1);
+    if (!h->d_lin_theta) HIPCHK(h, hipMalloc(&h->d_lin_theta, (size_t)h->cfg.num_envs * E * sizeof(float)));
+    h->lin_per_env = per_env != 0;
+    int rc = launch_linear_theta_copy(h, const_cast<float *>(theta_dev), true, (hipStream_t)stream);
+    if (rc) { h->lin_ready = false; return rc; }
+    h->lin_ready = true;
+    return MDPP_OK;
+}
+
+// the checks every linear-policy call makes after its own arguments'
+static int linear_ready(mdpp_env *h, const char *what) {
+    const std::string why = continuous_linear_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
+    if (!h->lin_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no linear policy set (mdpp_set_linear_policy)");
+    int rc = check_ready(h, what);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_get_linear_policy(mdpp_env *h, float *theta_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!theta_dev) return fail(h, MDPP_EINVAL, "mdpp_get_linear_policy: null buffer");
+    int rc = linear_ready(h, "mdpp_get_linear_policy");
+    if (rc) return rc;
+    return launch_linear_theta_copy(h, theta_dev, false, (hipStream_t)stream);
+}
+
+extern "C" int mdpp_clear_linear_policy(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->lin_ready = false;        // (the buffer stays: a launch queued earlier may still read it)
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_step_n_linear(mdpp_env *h, int K, float *actions_out_dev, float *obs_dev, float *reward_dev,
+                                  uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear: K < 1");
+    if (!actions_out_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear: null buffer");
+    int rc = linear_ready(h, "mdpp_step_n_linear");
+    if (rc) return rc;
+    return launch_continuous_linear(h, ContinuousIO{K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, nullptr, (hipStream_t)stream, nullptr});
+}
+
+extern "C" int mdpp_step_n_linear_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                          double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_summary: K < 1");
+    if (!ret_dev || !len_dev || !episodes_dev || !return_sum_dev || !length_sum_dev) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_summary: null buffer");
+    int rc = linear_ready(h, "mdpp_step_n_linear_summary");
+    if (rc) return rc;
+    const EpisodeSummaryArgs sm{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u};
+    ContinuousIO io{};
+    io.K = K; io.s = (hipStream_t)stream; io.summary = &sm;
+    return launch_continuous_linear(h, io);
+}
+
+// (a dry run: the launcher writes the kernel's name and launches nothing)
+extern "C" const char *mdpp_linear_kernel_name(mdpp_env *h, int K, int summary) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1 || linear_ready(h, "mdpp_linear_kernel_name")) return h->kname;
+    static const EpisodeSummaryArgs none{};
+    ContinuousIO dry{};
+    dry.K = K; dry.name_out = h->kname; dry.summary = summary ? &none : nullptr;
+    (void)launch_continuous_linear(h, dry);
+    return h->kname;
 }
 
 // Python round(v, 15) for |v| <= 1: correctly rounded decimal conversion, like Pillow's rotate().

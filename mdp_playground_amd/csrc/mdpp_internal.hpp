@@ -374,6 +374,11 @@ struct mdpp_env {
     int32_t sched_R, sched_M;
     size_t sched_cap;
     void *d_sched_E, *d_sched_alpha, *d_sched_row, *d_sched_ep;
+    // the linear policy of closed-loop continuous rollouts (mdpp_set_linear_policy; mdpp_continuous_linear.hip): float32 parameters,
+    // entry-major -- entry e = r (D + 1) + c of env i at [e N + i] (lin_per_env) or one shared set at [e]; allocated once for
+    // N D (D + 1) entries
+    void *d_lin_theta;
+    bool lin_per_env, lin_ready;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -596,6 +601,14 @@ int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t 
 int launch_discrete_eval(mdpp_env *h, const DiscreteIO &io);
 // the observation every env shows now, from the state record, to obs [N] (mdpp_discrete_eval.hip)
 int launch_discrete_current_obs(mdpp_env *h, void *obs, hipStream_t s);
+// closed-loop continuous rollout under the handle's linear policy (mdpp_continuous_linear.hip; the step: mdpp_continuous_closed.hpp):
+// why the handle has none (empty: it is served); io.K steps, the actions taken written to io.actions, or with io.summary the
+// summary form (mdpp_continuous_summary_linear.hip); the parameters between the caller's layout and the handle's buffer; the
+// state in every env's record as its observation [N][D]
+std::string continuous_linear_refusal(const mdpp_env *h);
+int launch_continuous_linear(mdpp_env *h, const ContinuousIO &io);
+int launch_linear_theta_copy(mdpp_env *h, float *user, bool to_handle, hipStream_t s);
+int launch_continuous_current_obs(mdpp_env *h, float *obs, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // phase bits: 1 = draw + records, 2 = render (phase == 2 exactly: pipelined, the persistent grid leaves slots

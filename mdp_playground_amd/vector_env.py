@@ -765,6 +765,74 @@ class RLToyVectorEnv:
         name = self._lib.mdpp_policy_kernel_name(self._h, int(K))
         return name.decode() if name else ""
 
+    # ------------------------------------------------------------------ closed-loop continuous rollouts under a linear policy
+    def _linear_theta_arg(self, theta):
+        """theta as a contiguous float32 device tensor and whether it is per-env; ValueError for anything but float32
+        [D, D + 1] or [N, D, D + 1] (numpy or torch, any device), before any device work."""
+        if self.kind != "continuous":
+            raise NotImplementedError("linear-policy rollouts serve continuous envs only (this env is %s)" % self.kind)
+        D, N = self.mdps[0].D, self.num_envs
+        if isinstance(theta, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(theta)) if theta.dtype == np.float32 else None
+        else:
+            t = theta if torch.is_tensor(theta) and theta.dtype == torch.float32 else None
+        if t is None or tuple(t.shape) not in ((D, D + 1), (N, D, D + 1)):
+            raise ValueError(f"set_linear_policy: theta must be float32 of shape ({D}, {D + 1}) or ({N}, {D}, {D + 1})")
+        return t.to(self.device).contiguous(), t.dim() == 3
+
+    def set_linear_policy(self, theta=None):
+        """The handle's linear policy for rollout_linear(): float32 ``theta`` of shape [D, D + 1] -- one policy shared by every
+        env -- or [N, D, D + 1] -- one per env --, numpy or torch on any device; theta[..., r, :D] is row r of W and
+        theta[..., r, D] is b[r] of  a = clip(W o + b, +-action_space_max)  (include/mdpp.h "Linear policies").  Copied on
+        the current stream: parameters are replaced between rollouts without a host round trip.  None clears the policy.
+        Handles the kernel does not serve raise NotImplementedError with the reason."""
+        if theta is None:
+            capi.check(self._lib, self._h, self._lib.mdpp_clear_linear_policy(self._h), "mdpp_clear_linear_policy")
+            self._linear_per_env = None
+            return
+        t, per_env = self._linear_theta_arg(theta)
+        rc = self._lib.mdpp_set_linear_policy(self._h, C.c_void_p(t.data_ptr()), int(per_env), self._stream())
+        self._closed_call(rc, "mdpp_set_linear_policy")
+        self._linear_theta = t           # (kept until the copy queued on the stream has certainly been made)
+        self._linear_per_env = per_env
+
+    def get_linear_policy(self):
+        """The handle's parameters as a device tensor, in the shape they were set in."""
+        if getattr(self, "_linear_per_env", None) is None:
+            raise capi.MdppError("get_linear_policy: no linear policy set")
+        D = self.mdps[0].D
+        out = torch.empty(((self.num_envs,) if self._linear_per_env else ()) + (D, D + 1), dtype=torch.float32, device=self.device)
+        self._closed_call(self._lib.mdpp_get_linear_policy(self._h, C.c_void_p(out.data_ptr()), self._stream()), "mdpp_get_linear_policy")
+        return out
+
+    def alloc_rollout_linear(self, K):
+        """Output buffers of rollout_linear(K): alloc_rollout(K) and the actions, float32 [K, N, D]."""
+        return self.alloc_rollout(K) + (torch.empty((K, self.num_envs, self.mdps[0].D), dtype=torch.float32, device=self.device),)
+
+    def rollout_linear(self, K, out=None, *, summary=None):
+        """K closed-loop steps in ONE kernel launch: at every step each env forms its action from the state it shows with its
+        linear policy and takes it.  Returns (obs, reward, terminated, truncated, actions), each with a leading K axis;
+        rollout(actions) on an identically built env returns the same first four, bit for bit.  ``summary`` (an
+        EpisodeSummary from env.episode_summary()): the same K steps with no [K, N] output -- the summary is updated and
+        returned."""
+        if self.kind != "continuous":
+            raise NotImplementedError("linear-policy rollouts serve continuous envs only (this env is %s)" % self.kind)
+        if summary is not None:
+            if out is not None:
+                raise ValueError("rollout_linear: a summary launch writes no [K, N] output (out must be None)")
+            return self._rollout_summary(self._lib.mdpp_step_n_linear_summary, "mdpp_step_n_linear_summary", int(K), summary)
+        if out is None:
+            out = self.alloc_rollout_linear(int(K))
+        return self._rollout_closed(self._lib.mdpp_step_n_linear, "mdpp_step_n_linear", int(K), out)
+
+    def linear_kernel_name(self, K, summary=False):
+        """Name (with template arguments) of the kernel rollout_linear(K) launches (mdpp_linear_kernel_name; nothing is
+        launched); empty for a handle it does not serve or without a policy."""
+        if self.kind != "continuous":
+            return ""
+        name = self._lib.mdpp_linear_kernel_name(self._h, int(K), int(bool(summary)))
+        return name.decode() if name else ""
+
     # ------------------------------------------------------------------ in-kernel tabular TD learners
     def _learn_check_kind(self):
         if self.kind != "discrete":
