@@ -560,6 +560,61 @@ int mdpp_step_n_linear_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len
                                double *return_sum_dev, int32_t *length_sum_dev, void *stream);
 const char *mdpp_linear_kernel_name(mdpp_env *h, int K, int summary);
 
+/* Linear policy search: one (1+1)-ES per env on the linear policy, inside the launch.  Served: the handles of
+ * mdpp_set_linear_policy that hold PER-ENV parameters [N][D][D + 1].  E = D (D + 1) entries, e = r (D + 1) + c (c == D: b[r]).
+ * The CANDIDATE of env i -- the policy it acts with -- is the handle's own linear-policy buffer (mdpp_get_linear_policy reads
+ * it); everything else is caller-owned DEVICE memory, one struct passed by pointer and copied by value at the call:
+ *   best     float32 [E][N], entry-major (entry e of env i at best[e N + i]): the incumbent
+ *   sigma    float32 [N]: step size per env, >= 0 and finite on entry
+ *   score    float64 [N]: the incumbent's score, -inf at the start
+ *   acc      float64 [N]: sum of the returns of the candidate's finished episodes in this trial
+ *   ret      float64 [N]: running return of the candidate's current episode
+ *   eps      int32 [N]: episodes finished in this trial
+ *   trial    int32 [N]: index of the current trial, 0 at the start
+ *   accepted int32 [N]: accepted trials
+ *   by value: seed (u64), episodes_per_trial T >= 1, sigma_up, sigma_down, sigma_max (float32)
+ * At every step that is not a reset call (the steps the summary rule counts), after the step's float32 reward rw is final:
+ *   ret += (double)rw
+ *   if terminated or truncated:
+ *       acc += ret; ret = 0; eps += 1
+ *       if eps == T:                                   -- the trial ends
+ *           improved = (acc >= score)                  -- false for a NaN acc
+ *           if trial > 0: sigma = improved ? min(sigma * sigma_up, sigma_max) : sigma * sigma_down      (float32)
+ *           if improved: score = acc; best[e] = cand[e] for all e; accepted += 1
+ *           trial += 1; acc = 0; eps = 0
+ *           z[0 .. E-1] = the first E normals of Philox stream (seed, env_id_offset + i, tick = trial, stream id 18)
+ *           cand[e] = best[e] + sigma * z[e]           -- float32 product, rounded, then float32 sum, rounded: no FMA
+ * Trial 0 evaluates the start policy unperturbed; the caller initialises best from the handle's parameters, so a rejected
+ * trial 0 (NaN return) leaves a defined incumbent.  The normals are Philox::normal() in sequence: float32 Box-Muller pairs of
+ * words (0,1) then (2,3) of blocks 0, 1, ....  The search draws from this stream only, on numpy-stream and Philox handles
+ * alike; the env's own streams are never read, so the twin property of "Linear policies" holds: mdpp_step_n on an identically
+ * built handle, fed the actions the search launch wrote, gives the same outputs, state, streams, status words and step counter.
+ * The new candidate acts from the next action on -- the formed, written and ignored action of a next-step-autoreset reset
+ * call included.  With autoreset disabled the rule is driven by the flags of every step, as the summary rule is.  mdpp_reset
+ * does not touch the arrays (a caller that abandons the running episode zeroes ret).
+ * mdpp_step_n_linear_search: K steps in ONE launch, outputs as mdpp_step_n_linear.  mdpp_step_n_linear_search_summary: the same
+ * K steps and the same search with no [K][N] output, keeping the caller's five summary arrays as mdpp_step_n_linear_summary.
+ * Refusals: everything mdpp_step_n_linear refuses, with its text; no linear policy set: MDPP_ESTATE; a shared policy:
+ * MDPP_EUNSUPPORTED ("the search needs one parameter set per env"); episodes_per_trial < 1, a null array, a non-finite or
+ * negative sigma_up / sigma_down, a NaN or negative sigma_max (+inf: no clamp): MDPP_EINVAL.
+ * Kernels: k_continuous_search_rollout / k_continuous_search_summary<D,ORDER,PHILOX,NOISE,PLDS>; the placement rule is the
+ * linear kernels' (PLDS=1: the candidate staged in dynamic LDS, rewritten there at a trial end and written back to the buffer
+ * after the last step for the lanes whose trial moved; PLDS=0: read and rewritten in the buffer; MDPP_OPT_NO_LINEAR_LDS forces
+ * it).  The incumbent is touched at trial ends only.  mdpp_linear_search_kernel_name: as mdpp_linear_kernel_name. */
+typedef struct mdpp_linear_search {
+    float *best, *sigma;
+    double *score, *acc, *ret;
+    int32_t *eps, *trial, *accepted;
+    uint64_t seed;
+    int32_t episodes_per_trial;
+    float sigma_up, sigma_down, sigma_max;
+} mdpp_linear_search;
+int mdpp_step_n_linear_search(mdpp_env *h, int K, const mdpp_linear_search *search, float *actions_out_dev, float *obs_dev,
+                              float *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+int mdpp_step_n_linear_search_summary(mdpp_env *h, int K, const mdpp_linear_search *search, double *ret_dev, int32_t *len_dev,
+                                      int32_t *episodes_dev, double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+const char *mdpp_linear_search_kernel_name(mdpp_env *h, int K, int summary);
+
 /* Per-env noise levels for the learner and evaluation launches.  A handle mdpp_set_learner serves may give each env its own
  * reward-noise sigma and its own transition-noise probability; mdpp_step_n_learn, mdpp_step_n_eval and their _summary forms
  * then run ONE launch over all levels (the kernel's name gains ",NLEV=1"; the learner always in its PE form).
@@ -686,6 +741,10 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   A linear policy (mdpp_step_n_linear / mdpp_step_n_linear_summary): shared or per-env parameters and their placement (PLDS)
  *   go by value; the parameter buffer is READ at replay (mdpp_set_linear_policy with the same per_env between replays, on the
  *   replay's stream).  The policy reads no stream, so only a Philox handle or a delay line in memory needs capture mode.
+ *   A linear policy search (mdpp_step_n_linear_search / _summary): the struct travels BY VALUE -- the eight pointers, seed,
+ *   episodes_per_trial and the three sigma factors are those of the capture --; the eight arrays and the handle's parameter
+ *   buffer (the candidate) are READ AND WRITTEN at replay, so a search goes on across replays.  Its stream (id 18) is keyed by
+ *   the trial index, not by the step counter: it needs capture mode no more than the linear policy does.
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

@@ -60,6 +60,7 @@ EXPORTS = [
     "mdpp_step_n_learn_log",
     "mdpp_set_linear_policy", "mdpp_get_linear_policy", "mdpp_clear_linear_policy", "mdpp_step_n_linear",
     "mdpp_step_n_linear_summary", "mdpp_linear_kernel_name",
+    "mdpp_step_n_linear_search", "mdpp_step_n_linear_search_summary", "mdpp_linear_search_kernel_name",
 ]
 
 
@@ -97,6 +98,16 @@ class MdppGenParams(C.Structure):
         ("diameter", C.c_int32), ("n_term", C.c_int32), ("maximally_connected", C.c_int32), ("repeats", C.c_int32),
         ("total", C.c_uint64), ("n_sel", C.c_uint32), ("n_radices", C.c_int32), ("radices", C.c_uint32 * 16),
         ("rews", C.c_void_p), ("n_rews", C.c_uint32), ("image", C.c_int32), ("seed_dicts", C.c_void_p),
+    ]
+
+
+class MdppLinearSearch(C.Structure):
+    """struct mdpp_linear_search (include/mdpp.h "Linear policy search"): eight device arrays and the search's constants."""
+    _fields_ = [
+        ("best", C.c_void_p), ("sigma", C.c_void_p), ("score", C.c_void_p), ("acc", C.c_void_p), ("ret", C.c_void_p),
+        ("eps", C.c_void_p), ("trial", C.c_void_p), ("accepted", C.c_void_p),
+        ("seed", C.c_uint64), ("episodes_per_trial", C.c_int32),
+        ("sigma_up", C.c_float), ("sigma_down", C.c_float), ("sigma_max", C.c_float),
     ]
 
 
@@ -196,6 +207,10 @@ def load():
     L.mdpp_step_n_linear_summary.argtypes = [vp, i32] + [vp] * 6
     L.mdpp_linear_kernel_name.argtypes = [vp, i32, i32]
     L.mdpp_linear_kernel_name.restype = C.c_char_p
+    L.mdpp_step_n_linear_search.argtypes = [vp, i32, C.POINTER(MdppLinearSearch)] + [vp] * 6
+    L.mdpp_step_n_linear_search_summary.argtypes = [vp, i32, C.POINTER(MdppLinearSearch)] + [vp] * 6
+    L.mdpp_linear_search_kernel_name.argtypes = [vp, i32, i32]
+    L.mdpp_linear_search_kernel_name.restype = C.c_char_p
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]

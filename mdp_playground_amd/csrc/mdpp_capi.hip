@@ -1920,6 +1920,58 @@ extern "C" const char *mdpp_linear_kernel_name(mdpp_env *h, int K, int summary) 
     return h->kname;
 }
 
+// ---- one (1+1)-ES per env on the linear policy (include/mdpp.h "Linear policy search"; mdpp_continuous_search.hip) ----
+// the checks of a search call after linear_ready's: per-env parameters, then (sr != null) the struct
+static int linear_search_ready(mdpp_env *h, const char *what, const mdpp_linear_search *sr, bool need_struct) {
+    int rc = linear_ready(h, what);
+    if (rc) return rc;
+    if (!h->lin_per_env) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": the search needs one parameter set per env");
+    if (!need_struct) return MDPP_OK;
+    if (!sr) return fail(h, MDPP_EINVAL, std::string(what) + ": null search");
+    if (sr->episodes_per_trial < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": episodes_per_trial < 1");
+    if (!sr->best || !sr->sigma || !sr->score || !sr->acc || !sr->ret || !sr->eps || !sr->trial || !sr->accepted)
+        return fail(h, MDPP_EINVAL, std::string(what) + ": null search array");
+    if (!(sr->sigma_up >= 0.0f && sr->sigma_up <= FLT_MAX) || !(sr->sigma_down >= 0.0f && sr->sigma_down <= FLT_MAX))
+        return fail(h, MDPP_EINVAL, std::string(what) + ": sigma_up and sigma_down must be finite and >= 0");
+    if (!(sr->sigma_max >= 0.0f))        // (NaN fails; +inf: no clamp)
+        return fail(h, MDPP_EINVAL, std::string(what) + ": sigma_max must be >= 0 (+inf: no clamp)");
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_step_n_linear_search(mdpp_env *h, int K, const mdpp_linear_search *search, float *actions_out_dev, float *obs_dev,
+                                         float *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_search: K < 1");
+    if (!actions_out_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_search: null buffer");
+    int rc = linear_search_ready(h, "mdpp_step_n_linear_search", search, true);
+    if (rc) return rc;
+    return launch_continuous_search(h, ContinuousIO{K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, nullptr, (hipStream_t)stream, nullptr}, *search);
+}
+
+extern "C" int mdpp_step_n_linear_search_summary(mdpp_env *h, int K, const mdpp_linear_search *search, double *ret_dev, int32_t *len_dev,
+                                                 int32_t *episodes_dev, double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_search_summary: K < 1");
+    if (!ret_dev || !len_dev || !episodes_dev || !return_sum_dev || !length_sum_dev) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_search_summary: null buffer");
+    int rc = linear_search_ready(h, "mdpp_step_n_linear_search_summary", search, true);
+    if (rc) return rc;
+    const EpisodeSummaryArgs sm{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u};
+    ContinuousIO io{};
+    io.K = K; io.s = (hipStream_t)stream; io.summary = &sm;
+    return launch_continuous_search(h, io, *search);
+}
+
+extern "C" const char *mdpp_linear_search_kernel_name(mdpp_env *h, int K, int summary) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1 || linear_search_ready(h, "mdpp_linear_search_kernel_name", nullptr, false)) return h->kname;
+    static const EpisodeSummaryArgs none{};
+    ContinuousIO dry{};
+    dry.K = K; dry.name_out = h->kname; dry.summary = summary ? &none : nullptr;
+    (void)launch_continuous_search(h, dry, mdpp_linear_search{});
+    return h->kname;
+}
+
 // Python round(v, 15) for |v| <= 1: correctly rounded decimal conversion, like Pillow's rotate().
 static double round15(double v) {
     char buf[64];

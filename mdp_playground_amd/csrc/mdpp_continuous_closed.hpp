@@ -1,6 +1,7 @@
 // The closed-loop step of a continuous move_to_a_point env, stated once: K steps of "an agent forms its action from the state
 // the env shows, the env steps" in ONE launch.  k_continuous_linear_rollout / k_continuous_linear_summary
-// (mdpp_continuous_linear.hip) are this body, continuous_closed_rollout, around their Agent; a later agent shares the step.
+// (mdpp_continuous_linear.hip) are this body, continuous_closed_rollout, around their Agent; k_continuous_search_rollout /
+// k_continuous_search_summary (mdpp_continuous_search.hip) around an agent that also searches.
 //
 // The step restates C1-C8 and R2 of k_continuous_step (mdpp_continuous.hip) with its noise branches, on the same lines of the
 // reference's rl_toy_env.py, and leaves out what the closed-loop handles do not have: the line reward, the per-episode noise
@@ -16,6 +17,9 @@
 //   begin(i)              per lane, after the `i >= N` return
 //   act(cur, act_out)     the action of this step from the state in the record (cur: the last observation returned for
 //                         the env); also called on the reset call of a next-step-autoreset env, where it is written and ignored
+//   observe(rw, end)      once per step that is not a reset call, after the step's float32 reward is final; end: the episode
+//                         terminated or was truncated at this step (a same-step reset has already been made: `cur` is the
+//                         new episode's first state).  What it changes acts from the next act() on
 //   finish(i)             per lane, after the last step
 // The agent reads no stream of the env, so the launch leaves the state, every stream, the status words and the step counter
 // where mdpp_step_n fed with the same actions leaves them.
@@ -383,6 +387,7 @@ __device__ __forceinline__ void continuous_closed_rollout(const ContinuousArgs &
         if (next_step) pending = done || truncated;
         if (a.autoreset == MDPP_AUTORESET_SAME_STEP && (done || truncated)) lane_reset();
         const float rw = (float)r.v;
+        agent.observe(rw, done || truncated);
         if constexpr (SUMMARY) {
             s_ret += (double)rw; s_len += 1;
             if (done || truncated) { s_eps += 1; s_rsum += s_ret; s_lsum += s_len; s_ret = 0.0; s_len = 0; }

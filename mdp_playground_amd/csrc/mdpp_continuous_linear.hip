@@ -66,6 +66,7 @@ struct LinearAgent {
             a[r] = acc;
         }
     }
+    __device__ __forceinline__ void observe(float, bool) const {}
     __device__ __forceinline__ void finish(long) const {}
 };
 

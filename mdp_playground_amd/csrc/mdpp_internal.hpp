@@ -37,6 +37,7 @@ constexpr uint32_t kPhiloxPolicyStream = 14;  // discrete: the tabular policy's 
 constexpr uint32_t kPhiloxLearnExploreStream = 15; // discrete: the tabular learner's explore-or-not word, one per tick, keyed by the LEARNER's seed (mdpp_discrete_learn.hip)
 constexpr uint32_t kPhiloxLearnActionStream = 16;  // ... and the word of its exploring action
 constexpr uint32_t kPhiloxLearnUpdateStream = 17;  // ... double Q-learning: the word whose top bit says which table learns (0: A, 1: B)
+constexpr uint32_t kPhiloxLinearSearchStream = 18; // continuous: the linear policy search's normals, keyed by the SEARCH's seed and the TRIAL index (mdpp_continuous_search.hip)
 
 // ---- per-episode noise statistics (cfg.episode_stats; general kernels only) ------------------------------------
 // What the reference accumulates per env object and logs at every reset() (rl_toy_env.py:2231-2247; cleared
@@ -608,6 +609,9 @@ int launch_discrete_current_obs(mdpp_env *h, void *obs, hipStream_t s);
 std::string continuous_linear_refusal(const mdpp_env *h);
 int launch_continuous_linear(mdpp_env *h, const ContinuousIO &io);
 int launch_linear_theta_copy(mdpp_env *h, float *user, bool to_handle, hipStream_t s);
+// ... and with one (1+1)-ES per env on that policy (include/mdpp.h "Linear policy search"; mdpp_continuous_search.hip, the
+// summary form: mdpp_continuous_summary_search.hip): the candidate is the handle's parameter buffer, sr the caller's arrays
+int launch_continuous_search(mdpp_env *h, const ContinuousIO &io, const mdpp_linear_search &sr);
 int launch_continuous_current_obs(mdpp_env *h, float *obs, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);

@@ -29,6 +29,7 @@ import torch
 from . import _capi as capi
 from . import mdp as mdp_mod
 from . import policy as policy_mod
+from .linear_search import LinearSearch
 from .summary import EpisodeLog, EpisodeSummary
 from .spaces import BatchedSpace, BoxSpace, DiscreteSpace, ImageSpace, TupleSpace
 
@@ -809,28 +810,63 @@ class RLToyVectorEnv:
         """Output buffers of rollout_linear(K): alloc_rollout(K) and the actions, float32 [K, N, D]."""
         return self.alloc_rollout(K) + (torch.empty((K, self.num_envs, self.mdps[0].D), dtype=torch.float32, device=self.device),)
 
-    def rollout_linear(self, K, out=None, *, summary=None):
+    def linear_search(self, sigma, *, seed, episodes_per_trial=1, sigma_up=1.0, sigma_down=1.0, sigma_max=float("inf")):
+        """A new LinearSearch (linear_search.py) for rollout_linear(K, search=): one (1+1)-ES per env on the per-env linear policy
+        this handle holds, which becomes each env's trial 0 and first incumbent.  ``sigma``: the step size, a scalar or a float32
+        array [N]; after trial 0 an accepted trial multiplies an env's sigma by ``sigma_up`` (clamped to ``sigma_max``), a
+        rejected one by ``sigma_down``; a trial is ``episodes_per_trial`` whole episodes of the env's own.  ValueError for bad
+        shapes, dtypes or values; NotImplementedError for a shared policy or a handle the kernel does not serve."""
+        if self.kind != "continuous":
+            raise NotImplementedError("linear-policy rollouts serve continuous envs only (this env is %s)" % self.kind)
+        if not self._lib.mdpp_linear_search_kernel_name(self._h, 1, 0):       # (a dry run: the C side's own refusals and their text)
+            msg = (self._lib.mdpp_last_error(self._h) or b"").decode()
+            if "no linear policy set" in msg:
+                raise capi.MdppError(msg)
+            raise NotImplementedError(msg or "linear_search: this handle is not served")
+        return LinearSearch(self.get_linear_policy(), sigma, seed=seed, episodes_per_trial=episodes_per_trial, sigma_up=sigma_up,
+                            sigma_down=sigma_down, sigma_max=sigma_max)
+
+    def _linear_search_arg(self, search, what):
+        if not isinstance(search, LinearSearch):
+            raise ValueError(f"{what}: search must be a LinearSearch (env.linear_search(sigma, seed=...))")
+        search.check(self.num_envs, self.mdps[0].D, self.device, what)
+        return C.byref(search.c_struct())
+
+    def rollout_linear(self, K, out=None, *, summary=None, search=None):
         """K closed-loop steps in ONE kernel launch: at every step each env forms its action from the state it shows with its
         linear policy and takes it.  Returns (obs, reward, terminated, truncated, actions), each with a leading K axis;
         rollout(actions) on an identically built env returns the same first four, bit for bit.  ``summary`` (an
         EpisodeSummary from env.episode_summary()): the same K steps with no [K, N] output -- the summary is updated and
-        returned."""
+        returned.  ``search`` (a LinearSearch from env.linear_search()): every env also runs its (1+1)-ES in the launch --
+        trials end with the env's own episodes, accepted candidates become ``search.best`` and the next candidate replaces the
+        env's parameters (get_linear_policy()); what is returned is the same."""
         if self.kind != "continuous":
             raise NotImplementedError("linear-policy rollouts serve continuous envs only (this env is %s)" % self.kind)
+        K = int(K)
+        if search is not None:
+            what = "mdpp_step_n_linear_search_summary" if summary is not None else "mdpp_step_n_linear_search"
+            sr = self._linear_search_arg(search, what)
+            step_n = getattr(self._lib, what)
+            bound = lambda h, k, *rest: step_n(h, k, sr, *rest)      # (the struct goes before the outputs)
         if summary is not None:
             if out is not None:
                 raise ValueError("rollout_linear: a summary launch writes no [K, N] output (out must be None)")
-            return self._rollout_summary(self._lib.mdpp_step_n_linear_summary, "mdpp_step_n_linear_summary", int(K), summary)
+            if search is not None:
+                return self._rollout_summary(bound, what, K, summary)
+            return self._rollout_summary(self._lib.mdpp_step_n_linear_summary, "mdpp_step_n_linear_summary", K, summary)
         if out is None:
-            out = self.alloc_rollout_linear(int(K))
-        return self._rollout_closed(self._lib.mdpp_step_n_linear, "mdpp_step_n_linear", int(K), out)
+            out = self.alloc_rollout_linear(K)
+        if search is not None:
+            return self._rollout_closed(bound, what, K, out)
+        return self._rollout_closed(self._lib.mdpp_step_n_linear, "mdpp_step_n_linear", K, out)
 
-    def linear_kernel_name(self, K, summary=False):
-        """Name (with template arguments) of the kernel rollout_linear(K) launches (mdpp_linear_kernel_name; nothing is
-        launched); empty for a handle it does not serve or without a policy."""
+    def linear_kernel_name(self, K, summary=False, search=False):
+        """Name (with template arguments) of the kernel rollout_linear(K) launches (mdpp_linear_kernel_name, or with ``search``
+        mdpp_linear_search_kernel_name; nothing is launched); empty for a handle it does not serve or without a policy."""
         if self.kind != "continuous":
             return ""
-        name = self._lib.mdpp_linear_kernel_name(self._h, int(K), int(bool(summary)))
+        fn = self._lib.mdpp_linear_search_kernel_name if search else self._lib.mdpp_linear_kernel_name
+        name = fn(self._h, int(K), int(bool(summary)))
         return name.decode() if name else ""
 
     # ------------------------------------------------------------------ in-kernel tabular TD learners
