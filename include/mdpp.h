@@ -615,6 +615,82 @@ int mdpp_step_n_linear_search_summary(mdpp_env *h, int K, const mdpp_linear_sear
                                       int32_t *episodes_dev, double *return_sum_dev, int32_t *length_sum_dev, void *stream);
 const char *mdpp_linear_search_kernel_name(mdpp_env *h, int K, int summary);
 
+/* Linear policy ES: one antithetic evolution strategy per 64 linear policies, inside the launch.  Served: the handles
+ * mdpp_step_n_linear_search serves (per-env parameters, move_to_a_point, D <= 12, order <= 2) with N % 64 == 0; anything else
+ * is MDPP_EUNSUPPORTED ("the ES needs whole groups of 64 envs"): a population is one full wave.
+ * Group g is the local envs 64g .. 64g+63, G = N / 64.  Member m = i - 64g, pair p = m >> 1, sign s_m = +1 for even m and -1
+ * for odd m.  E = D (D + 1), entry e = r (D + 1) + c, as in the search.
+ * The CANDIDATE of env i is the handle's own linear-policy buffer, as in the search.  Everything else is caller-owned DEVICE
+ * memory in one struct, passed by pointer and copied by value; nothing lives in the handle:
+ *   mean     float32 [E][G], entry-major (entry e of group g at mean[e G + g]): the population means
+ *   sigma    float32 [G]: perturbation scale per group, finite and > 0
+ *   gain     float32 [G]: step per unit of rank-weighted sum (the binding: lr / (sigma * 4032) in float32; the kernel never divides)
+ *   gen      int32 [G]: generation index
+ *   acc      float64 [N]: summed return of the candidate's counted episodes
+ *   ret      float64 [N]: running return of the current counted episode
+ *   fitness  float64 [N]: each member's acc at the last generation end
+ *   eps      int32 [N]: -1: waiting for an episode boundary; 0 .. T-1: counting; T: done, spare episodes ignored
+ *   log_mean float64 [M][G], may be null with M = 0: mean member score of generation j in row j
+ *   by value: seed (u64), episodes_per_member T >= 1, log_rows M
+ * Per env, at every step that is not a reset call, after the step's float32 reward rw is final:
+ *   if 0 <= eps < T:
+ *       ret += (double)rw
+ *   if the episode ended (terminated or truncated):
+ *       if 0 <= eps < T:
+ *           acc += ret; ret = 0; eps += 1
+ *       elif eps == -1:
+ *           eps = 0
+ * Per group, after every step (once all 64 members have completed it, reset calls included) and before any member forms its
+ * next action -- after the last step of a launch too --: if every member has eps == T, the generation ends:
+ *   1. fitness[i] = acc.  The sort key is k_m = isnan(acc) ? -inf : acc.  Ties get the average rank, so that equal scores
+ *      cancel within a pair:
+ *        rank2_m = 2 #{j : k_j < k_m} + #{j != m : k_j == k_m}
+ *        r_m = rank2_m - 63, an integer in [-63, 63].
+ *   2. If gen < M: log_mean[gen][g] = (sum_m acc_m) * (1/64), the sum taken in float64 by the butterfly of point 3.  A NaN
+ *      propagates.
+ *   3. For each entry e in order:
+ *        z0[e] = normal e of Philox stream (seed, env_id_offset + 64g + 2p, tick = gen, stream id 19) -- the even member's
+ *                id, so both members of a pair read the same stream;  z1[e] = the same stream at tick gen + 1.
+ *                The normals are Philox::normal() in sequence, as in the search.
+ *        v_m = (float)r_m * (s_m > 0 ? z0 : -z0)            -- a float32 product
+ *        S = the butterfly sum: for k = 0 .. 5: v = v + shfl_xor(v, 1 << k), in float32.  Float addition is commutative, so
+ *            every lane ends with the same bits.
+ *        mu = mean[e][g] + gain[g] * S                      -- the product rounded, then the sum rounded: no FMA
+ *        t = sigma[g] * z1[e]
+ *        cand_m[e] = s_m > 0 ? mu + t : mu - t
+ *        member 0 stores mean[e][g] = mu
+ *   4. gen += 1; acc = 0; ret = 0.  eps = 0 for a member whose step just completed was not a reset call and ended an
+ *      episode; eps = -1 otherwise: a candidate is judged on whole episodes only.
+ * The new candidates act from the next action on, the ignored action of a reset call included.
+ * mdpp_linear_es_init writes the candidates of the current gen into the handle's buffer -- mean +- sigma z, z at tick = gen
+ * (t = sigma z; s_m > 0 ? mean + t : mean - t) -- and sets acc = ret = 0 and eps = 0; one small kernel on `stream`.  Call it
+ * after mdpp_reset; it is also how a search continues from saved arrays.
+ * The ES reads no stream of the env: the twin property of "Linear policies" holds.  A member whose env stays in
+ * MDPP_STATUS_BAD_ACTION (a NaN candidate) never ends an episode, so its group's generation stands still; the other groups go
+ * on.  With autoreset disabled the rule follows every step's flags, as in the search.  mdpp_reset touches nothing.
+ * mdpp_step_n_linear_es / mdpp_step_n_linear_es_summary: K steps in ONE launch, outputs as mdpp_step_n_linear /
+ * mdpp_step_n_linear_summary.  Refusals: everything the search refuses, with its text; a shared policy or N % 64 != 0:
+ * MDPP_EUNSUPPORTED; a null array (log_mean with M = 0 excepted), T < 1, M < 0: MDPP_EINVAL.  sigma and gain are the binding's
+ * to validate.
+ * Kernels: k_continuous_es_rollout / k_continuous_es_summary<D,ORDER,PHILOX,NOISE,PLDS>, the placement rule the search's
+ * (MDPP_OPT_NO_LINEAR_LDS forces PLDS=0).  The cross-lane work is ballots and shuffles: no LDS, no barrier.
+ * mdpp_linear_es_kernel_name: as mdpp_linear_kernel_name. */
+typedef struct mdpp_linear_es {
+    float *mean, *sigma, *gain;
+    int32_t *gen;
+    double *acc, *ret, *fitness;
+    int32_t *eps;
+    double *log_mean;
+    uint64_t seed;
+    int32_t episodes_per_member, log_rows;
+} mdpp_linear_es;
+int mdpp_linear_es_init(mdpp_env *h, const mdpp_linear_es *es, void *stream);
+int mdpp_step_n_linear_es(mdpp_env *h, int K, const mdpp_linear_es *es, float *actions_out_dev, float *obs_dev,
+                          float *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+int mdpp_step_n_linear_es_summary(mdpp_env *h, int K, const mdpp_linear_es *es, double *ret_dev, int32_t *len_dev,
+                                  int32_t *episodes_dev, double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+const char *mdpp_linear_es_kernel_name(mdpp_env *h, int K, int summary);
+
 /* Per-env noise levels for the learner and evaluation launches.  A handle mdpp_set_learner serves may give each env its own
  * reward-noise sigma and its own transition-noise probability; mdpp_step_n_learn, mdpp_step_n_eval and their _summary forms
  * then run ONE launch over all levels (the kernel's name gains ",NLEV=1"; the learner always in its PE form).
@@ -745,6 +821,9 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   episodes_per_trial and the three sigma factors are those of the capture --; the eight arrays and the handle's parameter
  *   buffer (the candidate) are READ AND WRITTEN at replay, so a search goes on across replays.  Its stream (id 18) is keyed by
  *   the trial index, not by the step counter: it needs capture mode no more than the linear policy does.
+ *   A linear policy ES (mdpp_step_n_linear_es / _summary): likewise -- the nine pointers, seed, episodes_per_member and
+ *   log_rows are those of the capture; the arrays and the candidates are read and written at replay; stream id 19 is keyed
+ *   by the generation index.
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

@@ -61,6 +61,7 @@ EXPORTS = [
     "mdpp_set_linear_policy", "mdpp_get_linear_policy", "mdpp_clear_linear_policy", "mdpp_step_n_linear",
     "mdpp_step_n_linear_summary", "mdpp_linear_kernel_name",
     "mdpp_step_n_linear_search", "mdpp_step_n_linear_search_summary", "mdpp_linear_search_kernel_name",
+    "mdpp_linear_es_init", "mdpp_step_n_linear_es", "mdpp_step_n_linear_es_summary", "mdpp_linear_es_kernel_name",
 ]
 
 
@@ -108,6 +109,15 @@ class MdppLinearSearch(C.Structure):
         ("eps", C.c_void_p), ("trial", C.c_void_p), ("accepted", C.c_void_p),
         ("seed", C.c_uint64), ("episodes_per_trial", C.c_int32),
         ("sigma_up", C.c_float), ("sigma_down", C.c_float), ("sigma_max", C.c_float),
+    ]
+
+
+class MdppLinearEs(C.Structure):
+    """struct mdpp_linear_es (include/mdpp.h "Linear policy ES"): nine device arrays and the ES's constants."""
+    _fields_ = [
+        ("mean", C.c_void_p), ("sigma", C.c_void_p), ("gain", C.c_void_p), ("gen", C.c_void_p), ("acc", C.c_void_p),
+        ("ret", C.c_void_p), ("fitness", C.c_void_p), ("eps", C.c_void_p), ("log_mean", C.c_void_p),
+        ("seed", C.c_uint64), ("episodes_per_member", C.c_int32), ("log_rows", C.c_int32),
     ]
 
 
@@ -211,6 +221,11 @@ def load():
     L.mdpp_step_n_linear_search_summary.argtypes = [vp, i32, C.POINTER(MdppLinearSearch)] + [vp] * 6
     L.mdpp_linear_search_kernel_name.argtypes = [vp, i32, i32]
     L.mdpp_linear_search_kernel_name.restype = C.c_char_p
+    L.mdpp_linear_es_init.argtypes = [vp, C.POINTER(MdppLinearEs), vp]
+    L.mdpp_step_n_linear_es.argtypes = [vp, i32, C.POINTER(MdppLinearEs)] + [vp] * 6
+    L.mdpp_step_n_linear_es_summary.argtypes = [vp, i32, C.POINTER(MdppLinearEs)] + [vp] * 6
+    L.mdpp_linear_es_kernel_name.argtypes = [vp, i32, i32]
+    L.mdpp_linear_es_kernel_name.restype = C.c_char_p
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]

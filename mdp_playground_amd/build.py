@@ -33,6 +33,7 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_discrete_learn_double_pe_pm_nlev_sched.hip", "mdpp_discrete_learn_double_pe_pm_nlev_sched_summary.hip",
            "mdpp_continuous.hip", "mdpp_continuous_line8.hip", "mdpp_continuous_linear.hip", "mdpp_continuous_summary_linear.hip",
            "mdpp_continuous_search.hip", "mdpp_continuous_summary_search.hip",
+           "mdpp_continuous_es.hip", "mdpp_continuous_summary_es.hip",
            "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
            "mdpp_generate.hip"]
 HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdpp_pcg64_limbs.inc", "np_ziggurat_tables.inc",
@@ -46,7 +47,9 @@ INCLUDED_SOURCES = {"mdpp_discrete_lean.hip": ["mdpp_discrete_lean_e.inc"], "mdp
                     "mdpp_continuous_linear.hip": ["mdpp_continuous_closed.hpp"],
                     "mdpp_continuous_summary_linear.hip": ["mdpp_continuous_linear.hip", "mdpp_continuous_closed.hpp"],
                     "mdpp_continuous_search.hip": ["mdpp_continuous_closed.hpp"],
-                    "mdpp_continuous_summary_search.hip": ["mdpp_continuous_search.hip", "mdpp_continuous_closed.hpp"]}
+                    "mdpp_continuous_summary_search.hip": ["mdpp_continuous_search.hip", "mdpp_continuous_closed.hpp"],
+                    "mdpp_continuous_es.hip": ["mdpp_continuous_closed.hpp"],
+                    "mdpp_continuous_summary_es.hip": ["mdpp_continuous_es.hip", "mdpp_continuous_closed.hpp"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # The GENERAL kernels keep whole state vectors in registers and spill (k_continuous_step<DMAX=32, OMAX=4>: 3 KB of scratch per lane).
@@ -62,7 +65,8 @@ EXTRA_FLAGS = {s: SPILL_SAFE for s in ("mdpp_continuous.hip", "mdpp_continuous_l
 # (mdpp_continuous_linear.hip, mdpp_continuous_summary_linear.hip keep the default: their kernels spill SGPRs but no VGPR -- none is exposed by the rule of
 #  tests/spill_exposed.py, whose pinned list of flagged units tests/test_kernel_spills.py holds this table to;
 #  profiles/linear_rollout_resources.txt has every instantiation, tests/test_gpu_linear_rollout.py runs every lane against a twin;
-#  mdpp_continuous_search.hip, mdpp_continuous_summary_search.hip likewise: profiles/linear_search_resources.txt, tests/test_gpu_linear_search.py)
+#  mdpp_continuous_search.hip, mdpp_continuous_summary_search.hip likewise: profiles/linear_search_resources.txt, tests/test_gpu_linear_search.py;
+#  mdpp_continuous_es.hip, mdpp_continuous_summary_es.hip likewise: profiles/linear_es_resources.txt, tests/test_gpu_linear_es.py)
 
 
 def _hipcc():
@@ -130,7 +134,7 @@ def build(force=False, verbose=False):
     if jobs:
         # the long compiles first (template-heavy kernels: 1.5-3 min each), as many at once as there are cores to spare
         heavy = ("mdpp_continuous_fast", "mdpp_discrete_lean", "mdpp_discrete_quiet", "mdpp_grid", "mdpp_continuous.", "mdpp_continuous_step1", "mdpp_continuous_linear", "mdpp_continuous_summary_linear",
-                 "mdpp_continuous_search", "mdpp_continuous_summary_search")
+                 "mdpp_continuous_search", "mdpp_continuous_summary_search", "mdpp_continuous_es", "mdpp_continuous_summary_es")
         jobs.sort(key=lambda c: next((k for k, h in enumerate(heavy) if h in c[-3]), len(heavy)))
         with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), (os.cpu_count() or 4) - 1, 7))) as ex:
             for out in ex.map(run, jobs):

@@ -1972,6 +1972,62 @@ extern "C" const char *mdpp_linear_search_kernel_name(mdpp_env *h, int K, int su
     return h->kname;
 }
 
+// ---- one antithetic ES per 64 linear policies (include/mdpp.h "Linear policy ES"; mdpp_continuous_es.hip) ----
+// the checks of an ES call after the search's own: whole groups of 64 envs, then (need_struct) the struct
+static int linear_es_ready(mdpp_env *h, const char *what, const mdpp_linear_es *es, bool need_struct) {
+    int rc = linear_search_ready(h, what, nullptr, false);
+    if (rc) return rc;
+    if (h->cfg.num_envs % 64 != 0) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": the ES needs whole groups of 64 envs");
+    if (!need_struct) return MDPP_OK;
+    if (!es) return fail(h, MDPP_EINVAL, std::string(what) + ": null es");
+    if (es->episodes_per_member < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": episodes_per_member < 1");
+    if (es->log_rows < 0) return fail(h, MDPP_EINVAL, std::string(what) + ": log_rows < 0");
+    if (!es->mean || !es->sigma || !es->gain || !es->gen || !es->acc || !es->ret || !es->fitness || !es->eps || (es->log_rows > 0 && !es->log_mean))
+        return fail(h, MDPP_EINVAL, std::string(what) + ": null es array");
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_linear_es_init(mdpp_env *h, const mdpp_linear_es *es, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    int rc = linear_es_ready(h, "mdpp_linear_es_init", es, true);
+    if (rc) return rc;
+    return launch_linear_es_init(h, *es, (hipStream_t)stream);
+}
+
+extern "C" int mdpp_step_n_linear_es(mdpp_env *h, int K, const mdpp_linear_es *es, float *actions_out_dev, float *obs_dev,
+                                     float *reward_dev, uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_es: K < 1");
+    if (!actions_out_dev || !obs_dev || !reward_dev || !terminated_dev || !truncated_dev) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_es: null buffer");
+    int rc = linear_es_ready(h, "mdpp_step_n_linear_es", es, true);
+    if (rc) return rc;
+    return launch_continuous_es(h, ContinuousIO{K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, nullptr, (hipStream_t)stream, nullptr}, *es);
+}
+
+extern "C" int mdpp_step_n_linear_es_summary(mdpp_env *h, int K, const mdpp_linear_es *es, double *ret_dev, int32_t *len_dev,
+                                             int32_t *episodes_dev, double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_es_summary: K < 1");
+    if (!ret_dev || !len_dev || !episodes_dev || !return_sum_dev || !length_sum_dev) return fail(h, MDPP_EINVAL, "mdpp_step_n_linear_es_summary: null buffer");
+    int rc = linear_es_ready(h, "mdpp_step_n_linear_es_summary", es, true);
+    if (rc) return rc;
+    const EpisodeSummaryArgs sm{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u};
+    ContinuousIO io{};
+    io.K = K; io.s = (hipStream_t)stream; io.summary = &sm;
+    return launch_continuous_es(h, io, *es);
+}
+
+extern "C" const char *mdpp_linear_es_kernel_name(mdpp_env *h, int K, int summary) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1 || linear_es_ready(h, "mdpp_linear_es_kernel_name", nullptr, false)) return h->kname;
+    static const EpisodeSummaryArgs none{};
+    ContinuousIO dry{};
+    dry.K = K; dry.name_out = h->kname; dry.summary = summary ? &none : nullptr;
+    (void)launch_continuous_es(h, dry, mdpp_linear_es{});
+    return h->kname;
+}
+
 // Python round(v, 15) for |v| <= 1: correctly rounded decimal conversion, like Pillow's rotate().
 static double round15(double v) {
     char buf[64];

@@ -38,6 +38,7 @@ constexpr uint32_t kPhiloxLearnExploreStream = 15; // discrete: the tabular lear
 constexpr uint32_t kPhiloxLearnActionStream = 16;  // ... and the word of its exploring action
 constexpr uint32_t kPhiloxLearnUpdateStream = 17;  // ... double Q-learning: the word whose top bit says which table learns (0: A, 1: B)
 constexpr uint32_t kPhiloxLinearSearchStream = 18; // continuous: the linear policy search's normals, keyed by the SEARCH's seed and the TRIAL index (mdpp_continuous_search.hip)
+constexpr uint32_t kPhiloxLinearEsStream = 19;     // continuous: the linear policy ES's normals, keyed by the ES's seed, the PAIR's even env id and the GENERATION index (mdpp_continuous_es.hip)
 
 // ---- per-episode noise statistics (cfg.episode_stats; general kernels only) ------------------------------------
 // What the reference accumulates per env object and logs at every reset() (rl_toy_env.py:2231-2247; cleared
@@ -612,6 +613,10 @@ int launch_linear_theta_copy(mdpp_env *h, float *user, bool to_handle, hipStream
 // ... and with one (1+1)-ES per env on that policy (include/mdpp.h "Linear policy search"; mdpp_continuous_search.hip, the
 // summary form: mdpp_continuous_summary_search.hip): the candidate is the handle's parameter buffer, sr the caller's arrays
 int launch_continuous_search(mdpp_env *h, const ContinuousIO &io, const mdpp_linear_search &sr);
+// ... and with one antithetic ES per wave of 64 such policies (include/mdpp.h "Linear policy ES"; mdpp_continuous_es.hip, the
+// summary form: mdpp_continuous_summary_es.hip); launch_linear_es_init: the candidates of the current generation
+int launch_continuous_es(mdpp_env *h, const ContinuousIO &io, const mdpp_linear_es &es);
+int launch_linear_es_init(mdpp_env *h, const mdpp_linear_es &es, hipStream_t s);
 int launch_continuous_current_obs(mdpp_env *h, float *obs, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);

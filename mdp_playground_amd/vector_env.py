@@ -29,6 +29,7 @@ import torch
 from . import _capi as capi
 from . import mdp as mdp_mod
 from . import policy as policy_mod
+from .linear_es import LinearES
 from .linear_search import LinearSearch
 from .summary import EpisodeLog, EpisodeSummary
 from .spaces import BatchedSpace, BoxSpace, DiscreteSpace, ImageSpace, TupleSpace
@@ -832,40 +833,89 @@ class RLToyVectorEnv:
         search.check(self.num_envs, self.mdps[0].D, self.device, what)
         return C.byref(search.c_struct())
 
-    def rollout_linear(self, K, out=None, *, summary=None, search=None):
+    def linear_es(self, mean_theta, sigma, lr, *, seed, episodes_per_member=1, log_generations=0):
+        """A new LinearES (linear_es.py) for rollout_linear(K, es=): one antithetic ES per group of 64 envs on the per-env linear
+        policy this handle holds.  ``mean_theta``: the start means, float32 [G, D, D + 1] with G = N / 64, or one [D, D + 1]
+        start for every group (numpy or torch); ``sigma`` (> 0) and ``lr`` (>= 0): scalars or float32 arrays [G]; a member is
+        judged on ``episodes_per_member`` whole episodes; ``log_generations`` rows of the per-generation mean score are kept.
+        The candidates of generation 0 are written into the handle's parameters (mdpp_linear_es_init): call it after
+        reset().  ValueError for bad shapes, dtypes or values; NotImplementedError for a shared policy, N % 64 != 0 or a
+        handle the kernel does not serve."""
+        if self.kind != "continuous":
+            raise NotImplementedError("linear-policy rollouts serve continuous envs only (this env is %s)" % self.kind)
+        if not self._lib.mdpp_linear_es_kernel_name(self._h, 1, 0):           # (a dry run: the C side's own refusals and their text)
+            msg = (self._lib.mdpp_last_error(self._h) or b"").decode()
+            if "no linear policy set" in msg:
+                raise capi.MdppError(msg)
+            raise NotImplementedError(msg or "linear_es: this handle is not served")
+        D, G = self.mdps[0].D, self.num_envs // 64
+        m = torch.from_numpy(np.ascontiguousarray(mean_theta)) if isinstance(mean_theta, np.ndarray) else mean_theta
+        if not (torch.is_tensor(m) and m.dtype == torch.float32 and tuple(m.shape) in ((D, D + 1), (G, D, D + 1))):
+            raise ValueError(f"linear_es: mean_theta must be float32 of shape ({D}, {D + 1}) or ({G}, {D}, {D + 1})")
+        if m.dim() == 2:
+            m = m.unsqueeze(0).expand(G, D, D + 1)
+        es = LinearES(m.to(self.device).contiguous(), sigma, lr, seed=seed, episodes_per_member=episodes_per_member,
+                      log_generations=log_generations)
+        self.linear_es_init(es)
+        return es
+
+    def linear_es_init(self, es):
+        """mdpp_linear_es_init: write the candidates of ``es``'s current generation (mean +- sigma z) into the handle's
+        parameters and start every member on a fresh episode count (acc = ret = 0, eps = 0), on the current stream.  After
+        reset(), and after LinearES.load_state_dict()."""
+        sr = self._linear_es_arg(es, "mdpp_linear_es_init")
+        self._closed_call(self._lib.mdpp_linear_es_init(self._h, sr, self._stream()), "mdpp_linear_es_init")
+
+    def _linear_es_arg(self, es, what):
+        if not isinstance(es, LinearES):
+            raise ValueError(f"{what}: es must be a LinearES (env.linear_es(mean_theta, sigma, lr, seed=...))")
+        es.check(self.num_envs, self.mdps[0].D, self.device, what)
+        return C.byref(es.c_struct())
+
+    def rollout_linear(self, K, out=None, *, summary=None, search=None, es=None):
         """K closed-loop steps in ONE kernel launch: at every step each env forms its action from the state it shows with its
         linear policy and takes it.  Returns (obs, reward, terminated, truncated, actions), each with a leading K axis;
         rollout(actions) on an identically built env returns the same first four, bit for bit.  ``summary`` (an
         EpisodeSummary from env.episode_summary()): the same K steps with no [K, N] output -- the summary is updated and
         returned.  ``search`` (a LinearSearch from env.linear_search()): every env also runs its (1+1)-ES in the launch --
         trials end with the env's own episodes, accepted candidates become ``search.best`` and the next candidate replaces the
-        env's parameters (get_linear_policy()); what is returned is the same."""
+        env's parameters (get_linear_policy()); what is returned is the same.  ``es`` (a LinearES from env.linear_es()): every
+        group of 64 envs runs one antithetic ES in the launch -- ``es.mean`` moves at every generation end and the next
+        candidates replace the envs' parameters; exclusive with ``search``."""
         if self.kind != "continuous":
             raise NotImplementedError("linear-policy rollouts serve continuous envs only (this env is %s)" % self.kind)
+        if search is not None and es is not None:
+            raise ValueError("rollout_linear: search and es are exclusive")
         K = int(K)
-        if search is not None:
-            what = "mdpp_step_n_linear_search_summary" if summary is not None else "mdpp_step_n_linear_search"
-            sr = self._linear_search_arg(search, what)
+        agent = search is not None or es is not None
+        if agent:
+            stem = "mdpp_step_n_linear_search" if search is not None else "mdpp_step_n_linear_es"
+            what = stem + "_summary" if summary is not None else stem
+            sr = self._linear_search_arg(search, what) if search is not None else self._linear_es_arg(es, what)
             step_n = getattr(self._lib, what)
             bound = lambda h, k, *rest: step_n(h, k, sr, *rest)      # (the struct goes before the outputs)
         if summary is not None:
             if out is not None:
                 raise ValueError("rollout_linear: a summary launch writes no [K, N] output (out must be None)")
-            if search is not None:
+            if agent:
                 return self._rollout_summary(bound, what, K, summary)
             return self._rollout_summary(self._lib.mdpp_step_n_linear_summary, "mdpp_step_n_linear_summary", K, summary)
         if out is None:
             out = self.alloc_rollout_linear(K)
-        if search is not None:
+        if agent:
             return self._rollout_closed(bound, what, K, out)
         return self._rollout_closed(self._lib.mdpp_step_n_linear, "mdpp_step_n_linear", K, out)
 
-    def linear_kernel_name(self, K, summary=False, search=False):
-        """Name (with template arguments) of the kernel rollout_linear(K) launches (mdpp_linear_kernel_name, or with ``search``
-        mdpp_linear_search_kernel_name; nothing is launched); empty for a handle it does not serve or without a policy."""
+    def linear_kernel_name(self, K, summary=False, search=False, es=False):
+        """Name (with template arguments) of the kernel rollout_linear(K) launches (mdpp_linear_kernel_name, with ``search``
+        mdpp_linear_search_kernel_name, with ``es`` mdpp_linear_es_kernel_name; nothing is launched); empty for a handle it
+        does not serve or without a policy."""
         if self.kind != "continuous":
             return ""
-        fn = self._lib.mdpp_linear_search_kernel_name if search else self._lib.mdpp_linear_kernel_name
+        if search and es:
+            raise ValueError("linear_kernel_name: search and es are exclusive")
+        fn = (self._lib.mdpp_linear_search_kernel_name if search else self._lib.mdpp_linear_es_kernel_name if es
+              else self._lib.mdpp_linear_kernel_name)
         name = fn(self._h, int(K), int(bool(summary)))
         return name.decode() if name else ""
 
