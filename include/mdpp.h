@@ -560,6 +560,34 @@ int mdpp_step_n_linear_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len
                                double *return_sum_dev, int32_t *length_sum_dev, void *stream);
 const char *mdpp_linear_kernel_name(mdpp_env *h, int K, int summary);
 
+/* Linear policies with memory.  A linear policy has a HISTORY, 1 (the policy above, unchanged in every bit and kernel name) or 2.
+ * With history = 2 theta is float32 [D][2 D + 1] (shared) or [N][D][2 D + 1] (per env): theta[.., r, c] = W[r][c] for c < D,
+ * theta[.., r, D + c] = V[r][c] for c < D, theta[.., r, 2 D] = b[r]; entry number e = r (2 D + 1) + c, E = D (2 D + 1).
+ * At every step env i reads o exactly as "Linear policies" defines it, and p:
+ *   p = o  when the env's count of steps taken in its current episode -- word meta.x of its record,
+ *          total_transitions_episode -- is 0 at the moment the action is formed;
+ *   p = the env's MEMORY otherwise: the o it read the last time it formed an action.
+ * After the action is formed the memory becomes o, on the reset call of a next-step-autoreset env too (where the action is
+ * formed, written and ignored as above).  Per row
+ *   acc = b[r];  for c = 0 .. D-1: acc = acc + W[r][c] * o[c];  then for c = 0 .. D-1: acc = acc + V[r][c] * p[c]
+ * every product and every sum rounded to float32, no fused multiply-add; then the clamp and the NaN rule of "Linear policies".
+ * The memory is a float32 [D][N] buffer of the handle.  It persists across launches.  Setting a history = 2 policy sets every
+ * env's memory to its current state, and so does mdpp_set_state_continuous; mdpp_reset and a masked reset need nothing (the
+ * step count is 0).  The policy reads no stream: the twin property of "Linear policies" holds as it stands.
+ * mdpp_set_linear_policy_history: history = 1 is mdpp_set_linear_policy; history = 2 as above; anything else MDPP_EINVAL.  The
+ * first history = 2 policy of a handle allocates the larger parameter buffer (it waits for the launches queued on the old one).
+ * mdpp_linear_policy_history: the history of the policy in force (0: none).  mdpp_linear_memory: set == 0 writes the memory to
+ * buf_dev as float32 [N][D], set != 0 replaces it from there, on `stream`; MDPP_ESTATE unless a history = 2 policy is in force.
+ * Every launch, summary, search, ES and kernel-name entry point serves the handle as it stands: E and the act are those of the
+ * history in force, and the [E][.] arrays of mdpp_linear_search and mdpp_linear_es are simply longer -- they are the CALLER's and
+ * the library cannot see their size: after a change of history they must hold E rows for the history now in force (the normal of entry e is
+ * the e-th draw of the same streams 18 and 19).  Kernels: the HIST = 2 forms of the six kernels, named with ",HIST=2" after
+ * everything else (k_continuous_linear_rollout<D=4,ORDER=2,PHILOX=1,NOISE=0,PLDS=1,HIST=2>); PLDS is decided as before, on
+ * 256 E 4 bytes.  The memory is not staged: the V pass reads it from the buffer and the act overwrites it, 8 D bytes per env step. */
+int mdpp_set_linear_policy_history(mdpp_env *h, const float *theta_dev, int per_env, int history, void *stream);
+int mdpp_linear_policy_history(mdpp_env *h);
+int mdpp_linear_memory(mdpp_env *h, float *buf_dev, int set, void *stream);
+
 /* Linear policy search: one (1+1)-ES per env on the linear policy, inside the launch.  Served: the handles of
  * mdpp_set_linear_policy that hold PER-ENV parameters [N][D][D + 1].  E = D (D + 1) entries, e = r (D + 1) + c (c == D: b[r]).
  * The CANDIDATE of env i -- the policy it acts with -- is the handle's own linear-policy buffer (mdpp_get_linear_policy reads
@@ -817,6 +845,10 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   A linear policy (mdpp_step_n_linear / mdpp_step_n_linear_summary): shared or per-env parameters and their placement (PLDS)
  *   go by value; the parameter buffer is READ at replay (mdpp_set_linear_policy with the same per_env between replays, on the
  *   replay's stream).  The policy reads no stream, so only a Philox handle or a delay line in memory needs capture mode.
+ *   A linear policy with memory (history = 2): the history goes by value too (the same history between replays); the memory
+ *   buffer is READ AND WRITTEN at replay, in the search and ES launches alike, so p crosses replays as it crosses launches.
+ *   The FIRST history = 2 policy of a handle frees the parameter buffer and allocates the larger one: every graph captured
+ *   from a linear, search or ES launch of that handle before it holds the old address and must be captured again.
  *   A linear policy search (mdpp_step_n_linear_search / _summary): the struct travels BY VALUE -- the eight pointers, seed,
  *   episodes_per_trial and the three sigma factors are those of the capture --; the eight arrays and the handle's parameter
  *   buffer (the candidate) are READ AND WRITTEN at replay, so a search goes on across replays.  Its stream (id 18) is keyed by

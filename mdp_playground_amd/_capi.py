@@ -62,6 +62,7 @@ EXPORTS = [
     "mdpp_step_n_linear_summary", "mdpp_linear_kernel_name",
     "mdpp_step_n_linear_search", "mdpp_step_n_linear_search_summary", "mdpp_linear_search_kernel_name",
     "mdpp_linear_es_init", "mdpp_step_n_linear_es", "mdpp_step_n_linear_es_summary", "mdpp_linear_es_kernel_name",
+    "mdpp_set_linear_policy_history", "mdpp_linear_policy_history", "mdpp_linear_memory",
 ]
 
 
@@ -226,6 +227,9 @@ def load():
     L.mdpp_step_n_linear_es_summary.argtypes = [vp, i32, C.POINTER(MdppLinearEs)] + [vp] * 6
     L.mdpp_linear_es_kernel_name.argtypes = [vp, i32, i32]
     L.mdpp_linear_es_kernel_name.restype = C.c_char_p
+    L.mdpp_set_linear_policy_history.argtypes = [vp, vp, i32, i32, vp]
+    L.mdpp_linear_policy_history.argtypes = [vp]
+    L.mdpp_linear_memory.argtypes = [vp, vp, i32, vp]
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]

@@ -34,22 +34,22 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_continuous.hip", "mdpp_continuous_line8.hip", "mdpp_continuous_linear.hip", "mdpp_continuous_summary_linear.hip",
            "mdpp_continuous_search.hip", "mdpp_continuous_summary_search.hip",
            "mdpp_continuous_es.hip", "mdpp_continuous_summary_es.hip",
+           "mdpp_continuous_linear_h2.hip", "mdpp_continuous_summary_linear_h2.hip", "mdpp_continuous_search_h2.hip",
+           "mdpp_continuous_summary_search_h2.hip", "mdpp_continuous_es_h2.hip", "mdpp_continuous_summary_es_h2.hip",
            "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
            "mdpp_generate.hip"]
 HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdpp_pcg64_limbs.inc", "np_ziggurat_tables.inc",
            os.path.join("..", "..", "include", "mdpp.h")]
+_CLOSED_DEPS = ["mdpp_continuous_closed.hpp", "mdpp_linear_history.hpp"]
 _LEAN_DEPS = ["mdpp_discrete_lean.hip", "mdpp_discrete_lean_e.inc"]      # (the kernel and its E role, included into its body)
 INCLUDED_SOURCES = {"mdpp_discrete_lean.hip": ["mdpp_discrete_lean_e.inc"], "mdpp_discrete_wide.hip": ["mdpp_discrete.hip"], "mdpp_discrete_long.hip": ["mdpp_discrete.hip"], "mdpp_discrete_lean_next.hip": _LEAN_DEPS, "mdpp_discrete_lean_noise.hip": _LEAN_DEPS, "mdpp_discrete_lean_npnoise.hip": _LEAN_DEPS,
                     "mdpp_continuous_line8.hip": ["mdpp_continuous.hip"], "mdpp_continuous_step1.hip": ["mdpp_continuous_fast.hip"], "mdpp_discrete_quiet_nu.hip": ["mdpp_discrete_quiet.hip"],   # a .hip that #includes another one
                     # ... or a header of its own
                     **{u: ["mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith("mdpp_discrete_learn")},
                     **{u: ["mdpp_discrete_eval.hpp"] for u in SOURCES if u.startswith("mdpp_discrete_eval")},
-                    "mdpp_continuous_linear.hip": ["mdpp_continuous_closed.hpp"],
-                    "mdpp_continuous_summary_linear.hip": ["mdpp_continuous_linear.hip", "mdpp_continuous_closed.hpp"],
-                    "mdpp_continuous_search.hip": ["mdpp_continuous_closed.hpp"],
-                    "mdpp_continuous_summary_search.hip": ["mdpp_continuous_search.hip", "mdpp_continuous_closed.hpp"],
-                    "mdpp_continuous_es.hip": ["mdpp_continuous_closed.hpp"],
-                    "mdpp_continuous_summary_es.hip": ["mdpp_continuous_es.hip", "mdpp_continuous_closed.hpp"]}
+                    # the closed-loop continuous units: the step and the history-2 act; the _summary and _h2 units include their family's .hip
+                    **{f"mdpp_continuous_{pre}{fam}{suf}.hip": ([f"mdpp_continuous_{fam}.hip"] if pre or suf else []) + _CLOSED_DEPS
+                       for fam in ("linear", "search", "es") for pre in ("", "summary_") for suf in ("", "_h2")}}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 # The GENERAL kernels keep whole state vectors in registers and spill (k_continuous_step<DMAX=32, OMAX=4>: 3 KB of scratch per lane).
@@ -66,7 +66,9 @@ EXTRA_FLAGS = {s: SPILL_SAFE for s in ("mdpp_continuous.hip", "mdpp_continuous_l
 #  tests/spill_exposed.py, whose pinned list of flagged units tests/test_kernel_spills.py holds this table to;
 #  profiles/linear_rollout_resources.txt has every instantiation, tests/test_gpu_linear_rollout.py runs every lane against a twin;
 #  mdpp_continuous_search.hip, mdpp_continuous_summary_search.hip likewise: profiles/linear_search_resources.txt, tests/test_gpu_linear_search.py;
-#  mdpp_continuous_es.hip, mdpp_continuous_summary_es.hip likewise: profiles/linear_es_resources.txt, tests/test_gpu_linear_es.py)
+#  mdpp_continuous_es.hip, mdpp_continuous_summary_es.hip likewise: profiles/linear_es_resources.txt, tests/test_gpu_linear_es.py;
+#  the six *_h2.hip units -- the same kernels under a policy with memory -- likewise: profiles/linear_history_resources.txt,
+#  tests/test_gpu_linear_history.py, tests/test_gpu_linear_history_search.py)
 
 
 def _hipcc():

@@ -59,7 +59,7 @@ static void free_all(mdpp_env *h) {
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
                     h->d_img_near, h->d_s1_blob, h->d_lean_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
                     h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E, h->d_sched_E, h->d_sched_alpha, h->d_sched_row, h->d_sched_ep,
-                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta};
+                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta, h->d_lin_mem};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -128,6 +128,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->sched_on = h->sched_eps = h->sched_alpha = h->sched_sweep = false; h->sched_R = h->sched_M = 0; h->sched_cap = 0;
     h->d_sched_E = h->d_sched_alpha = h->d_sched_row = h->d_sched_ep = nullptr;
     h->d_lin_theta = nullptr; h->lin_per_env = h->lin_ready = false;
+    h->lin_hist = 1; h->lin_cap = 0; h->d_lin_mem = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
     h->d_imgc_boxes = nullptr;
     h->d_hist_hi = nullptr;
@@ -1844,20 +1845,46 @@ extern "C" int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream) {
 }
 
 // ---- closed-loop CONTINUOUS rollouts under a linear policy per env (mdpp_continuous_linear.hip) ----
-extern "C" int mdpp_set_linear_policy(mdpp_env *h, const float *theta_dev, int per_env, void *stream) {
+static int set_linear_policy(mdpp_env *h, const char *what, const float *theta_dev, int per_env, int history, void *stream) {
     if (!h) return MDPP_EINVAL;
-    if (!theta_dev) return fail(h, MDPP_EINVAL, "mdpp_set_linear_policy: null parameters");
+    if (!theta_dev) return fail(h, MDPP_EINVAL, std::string(what) + ": null parameters");
+    if (history != 1 && history != 2) return fail(h, MDPP_EINVAL, std::string(what) + ": history must be 1 or 2");
     const std::string why = continuous_linear_refusal(h);
-    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_linear_policy: " + why);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
     HIPCHK(h, hipSetDevice(h->device));
-    // (one allocation for the larger layout: a launch queued earlier may still read the buffer when the layout changes)
-    const size_t E = (size_t)h->cfg.D * (size_t)(h->cfg.D + 1);
-    if (!h->d_lin_theta) HIPCHK(h, hipMalloc(&h->d_lin_theta, (size_t)h->cfg.num_envs * E * sizeof(float)));
+    // (one allocation for the larger layout: a launch queued earlier may still read the buffer when the layout changes.  The
+    //  first history = 2 policy needs a larger one: hipFree waits for the work queued on the old buffer)
+    const size_t N = (size_t)h->cfg.num_envs, D = (size_t)h->cfg.D;
+    const size_t need = N * D * ((size_t)history * D + 1);
+    if (h->lin_cap < need) {
+        if (h->d_lin_theta) { HIPCHK(h, hipFree(h->d_lin_theta)); h->d_lin_theta = nullptr; h->lin_cap = 0; h->lin_ready = false; }
+        HIPCHK(h, hipMalloc(&h->d_lin_theta, need * sizeof(float)));
+        h->lin_cap = need;
+    }
+    if (history == 2) {
+        // the memory starts as every env's current state (cur and the memory share the [D][N] layout)
+        if (!h->d_lin_mem) HIPCHK(h, hipMalloc(&h->d_lin_mem, N * D * sizeof(float)));
+        HIPCHK(h, hipMemcpyAsync(h->d_lin_mem, h->d_cur, N * D * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
     h->lin_per_env = per_env != 0;
+    h->lin_hist = history;
     int rc = launch_linear_theta_copy(h, const_cast<float *>(theta_dev), true, (hipStream_t)stream);
     if (rc) { h->lin_ready = false; return rc; }
     h->lin_ready = true;
     return MDPP_OK;
+}
+
+extern "C" int mdpp_set_linear_policy(mdpp_env *h, const float *theta_dev, int per_env, void *stream) {
+    return set_linear_policy(h, "mdpp_set_linear_policy", theta_dev, per_env, 1, stream);
+}
+
+// ---- linear policies with memory (include/mdpp.h "Linear policies with memory"; mdpp_linear_history.hpp) ----
+extern "C" int mdpp_set_linear_policy_history(mdpp_env *h, const float *theta_dev, int per_env, int history, void *stream) {
+    return set_linear_policy(h, "mdpp_set_linear_policy_history", theta_dev, per_env, history, stream);
+}
+
+extern "C" int mdpp_linear_policy_history(mdpp_env *h) {
+    return h && h->lin_ready ? h->lin_hist : 0;
 }
 
 // the checks every linear-policy call makes after its own arguments'
@@ -1877,6 +1904,15 @@ extern "C" int mdpp_get_linear_policy(mdpp_env *h, float *theta_dev, void *strea
     int rc = linear_ready(h, "mdpp_get_linear_policy");
     if (rc) return rc;
     return launch_linear_theta_copy(h, theta_dev, false, (hipStream_t)stream);
+}
+
+extern "C" int mdpp_linear_memory(mdpp_env *h, float *buf_dev, int set, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!buf_dev) return fail(h, MDPP_EINVAL, "mdpp_linear_memory: null buffer");
+    int rc = linear_ready(h, "mdpp_linear_memory");
+    if (rc) return rc;
+    if (h->lin_hist != 2) return fail(h, MDPP_ESTATE, "mdpp_linear_memory: the linear policy in force has no memory (history = 1)");
+    return launch_linear_memory_copy(h, buf_dev, set != 0, (hipStream_t)stream);
 }
 
 extern "C" int mdpp_clear_linear_policy(mdpp_env *h) {
@@ -2349,6 +2385,7 @@ extern "C" int mdpp_set_state_continuous(mdpp_env *h, const float *derivs, const
     }
     HIPCHK(h, hipMemcpy(h->d_sd, sd.data(), sd.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->d_cur, cu.data(), cu.size() * 4, hipMemcpyHostToDevice));
+    if (h->d_lin_mem) HIPCHK(h, hipMemcpy(h->d_lin_mem, cu.data(), cu.size() * 4, hipMemcpyHostToDevice));   // a linear policy's memory: the state set
     HIPCHK(h, hipMemcpy(h->d_meta, me.data(), N * 8, hipMemcpyHostToDevice));
     if (ring && d > 0 && h->cargs.rew64) {          // the default float64 target with a dense reward: a float64 delay line
         std::vector<double> rg((size_t)d * N);

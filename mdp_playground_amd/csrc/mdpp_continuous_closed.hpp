@@ -17,6 +17,9 @@
 //   begin(i)              per lane, after the `i >= N` return
 //   act(cur, act_out)     the action of this step from the state in the record (cur: the last observation returned for
 //                         the env); also called on the reset call of a next-step-autoreset env, where it is written and ignored
+//   act(cur, act_out, first)  in its place for an agent with kHist == 2 (a linear policy with memory, mdpp_linear_history.hpp);
+//                         first: the env has taken no step in its current episode (the record's step count is 0)
+//   kHist                 1 or 2, a static constant
 //   observe(rw, end)      once per step that is not a reset call, after the step's float32 reward is final; end: the episode
 //                         terminated or was truncated at this step (a same-step reset has already been made: `cur` is the
 //                         new episode's first state).  What it changes acts from the next act() on
@@ -228,7 +231,8 @@ __device__ __forceinline__ void continuous_closed_rollout(const ContinuousArgs &
             sp_phx.init(a.philox_seed, (uint64_t)(a.env_id_offset + i), ptick, MDPP_STREAM_SPACE);
         }
         // ---- the agent's action, from the state in the record
-        agent.act(cur, act);
+        if constexpr (Agent::kHist == 2) agent.act(cur, act, steps == 0);
+        else agent.act(cur, act);
         if constexpr (!SUMMARY) put_row(out.actions, o, act);
         if (pending) {               // next-step autoreset: this call is the env's reset(), :2284-2323 (the action is ignored)
             lane_reset();

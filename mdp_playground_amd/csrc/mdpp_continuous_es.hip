@@ -22,11 +22,16 @@
 //
 // The candidate's placement is the search's: PLDS = 1, staged once per launch at p_lds[e 256 + tid], rewritten there at a
 // generation end (the lane's own column) and written back by finish() when a generation moved; PLDS = 0, in the buffer itself.
+//
+// History 2 (include/mdpp.h "Linear policies with memory"): the *_h2.hip units include this file with MDPP_LINEAR_HIST = 2 and hold
+// the HIST=2 forms of the two kernels and their launchers, nothing else; the act is mdpp_linear_history.hpp's, and everything
+// below that walks the entries walks E = D (HIST D + 1) of them.
 #ifndef MDPP_CES_TU_SUMMARY
 #define MDPP_CES_TU_SUMMARY 0    // 1: this translation unit holds k_continuous_es_summary (mdpp_continuous_summary_es.hip)
 #endif
 
 #include "mdpp_continuous_closed.hpp"
+#include "mdpp_linear_history.hpp"
 
 namespace mdpp {
 
@@ -35,8 +40,10 @@ struct EsParams {
     float *cand;                // the handle's entry-major buffer: entry e of env i at cand[e N + i]
 };
 
-template <int DMAX, bool PLDS>
+template <int DMAX, bool PLDS, int HIST>
 struct EsAgent {
+    static constexpr int kHist = HIST;
+    float *mem;                 // HIST = 2: the handle's memory [D][N]; from begin() on component 0 of this lane's
     float *cand;                // entry 0 of this lane in the handle's buffer, entry e at cand[e N]
     float *lds;                 // PLDS = 1: entry 0 of this lane, entry e at lds[e 256]
     float *stage;
@@ -52,9 +59,10 @@ struct EsAgent {
     __device__ __forceinline__ void begin(long lane) {
         i = lane;
         cand = sp.cand + i;
+        if constexpr (HIST == 2) mem += i;
         if constexpr (PLDS) {
             float *mine = stage + threadIdx.x;
-            const int E = D * (D + 1);
+            const int E = D * (HIST * D + 1);
             for (int e = 0; e < E; e++) mine[e * kBlock] = cand[(long)e * N];
             lds = mine;         // (this lane's column alone: no barrier)
         }
@@ -91,7 +99,7 @@ struct EsAgent {
         g1.init(s.seed, id, (uint64_t)(uint32_t)(gen + 1), kPhiloxLinearEsStream);
         const long stride = PLDS ? (long)kBlock : N;
         float *c = PLDS ? lds : cand, *mu_p = s.mean + g;
-        const int E = D * (D + 1);
+        const int E = D * (HIST * D + 1);
 #pragma unroll 1
         for (int e = 0; e < E; e++) {
             const float z0 = (float)g0.normal(), z1 = (float)g1.normal();
@@ -137,6 +145,12 @@ struct EsAgent {
             a[r] = acc;
         }
     }
+    // HIST = 2: the step calls this form (first: no step taken in the env's current episode) -- after the vote, like act() above
+    __device__ __forceinline__ void act(const float (&o)[DMAX], float (&a)[DMAX], bool first) {
+        if (stepped) vote();
+        stepped = true;
+        linear_act_h2<DMAX>(PLDS ? lds : cand, PLDS ? (long)kBlock : N, D, amax, o, mem, N, first, a);
+    }
     __device__ __forceinline__ void observe(float rw, bool end) {
         const int32_t T = sp.s.episodes_per_member;
         const bool counting = eps >= 0 && eps < T;
@@ -152,7 +166,7 @@ struct EsAgent {
         sp.s.eps[i] = eps;
         if constexpr (PLDS) {
             if (moved) {
-                const int E = D * (D + 1);
+                const int E = D * (HIST * D + 1);
                 for (int e = 0; e < E; e++) cand[(long)e * N] = lds[e * kBlock];
             }
         }
@@ -160,21 +174,21 @@ struct EsAgent {
 };
 
 #if MDPP_CES_TU_SUMMARY
-template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS>
-__global__ __launch_bounds__(kBlock) void k_continuous_es_summary(ContinuousArgs a, int K, EsParams sp, EpisodeSummaryArgs sm) {
+template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS MDPP_HIST_TPARAM>
+__global__ __launch_bounds__(kBlock) void k_continuous_es_summary(ContinuousArgs a, int K, EsParams sp, EpisodeSummaryArgs sm MDPP_HIST_KPARAM) {
     extern __shared__ __align__(16) float s_theta[];
-    EsAgent<DMAX, PLDS> agent;
-    agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
+    EsAgent<DMAX, PLDS, MDPP_LINEAR_HIST> agent;
+    MDPP_HIST_SET_MEM(agent, a.N) agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
     continuous_closed_rollout<DMAX, OMAX, PHILOX, NOISE, true>(a, K, agent, ContinuousClosedOut{}, sm);
 }
 #define MDPP_CES_KERNEL k_continuous_es_summary
 #define MDPP_CES_NAME "k_continuous_es_summary"
 #else
-template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS>
-__global__ __launch_bounds__(kBlock) void k_continuous_es_rollout(ContinuousArgs a, int K, EsParams sp, ContinuousClosedOut out) {
+template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS MDPP_HIST_TPARAM>
+__global__ __launch_bounds__(kBlock) void k_continuous_es_rollout(ContinuousArgs a, int K, EsParams sp, ContinuousClosedOut out MDPP_HIST_KPARAM) {
     extern __shared__ __align__(16) float s_theta[];
-    EsAgent<DMAX, PLDS> agent;
-    agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
+    EsAgent<DMAX, PLDS, MDPP_LINEAR_HIST> agent;
+    MDPP_HIST_SET_MEM(agent, a.N) agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
     continuous_closed_rollout<DMAX, OMAX, PHILOX, NOISE, false>(a, K, agent, out, EpisodeSummaryArgs{});
 }
 #define MDPP_CES_KERNEL k_continuous_es_rollout
@@ -183,48 +197,58 @@ __global__ __launch_bounds__(kBlock) void k_continuous_es_rollout(ContinuousArgs
 
 // One form of this unit's kernel on (padded D, padded order): the placement, the name, the launch
 template <int DMAX, int OMAX>
-static void launch_es_t(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp) {
+static void launch_es_t(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp, float *mem) {
     const long grid = ((long)a.N + kBlock - 1) / kBlock;
     const bool noise = a.has_p_noise || a.has_r_noise;
-    const size_t want = (size_t)kBlock * a.D * (a.D + 1) * sizeof(float);
+    const size_t want = (size_t)kBlock * a.D * (MDPP_LINEAR_HIST * a.D + 1) * sizeof(float);
     with_bools([&](auto PH, auto NZ) {
         constexpr bool kPh = decltype(PH)::value, kNz = decltype(NZ)::value;
         const bool plds = !(a.opts & MDPP_OPT_NO_LINEAR_LDS) &&
-                          dynamic_lds_ok((const void *)MDPP_CES_KERNEL<DMAX, OMAX, kPh, kNz, true>, want);
+                          dynamic_lds_ok((const void *)MDPP_CES_KERNEL<DMAX, OMAX, kPh, kNz, true MDPP_HIST_TARG>, want);
         with_bools([&](auto PL) {
             constexpr bool kPl = decltype(PL)::value;
             if (io.name_out) {
-                snprintf(io.name_out, kNameLen, MDPP_CES_NAME "<D=%d,ORDER=%d,PHILOX=%d,NOISE=%d,PLDS=%d>", DMAX, OMAX, (int)kPh, (int)kNz, (int)kPl);
+                snprintf(io.name_out, kNameLen, MDPP_CES_NAME "<D=%d,ORDER=%d,PHILOX=%d,NOISE=%d,PLDS=%d" MDPP_HIST_NAME ">", DMAX, OMAX, (int)kPh, (int)kNz, (int)kPl);
                 return;
             }
             const size_t lds = kPl ? want : 0;
 #if MDPP_CES_TU_SUMMARY
-            hipLaunchKernelGGL((k_continuous_es_summary<DMAX, OMAX, kPh, kNz, kPl>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp, *io.summary);
+            hipLaunchKernelGGL((k_continuous_es_summary<DMAX, OMAX, kPh, kNz, kPl MDPP_HIST_TARG>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp, *io.summary MDPP_HIST_KARG);
 #else
             // (ContinuousIO::actions is const for the open-loop launchers; the closed-loop launchers WRITE the actions taken there)
-            hipLaunchKernelGGL((k_continuous_es_rollout<DMAX, OMAX, kPh, kNz, kPl>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp,
-                               ContinuousClosedOut{const_cast<float *>(io.actions), io.obs, io.reward, io.term, io.trunc});
+            hipLaunchKernelGGL((k_continuous_es_rollout<DMAX, OMAX, kPh, kNz, kPl MDPP_HIST_TARG>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp,
+                               ContinuousClosedOut{const_cast<float *>(io.actions), io.obs, io.reward, io.term, io.trunc} MDPP_HIST_KARG);
 #endif
         }, plds);
     }, a.philox != 0, noise);
 }
 
 // the (2,2), (4,2), (12,1) and (12,2) shapes of the linear kernels; false: D > 12 or order > 2
-static bool launch_es_dispatch(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp) {
+static bool launch_es_dispatch(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp, float *mem = nullptr) {
     if (a.order > 2 || a.D > 12) return false;
-    if (a.D <= 2) launch_es_t<2, 2>(a, io, sp);
-    else if (a.D <= 4) launch_es_t<4, 2>(a, io, sp);
-    else if (a.order <= 1) launch_es_t<12, 1>(a, io, sp);
-    else launch_es_t<12, 2>(a, io, sp);
+    if (a.D <= 2) launch_es_t<2, 2>(a, io, sp, mem);
+    else if (a.D <= 4) launch_es_t<4, 2>(a, io, sp, mem);
+    else if (a.order <= 1) launch_es_t<12, 1>(a, io, sp, mem);
+    else launch_es_t<12, 2>(a, io, sp, mem);
     return true;
 }
 
-#if MDPP_CES_TU_SUMMARY
+#if MDPP_LINEAR_HIST == 2 && MDPP_CES_TU_SUMMARY
+bool launch_continuous_es_summary_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp, float *mem) {
+    return launch_es_dispatch(a, io, sp, mem);
+}
+#elif MDPP_LINEAR_HIST == 2
+bool launch_continuous_es_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp, float *mem) {
+    return launch_es_dispatch(a, io, sp, mem);
+}
+#elif MDPP_CES_TU_SUMMARY
 bool launch_continuous_es_summary_form(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp) {
     return launch_es_dispatch(a, io, sp);
 }
 #else
 bool launch_continuous_es_summary_form(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp);
+bool launch_continuous_es_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp, float *mem);
+bool launch_continuous_es_summary_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const EsParams &sp, float *mem);
 
 // io.K steps of the ES on the handle's per-env linear policy (the caller has checked that there is one and that N % 64 == 0);
 // io.summary: the summary form; io.name_out: a dry run, es is not read
@@ -232,14 +256,17 @@ int launch_continuous_es(mdpp_env *h, const ContinuousIO &io, const mdpp_linear_
     ContinuousArgs a = h->cargs;
     stamp_step(a, h);
     const EsParams sp{es, (float *)h->d_lin_theta};
+    float *mem = (float *)h->d_lin_mem;
     const bool summary = io.summary != nullptr;
-    const bool served = summary ? launch_continuous_es_summary_form(a, io, sp) : launch_es_dispatch(a, io, sp);
+    const bool served = h->lin_hist == 2 ? (summary ? launch_continuous_es_summary_h2_form(a, io, sp, mem) : launch_continuous_es_h2_form(a, io, sp, mem))
+                        : summary        ? launch_continuous_es_summary_form(a, io, sp)
+                                         : launch_es_dispatch(a, io, sp);
     if (!served) { h->err = "linear-policy rollouts serve state_space_dim <= 12 and transition_dynamics_order <= 2"; return MDPP_EUNSUPPORTED; }
     return io.name_out ? MDPP_OK : step_done(h, io.K, summary ? "k_continuous_es_summary" : "k_continuous_es_rollout");
 }
 
 // mdpp_linear_es_init: the candidates of the current generation, mean +- sigma z with z the normals of tick gen; one lane per env
-__global__ __launch_bounds__(kBlock) void k_linear_es_init(mdpp_linear_es s, float *cand, long N, int D, uint64_t env0) {
+__global__ __launch_bounds__(kBlock) void k_linear_es_init(mdpp_linear_es s, float *cand, long N, int E, uint64_t env0) {
     const long i = (long)blockIdx.x * kBlock + threadIdx.x;
     if (i >= N) return;
     const long g = i >> 6, G = N >> 6;
@@ -247,7 +274,6 @@ __global__ __launch_bounds__(kBlock) void k_linear_es_init(mdpp_linear_es s, flo
     const float sg = s.sigma[g];
     Philox z;
     z.init(s.seed, env0 + (uint64_t)(i & ~1L), (uint64_t)(uint32_t)s.gen[g], kPhiloxLinearEsStream);
-    const int E = D * (D + 1);
     const float *mu_p = s.mean + g;
     float *c = cand + i;
 #pragma unroll 1
@@ -262,8 +288,8 @@ __global__ __launch_bounds__(kBlock) void k_linear_es_init(mdpp_linear_es s, flo
 
 int launch_linear_es_init(mdpp_env *h, const mdpp_linear_es &es, hipStream_t s) {
     const long N = h->cfg.num_envs;
-    hipLaunchKernelGGL(k_linear_es_init, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, es, (float *)h->d_lin_theta, N, h->cfg.D,
-                       (uint64_t)h->cfg.env_id_offset);
+    hipLaunchKernelGGL(k_linear_es_init, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, es, (float *)h->d_lin_theta, N,
+                       h->cfg.D * (h->lin_hist * h->cfg.D + 1), (uint64_t)h->cfg.env_id_offset);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->err = std::string("k_linear_es_init launch: ") + hipGetErrorString(e); return MDPP_EHIP; }
     return MDPP_OK;

@@ -14,11 +14,16 @@
 // The candidate's placement is the linear kernels': PLDS = 1, staged once per launch at p_lds[e 256 + tid], rewritten there at
 // a trial end (the lane's own column: no barrier) and written back to the buffer by finish() for the lanes whose trial moved;
 // PLDS = 0, read at every step and rewritten at a trial end in the buffer itself.
+//
+// History 2 (include/mdpp.h "Linear policies with memory"): the *_h2.hip units include this file with MDPP_LINEAR_HIST = 2 and hold
+// the HIST=2 forms of the two kernels and their launchers, nothing else; the act is mdpp_linear_history.hpp's, and everything
+// below that walks the entries walks E = D (HIST D + 1) of them.
 #ifndef MDPP_CSRCH_TU_SUMMARY
 #define MDPP_CSRCH_TU_SUMMARY 0    // 1: this translation unit holds k_continuous_search_summary (mdpp_continuous_summary_search.hip)
 #endif
 
 #include "mdpp_continuous_closed.hpp"
+#include "mdpp_linear_history.hpp"
 
 namespace mdpp {
 
@@ -27,8 +32,10 @@ struct SearchParams {
     float *cand;                // the handle's entry-major buffer: entry e of env i at cand[e N + i]
 };
 
-template <int DMAX, bool PLDS>
+template <int DMAX, bool PLDS, int HIST>
 struct SearchAgent {
+    static constexpr int kHist = HIST;
+    float *mem;                 // HIST = 2: the handle's memory [D][N]; from begin() on component 0 of this lane's
     float *cand;                // entry 0 of this lane in the handle's buffer, entry e at cand[e N]
     float *lds;                 // PLDS = 1: entry 0 of this lane, entry e at lds[e 256]
     float *stage;
@@ -42,9 +49,10 @@ struct SearchAgent {
     __device__ __forceinline__ void begin(long lane) {
         i = lane;
         cand = sp.cand + i;
+        if constexpr (HIST == 2) mem += i;
         if constexpr (PLDS) {
             float *mine = stage + threadIdx.x;
-            const int E = D * (D + 1);
+            const int E = D * (HIST * D + 1);
             for (int e = 0; e < E; e++) mine[e * kBlock] = cand[(long)e * N];
             lds = mine;         // (this lane's column alone: no barrier)
         }
@@ -70,6 +78,10 @@ struct SearchAgent {
             a[r] = acc;
         }
     }
+    // HIST = 2: the step calls this form (first: no step taken in the env's current episode)
+    __device__ __forceinline__ void act(const float (&o)[DMAX], float (&a)[DMAX], bool first) const {
+        linear_act_h2<DMAX>(PLDS ? lds : cand, PLDS ? (long)kBlock : N, D, amax, o, mem, N, first, a);
+    }
     // eps == T: accept or reject the candidate on acc, adapt sigma, draw the next candidate around the incumbent
     __device__ __forceinline__ void trial_end(double acc) {
         const mdpp_linear_search &s = sp.s;
@@ -87,7 +99,7 @@ struct SearchAgent {
         g.init(s.seed, env0 + (uint64_t)i, (uint64_t)(uint32_t)(trial + 1), kPhiloxLinearSearchStream);
         const long stride = PLDS ? (long)kBlock : N;
         float *c = PLDS ? lds : cand, *b = s.best + i;
-        const int E = D * (D + 1);
+        const int E = D * (HIST * D + 1);
 #pragma unroll 1
         for (int e = 0; e < E; e++) {
             float inc;
@@ -113,7 +125,7 @@ struct SearchAgent {
         sp.s.ret[i] = ret;
         if constexpr (PLDS) {
             if (moved) {
-                const int E = D * (D + 1);
+                const int E = D * (HIST * D + 1);
                 for (int e = 0; e < E; e++) cand[(long)e * N] = lds[e * kBlock];
             }
         }
@@ -121,21 +133,21 @@ struct SearchAgent {
 };
 
 #if MDPP_CSRCH_TU_SUMMARY
-template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS>
-__global__ __launch_bounds__(kBlock) void k_continuous_search_summary(ContinuousArgs a, int K, SearchParams sp, EpisodeSummaryArgs sm) {
+template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS MDPP_HIST_TPARAM>
+__global__ __launch_bounds__(kBlock) void k_continuous_search_summary(ContinuousArgs a, int K, SearchParams sp, EpisodeSummaryArgs sm MDPP_HIST_KPARAM) {
     extern __shared__ __align__(16) float s_theta[];
-    SearchAgent<DMAX, PLDS> agent;
-    agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
+    SearchAgent<DMAX, PLDS, MDPP_LINEAR_HIST> agent;
+    MDPP_HIST_SET_MEM(agent, a.N) agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
     continuous_closed_rollout<DMAX, OMAX, PHILOX, NOISE, true>(a, K, agent, ContinuousClosedOut{}, sm);
 }
 #define MDPP_CSRCH_KERNEL k_continuous_search_summary
 #define MDPP_CSRCH_NAME "k_continuous_search_summary"
 #else
-template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS>
-__global__ __launch_bounds__(kBlock) void k_continuous_search_rollout(ContinuousArgs a, int K, SearchParams sp, ContinuousClosedOut out) {
+template <int DMAX, int OMAX, bool PHILOX, bool NOISE, bool PLDS MDPP_HIST_TPARAM>
+__global__ __launch_bounds__(kBlock) void k_continuous_search_rollout(ContinuousArgs a, int K, SearchParams sp, ContinuousClosedOut out MDPP_HIST_KPARAM) {
     extern __shared__ __align__(16) float s_theta[];
-    SearchAgent<DMAX, PLDS> agent;
-    agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
+    SearchAgent<DMAX, PLDS, MDPP_LINEAR_HIST> agent;
+    MDPP_HIST_SET_MEM(agent, a.N) agent.sp = sp; agent.N = a.N; agent.env0 = (uint64_t)a.env_id_offset; agent.D = a.D; agent.amax = a.amax32; agent.stage = s_theta;
     continuous_closed_rollout<DMAX, OMAX, PHILOX, NOISE, false>(a, K, agent, out, EpisodeSummaryArgs{});
 }
 #define MDPP_CSRCH_KERNEL k_continuous_search_rollout
@@ -144,48 +156,58 @@ __global__ __launch_bounds__(kBlock) void k_continuous_search_rollout(Continuous
 
 // One form of this unit's kernel on (padded D, padded order): the placement, the name, the launch
 template <int DMAX, int OMAX>
-static void launch_search_t(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp) {
+static void launch_search_t(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp, float *mem) {
     const long grid = ((long)a.N + kBlock - 1) / kBlock;
     const bool noise = a.has_p_noise || a.has_r_noise;
-    const size_t want = (size_t)kBlock * a.D * (a.D + 1) * sizeof(float);
+    const size_t want = (size_t)kBlock * a.D * (MDPP_LINEAR_HIST * a.D + 1) * sizeof(float);
     with_bools([&](auto PH, auto NZ) {
         constexpr bool kPh = decltype(PH)::value, kNz = decltype(NZ)::value;
         const bool plds = !(a.opts & MDPP_OPT_NO_LINEAR_LDS) &&
-                          dynamic_lds_ok((const void *)MDPP_CSRCH_KERNEL<DMAX, OMAX, kPh, kNz, true>, want);
+                          dynamic_lds_ok((const void *)MDPP_CSRCH_KERNEL<DMAX, OMAX, kPh, kNz, true MDPP_HIST_TARG>, want);
         with_bools([&](auto PL) {
             constexpr bool kPl = decltype(PL)::value;
             if (io.name_out) {
-                snprintf(io.name_out, kNameLen, MDPP_CSRCH_NAME "<D=%d,ORDER=%d,PHILOX=%d,NOISE=%d,PLDS=%d>", DMAX, OMAX, (int)kPh, (int)kNz, (int)kPl);
+                snprintf(io.name_out, kNameLen, MDPP_CSRCH_NAME "<D=%d,ORDER=%d,PHILOX=%d,NOISE=%d,PLDS=%d" MDPP_HIST_NAME ">", DMAX, OMAX, (int)kPh, (int)kNz, (int)kPl);
                 return;
             }
             const size_t lds = kPl ? want : 0;
 #if MDPP_CSRCH_TU_SUMMARY
-            hipLaunchKernelGGL((k_continuous_search_summary<DMAX, OMAX, kPh, kNz, kPl>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp, *io.summary);
+            hipLaunchKernelGGL((k_continuous_search_summary<DMAX, OMAX, kPh, kNz, kPl MDPP_HIST_TARG>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp, *io.summary MDPP_HIST_KARG);
 #else
             // (ContinuousIO::actions is const for the open-loop launchers; the closed-loop launchers WRITE the actions taken there)
-            hipLaunchKernelGGL((k_continuous_search_rollout<DMAX, OMAX, kPh, kNz, kPl>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp,
-                               ContinuousClosedOut{const_cast<float *>(io.actions), io.obs, io.reward, io.term, io.trunc});
+            hipLaunchKernelGGL((k_continuous_search_rollout<DMAX, OMAX, kPh, kNz, kPl MDPP_HIST_TARG>), dim3((unsigned)grid), dim3(kBlock), lds, io.s, a, io.K, sp,
+                               ContinuousClosedOut{const_cast<float *>(io.actions), io.obs, io.reward, io.term, io.trunc} MDPP_HIST_KARG);
 #endif
         }, plds);
     }, a.philox != 0, noise);
 }
 
 // the (2,2), (4,2), (12,1) and (12,2) shapes of the linear kernels; false: D > 12 or order > 2
-static bool launch_search_dispatch(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp) {
+static bool launch_search_dispatch(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp, float *mem = nullptr) {
     if (a.order > 2 || a.D > 12) return false;
-    if (a.D <= 2) launch_search_t<2, 2>(a, io, sp);
-    else if (a.D <= 4) launch_search_t<4, 2>(a, io, sp);
-    else if (a.order <= 1) launch_search_t<12, 1>(a, io, sp);
-    else launch_search_t<12, 2>(a, io, sp);
+    if (a.D <= 2) launch_search_t<2, 2>(a, io, sp, mem);
+    else if (a.D <= 4) launch_search_t<4, 2>(a, io, sp, mem);
+    else if (a.order <= 1) launch_search_t<12, 1>(a, io, sp, mem);
+    else launch_search_t<12, 2>(a, io, sp, mem);
     return true;
 }
 
-#if MDPP_CSRCH_TU_SUMMARY
+#if MDPP_LINEAR_HIST == 2 && MDPP_CSRCH_TU_SUMMARY
+bool launch_continuous_search_summary_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp, float *mem) {
+    return launch_search_dispatch(a, io, sp, mem);
+}
+#elif MDPP_LINEAR_HIST == 2
+bool launch_continuous_search_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp, float *mem) {
+    return launch_search_dispatch(a, io, sp, mem);
+}
+#elif MDPP_CSRCH_TU_SUMMARY
 bool launch_continuous_search_summary_form(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp) {
     return launch_search_dispatch(a, io, sp);
 }
 #else
 bool launch_continuous_search_summary_form(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp);
+bool launch_continuous_search_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp, float *mem);
+bool launch_continuous_search_summary_h2_form(const ContinuousArgs &a, const ContinuousIO &io, const SearchParams &sp, float *mem);
 
 // io.K steps of the search on the handle's per-env linear policy (the caller has checked that there is one); io.summary: the
 // summary form; io.name_out: a dry run, sr is not read
@@ -193,8 +215,11 @@ int launch_continuous_search(mdpp_env *h, const ContinuousIO &io, const mdpp_lin
     ContinuousArgs a = h->cargs;
     stamp_step(a, h);
     const SearchParams sp{sr, (float *)h->d_lin_theta};
+    float *mem = (float *)h->d_lin_mem;
     const bool summary = io.summary != nullptr;
-    const bool served = summary ? launch_continuous_search_summary_form(a, io, sp) : launch_search_dispatch(a, io, sp);
+    const bool served = h->lin_hist == 2 ? (summary ? launch_continuous_search_summary_h2_form(a, io, sp, mem) : launch_continuous_search_h2_form(a, io, sp, mem))
+                        : summary        ? launch_continuous_search_summary_form(a, io, sp)
+                                         : launch_search_dispatch(a, io, sp);
     if (!served) { h->err = "linear-policy rollouts serve state_space_dim <= 12 and transition_dynamics_order <= 2"; return MDPP_EUNSUPPORTED; }
     return io.name_out ? MDPP_OK : step_done(h, io.K, summary ? "k_continuous_search_summary" : "k_continuous_search_rollout");
 }

@@ -381,6 +381,13 @@ struct mdpp_env {
     // N D (D + 1) entries
     void *d_lin_theta;
     bool lin_per_env, lin_ready;
+    // a linear policy with memory (mdpp_set_linear_policy_history; mdpp_linear_history.hpp): lin_hist 1 or 2 -- E = D (lin_hist D + 1)
+    // entries per policy, r (lin_hist D + 1) + c --, lin_cap the floats d_lin_theta was allocated for (N D (D + 1) until a
+    // history = 2 policy is first set), d_lin_mem the memory p, float32 [D][N] in cur's layout, allocated with the first
+    // history = 2 policy
+    int lin_hist;
+    size_t lin_cap;
+    void *d_lin_mem;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -610,6 +617,8 @@ int launch_discrete_current_obs(mdpp_env *h, void *obs, hipStream_t s);
 std::string continuous_linear_refusal(const mdpp_env *h);
 int launch_continuous_linear(mdpp_env *h, const ContinuousIO &io);
 int launch_linear_theta_copy(mdpp_env *h, float *user, bool to_handle, hipStream_t s);
+// the memory of a history = 2 policy between the handle's [D][N] and the caller's [N][D] (mdpp_linear_memory)
+int launch_linear_memory_copy(mdpp_env *h, float *user, bool to_handle, hipStream_t s);
 // ... and with one (1+1)-ES per env on that policy (include/mdpp.h "Linear policy search"; mdpp_continuous_search.hip, the
 // summary form: mdpp_continuous_summary_search.hip): the candidate is the handle's parameter buffer, sr the caller's arrays
 int launch_continuous_search(mdpp_env *h, const ContinuousIO &io, const mdpp_linear_search &sr);

@@ -4,7 +4,8 @@ with es=; include/mdpp.h "Linear policy ES").
 The 64 envs of group g -- local envs 64g .. 64g+63, one wave of the kernel -- are one population: 32 antithetic pairs
 mean +- sigma z around the group's mean.  The candidate of env i is the env handle's own parameter buffer
 (env.get_linear_policy()).  A LinearES owns everything else, device tensors that the kernel reads and writes, E = D (D + 1),
-G = N / 64:
+G = N / 64 -- under a policy with memory (set_linear_policy(theta, history=2)) every D + 1 below is 2 D + 1, the policy's own
+column count:
 
     mean      float32  [E, G]  the population means, entry-major: entry e = r (D + 1) + c of group g at [e, g]
     sigma     float32  [G]     perturbation scale per group
@@ -50,13 +51,14 @@ def _per_group(value, G, name, positive):
 
 class LinearES:
     def __init__(self, mean_theta, sigma, lr, *, seed, episodes_per_member=1, log_generations=0):
-        """mean_theta: the start means, a float32 tensor [G, D, D + 1] (its device is the ES's); sigma, lr: scalars or float32
+        """mean_theta: the start means, a float32 tensor [G, D, D + 1] -- [G, D, 2 D + 1] for policies with memory -- (its device is the ES's); sigma, lr: scalars or float32
         arrays [G], sigma finite and > 0, lr finite and >= 0."""
         if not (torch.is_tensor(mean_theta) and mean_theta.dtype == torch.float32 and mean_theta.dim() == 3
-                and mean_theta.shape[0] >= 1 and mean_theta.shape[2] == mean_theta.shape[1] + 1):
-            raise ValueError("LinearES: mean_theta must be a float32 tensor of shape (G, D, D + 1)")
+                and mean_theta.shape[0] >= 1 and mean_theta.shape[2] in (mean_theta.shape[1] + 1, 2 * mean_theta.shape[1] + 1)):
+            raise ValueError("LinearES: mean_theta must be a float32 tensor of shape (G, D, D + 1) or (G, D, 2 D + 1)")
         G, D = int(mean_theta.shape[0]), int(mean_theta.shape[1])
         self.groups, self.num_envs, self.D, self.device = G, GROUP * G, D, mean_theta.device
+        self.cols = int(mean_theta.shape[2])     # D + 1, or 2 D + 1 for a policy with memory
         for name, v, low in (("episodes_per_member", episodes_per_member, 1), ("log_generations", log_generations, 0)):
             if isinstance(v, bool) or int(v) != v or int(v) < low:
                 raise ValueError(f"LinearES: {name} must be an integer >= {low}")
@@ -68,7 +70,7 @@ class LinearES:
         rate = _per_group(lr, G, "lr", False)
         with np.errstate(over="ignore"):
             gain = (rate / (sg * _RANK_NORM).astype(np.float32)).astype(np.float32)
-        E, N, dev = D * (D + 1), self.num_envs, self.device
+        E, N, dev = D * self.cols, self.num_envs, self.device
         self.mean = mean_theta.reshape(G, E).t().contiguous()
         self.sigma = torch.from_numpy(sg).to(dev)
         self.gain = torch.from_numpy(gain).to(dev)
@@ -81,7 +83,7 @@ class LinearES:
 
     def _shape(self, name):
         if name == "mean":
-            return (self.D * (self.D + 1), self.groups)
+            return (self.D * self.cols, self.groups)
         if name == "log_mean":
             return (self.log_generations, self.groups)
         return (self.groups,) if name in ("sigma", "gain", "gen") else (self.num_envs,)
@@ -90,9 +92,10 @@ class LinearES:
         """(mean, sigma, gain, gen, acc, ret, fitness, eps, log_mean), the order of struct mdpp_linear_es."""
         return tuple(getattr(self, name) for name, _ in _FIELDS)
 
-    def check(self, num_envs, D, device, what):
-        """ValueError unless the nine tensors are what a launch on (num_envs, D, device) can keep."""
-        if (self.num_envs, self.D) != (num_envs, D):
+    def check(self, num_envs, D, device, what, cols=None):
+        """ValueError unless the nine tensors are what a launch on (num_envs, D, device) can keep (cols: the column count of the
+        handle's policy, D + 1 by default)."""
+        if (self.num_envs, self.D, self.cols) != (num_envs, D, D + 1 if cols is None else cols):
             raise ValueError(f"{what}: es must be a LinearES of {num_envs} envs with D = {D}")
         for name, dtype in _FIELDS:
             t = getattr(self, name)
@@ -110,7 +113,7 @@ class LinearES:
 
     def mean_theta(self):
         """The means in the layout of one policy per group: float32 [G, D, D + 1]."""
-        return self.mean.t().reshape(self.groups, self.D, self.D + 1).contiguous()
+        return self.mean.t().reshape(self.groups, self.D, self.cols).contiguous()
 
     def curve(self):
         """(log_mean[:rows], valid): the rows any group has written, rows = min(max gen, M), and per group the number of them

@@ -2,7 +2,8 @@
 include/mdpp.h "Linear policy search").
 
 The candidate of env i -- the policy it acts with -- is the env handle's own parameter buffer (env.get_linear_policy()).  A
-LinearSearch owns everything else, device tensors that the kernel reads and writes, E = D (D + 1):
+LinearSearch owns everything else, device tensors that the kernel reads and writes, E = D (D + 1) -- under a policy with memory
+(set_linear_policy(theta, history=2)) every D + 1 below is 2 D + 1, the policy's own column count:
 
     best      float32  [E, N]  the incumbent, entry-major: entry e = r (D + 1) + c of env i at [e, i]
     sigma     float32  [N]     step size per env
@@ -35,12 +36,14 @@ _FIELDS = (("best", torch.float32), ("sigma", torch.float32), ("score", torch.fl
 
 class LinearSearch:
     def __init__(self, theta, sigma, *, seed, episodes_per_trial=1, sigma_up=1.0, sigma_down=1.0, sigma_max=math.inf):
-        """theta: the start policies, a float32 tensor [N, D, D + 1] (its device is the search's); sigma: a scalar or a float32
+        """theta: the start policies, a float32 tensor [N, D, D + 1] -- [N, D, 2 D + 1] for policies with memory -- (its device is the search's); sigma: a scalar or a float32
         array [N], >= 0 and finite."""
-        if not (torch.is_tensor(theta) and theta.dtype == torch.float32 and theta.dim() == 3 and theta.shape[2] == theta.shape[1] + 1):
-            raise ValueError("LinearSearch: theta must be a float32 tensor of shape (N, D, D + 1)")
+        if not (torch.is_tensor(theta) and theta.dtype == torch.float32 and theta.dim() == 3
+                and theta.shape[2] in (theta.shape[1] + 1, 2 * theta.shape[1] + 1)):
+            raise ValueError("LinearSearch: theta must be a float32 tensor of shape (N, D, D + 1) or (N, D, 2 D + 1)")
         N, D = int(theta.shape[0]), int(theta.shape[1])
         self.num_envs, self.D, self.device = N, D, theta.device
+        self.cols = int(theta.shape[2])          # D + 1, or 2 D + 1 for a policy with memory
         if isinstance(episodes_per_trial, bool) or int(episodes_per_trial) != episodes_per_trial or int(episodes_per_trial) < 1:
             raise ValueError("LinearSearch: episodes_per_trial must be an integer >= 1")
         self.episodes_per_trial = int(episodes_per_trial)
@@ -60,7 +63,7 @@ class LinearSearch:
                 raise ValueError(f"LinearSearch: sigma must be a scalar or a float32 array of shape ({N},)")
         if not (np.isfinite(sg).all() and (sg >= 0).all()):
             raise ValueError("LinearSearch: sigma must be finite and >= 0")
-        E = D * (D + 1)
+        E = D * self.cols
         dev = self.device
         self.best = theta.reshape(N, E).t().contiguous()
         self.sigma = torch.from_numpy(np.ascontiguousarray(sg)).to(dev)
@@ -72,15 +75,16 @@ class LinearSearch:
         self.accepted = torch.zeros(N, dtype=torch.int32, device=dev)
 
     def _shape(self, name):
-        return (self.D * (self.D + 1), self.num_envs) if name == "best" else (self.num_envs,)
+        return (self.D * self.cols, self.num_envs) if name == "best" else (self.num_envs,)
 
     def tensors(self):
         """(best, sigma, score, acc, ret, eps, trial, accepted), the order of struct mdpp_linear_search."""
         return tuple(getattr(self, name) for name, _ in _FIELDS)
 
-    def check(self, num_envs, D, device, what):
-        """ValueError unless the eight tensors are what a launch on (num_envs, D, device) can keep."""
-        if (self.num_envs, self.D) != (num_envs, D):
+    def check(self, num_envs, D, device, what, cols=None):
+        """ValueError unless the eight tensors are what a launch on (num_envs, D, device) can keep (cols: the column count of
+        the handle's policy, D + 1 by default)."""
+        if (self.num_envs, self.D, self.cols) != (num_envs, D, D + 1 if cols is None else cols):
             raise ValueError(f"{what}: search must be a LinearSearch of {num_envs} envs with D = {D}")
         for name, dtype in _FIELDS:
             t = getattr(self, name)
@@ -99,7 +103,7 @@ class LinearSearch:
 
     def best_theta(self):
         """The incumbents in the layout of set_linear_policy: float32 [N, D, D + 1]."""
-        return self.best.t().reshape(self.num_envs, self.D, self.D + 1).contiguous()
+        return self.best.t().reshape(self.num_envs, self.D, self.cols).contiguous()
 
     def abandon_episode(self, mask=None):
         """Drop the running episode's return (after an env.reset() that cut it short): ret = 0 for every env, or where ``mask``

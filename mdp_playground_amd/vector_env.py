@@ -768,44 +768,81 @@ class RLToyVectorEnv:
         return name.decode() if name else ""
 
     # ------------------------------------------------------------------ closed-loop continuous rollouts under a linear policy
-    def _linear_theta_arg(self, theta):
+    def _linear_theta_arg(self, theta, history=1):
         """theta as a contiguous float32 device tensor and whether it is per-env; ValueError for anything but float32
-        [D, D + 1] or [N, D, D + 1] (numpy or torch, any device), before any device work."""
+        [D, C] or [N, D, C] with C = history * D + 1 (numpy or torch, any device), before any device work."""
         if self.kind != "continuous":
             raise NotImplementedError("linear-policy rollouts serve continuous envs only (this env is %s)" % self.kind)
         D, N = self.mdps[0].D, self.num_envs
+        cols = history * D + 1
         if isinstance(theta, np.ndarray):
             t = torch.from_numpy(np.ascontiguousarray(theta)) if theta.dtype == np.float32 else None
         else:
             t = theta if torch.is_tensor(theta) and theta.dtype == torch.float32 else None
-        if t is None or tuple(t.shape) not in ((D, D + 1), (N, D, D + 1)):
-            raise ValueError(f"set_linear_policy: theta must be float32 of shape ({D}, {D + 1}) or ({N}, {D}, {D + 1})")
+        if t is None or tuple(t.shape) not in ((D, cols), (N, D, cols)):
+            raise ValueError(f"set_linear_policy: theta must be float32 of shape ({D}, {cols}) or ({N}, {D}, {cols})")
         return t.to(self.device).contiguous(), t.dim() == 3
 
-    def set_linear_policy(self, theta=None):
+    def set_linear_policy(self, theta=None, history=1):
         """The handle's linear policy for rollout_linear(): float32 ``theta`` of shape [D, D + 1] -- one policy shared by every
         env -- or [N, D, D + 1] -- one per env --, numpy or torch on any device; theta[..., r, :D] is row r of W and
         theta[..., r, D] is b[r] of  a = clip(W o + b, +-action_space_max)  (include/mdpp.h "Linear policies").  Copied on
         the current stream: parameters are replaced between rollouts without a host round trip.  None clears the policy.
-        Handles the kernel does not serve raise NotImplementedError with the reason."""
+        Handles the kernel does not serve raise NotImplementedError with the reason.
+        ``history=2``: a policy with memory, a = clip(W o + V p + b) with p the observation the env acted on at its previous
+        step (o itself on the first step of an episode); theta is [D, 2 D + 1] or [N, D, 2 D + 1], theta[..., r, D:2 D] row r
+        of V and theta[..., r, 2 D] b[r] (include/mdpp.h "Linear policies with memory").  Setting one sets every env's memory
+        to its current state.  Any other history raises ValueError."""
         if theta is None:
             capi.check(self._lib, self._h, self._lib.mdpp_clear_linear_policy(self._h), "mdpp_clear_linear_policy")
             self._linear_per_env = None
             return
-        t, per_env = self._linear_theta_arg(theta)
-        rc = self._lib.mdpp_set_linear_policy(self._h, C.c_void_p(t.data_ptr()), int(per_env), self._stream())
-        self._closed_call(rc, "mdpp_set_linear_policy")
+        if isinstance(history, bool) or history not in (1, 2):
+            raise ValueError("set_linear_policy: history must be 1 or 2")
+        t, per_env = self._linear_theta_arg(theta, int(history))
+        if history == 1:
+            rc, what = self._lib.mdpp_set_linear_policy(self._h, C.c_void_p(t.data_ptr()), int(per_env), self._stream()), "mdpp_set_linear_policy"
+        else:
+            rc = self._lib.mdpp_set_linear_policy_history(self._h, C.c_void_p(t.data_ptr()), int(per_env), 2, self._stream())
+            what = "mdpp_set_linear_policy_history"
+        self._closed_call(rc, what)
         self._linear_theta = t           # (kept until the copy queued on the stream has certainly been made)
         self._linear_per_env = per_env
+
+    @property
+    def linear_policy_history(self):
+        """The history of the linear policy in force, 1 or 2, as the handle itself says (mdpp_linear_policy_history); 0 without
+        a policy."""
+        return int(self._lib.mdpp_linear_policy_history(self._h)) if self.kind == "continuous" else 0
+
+    def _linear_cols(self):
+        """The columns of one row of theta: D + 1, or 2 D + 1 under a policy with memory."""
+        return max(1, self.linear_policy_history) * self.mdps[0].D + 1
 
     def get_linear_policy(self):
         """The handle's parameters as a device tensor, in the shape they were set in."""
         if getattr(self, "_linear_per_env", None) is None:
             raise capi.MdppError("get_linear_policy: no linear policy set")
         D = self.mdps[0].D
-        out = torch.empty(((self.num_envs,) if self._linear_per_env else ()) + (D, D + 1), dtype=torch.float32, device=self.device)
+        out = torch.empty(((self.num_envs,) if self._linear_per_env else ()) + (D, self._linear_cols()), dtype=torch.float32, device=self.device)
         self._closed_call(self._lib.mdpp_get_linear_policy(self._h, C.c_void_p(out.data_ptr()), self._stream()), "mdpp_get_linear_policy")
         return out
+
+    def get_linear_memory(self):
+        """The memory of a history=2 policy -- per env the observation it last acted on -- as a float32 device tensor [N, D]."""
+        out = torch.empty((self.num_envs, self.mdps[0].D), dtype=torch.float32, device=self.device)
+        self._closed_call(self._lib.mdpp_linear_memory(self._h, C.c_void_p(out.data_ptr()), 0, self._stream()), "mdpp_linear_memory")
+        return out
+
+    def set_linear_memory(self, p):
+        """Replace the memory of a history=2 policy: float32 [N, D], numpy or torch on any device (checkpoints)."""
+        D, N = self.mdps[0].D, self.num_envs
+        t = torch.from_numpy(np.ascontiguousarray(p)) if isinstance(p, np.ndarray) else p
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and tuple(t.shape) == (N, D)):
+            raise ValueError(f"set_linear_memory: p must be float32 of shape ({N}, {D})")
+        t = t.to(self.device).contiguous()
+        self._closed_call(self._lib.mdpp_linear_memory(self._h, C.c_void_p(t.data_ptr()), 1, self._stream()), "mdpp_linear_memory")
+        self._linear_memory_arg = t      # (kept until the copy queued on the stream has certainly been made)
 
     def alloc_rollout_linear(self, K):
         """Output buffers of rollout_linear(K): alloc_rollout(K) and the actions, float32 [K, N, D]."""
@@ -830,7 +867,7 @@ class RLToyVectorEnv:
     def _linear_search_arg(self, search, what):
         if not isinstance(search, LinearSearch):
             raise ValueError(f"{what}: search must be a LinearSearch (env.linear_search(sigma, seed=...))")
-        search.check(self.num_envs, self.mdps[0].D, self.device, what)
+        search.check(self.num_envs, self.mdps[0].D, self.device, what, cols=self._linear_cols())
         return C.byref(search.c_struct())
 
     def linear_es(self, mean_theta, sigma, lr, *, seed, episodes_per_member=1, log_generations=0):
@@ -848,12 +885,12 @@ class RLToyVectorEnv:
             if "no linear policy set" in msg:
                 raise capi.MdppError(msg)
             raise NotImplementedError(msg or "linear_es: this handle is not served")
-        D, G = self.mdps[0].D, self.num_envs // 64
+        D, G, cols = self.mdps[0].D, self.num_envs // 64, self._linear_cols()
         m = torch.from_numpy(np.ascontiguousarray(mean_theta)) if isinstance(mean_theta, np.ndarray) else mean_theta
-        if not (torch.is_tensor(m) and m.dtype == torch.float32 and tuple(m.shape) in ((D, D + 1), (G, D, D + 1))):
-            raise ValueError(f"linear_es: mean_theta must be float32 of shape ({D}, {D + 1}) or ({G}, {D}, {D + 1})")
+        if not (torch.is_tensor(m) and m.dtype == torch.float32 and tuple(m.shape) in ((D, cols), (G, D, cols))):
+            raise ValueError(f"linear_es: mean_theta must be float32 of shape ({D}, {cols}) or ({G}, {D}, {cols})")
         if m.dim() == 2:
-            m = m.unsqueeze(0).expand(G, D, D + 1)
+            m = m.unsqueeze(0).expand(G, D, cols)
         es = LinearES(m.to(self.device).contiguous(), sigma, lr, seed=seed, episodes_per_member=episodes_per_member,
                       log_generations=log_generations)
         self.linear_es_init(es)
@@ -869,7 +906,7 @@ class RLToyVectorEnv:
     def _linear_es_arg(self, es, what):
         if not isinstance(es, LinearES):
             raise ValueError(f"{what}: es must be a LinearES (env.linear_es(mean_theta, sigma, lr, seed=...))")
-        es.check(self.num_envs, self.mdps[0].D, self.device, what)
+        es.check(self.num_envs, self.mdps[0].D, self.device, what, cols=self._linear_cols())
         return C.byref(es.c_struct())
 
     def rollout_linear(self, K, out=None, *, summary=None, search=None, es=None):
