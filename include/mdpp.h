@@ -113,6 +113,7 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
 
 /* the tabular learner's algorithm (mdpp_set_learner); 2 is double Q-learning: two tables per env */
 enum { MDPP_LEARN_Q_LEARNING = 0, MDPP_LEARN_SARSA = 1, MDPP_LEARN_DOUBLE_Q = 2 };
+enum { MDPP_TRACE_ACCUMULATING = 1, MDPP_TRACE_REPLACING = 2 };    /* mdpp_set_learner_traces */
 
 /* what a discrete env's reward table is keyed by */
 enum { MDPP_REWARD_SEQUENCES = 0,     /* the last L states (rewardable_sequences, rl_toy_env.py:1837-1841) */
@@ -440,6 +441,50 @@ int mdpp_clear_learner_schedule(mdpp_env *h);
 int mdpp_get_learner_episodes(mdpp_env *h, int32_t *dev_out, void *stream);
 int mdpp_set_learner_episodes(mdpp_env *h, const int32_t *dev_in, void *stream);
 int mdpp_learner_schedule_sweep(mdpp_env *h, int on);
+
+/* Eligibility traces: SARSA(lambda) and Watkins's Q(lambda).  A handle with a q_learning or sarsa learner may carry traces: a
+ * kind (MDPP_TRACE_ACCUMULATING or MDPP_TRACE_REPLACING), float32 lambda in [0, 1] -- uniform or one per env -- and one table Z
+ * float32 [S][A] PER ENV, zeros when traces are set.  Everything in "In-kernel tabular TD learners" holds word for word -- sel,
+ * stream ids 15 and 16, the step, the target y, sarsa's carry, the reset call -- except the update.
+ * For a step that is not a reset call, with q = Q[s][a] read before anything is written, all arithmetic float32 with one
+ * rounding per operation and no FMA: d = y - q and u = alpha d are formed first; c = gamma lambda is formed once, when the
+ * lane's parameters are loaded.  Then, in order:
+ *   1. cut (q_learning only): if this step's action came from the explore branch of sel ((wE >> 1) < E, whatever action that
+ *      drew), every entry of Z becomes +0;
+ *   2. mark: accumulating Z[s][a] = Z[s][a] + 1.0f; replacing Z[s][a] = 1.0f;
+ *   3. sweep: for every entry e = 0 ... S A - 1 in ascending order, unconditionally: z = Z[e]; Q[e] = Q[e] + u z (the product
+ *      is rounded, then the sum); Z[e] = c z;
+ *   4. episode end: where the summary's `episodes` moves (terminated or truncated), Z becomes +0 for that env, after the sweep.
+ * The reset call of a next-step-autoreset env selects an action, writes it and ignores it; it touches neither Q nor Z.
+ * Z lives in a buffer of the handle, entry-major [S A][N] like Q: it crosses launches, the pieces of one call and graph
+ * replays.  mdpp_step_n_eval and its summary form neither read nor write Z.  mdpp_set_learner and mdpp_clear_learner drop the
+ * traces, as they drop a schedule; mdpp_set_q leaves Z alone.  Non-finite Q or Z: unspecified.  Denormal traces are kept, not
+ * flushed.  With lambda = 0 and a Q that holds no -0 the launch equals the traceless learner's bit for bit (q + u 1 = q + u,
+ * Q[e] + u 0 = Q[e]).
+ * mdpp_set_learner_traces(h, kind, lambda, stream): allocates and zeroes Z (on `stream`), uniform lambda.  Without a learner:
+ * MDPP_ESTATE; an unknown kind, a lambda outside [0, 1] or NaN: MDPP_EINVAL, nothing changed.
+ * mdpp_set_learner_lambda takes a HOST pointer to float32 [N]: one lambda per env (the handle's LOCAL index), range-checked
+ * like the other per-env parameters (NaN refused: MDPP_EINVAL, nothing changed), copied on `stream`; it forces the PE form as
+ * mdpp_set_learner_params does (alpha, gamma and epsilon travel as arrays).  Without traces: MDPP_ESTATE.
+ * mdpp_set_learner_traces makes lambda uniform again.  mdpp_clear_learner_traces drops the traces (the buffers stay).
+ * mdpp_get_traces / mdpp_set_traces: device pointers, float32 [N][S][A], ordered on `stream`; without traces: MDPP_ESTATE.
+ * mdpp_learner_traces: the kind in force, or 0.
+ * Served: what mdpp_set_learner serves for q_learning / sarsa on one shared MDP -- uniform and per-env parameters, the
+ * full-output, _summary and _log launches, a per-episode schedule on a shared-MDP handle.  Refused with MDPP_EUNSUPPORTED,
+ * "... eligibility traces with <what>: not built", what is in force staying as it is: double_q; per-env noise levels; one
+ * MDP per env; the schedule of mdpp_learner_schedule_sweep.  In both orders: mdpp_set_learner_traces on such a handle, and
+ * mdpp_set_noise_levels, turning mdpp_learner_per_env_mdp on (a handle with one MDP per env) or mdpp_learner_schedule_sweep on
+ * while traces are set.
+ * The launch is k_discrete_trace_rollout / k_discrete_trace_summary (mdpp_learn_kernel_name names it, with PHILOX, NOISE, UNIT,
+ * QLDS and, when present, ",PE=1" and ",SCHED=1"; the kind is a run-time field).  QLDS=1: Q and Z are both staged in LDS, entry e
+ * of lane l at dword (256 e + l) of its table, and both written back when the launch ends; QLDS=0 when a workgroup's 256 x 2
+ * tables do not fit beside the MDP's, or under MDPP_OPT_NO_LEARN_LDS: the same indexing on the two buffers. */
+int mdpp_set_learner_traces(mdpp_env *h, int kind, float lambda, void *stream);
+int mdpp_set_learner_lambda(mdpp_env *h, const float *lambda, void *stream);
+int mdpp_clear_learner_traces(mdpp_env *h);
+int mdpp_get_traces(mdpp_env *h, float *z_out_dev, void *stream);
+int mdpp_set_traces(mdpp_env *h, const float *z_in_dev, void *stream);
+int mdpp_learner_traces(mdpp_env *h);
 
 /* One MDP per env for the learner and evaluation launches.  mdpp_learner_per_env_mdp(h, on) sets a flag of the handle, off at
  * creation.  With the flag on, a handle with cfg.num_tables == cfg.num_envs (each env its own P, terminal states, rewardable
@@ -840,6 +885,9 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   env's table set are read from the handle's buffers at replay.  A schedule (mdpp_set_learner_schedule): which tables are
  *   scheduled and M go by value; the tables, the rows and the episode counters are read -- and the counters written -- at
  *   replay (mdpp_set_learner_schedule with the same tables given and the same M, or mdpp_set_learner_episodes, between replays).
+ *   Eligibility traces (mdpp_set_learner_traces): the kind and the uniform lambda go by value; Z is READ AND WRITTEN in the
+ *   handle's buffer at replay, like Q, so the traces cross replays as they cross launches (mdpp_set_traces between replays,
+ *   on the replay's stream); per-env lambdas are read from their array at replay.
  *   An episode log (mdpp_step_n_learn_log): the three log pointers and M go by value; log_count is read and written at replay and
  *   log_ret / log_len are written, so a log accumulates across replays like the five summary arrays.
  *   A linear policy (mdpp_step_n_linear / mdpp_step_n_linear_summary): shared or per-env parameters and their placement (PLDS)

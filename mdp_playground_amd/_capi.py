@@ -30,6 +30,7 @@ MAX_SCHEDULE_ENTRIES = 1 << 22                     # MDPP_MAX_SCHEDULE_ENTRIES
 ESTATE = -4               # MDPP_ESTATE
 LEARN_ALGOS = {"q_learning": 0, "sarsa": 1}        # MDPP_LEARN_*: the one-table algorithms
 MDPP_LEARN_DOUBLE_Q = 2                            # "double_q": two tables per env
+TRACE_KINDS = {"accumulating": 1, "replacing": 2}  # MDPP_TRACE_*: eligibility traces of the one-table algorithms
 
 EXPORTS = [
     "mdpp_abi_version", "mdpp_create", "mdpp_destroy", "mdpp_last_error",
@@ -57,6 +58,8 @@ EXPORTS = [
     "mdpp_noise_levels_per_env_mdp",
     "mdpp_set_learner_schedule", "mdpp_clear_learner_schedule", "mdpp_get_learner_episodes", "mdpp_set_learner_episodes",
     "mdpp_learner_schedule_sweep",
+    "mdpp_set_learner_traces", "mdpp_set_learner_lambda", "mdpp_clear_learner_traces", "mdpp_get_traces", "mdpp_set_traces",
+    "mdpp_learner_traces",
     "mdpp_step_n_learn_log",
     "mdpp_set_linear_policy", "mdpp_get_linear_policy", "mdpp_clear_linear_policy", "mdpp_step_n_linear",
     "mdpp_step_n_linear_summary", "mdpp_linear_kernel_name",
@@ -240,6 +243,12 @@ def load():
     L.mdpp_get_learner_episodes.argtypes = [vp, vp, vp]
     L.mdpp_set_learner_episodes.argtypes = [vp, vp, vp]
     L.mdpp_learner_schedule_sweep.argtypes = [vp, i32]
+    L.mdpp_set_learner_traces.argtypes = [vp, i32, C.c_float, vp]
+    L.mdpp_set_learner_lambda.argtypes = [vp, vp, vp]
+    L.mdpp_clear_learner_traces.argtypes = [vp]
+    L.mdpp_get_traces.argtypes = [vp, vp, vp]
+    L.mdpp_set_traces.argtypes = [vp, vp, vp]
+    L.mdpp_learner_traces.argtypes = [vp]
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

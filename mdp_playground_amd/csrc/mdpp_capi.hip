@@ -59,7 +59,7 @@ static void free_all(mdpp_env *h) {
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
                     h->d_img_near, h->d_s1_blob, h->d_lean_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
                     h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E, h->d_sched_E, h->d_sched_alpha, h->d_sched_row, h->d_sched_ep,
-                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta, h->d_lin_mem};
+                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta, h->d_lin_mem, h->d_trace_z, h->d_trace_lambda};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -127,6 +127,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
     h->sched_on = h->sched_eps = h->sched_alpha = h->sched_sweep = false; h->sched_R = h->sched_M = 0; h->sched_cap = 0;
     h->d_sched_E = h->d_sched_alpha = h->d_sched_row = h->d_sched_ep = nullptr;
+    h->trace_kind = 0; h->trace_lambda = 0.0f; h->d_trace_z = h->d_trace_lambda = nullptr;
     h->d_lin_theta = nullptr; h->lin_per_env = h->lin_ready = false;
     h->lin_hist = 1; h->lin_cap = 0; h->d_lin_mem = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
@@ -1424,6 +1425,8 @@ extern "C" const char *mdpp_policy_kernel_name(mdpp_env *h, int K) {
 // ---- ... of in-kernel tabular TD learners (mdpp_discrete_learn.hip) ----
 // what a handle that would need SCHED on the NLEV or PM forms is told while mdpp_learner_schedule_sweep is off
 static const char *const kSchedNotBuilt = "an epsilon/alpha schedule with per-env noise levels / one MDP per env: not built";
+// what a handle that would need traces on a form that has no trace kernel is told (+ "<what>: not built")
+static const char *const kTraceNotBuilt = "eligibility traces with ";
 static std::string sched_owns(const char *fn, const char *what) {
     return std::string(fn) + ": " + what + " follows the schedule in force (mdpp_set_learner_schedule); mdpp_clear_learner_schedule first";
 }
@@ -1471,6 +1474,7 @@ extern "C" int mdpp_set_learner(mdpp_env *h, int algo, float alpha, float gamma,
     h->learn_pe = h->learn_pe_stale = 0;                         // all three uniform
     h->nl_fill_valid = false;
     h->sched_on = false;         // (a new learner starts without a schedule: the next one zeroes the counters)
+    h->trace_kind = 0;           // ... and without traces
     h->learn_ready = true;
     return MDPP_OK;
 }
@@ -1480,6 +1484,7 @@ extern "C" int mdpp_learner_per_env_mdp(mdpp_env *h, int on) {
     // (a shared MDP, or no discrete handle: accepted, nothing changes)
     if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
     if (on && h->sched_on && !h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kSchedNotBuilt);
+    if (on && h->trace_kind) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kTraceNotBuilt + "one MDP per env: not built");
     if (h->learn_pm && !on) {
         h->learn_ready = false;                          // (as mdpp_clear_learner: the buffers stay, the schedule goes)
         h->sched_on = false;
@@ -1503,6 +1508,8 @@ extern "C" int mdpp_clear_learner(mdpp_env *h) {
     if (!h) return MDPP_EINVAL;
     h->learn_ready = false;      // (the buffers stay: a launch queued earlier may still use them)
     h->sched_on = false;
+    h->trace_kind = 0;
+    h->learn_pe &= ~8u;
     return MDPP_OK;
 }
 
@@ -1622,6 +1629,7 @@ extern "C" int mdpp_clear_learner_schedule(mdpp_env *h) {
 extern "C" int mdpp_learner_schedule_sweep(mdpp_env *h, int on) {
     if (!h) return MDPP_EINVAL;
     if (h->cfg.kind != MDPP_KIND_DISCRETE) return MDPP_OK;       // (no discrete handle: accepted, nothing changes)
+    if (on && h->trace_kind) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_schedule_sweep: ") + kTraceNotBuilt + "the schedule of mdpp_learner_schedule_sweep: not built");
     // (off: a schedule that runs with levels or one MDP per env goes, as by mdpp_clear_learner_schedule; any other stays)
     if (h->sched_sweep && !on && h->sched_on && (h->nl_on || h->learn_pm)) h->sched_on = false;
     h->sched_sweep = on != 0;
@@ -1651,12 +1659,88 @@ extern "C" int mdpp_set_learner_episodes(mdpp_env *h, const int32_t *dev_in, voi
     return MDPP_OK;
 }
 
+// ---- eligibility traces of the q_learning / sarsa learner (mdpp_discrete_trace.hpp) ----
+extern "C" int mdpp_set_learner_traces(mdpp_env *h, int kind, float lambda, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    const char *const fn = "mdpp_set_learner_traces: ";
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, std::string(fn) + "no learner set (mdpp_set_learner)");
+    if (kind != MDPP_TRACE_ACCUMULATING && kind != MDPP_TRACE_REPLACING) return fail(h, MDPP_EINVAL, std::string(fn) + "unknown kind");
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(h, MDPP_EINVAL, std::string(fn) + "need lambda in [0, 1]");      // (NaN fails both)
+    if (h->learn_algo == MDPP_LEARN_DOUBLE_Q) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "double_q: not built");
+    if (h->nl_on) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "per-env noise levels: not built");
+    if (h->learn_pm && h->cfg.num_tables != 1) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "one MDP per env: not built");
+    if (h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "the schedule of mdpp_learner_schedule_sweep: not built");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t N = (size_t)h->cfg.num_envs, bytes = N * (size_t)h->cfg.S * (size_t)h->cfg.A * sizeof(float);
+    if (!h->d_trace_z) HIPCHK(h, hipMalloc(&h->d_trace_z, bytes));
+    if (!h->d_trace_lambda) HIPCHK(h, hipMalloc(&h->d_trace_lambda, N * 4u));
+    HIPCHK(h, hipMemsetAsync(h->d_trace_z, 0, bytes, s));
+    {   // (every env's lambda as an array too: the PE form reads it)
+        const std::vector<float> lam(N, lambda);
+        HIPCHK(h, hipMemcpyAsync(h->d_trace_lambda, lam.data(), N * 4u, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipStreamSynchronize(s));                      // (lam is this call's own: gone at return)
+    }
+    h->trace_kind = kind;
+    h->trace_lambda = lambda;
+    h->learn_pe &= ~8u;          // lambda is uniform (again)
+    if (!h->learn_pe) h->learn_pe_stale = 0;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_learner_lambda(mdpp_env *h, const float *lambda, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, "mdpp_set_learner_lambda: no learner set (mdpp_set_learner)");
+    if (!h->trace_kind) return fail(h, MDPP_ESTATE, "mdpp_set_learner_lambda: no traces set (mdpp_set_learner_traces)");
+    if (!lambda) return fail(h, MDPP_EINVAL, "mdpp_set_learner_lambda: null buffer");
+    const size_t N = (size_t)h->cfg.num_envs;
+    for (size_t i = 0; i < N; i++)                               // (NaN fails every comparison)
+        if (!(lambda[i] >= 0.0f && lambda[i] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_learner_lambda: need every lambda in [0, 1]");
+    HIPCHK(h, hipSetDevice(h->device));
+    for (void **d : {&h->d_learn_alpha, &h->d_learn_gamma, &h->d_learn_E})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
+    // (host to device from the caller's pageable memory: the runtime has read the source when the call returns)
+    HIPCHK(h, hipMemcpyAsync(h->d_trace_lambda, lambda, N * 4u, hipMemcpyHostToDevice, (hipStream_t)stream));
+    const uint32_t was = h->learn_pe;
+    h->nl_fill_valid = false;
+    h->learn_pe = was | 8u;
+    // alpha, gamma and epsilon travel as arrays now: the uniform ones are filled on the stream of the next launch
+    h->learn_pe_stale = (was ? h->learn_pe_stale : 7u) & ~h->learn_pe;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_learner_traces(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->trace_kind = 0;           // (the buffers stay: a launch queued earlier may still use them)
+    h->learn_pe &= ~8u;
+    if (!h->learn_pe) h->learn_pe_stale = 0;
+    return MDPP_OK;
+}
+
+static int learner_z_copy(mdpp_env *h, float *z_dev, bool to_handle, void *stream, const char *what) {
+    if (!h) return MDPP_EINVAL;
+    if (!z_dev) return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    if (!h->learn_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_learner)");
+    if (!h->trace_kind) return fail(h, MDPP_ESTATE, std::string(what) + ": no traces set (mdpp_set_learner_traces)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_trace_z_copy(h, z_dev, to_handle, (hipStream_t)stream);
+}
+
+extern "C" int mdpp_get_traces(mdpp_env *h, float *z_out_dev, void *stream) { return learner_z_copy(h, z_out_dev, false, stream, "mdpp_get_traces"); }
+
+extern "C" int mdpp_set_traces(mdpp_env *h, const float *z_in_dev, void *stream) {
+    return learner_z_copy(h, const_cast<float *>(z_in_dev), true, stream, "mdpp_set_traces");
+}
+
+extern "C" int mdpp_learner_traces(mdpp_env *h) { return h && h->learn_ready ? h->trace_kind : 0; }
+
 // ---- per-env noise levels of the learner and evaluation launches (mdpp_discrete_closed.hpp: NLEV) ----
 extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream) {
     if (!h) return MDPP_EINVAL;
     const std::string why = discrete_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_ESTATE, "mdpp_set_noise_levels: " + why);
     if (h->sched_on && !h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_noise_levels: ") + kSchedNotBuilt + "; mdpp_clear_learner_schedule first");
+    if (h->trace_kind) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_set_noise_levels: ") + kTraceNotBuilt + "per-env noise levels: not built; mdpp_clear_learner_traces first");
     if (h->cfg.num_tables != 1 && !(h->nl_pm && h->learn_pm)) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_noise_levels: per-env noise levels on one MDP per env: not built");
     const mdpp_config &c = h->cfg;
     if (transition_noise && !c.has_transition_noise)

@@ -73,6 +73,7 @@ int launch_discrete_learn(mdpp_env *h, const DiscreteIO &io) {
         h->learn_pe_stale = 0;
         if (!h->learn_pe) { h->nl_fill_valid = true; h->nl_fill_alpha = h->learn_alpha; h->nl_fill_gamma = h->learn_gamma; h->nl_fill_E = h->learn_E; }
     }
+    if (h->trace_kind) return launch_discrete_trace(h, io, pe);        // eligibility traces: the trace kernels (mdpp_discrete_trace.hip)
     int rc = MDPP_OK;
     if (pm) {
         with_bools([&](auto DB, auto SM, auto NL, auto SC) { rc = launch_learn_form_pm<DB(), SM(), NL(), SC()>(h, io); }, dbl, io.summary != nullptr, h->nl_on, h->sched_on);

@@ -376,6 +376,13 @@ struct mdpp_env {
     int32_t sched_R, sched_M;
     size_t sched_cap;
     void *d_sched_E, *d_sched_alpha, *d_sched_row, *d_sched_ep;
+    // Eligibility traces of the q_learning / sarsa learner (mdpp_set_learner_traces; mdpp_discrete_trace.hpp): trace_kind
+    // MDPP_TRACE_* or 0 (none) -- the learning launches take the trace kernels.  Device: one table Z per env beside Q,
+    // entry-major float32 [S A][N], and every env's lambda float32 [N] (always filled: the PE form reads it, the uniform
+    // form takes trace_lambda); per-env lambdas are bit 3 of learn_pe
+    int32_t trace_kind;
+    float trace_lambda;
+    void *d_trace_z, *d_trace_lambda;
     // the linear policy of closed-loop continuous rollouts (mdpp_set_linear_policy; mdpp_continuous_linear.hip): float32 parameters,
     // entry-major -- entry e = r (D + 1) + c of env i at [e N + i] (lin_per_env) or one shared set at [e]; allocated once for
     // N D (D + 1) entries
@@ -605,6 +612,11 @@ int launch_learn_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t 
 // (the learner's forms -- per-env hyper-parameters, double Q-learning, episode summaries with io.summary, per-env noise
 // levels, one MDP per env -- are instantiations of mdpp_discrete_learn.hpp's launch_learn_form, one translation unit each
 // (mdpp_discrete_learn_*.hip); launch_discrete_learn picks the handle's)
+// ... of a learner with eligibility traces (h->trace_kind != 0; mdpp_discrete_trace.hip, the forms: mdpp_discrete_trace.hpp,
+// one translation unit each); launch_discrete_learn hands such a handle on after filling the per-env arrays.  Z between the
+// caller's [N][S][A] and the handle's entry-major buffer
+int launch_discrete_trace(mdpp_env *h, const DiscreteIO &io, bool pe);
+int launch_trace_z_copy(mdpp_env *h, float *user_z, bool to_handle, hipStream_t s);
 // io.K steps of greedy evaluation of the learner's tables (mdpp_discrete_eval.hip; the forms with io.summary or per-env noise
 // levels: mdpp_discrete_eval.hpp's launch_eval_form, in mdpp_discrete_eval_{summary,nlev,nlev_summary}.hip)
 int launch_discrete_eval(mdpp_env *h, const DiscreteIO &io);

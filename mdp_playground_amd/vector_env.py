@@ -95,6 +95,7 @@ class RLToyVectorEnv:
         self._learn_rates = None              # [alpha, epsilon] of the learner (set_learner); None: no learner
         self._noise_levels_set = False        # set_noise_levels is in force
         self._learn_q_init = None             # the tensor last handed to set_learner / set_q, kept until its copy has been made
+        self._learn_z_init = None             # ... to set_traces
         self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
         self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
@@ -1072,6 +1073,64 @@ class RLToyVectorEnv:
             self._closed_call(self._lib.mdpp_set_learner_gamma(self._h, float(gamma)), "mdpp_set_learner_gamma")
         self._learn_send_arrays(arrays["alpha"], arrays["gamma"], arrays["epsilon"])
 
+    # ------------------------------------------------------------------ eligibility traces: SARSA(lambda) and Q(lambda)
+    def set_learner_traces(self, lam, kind="replacing"):
+        """Eligibility traces for the "q_learning" / "sarsa" learner in force (include/mdpp.h "Eligibility
+        traces"): rollout_learn then runs Watkins's Q(lambda) / SARSA(lambda) -- a second table Z [S, A] per env beside Q,
+        zeros after this call; every step cuts (q_learning, on an exploring step), marks (``kind`` "accumulating": Z[s, a] += 1;
+        "replacing": Z[s, a] = 1), sweeps Q += alpha (y - Q[s, a]) Z, Z *= gamma lambda over the whole table, and zeroes Z
+        where an episode ends.  ``lam`` is a float32 scalar in [0, 1] or a 1-D array of num_envs entries (numpy, or a torch
+        tensor on any device; env i of THIS handle learns with entry i): a lambda sweep in one launch.  Z crosses launches
+        and graph replays like Q; rollout_eval neither reads nor writes it; set_q leaves it alone; set_learner drops the
+        traces.  rollout_learn (summary= and log= too), learn_kernel_name, set_learner_rates and set_learner_schedule serve
+        the handle as it stands.  NotImplementedError, nothing changed, for "double_q", per-env noise levels, a per_env_mdp
+        learner and a sweep=True schedule (not built) -- and for turning any of those on while traces are set."""
+        self._learn_check_kind()
+        if kind not in capi.TRACE_KINDS:
+            raise ValueError(f"set_learner_traces: kind must be one of {sorted(capi.TRACE_KINDS)}, got {kind!r}")
+        arr = policy_mod.learner_param_array("lam", lam, self.num_envs)
+        if arr is None and not 0.0 <= float(np.float32(lam)) <= 1.0:
+            raise ValueError(f"lam must lie in [0, 1], got {lam!r}")
+        if self._learn_rates is None:
+            raise capi.MdppError("set_learner_traces: no learner set (set_learner)")
+        scalar = float(lam) if arr is None else float(arr[0])
+        rc = self._lib.mdpp_set_learner_traces(self._h, capi.TRACE_KINDS[kind], C.c_float(scalar), self._stream())
+        self._closed_call(rc, "mdpp_set_learner_traces")
+        if arr is not None:
+            self._closed_call(self._lib.mdpp_set_learner_lambda(self._h, capi.nptr(arr), self._stream()), "mdpp_set_learner_lambda")
+
+    def clear_learner_traces(self):
+        """Drop the traces: rollout_learn is the one-step learner again (Q stays as it is)."""
+        capi.check(self._lib, self._h, self._lib.mdpp_clear_learner_traces(self._h), "mdpp_clear_learner_traces")
+
+    @property
+    def learner_traces(self):
+        """None, "accumulating" or "replacing": the traces in force (set_learner_traces)."""
+        if self.kind != "discrete":
+            return None
+        code = self._lib.mdpp_learner_traces(self._h)
+        return {v: k for k, v in capi.TRACE_KINDS.items()}.get(code)
+
+    def _trace_shape(self):
+        return (self.num_envs, self.mdps[0].S, self.mdps[0].A)
+
+    def get_traces(self):
+        """The traces Z, float32 [N, S, A]; a copy, made on the current stream."""
+        self._learn_check_kind()
+        z = torch.empty(self._trace_shape(), dtype=torch.float32, device=self.device)
+        self._closed_call(self._lib.mdpp_get_traces(self._h, C.c_void_p(z.data_ptr()), self._stream()), "mdpp_get_traces")
+        return z
+
+    def set_traces(self, z):
+        """Replace the traces: float32 [N, S, A] on the device (copied on the current stream)."""
+        self._learn_check_kind()
+        shape = self._trace_shape()
+        if not (torch.is_tensor(z) and z.dtype == torch.float32 and z.device == self.device and tuple(z.shape) == shape):
+            raise ValueError(f"set_traces: z must be a float32 tensor of shape {shape} on {self.device}")
+        z = z.contiguous()
+        self._closed_call(self._lib.mdpp_set_traces(self._h, C.c_void_p(z.data_ptr()), self._stream()), "mdpp_set_traces")
+        self._learn_z_init = z           # (kept until the copy queued on the stream has certainly been made)
+
     # ------------------------------------------------------------------ per-episode epsilon / alpha schedules
     def set_learner_schedule(self, epsilon=None, alpha=None, row=None, sweep=False):
         """Per-EPISODE epsilon and / or alpha for rollout_learn.  ``epsilon`` and ``alpha`` are tables [M] or
@@ -1106,7 +1165,8 @@ class RLToyVectorEnv:
                                       "not built; the sweep=True schedule in force stays as it is")
         was = self._sched_sweep
         if sweep != was:
-            capi.check(self._lib, self._h, self._lib.mdpp_learner_schedule_sweep(self._h, int(sweep)), "mdpp_learner_schedule_sweep")
+            # (refused while eligibility traces are set -- not built: NotImplementedError, nothing changed)
+            self._closed_call(self._lib.mdpp_learner_schedule_sweep(self._h, int(sweep)), "mdpp_learner_schedule_sweep")
             self._sched_sweep = sweep
         rc = self._lib.mdpp_set_learner_schedule(self._h, capi.nptr(eps), capi.nptr(al), R, M, capi.nptr(rows), self._stream())
         if rc != 0 and sweep and not was:
@@ -1230,7 +1290,8 @@ class RLToyVectorEnv:
     def learn_kernel_name(self, K):
         """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
         launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning; NLEV=1: per-env
-        noise levels, set_noise_levels; SCHED=1, always last: a per-episode schedule, set_learner_schedule; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
+        noise levels, set_noise_levels; with set_learner_traces the kernel is k_discrete_trace_rollout / _summary<PHILOX, NOISE, UNIT,
+        QLDS[, PE=1][, SCHED=1]>, QLDS=1: Q and Z are both staged in LDS; SCHED=1, always last: a per-episode schedule, set_learner_schedule; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
         per-env noise levels on one MDP per env, set_noise_levels(..., per_env_mdp=True) -- the arguments come in template order,
         "...,PE=1[,DOUBLE=1],NLEV=1,PM=1|2>", and a set_learner_schedule(..., sweep=True) schedule on any of these appends
         ",SCHED=1" after everything else: "...,NLEV=1,PM=2,SCHED=1>"); empty for a handle it does not serve."""
