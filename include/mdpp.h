@@ -478,7 +478,28 @@ int mdpp_learner_schedule_sweep(mdpp_env *h, int on);
  * The launch is k_discrete_trace_rollout / k_discrete_trace_summary (mdpp_learn_kernel_name names it, with PHILOX, NOISE, UNIT,
  * QLDS and, when present, ",PE=1" and ",SCHED=1"; the kind is a run-time field).  QLDS=1: Q and Z are both staged in LDS, entry e
  * of lane l at dword (256 e + l) of its table, and both written back when the launch ends; QLDS=0 when a workgroup's 256 x 2
- * tables do not fit beside the MDP's, or under MDPP_OPT_NO_LEARN_LDS: the same indexing on the two buffers. */
+ * tables do not fit beside the MDP's, or under MDPP_OPT_NO_LEARN_LDS: the same indexing on the two buffers.
+ * Traces on one MDP per env: a lambda x seed sweep in one launch.  mdpp_learner_traces_per_env_mdp(h, on) sets a flag of the
+ * handle, off at creation.  With it off every call returns exactly what it returns without the flag, the refusals above and
+ * their messages included.  With it on AND mdpp_learner_per_env_mdp on, on a handle with cfg.num_tables == cfg.num_envs:
+ * mdpp_set_learner_traces is accepted, and so are traces together with the schedule of mdpp_learner_schedule_sweep, in either
+ * order (mdpp_learner_schedule_sweep / mdpp_set_learner_schedule while traces are set, mdpp_set_learner_traces while the flag
+ * of the schedule is on).  Nothing else changes: env i learns bit for bit (outputs, Q, Z, state record, streams, status,
+ * step counter) like env i of a handle with one shared MDP that has env i's table set, the same global env id
+ * (env_id_offset + i) and the same traces -- the rule above word for word, cut, mark, sweep and episode end, around the step
+ * of "One MDP per env"; the schedule's rules are those of mdpp_set_learner_schedule.  Still refused, with or without the flag
+ * and in both orders: double_q; per-env noise levels (mdpp_noise_levels_per_env_mdp included); the schedule of
+ * mdpp_learner_schedule_sweep on a handle with one shared MDP.
+ * The launch is the PE form with PM != 0: "k_discrete_trace_rollout<PHILOX=.,NOISE=.,UNIT=.,QLDS=.,PE=1,PM=1|2[,SCHED=1]>"
+ * (or _summary).  Placement per launch, never a refusal, by the rule of "One MDP per env" with Q and Z counted together
+ * (256 x 2 S A floats per workgroup, at most 160 KiB): {Q + Z, slots}, {Q + Z}, {slots}, {} -- QLDS=1,PM=2; QLDS=1,PM=1;
+ * QLDS=0,PM=2; QLDS=0,PM=1 -- the first one the device grants; Q and Z lie behind the slots and the shared noise cdf.
+ * What clears the flag and the traces: the flag stays until it is turned off; turning it off, or turning
+ * mdpp_learner_per_env_mdp off, on a handle with one MDP per env drops the traces (as mdpp_clear_learner_traces: the buffers
+ * stay); mdpp_set_learner and mdpp_clear_learner drop the traces as ever and leave the flag; mdpp_clear_learner_traces leaves
+ * the flag.  On a handle with one shared MDP, or one that is not discrete, the call is accepted and changes nothing.
+ * Under a graph a captured launch reads every env's table set, Q and Z from the handle's buffers at replay. */
+int mdpp_learner_traces_per_env_mdp(mdpp_env *h, int on);
 int mdpp_set_learner_traces(mdpp_env *h, int kind, float lambda, void *stream);
 int mdpp_set_learner_lambda(mdpp_env *h, const float *lambda, void *stream);
 int mdpp_clear_learner_traces(mdpp_env *h);
@@ -887,7 +908,8 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   replay (mdpp_set_learner_schedule with the same tables given and the same M, or mdpp_set_learner_episodes, between replays).
  *   Eligibility traces (mdpp_set_learner_traces): the kind and the uniform lambda go by value; Z is READ AND WRITTEN in the
  *   handle's buffer at replay, like Q, so the traces cross replays as they cross launches (mdpp_set_traces between replays,
- *   on the replay's stream); per-env lambdas are read from their array at replay.
+ *   on the replay's stream); per-env lambdas are read from their array at replay.  On one MDP per env
+ *   (mdpp_learner_traces_per_env_mdp) every env's table set is read from the handle's buffers at replay as well.
  *   An episode log (mdpp_step_n_learn_log): the three log pointers and M go by value; log_count is read and written at replay and
  *   log_ret / log_len are written, so a log accumulates across replays like the five summary arrays.
  *   A linear policy (mdpp_step_n_linear / mdpp_step_n_linear_summary): shared or per-env parameters and their placement (PLDS)

@@ -59,7 +59,7 @@ EXPORTS = [
     "mdpp_set_learner_schedule", "mdpp_clear_learner_schedule", "mdpp_get_learner_episodes", "mdpp_set_learner_episodes",
     "mdpp_learner_schedule_sweep",
     "mdpp_set_learner_traces", "mdpp_set_learner_lambda", "mdpp_clear_learner_traces", "mdpp_get_traces", "mdpp_set_traces",
-    "mdpp_learner_traces",
+    "mdpp_learner_traces", "mdpp_learner_traces_per_env_mdp",
     "mdpp_step_n_learn_log",
     "mdpp_set_linear_policy", "mdpp_get_linear_policy", "mdpp_clear_linear_policy", "mdpp_step_n_linear",
     "mdpp_step_n_linear_summary", "mdpp_linear_kernel_name",
@@ -249,6 +249,7 @@ def load():
     L.mdpp_get_traces.argtypes = [vp, vp, vp]
     L.mdpp_set_traces.argtypes = [vp, vp, vp]
     L.mdpp_learner_traces.argtypes = [vp]
+    L.mdpp_learner_traces_per_env_mdp.argtypes = [vp, i32]
     L.mdpp_graph_replay_exact.argtypes = [vp, i32]
     L.mdpp_graph_capture.argtypes = [vp, i32]
     L.mdpp_graph_set_tick_offset.argtypes = [vp, C.c_int64, vp]

@@ -33,6 +33,8 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_discrete_learn_double_pe_pm_nlev_sched.hip", "mdpp_discrete_learn_double_pe_pm_nlev_sched_summary.hip",
            "mdpp_discrete_trace.hip", "mdpp_discrete_trace_pe.hip", "mdpp_discrete_summary_trace.hip", "mdpp_discrete_summary_trace_pe.hip",
            "mdpp_discrete_trace_pe_sched.hip", "mdpp_discrete_summary_trace_pe_sched.hip",
+           "mdpp_discrete_lambda_pe_pm.hip", "mdpp_discrete_summary_lambda_pe_pm.hip",
+           "mdpp_discrete_lambda_pe_pm_sched.hip", "mdpp_discrete_summary_lambda_pe_pm_sched.hip",
            "mdpp_continuous.hip", "mdpp_continuous_line8.hip", "mdpp_continuous_linear.hip", "mdpp_continuous_summary_linear.hip",
            "mdpp_continuous_search.hip", "mdpp_continuous_summary_search.hip",
            "mdpp_continuous_es.hip", "mdpp_continuous_summary_es.hip",
@@ -50,6 +52,8 @@ INCLUDED_SOURCES = {"mdpp_discrete_lean.hip": ["mdpp_discrete_lean_e.inc"], "mdp
                     **{u: ["mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith("mdpp_discrete_learn")},
                     **{u: ["mdpp_discrete_eval.hpp"] for u in SOURCES if u.startswith("mdpp_discrete_eval")},
                     **{u: ["mdpp_discrete_trace.hpp", "mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith(("mdpp_discrete_trace", "mdpp_discrete_summary_trace"))},
+                    # (... on one MDP per env: the same header's PM forms)
+                    **{u: ["mdpp_discrete_trace.hpp", "mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith(("mdpp_discrete_lambda", "mdpp_discrete_summary_lambda"))},
                     # the closed-loop continuous units: the step and the history-2 act; the _summary and _h2 units include their family's .hip
                     **{f"mdpp_continuous_{pre}{fam}{suf}.hip": ([f"mdpp_continuous_{fam}.hip"] if pre or suf else []) + _CLOSED_DEPS
                        for fam in ("linear", "search", "es") for pre in ("", "summary_") for suf in ("", "_h2")}}
@@ -72,7 +76,9 @@ EXTRA_FLAGS = {s: SPILL_SAFE for s in ("mdpp_continuous.hip", "mdpp_continuous_l
 #  mdpp_continuous_es.hip, mdpp_continuous_summary_es.hip likewise: profiles/linear_es_resources.txt, tests/test_gpu_linear_es.py;
 #  the six *_h2.hip units -- the same kernels under a policy with memory -- likewise: profiles/linear_history_resources.txt,
 #  tests/test_gpu_linear_history.py, tests/test_gpu_linear_history_search.py;
-#  the six mdpp_discrete_trace*.hip / mdpp_discrete_summary_trace*.hip units likewise: profiles/learn_traces_resources.txt, tests/test_gpu_learn_traces.py)
+#  the six mdpp_discrete_trace*.hip / mdpp_discrete_summary_trace*.hip units likewise: profiles/learn_traces_resources.txt, tests/test_gpu_learn_traces.py;
+#  the four mdpp_discrete_lambda_pe_pm*.hip / mdpp_discrete_summary_lambda_pe_pm*.hip units -- the trace kernels on one MDP per env -- likewise:
+#  profiles/trace_seeds_resources.txt, tests/test_gpu_trace_seeds.py)
 
 
 def _hipcc():

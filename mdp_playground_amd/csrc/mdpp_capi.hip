@@ -127,7 +127,7 @@ extern "C" int mdpp_create(const mdpp_config *cfg, int device, mdpp_env **out) {
     h->d_nl_level = h->d_nl_sigma = h->d_nl_cdf = h->d_nl_T = h->d_nl_M = nullptr;
     h->sched_on = h->sched_eps = h->sched_alpha = h->sched_sweep = false; h->sched_R = h->sched_M = 0; h->sched_cap = 0;
     h->d_sched_E = h->d_sched_alpha = h->d_sched_row = h->d_sched_ep = nullptr;
-    h->trace_kind = 0; h->trace_lambda = 0.0f; h->d_trace_z = h->d_trace_lambda = nullptr;
+    h->trace_kind = 0; h->trace_lambda = 0.0f; h->trace_pm = false; h->d_trace_z = h->d_trace_lambda = nullptr;
     h->d_lin_theta = nullptr; h->lin_per_env = h->lin_ready = false;
     h->lin_hist = 1; h->lin_cap = 0; h->d_lin_mem = nullptr;
     h->d_img_state_out = h->d_img_state_final = h->d_img_rec = h->d_img_ctr = nullptr;
@@ -1431,6 +1431,10 @@ static std::string sched_owns(const char *fn, const char *what) {
     return std::string(fn) + ": " + what + " follows the schedule in force (mdpp_set_learner_schedule); mdpp_clear_learner_schedule first";
 }
 
+// mdpp_learner_traces_per_env_mdp is on and the handle runs the per-env-MDP learner: traces are served there, with the sweep
+// schedule too
+static bool trace_pm_handle(const mdpp_env *h) { return h->trace_pm && h->learn_pm && h->cfg.num_tables != 1; }
+
 static bool learner_rates_ok(float alpha, float epsilon) {
     return alpha > 0.0f && alpha <= 1.0f && epsilon >= 0.0f && epsilon <= 1.0f;      // (NaN fails both)
 }
@@ -1484,12 +1488,14 @@ extern "C" int mdpp_learner_per_env_mdp(mdpp_env *h, int on) {
     // (a shared MDP, or no discrete handle: accepted, nothing changes)
     if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
     if (on && h->sched_on && !h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kSchedNotBuilt);
-    if (on && h->trace_kind) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kTraceNotBuilt + "one MDP per env: not built");
+    if (on && h->trace_kind && !trace_pm_handle(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_per_env_mdp: ") + kTraceNotBuilt + "one MDP per env: not built");
     if (h->learn_pm && !on) {
         h->learn_ready = false;                          // (as mdpp_clear_learner: the buffers stay, the schedule goes)
         h->sched_on = false;
         if (h->nl_pm) h->nl_on = false;                  // ... and levels given on one MDP per env go with the learner that ran them
         h->nl_pm = false;
+        h->trace_kind = 0;                               // ... and so do its traces (mdpp_learner_traces_per_env_mdp; its flag stays)
+        h->learn_pe &= ~8u;
     }
     h->learn_pm = on != 0;
     return MDPP_OK;
@@ -1629,7 +1635,8 @@ extern "C" int mdpp_clear_learner_schedule(mdpp_env *h) {
 extern "C" int mdpp_learner_schedule_sweep(mdpp_env *h, int on) {
     if (!h) return MDPP_EINVAL;
     if (h->cfg.kind != MDPP_KIND_DISCRETE) return MDPP_OK;       // (no discrete handle: accepted, nothing changes)
-    if (on && h->trace_kind) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_schedule_sweep: ") + kTraceNotBuilt + "the schedule of mdpp_learner_schedule_sweep: not built");
+    // (traces: only on one MDP per env under mdpp_learner_traces_per_env_mdp, whose kernels have the SCHED form)
+    if (on && h->trace_kind && !trace_pm_handle(h)) return fail(h, MDPP_EUNSUPPORTED, std::string("mdpp_learner_schedule_sweep: ") + kTraceNotBuilt + "the schedule of mdpp_learner_schedule_sweep: not built");
     // (off: a schedule that runs with levels or one MDP per env goes, as by mdpp_clear_learner_schedule; any other stays)
     if (h->sched_sweep && !on && h->sched_on && (h->nl_on || h->learn_pm)) h->sched_on = false;
     h->sched_sweep = on != 0;
@@ -1668,8 +1675,8 @@ extern "C" int mdpp_set_learner_traces(mdpp_env *h, int kind, float lambda, void
     if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(h, MDPP_EINVAL, std::string(fn) + "need lambda in [0, 1]");      // (NaN fails both)
     if (h->learn_algo == MDPP_LEARN_DOUBLE_Q) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "double_q: not built");
     if (h->nl_on) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "per-env noise levels: not built");
-    if (h->learn_pm && h->cfg.num_tables != 1) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "one MDP per env: not built");
-    if (h->sched_sweep) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "the schedule of mdpp_learner_schedule_sweep: not built");
+    if (h->learn_pm && h->cfg.num_tables != 1 && !h->trace_pm) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "one MDP per env: not built");
+    if (h->sched_sweep && !trace_pm_handle(h)) return fail(h, MDPP_EUNSUPPORTED, std::string(fn) + kTraceNotBuilt + "the schedule of mdpp_learner_schedule_sweep: not built");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t N = (size_t)h->cfg.num_envs, bytes = N * (size_t)h->cfg.S * (size_t)h->cfg.A * sizeof(float);
@@ -1733,6 +1740,19 @@ extern "C" int mdpp_set_traces(mdpp_env *h, const float *z_in_dev, void *stream)
 }
 
 extern "C" int mdpp_learner_traces(mdpp_env *h) { return h && h->learn_ready ? h->trace_kind : 0; }
+
+extern "C" int mdpp_learner_traces_per_env_mdp(mdpp_env *h, int on) {
+    if (!h) return MDPP_EINVAL;
+    // (a shared MDP, or no discrete handle: accepted, nothing changes)
+    if (h->cfg.kind != MDPP_KIND_DISCRETE || h->cfg.num_tables == 1) return MDPP_OK;
+    if (h->trace_pm && !on && h->trace_kind) {           // (as mdpp_clear_learner_traces: the buffers stay)
+        h->trace_kind = 0;
+        h->learn_pe &= ~8u;
+        if (!h->learn_pe) h->learn_pe_stale = 0;
+    }
+    h->trace_pm = on != 0;
+    return MDPP_OK;
+}
 
 // ---- per-env noise levels of the learner and evaluation launches (mdpp_discrete_closed.hpp: NLEV) ----
 extern "C" int mdpp_set_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream) {

@@ -1,0 +1,6 @@
+// The trace-learner form <PE = 1, SUMMARY = 1, SCHED = 1> on one MDP per env, PM = 1 and PM = 2 (mdpp_discrete_trace.hpp): Q(lambda) and
+// SARSA(lambda) with every env on its own MDP and a per-episode epsilon / alpha schedule (mdpp_learner_schedule_sweep), keeping
+// episode summaries (and the episode log) -- in a translation unit of its own so that the forms compile in parallel.
+#include "mdpp_discrete_trace.hpp"
+
+template int mdpp::launch_trace_form_pm<true, true>(mdpp_env *, const mdpp::DiscreteIO &);

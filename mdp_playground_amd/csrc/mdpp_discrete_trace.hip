@@ -30,13 +30,19 @@ int launch_trace_z_copy(mdpp_env *h, float *user_z, bool to_handle, hipStream_t 
 }
 
 // K learning steps of a handle with traces (launch_discrete_learn has made its checks and filled the per-env arrays; pe: the
-// launch takes the PE form).  The setters keep such a handle to the forms built: one table, a shared MDP, no levels
+// launch takes the PE form).  The setters keep such a handle to the forms built: one table, no levels, and a shared MDP or --
+// under mdpp_learner_traces_per_env_mdp -- one MDP per env, the sweep schedule with the latter only
 int launch_discrete_trace(mdpp_env *h, const DiscreteIO &io, bool pe) {
-    if (h->learn_algo == MDPP_LEARN_DOUBLE_Q || h->nl_on || (h->learn_pm && h->cfg.num_tables != 1) || !h->d_trace_z || !h->d_trace_lambda) {
+    const bool pm = h->learn_pm && h->cfg.num_tables != 1;       // one MDP per env: the PM kernels
+    if (h->learn_algo == MDPP_LEARN_DOUBLE_Q || h->nl_on || (pm && !(h->trace_pm && pe)) || !h->d_trace_z || !h->d_trace_lambda) {
         h->err = "mdpp_step_n_learn: eligibility traces: the handle is not one the trace kernels serve";
         return MDPP_ESTATE;
     }
     int rc = MDPP_OK;
+    if (pm) {
+        with_bools([&](auto SM, auto SC) { rc = launch_trace_form_pm<SM(), SC()>(h, io); }, io.summary != nullptr, h->sched_on);
+        return rc;
+    }
     if (h->sched_on) {
         with_bools([&](auto SM) { rc = launch_trace_form<true, SM(), true>(h, io); }, io.summary != nullptr);
         return rc;

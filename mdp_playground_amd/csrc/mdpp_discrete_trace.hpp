@@ -28,7 +28,9 @@
 // everywhere else, which is what the folded loop writes, and Q[s][a] = q + u 1.0f, Z[s][a] = c 1.0f.
 //
 // The kind is a run-time, wave-uniform field of the argument block (one select at the mark): a template parameter would
-// double the 96 kernels for nothing.  Forms: <PE, SUMMARY, SCHED>, six translation units (mdpp_discrete_trace*.hip, mdpp_discrete_summary_trace*.hip).
+// double the 96 kernels for nothing.  Forms: <PE, SUMMARY, SCHED>, six translation units (mdpp_discrete_trace*.hip, mdpp_discrete_summary_trace*.hip);
+// with one MDP per env <PE = 1, SUMMARY, SCHED> x PM = 1 | 2, four more (mdpp_discrete_lambda_pe_pm*.hip, mdpp_discrete_summary_lambda_pe_pm*.hip:
+// named apart from the six, whose list a test of the shared-MDP traces pins by the word in their names).
 #pragma once
 #include "mdpp_discrete_learn.hpp"
 
@@ -198,6 +200,49 @@ __global__ __launch_bounds__(kBlock) void k_discrete_trace_summary_log(DiscreteA
     closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, 0, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
 }
 
+// PM = 1 / 2 (one MDP per env, mdpp_learner_traces_per_env_mdp): the same agent around the step's PM form, Q and Z behind the
+// envs' MDP slots and the shared noise cdf (closed_agent_lds_offset<PM>), as the traceless PM learners place Q.  Overloads
+// with PM as a seventh template argument and not a defaulted parameter of the three above: a template argument is spelled
+// out in a kernel's mangled name, and the shared-MDP kernels keep their symbols and their code.  PE = 1 always: a handle with
+// one MDP per env runs the PE learner.
+template <int PM, bool QLDS, bool PE, bool SCHED>
+__device__ __forceinline__ TraceAgent<QLDS, PE, SCHED> trace_agent_pm(const DiscreteArgs &a, const TraceArgs<PE, SCHED> &p, unsigned char *lds) {
+    const uint32_t SA = (uint32_t)a.S * (uint32_t)a.A;
+    float *const q_lds = (float *)(lds + closed_agent_lds_offset<PM>(a)) + threadIdx.x;
+    return TraceAgent<QLDS, PE, SCHED>{LearnAgent<QLDS, PE, false, SCHED>{p.l, q_lds, (uint32_t)a.A, SA, (uint32_t)a.N}, p.t, q_lds + (size_t)SA * kBlock};
+}
+
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE, bool SCHED, int PM>
+__global__ __launch_bounds__(kBlock) void k_discrete_trace_rollout(DiscreteArgs a, TraceArgs<PE, SCHED> p, int K,
+                                                                   void *__restrict__ obs,
+                                                                   float *__restrict__ reward,
+                                                                   uint8_t *__restrict__ term,
+                                                                   uint8_t *__restrict__ trunc) {
+    static_assert(PE && (PM == 1 || PM == 2), "one MDP per env runs the PE learner around the step's PM form");
+    extern __shared__ __align__(16) unsigned char lds[];
+    const ZigLds zig = closed_loop_zig_lds<NOISE>();
+    auto agent = trace_agent_pm<PM, QLDS, PE, SCHED>(a, p, lds);
+    closed_loop_rollout<PHILOX, NOISE, UNIT, false, false, PM>(a, K, !a.obs_i32, p.l.actions, obs, reward, term, trunc, lds, zig, agent);
+}
+
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE, bool SCHED, int PM>
+__global__ __launch_bounds__(kBlock) void k_discrete_trace_summary(DiscreteArgs a, TraceArgs<PE, SCHED> p, int K, EpisodeSummaryArgs sm) {
+    static_assert(PE && (PM == 1 || PM == 2), "one MDP per env runs the PE learner around the step's PM form");
+    extern __shared__ __align__(16) unsigned char lds[];
+    const ZigLds zig = closed_loop_zig_lds<NOISE>();
+    auto agent = trace_agent_pm<PM, QLDS, PE, SCHED>(a, p, lds);
+    closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, PM>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
+}
+
+template <bool PHILOX, bool NOISE, bool UNIT, bool QLDS, bool PE, bool SCHED, int PM>
+__global__ __launch_bounds__(kBlock) void k_discrete_trace_summary_log(DiscreteArgs a, TraceArgs<PE, SCHED> p, int K, EpisodeSummaryArgs sm) {
+    static_assert(PE && (PM == 1 || PM == 2), "one MDP per env runs the PE learner around the step's PM form");
+    extern __shared__ __align__(16) unsigned char lds[];
+    const ZigLds zig = closed_loop_zig_lds<NOISE>();
+    auto agent = trace_agent_pm<PM, QLDS, PE, SCHED>(a, p, lds);
+    closed_loop_rollout<PHILOX, NOISE, UNIT, true, false, PM, true>(a, K, false, nullptr, nullptr, nullptr, nullptr, nullptr, lds, zig, agent, sm);
+}
+
 // One form of the trace learner, as launch_closed_form (mdpp_discrete_closed.hpp) takes it
 template <bool PE, bool SUMMARY_, bool SCHED>
 struct TraceForm {
@@ -207,18 +252,27 @@ struct TraceForm {
     using Args = TraceArgs<PE, SCHED>;
     template <bool PH, bool NZ, bool UNIT, bool QL, int PM>
     static constexpr auto kernel() {
-        static_assert(PM == 0, "traces run on one shared MDP");
-        if constexpr (SUMMARY) return k_discrete_trace_summary<PH, NZ, UNIT, QL, PE, SCHED>;
-        else return k_discrete_trace_rollout<PH, NZ, UNIT, QL, PE, SCHED>;
+        static_assert(PM == 0 || PE, "one MDP per env runs the PE learner");
+        // (the casts pick the overload: with PM, or the shared MDP's six arguments)
+        if constexpr (PM != 0) {
+            if constexpr (SUMMARY) return static_cast<void (*)(DiscreteArgs, Args, int, EpisodeSummaryArgs)>(k_discrete_trace_summary<PH, NZ, UNIT, QL, PE, SCHED, PM>);
+            else return static_cast<void (*)(DiscreteArgs, Args, int, void *, float *, uint8_t *, uint8_t *)>(k_discrete_trace_rollout<PH, NZ, UNIT, QL, PE, SCHED, PM>);
+        } else {
+            if constexpr (SUMMARY) return static_cast<void (*)(DiscreteArgs, Args, int, EpisodeSummaryArgs)>(k_discrete_trace_summary<PH, NZ, UNIT, QL, PE, SCHED>);
+            else return static_cast<void (*)(DiscreteArgs, Args, int, void *, float *, uint8_t *, uint8_t *)>(k_discrete_trace_rollout<PH, NZ, UNIT, QL, PE, SCHED>);
+        }
     }
     template <bool PH, bool NZ, bool UNIT, bool QL, int PM>
     static constexpr auto kernel_log() {
-        static_assert(SUMMARY && PM == 0, "the episode log is kept by the summary form");
-        return k_discrete_trace_summary_log<PH, NZ, UNIT, QL, PE, SCHED>;
+        static_assert(SUMMARY, "the episode log is kept by the summary form");
+        if constexpr (PM != 0) return static_cast<void (*)(DiscreteArgs, Args, int, EpisodeSummaryArgs)>(k_discrete_trace_summary_log<PH, NZ, UNIT, QL, PE, SCHED, PM>);
+        else return static_cast<void (*)(DiscreteArgs, Args, int, EpisodeSummaryArgs)>(k_discrete_trace_summary_log<PH, NZ, UNIT, QL, PE, SCHED>);
     }
-    static void name(char *out, int ph, int nz, int unit, int ql, int) {
-        snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s>", SUMMARY ? "k_discrete_trace_summary" : "k_discrete_trace_rollout",
-                 ph, nz, unit, ql, PE ? ",PE=1" : "", SCHED ? ",SCHED=1" : "");
+    static void name(char *out, int ph, int nz, int unit, int ql, int pm) {
+        char pmtxt[16] = "";
+        if (pm) snprintf(pmtxt, sizeof pmtxt, ",PM=%d", pm);
+        snprintf(out, kNameLen, "%s<PHILOX=%d,NOISE=%d,UNIT=%d,QLDS=%d%s%s%s>", SUMMARY ? "k_discrete_trace_summary" : "k_discrete_trace_rollout",
+                 ph, nz, unit, ql, PE ? ",PE=1" : "", pmtxt, SCHED ? ",SCHED=1" : "");
     }
     static Args args(const mdpp_env *h, const DiscreteIO &io, int k0, int kc, int32_t *actions, uint32_t cdf_lds) {
         const TraceTail t{(float *)h->d_trace_z, (const float *)h->d_trace_lambda, h->trace_lambda, h->trace_kind};
@@ -232,12 +286,26 @@ int launch_trace_form(mdpp_env *h, const DiscreteIO &io) {
     return launch_closed_form<TraceForm<PE, SUMMARY, SCHED>, false>(h, io);
 }
 
-// the forms built <PE, SUMMARY, SCHED>, each defined (an explicit instantiation) in the translation unit named
+// K learning steps of one form of a handle with traces and one MDP per env (mdpp_learner_traces_per_env_mdp): the PE form's
+// PM = 1 and PM = 2 kernels; closed_agent_lds places Q + Z (TABLES = 2) and the envs' MDP slots together.  SCHED: with a
+// per-episode schedule in force (mdpp_learner_schedule_sweep)
+template <bool SUMMARY, bool SCHED>
+int launch_trace_form_pm(mdpp_env *h, const DiscreteIO &io) {
+    // (the queue of start states drawn ahead needs shared tables: the PM kernels do not carry it)
+    if (h->dargs.fast_ok || h->dargs.shared_tables) { h->err = "mdpp_step_n_learn: eligibility traces: one MDP per env: the handle has shared tables"; return MDPP_ESTATE; }
+    return launch_closed_form<TraceForm<true, SUMMARY, SCHED>, true>(h, io);
+}
+
+// the forms built <PE, SUMMARY, SCHED> and, with one MDP per env, <SUMMARY, SCHED>, each defined (an explicit instantiation) in the translation unit named
 extern template int launch_trace_form<false, false, false>(mdpp_env *, const DiscreteIO &);     // mdpp_discrete_trace.hip
 extern template int launch_trace_form<true, false, false>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_trace_pe.hip
 extern template int launch_trace_form<false, true, false>(mdpp_env *, const DiscreteIO &);      // mdpp_discrete_summary_trace.hip
 extern template int launch_trace_form<true, true, false>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_summary_trace_pe.hip
 extern template int launch_trace_form<true, false, true>(mdpp_env *, const DiscreteIO &);       // mdpp_discrete_trace_pe_sched.hip
 extern template int launch_trace_form<true, true, true>(mdpp_env *, const DiscreteIO &);        // mdpp_discrete_summary_trace_pe_sched.hip
+extern template int launch_trace_form_pm<false, false>(mdpp_env *, const DiscreteIO &);         // mdpp_discrete_lambda_pe_pm.hip
+extern template int launch_trace_form_pm<true, false>(mdpp_env *, const DiscreteIO &);          // mdpp_discrete_summary_lambda_pe_pm.hip
+extern template int launch_trace_form_pm<false, true>(mdpp_env *, const DiscreteIO &);          // mdpp_discrete_lambda_pe_pm_sched.hip
+extern template int launch_trace_form_pm<true, true>(mdpp_env *, const DiscreteIO &);           // mdpp_discrete_summary_lambda_pe_pm_sched.hip
 
 } // namespace mdpp

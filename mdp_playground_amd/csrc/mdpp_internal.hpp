@@ -379,9 +379,13 @@ struct mdpp_env {
     // Eligibility traces of the q_learning / sarsa learner (mdpp_set_learner_traces; mdpp_discrete_trace.hpp): trace_kind
     // MDPP_TRACE_* or 0 (none) -- the learning launches take the trace kernels.  Device: one table Z per env beside Q,
     // entry-major float32 [S A][N], and every env's lambda float32 [N] (always filled: the PE form reads it, the uniform
-    // form takes trace_lambda); per-env lambdas are bit 3 of learn_pe
+    // form takes trace_lambda); per-env lambdas are bit 3 of learn_pe.
+    // trace_pm: mdpp_learner_traces_per_env_mdp -- traces are accepted on a handle with one MDP per env whose learn_pm is on,
+    // and together with the schedule of mdpp_learner_schedule_sweep there (the trace kernels with PM != 0; only ever set on a
+    // discrete handle with num_tables != 1)
     int32_t trace_kind;
     float trace_lambda;
+    bool trace_pm;
     void *d_trace_z, *d_trace_lambda;
     // the linear policy of closed-loop continuous rollouts (mdpp_set_linear_policy; mdpp_continuous_linear.hip): float32 parameters,
     // entry-major -- entry e = r (D + 1) + c of env i at [e N + i] (lin_per_env) or one shared set at [e]; allocated once for

@@ -102,6 +102,7 @@ class RLToyVectorEnv:
         self._learn_sched = None              # set_learner_schedule's validated arrays while a schedule is in force
         self._nl_pm = False                   # set_noise_levels(per_env_mdp=True) is in force (the handle's second flag is on)
         self._sched_sweep = False             # set_learner_schedule(sweep=True) has turned the handle's mdpp_learner_schedule_sweep flag on
+        self._trace_pm = False                # set_learner_traces(per_env_mdp=True) is in force (the handle's mdpp_learner_traces_per_env_mdp flag is on)
         if seeds is not None:
             if num_envs is not None and num_envs != len(seeds):
                 raise ValueError("num_envs != len(seeds)")
@@ -1000,6 +1001,7 @@ class RLToyVectorEnv:
             self._learn_pm = False
             self._learn_sched = None
             self._drop_noise_levels_per_env_mdp()
+            RLToyVectorEnv._drop_traces_per_env_mdp(self)
             return
         if alpha is None or gamma is None or epsilon is None:
             raise ValueError("set_learner: alpha, gamma and epsilon are required")
@@ -1027,6 +1029,7 @@ class RLToyVectorEnv:
             capi.check(self._lib, self._h, self._lib.mdpp_learner_per_env_mdp(self._h, 0), "mdpp_learner_per_env_mdp")
             raise NotImplementedError(msg.decode() if msg else "mdpp_set_learner: unsupported")
         self._closed_call(rc, "mdpp_set_learner")
+        RLToyVectorEnv._drop_traces_per_env_mdp(self)      # (mdpp_set_learner has dropped the traces: their opt-in ends with them)
         self._learn_pm = bool(per_env_mdp)
         self._learn_sched = None         # (mdpp_set_learner drops the schedule and its counters)
         self._learn_q_init = q           # (kept until the copy queued on the stream has certainly been made)
@@ -1074,7 +1077,14 @@ class RLToyVectorEnv:
         self._learn_send_arrays(arrays["alpha"], arrays["gamma"], arrays["epsilon"])
 
     # ------------------------------------------------------------------ eligibility traces: SARSA(lambda) and Q(lambda)
-    def set_learner_traces(self, lam, kind="replacing"):
+    def _drop_traces_per_env_mdp(self):
+        # (the traces are gone: the opt-in of set_learner_traces(per_env_mdp=True) goes with them.  set_learner calls this unbound
+        #  and the flag is read with a default: an object that carries the learner's attributes alone never had the opt-in)
+        if getattr(self, "_trace_pm", False):
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_traces_per_env_mdp(self._h, 0), "mdpp_learner_traces_per_env_mdp")
+            self._trace_pm = False
+
+    def set_learner_traces(self, lam, kind="replacing", per_env_mdp=False):
         """Eligibility traces for the "q_learning" / "sarsa" learner in force (include/mdpp.h "Eligibility
         traces"): rollout_learn then runs Watkins's Q(lambda) / SARSA(lambda) -- a second table Z [S, A] per env beside Q,
         zeros after this call; every step cuts (q_learning, on an exploring step), marks (``kind`` "accumulating": Z[s, a] += 1;
@@ -1084,24 +1094,58 @@ class RLToyVectorEnv:
         and graph replays like Q; rollout_eval neither reads nor writes it; set_q leaves it alone; set_learner drops the
         traces.  rollout_learn (summary= and log= too), learn_kernel_name, set_learner_rates and set_learner_schedule serve
         the handle as it stands.  NotImplementedError, nothing changed, for "double_q", per-env noise levels, a per_env_mdp
-        learner and a sweep=True schedule (not built) -- and for turning any of those on while traces are set."""
+        learner and a sweep=True schedule (not built) -- and for turning any of those on while traces are set.
+        ``per_env_mdp=True`` on a handle built with ``seeds=[...]`` or ``mdps=[...]`` whose learner was set with
+        ``per_env_mdp=True``: the traces are accepted on one MDP per env, and together with a ``sweep=True``
+        schedule there, in either order -- a lambda x seed sweep with per-episode decay in ONE launch; env i learns bit for bit
+        like env i of a shared-MDP handle built on its seed.  get_traces / set_traces, set_learner_rates, per-env ``lam``,
+        summary= and log=, rollout_eval and learn_kernel_name ("...,PE=1,PM=1|2[,SCHED=1]>") serve the handle unchanged;
+        "double_q", per-env noise levels and a sweep=True schedule on a shared MDP stay refused.  ValueError on a handle with
+        one shared MDP, before any device work; a one-MDP-per-env handle whose learner lacks per_env_mdp=True raises the
+        learner's refusal.  While such traces are in force a call without ``per_env_mdp=True`` is refused
+        (NotImplementedError) and what is in force stays; a call the library refuses leaves the opt-in as it was.  The opt-in
+        ends with clear_learner_traces() and set_learner(...)."""
+        if per_env_mdp and not self._per_env:
+            raise ValueError("set_learner_traces: per_env_mdp=True needs one MDP per env (seeds=[...] or mdps=[...]); this handle has one shared MDP")
         self._learn_check_kind()
         if kind not in capi.TRACE_KINDS:
             raise ValueError(f"set_learner_traces: kind must be one of {sorted(capi.TRACE_KINDS)}, got {kind!r}")
         arr = policy_mod.learner_param_array("lam", lam, self.num_envs)
         if arr is None and not 0.0 <= float(np.float32(lam)) <= 1.0:
             raise ValueError(f"lam must lie in [0, 1], got {lam!r}")
+        want_pm = bool(per_env_mdp) and self._per_env
+        if want_pm and not self._learn_pm:
+            # (no learner can be in force here: set_learner refuses this handle without its own opt-in, in these words)
+            raise NotImplementedError("mdpp_set_learner_traces: learner rollouts need one shared MDP (this handle has one MDP per env: "
+                                      "seeds=[...]); set_learner(..., per_env_mdp=True) first")
         if self._learn_rates is None:
             raise capi.MdppError("set_learner_traces: no learner set (set_learner)")
         scalar = float(lam) if arr is None else float(arr[0])
+        if self._trace_pm and not want_pm:
+            # (the call without the opt-in, refused as on a handle that never had it -- before the handle is touched)
+            raise NotImplementedError("mdpp_set_learner_traces: eligibility traces with one MDP per env: not built; the per_env_mdp=True "
+                                      "traces in force stay as they are")
+        flipped = want_pm and not self._trace_pm
+        if flipped:
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_traces_per_env_mdp(self._h, 1), "mdpp_learner_traces_per_env_mdp")
         rc = self._lib.mdpp_set_learner_traces(self._h, capi.TRACE_KINDS[kind], C.c_float(scalar), self._stream())
+        if rc != 0 and flipped:
+            # (the opt-in goes back to what it was.  Read the reason first: the flag call keeps it)
+            msg = self._lib.mdpp_last_error(self._h)
+            capi.check(self._lib, self._h, self._lib.mdpp_learner_traces_per_env_mdp(self._h, 0), "mdpp_learner_traces_per_env_mdp")
+            if rc == capi.EUNSUPPORTED:
+                raise NotImplementedError(msg.decode() if msg else "mdpp_set_learner_traces: unsupported")
+            raise capi.MdppError("mdpp_set_learner_traces failed (%d): %s" % (rc, msg.decode() if msg else ""))
         self._closed_call(rc, "mdpp_set_learner_traces")
+        self._trace_pm = want_pm
         if arr is not None:
             self._closed_call(self._lib.mdpp_set_learner_lambda(self._h, capi.nptr(arr), self._stream()), "mdpp_set_learner_lambda")
 
     def clear_learner_traces(self):
-        """Drop the traces: rollout_learn is the one-step learner again (Q stays as it is)."""
+        """Drop the traces: rollout_learn is the one-step learner again (Q stays as it is).  The ``per_env_mdp=True`` opt-in of
+        set_learner_traces goes with them."""
         capi.check(self._lib, self._h, self._lib.mdpp_clear_learner_traces(self._h), "mdpp_clear_learner_traces")
+        self._drop_traces_per_env_mdp()
 
     @property
     def learner_traces(self):
@@ -1155,7 +1199,10 @@ class RLToyVectorEnv:
         refused (NotImplementedError) and what is in force stays; a call the library refuses leaves the opt-in as it was.
         Like noise levels the schedule is
         configuration, and its counters are the learner's, not the env's: get_augmented_state / set_augmented_state carry
-        neither -- a checkpoint keeps learner_episodes() beside get_q() and gives both back (set_learner_episodes, set_q)."""
+        neither -- a checkpoint keeps learner_episodes() beside get_q() and gives both back (set_learner_episodes, set_q).
+        With eligibility traces: a plain schedule is served on a shared MDP, a ``sweep=True`` one on a per_env_mdp learner whose
+        traces were set with ``per_env_mdp=True``, in either order; a ``sweep=True`` schedule with traces on a
+        shared MDP is refused."""
         eps, al, rows, R, M = policy_mod.learner_schedule_arrays(epsilon, alpha, row, self.num_envs)
         self._learn_check_kind()
         sweep = bool(sweep)
@@ -1165,7 +1212,8 @@ class RLToyVectorEnv:
                                       "not built; the sweep=True schedule in force stays as it is")
         was = self._sched_sweep
         if sweep != was:
-            # (refused while eligibility traces are set -- not built: NotImplementedError, nothing changed)
+            # (refused while eligibility traces are set on a shared MDP -- not built: NotImplementedError, nothing changed; with
+            #  set_learner_traces(..., per_env_mdp=True) traces it is accepted)
             self._closed_call(self._lib.mdpp_learner_schedule_sweep(self._h, int(sweep)), "mdpp_learner_schedule_sweep")
             self._sched_sweep = sweep
         rc = self._lib.mdpp_set_learner_schedule(self._h, capi.nptr(eps), capi.nptr(al), R, M, capi.nptr(rows), self._stream())
@@ -1291,7 +1339,7 @@ class RLToyVectorEnv:
         """Name (with template arguments) of the kernel rollout_learn(K) launches (mdpp_learn_kernel_name; nothing is
         launched; QLDS=1: the Q-tables are staged in LDS; PE=1: per-env parameters; DOUBLE=1: double Q-learning; NLEV=1: per-env
         noise levels, set_noise_levels; with set_learner_traces the kernel is k_discrete_trace_rollout / _summary<PHILOX, NOISE, UNIT,
-        QLDS[, PE=1][, SCHED=1]>, QLDS=1: Q and Z are both staged in LDS; SCHED=1, always last: a per-episode schedule, set_learner_schedule; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
+        QLDS[, PE=1][, PM=1|2][, SCHED=1]>, QLDS=1: Q and Z are both staged in LDS; SCHED=1, always last: a per-episode schedule, set_learner_schedule; PM=2 / PM=1: one MDP per env, staged in LDS / read in global memory; NLEV=1 with PM:
         per-env noise levels on one MDP per env, set_noise_levels(..., per_env_mdp=True) -- the arguments come in template order,
         "...,PE=1[,DOUBLE=1],NLEV=1,PM=1|2>", and a set_learner_schedule(..., sweep=True) schedule on any of these appends
         ",SCHED=1" after everything else: "...,NLEV=1,PM=2,SCHED=1>"); empty for a handle it does not serve."""

@@ -34,7 +34,7 @@ RULES = """## The rules behind the tables (first match wins; sources: the `launc
 | `k_discrete_rollout_quiet<...,ROLES,PN,RN,PHILOX,NPH,UNIT,SF,PE>` | K >= 16: one shared MDP whose tables fit 60 KiB of LDS, any S <= 255, L <= 7, irrelevant sub-space, both noises, non-unit sequence rewards (`UNIT=0`: numpy streams, no irrelevant sub-space); ROLES = 2 / 3 for full blocks and K >= 32 (3: autoreset without reward noise = a start-state queue wave; or reward noise alone on numpy streams = `XR`, the env stream by position); `SF`: ROLES = 3, L = 1, same-step autoreset, no step limit, every-step pay, S <= 128; `PE`: one MDP per env, S <= 16, unit rewards, numpy streams, no transition noise | `mdpp_discrete_quiet.hip`: `launch_discrete_quiet`, `launch_discrete_quiet_nu` |
 | `k_discrete_step<PHILOX,NOISE,UNIT,LDSTAB,IRR>` | everything else (per-env MDPs in short rollouts, custom R(s, a), tables beyond LDS, episode statistics, ...) | `mdpp_discrete.hip`: `launch_discrete_step` |
 | `k_discrete_learn_rollout` / `k_discrete_learn_summary<PHILOX,NOISE,UNIT,QLDS[,PE][,DOUBLE][,NLEV][,PM][,SCHED]>` | `mdpp_step_n_learn` / `mdpp_step_n_learn_summary` only (no `mdpp_step_n` launch; `mdpp_learn_kernel_name` answers): the in-kernel learners on a handle `mdpp_set_learner` serves.  `PE`: per-env parameters; `DOUBLE`: double Q-learning; `NLEV`: per-env noise levels (`mdpp_set_noise_levels`); `PM=2` / `PM=1`: one MDP per env, staged in LDS / read in global memory (`mdpp_learner_per_env_mdp`); `SCHED`, always last: a per-episode schedule (`mdpp_set_learner_schedule`) -- on a shared MDP without levels, and together with `NLEV` and / or `PM` under `mdpp_learner_schedule_sweep` (`...,PE=1,NLEV=1,PM=2,SCHED=1>`); a schedule changes no LDS placement | `mdpp_discrete_learn.hip`: `launch_discrete_learn`; `mdpp_discrete_closed.hpp`: `launch_closed_form`, `closed_agent_lds` |
-| `k_discrete_trace_rollout` / `k_discrete_trace_summary<PHILOX,NOISE,UNIT,QLDS[,PE][,SCHED]>` | `mdpp_step_n_learn` / `_summary` / `_log` on a handle with eligibility traces (`mdpp_set_learner_traces`: SARSA(lambda), Watkins's Q(lambda)): a `q_learning` or `sarsa` learner on one shared MDP without per-env noise levels.  `QLDS`: Q and Z are both staged in LDS (the placement of two tables, as `DOUBLE`); `PE`: per-env parameters (a per-env lambda forces it); `SCHED`: a per-episode schedule | `mdpp_discrete_trace.hip`: `launch_discrete_trace`; `mdpp_discrete_trace.hpp`: `TraceAgent`, `TraceForm` |
+| `k_discrete_trace_rollout` / `k_discrete_trace_summary<PHILOX,NOISE,UNIT,QLDS[,PE][,PM][,SCHED]>` | `mdpp_step_n_learn` / `_summary` / `_log` on a handle with eligibility traces (`mdpp_set_learner_traces`: SARSA(lambda), Watkins's Q(lambda)): a `q_learning` or `sarsa` learner without per-env noise levels, on one shared MDP or -- under `mdpp_learner_traces_per_env_mdp` -- on one MDP per env.  `QLDS`: Q and Z are both staged in LDS (the placement of two tables, as `DOUBLE`); `PE`: per-env parameters (a per-env lambda forces it, one MDP per env too); `PM = 1 / 2`: one MDP per env, read in global memory / staged in LDS slots (placed with Q + Z by `closed_agent_lds`); `SCHED`: a per-episode schedule (with `PM` under `mdpp_learner_schedule_sweep`) | `mdpp_discrete_trace.hip`: `launch_discrete_trace`; `mdpp_discrete_trace.hpp`: `TraceAgent`, `TraceForm`, `launch_trace_form_pm` (the four `mdpp_discrete_{,summary_}lambda_pe_pm{,_sched}.hip` units) |
 | `k_continuous_step1<...,PAR>` | `mdpp_step` on the fast continuous shapes (`PAR = 1`: transition noise on numpy streams at D >= 8) | `mdpp_continuous_fast.hip`: `launch_continuous_step1` |
 | `k_continuous_rollout_fast<D,ORDER,NREL,NOISE,HELPER,GEN,PHILOX,NPROD,Z0>` | move_to_a_point, relevant dimensions = the first n_rel, no pictures, an explicit target_point, <= 8 terminal cubes, (D, order, n_rel) one of the built shapes (D in {2, 4, 8, 12}, orders 1-2, n_rel = D or a prefix; D = 2 also order 3); `action_loss_weight` != 0 or `action_space_max` <= 1e18 (a box that admits actions whose squares overflow float32 needs the penalty computed at weight 0 too: the general kernel); next-step autoreset only without noise or on Philox streams; `HELPER`: noise, K >= 16, full blocks; `NPROD = 2` on numpy streams (generator / walker / consumer) at D >= 8 or D = 2; `Z0`: D = 2 with every present noise key at sigma 0 | `mdpp_continuous_fast.hip`: `launch_continuous_fast`; the shape flag: `mdpp_capi.hip` (`fast_ok`, `next_ok`) |
 | `k_continuous_line_rollout` | move_along_a_line with every dimension relevant, D in {2, 4}, order <= 2, no noise, delay 0, K >= 4 | `mdpp_continuous_line.hip`: `launch_continuous_line` |
