@@ -105,7 +105,8 @@ enum { MDPP_OPT_NO_PIPE = 1u << 0,         /* discrete: no three-role k_discrete
        MDPP_OPT_NO_PM_LDS = 1u << 21,      /* one MDP per env (mdpp_learner_per_env_mdp): the envs' tables stay in global memory (PM=1) */
        MDPP_OPT_NO_PM_NLEV_LDS = 1u << 22,   /* per-env noise levels on one MDP per env (mdpp_noise_levels_per_env_mdp): the per-level cdfs stay
                                               in global memory in the PM kernels (MDPP_OPT_NO_NLEV_LDS keeps its meaning for a shared MDP) */
-       MDPP_OPT_NO_LINEAR_LDS = 1u << 23 };  /* k_continuous_linear_rollout / _summary: the linear policies' parameters stay in global memory (PLDS=0) */
+       MDPP_OPT_NO_LINEAR_LDS = 1u << 23,    /* k_continuous_linear_rollout / _summary: the linear policies' parameters stay in global memory (PLDS=0) */
+       MDPP_OPT_NO_GRID_QLDS = 1u << 24 };   /* k_grid_learn_rollout: the grid learners' Q-tables stay in global memory (QLDS=0) */
 
 /* transition-noise levels one handle serves at a time (mdpp_set_noise_levels) */
 #define MDPP_MAX_NOISE_LEVELS 16
@@ -591,6 +592,67 @@ int mdpp_step_n_learn_log(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev,
                           int32_t *log_count_dev, double *log_ret_dev, int32_t *log_len_dev, int M, void *stream);
 int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream);
 
+/* Grid learners: one tabular TD agent per GRIDWORLD.  A grid handle with grid_dims == 2 may carry ONE learner -- algo
+ * (MDPP_LEARN_Q_LEARNING or MDPP_LEARN_SARSA), n_actions (4 or 5), a 64-bit seed, float32 alpha[N] in (0, 1], gamma[N] and
+ * epsilon[N] in [0, 1], and one table Q float32 [S][A] PER ENV -- and mdpp_step_n_grid_learn runs K steps of "select
+ * epsilon-greedily from the env's own Q, step, update that Q" in one launch.  The parameters always travel as [N] arrays (a
+ * uniform value is an array of equal entries: there is no separate uniform kernel form); env i of the handle (its LOCAL
+ * index) learns with alpha[i], gamma[i], E[i] = ceil((double)epsilon[i] 2^31), formed on the host.
+ *   State index: with (g0, g1) = grid_shape and the env in cell (c0, c1):  s = c0 (g1 + 1) + c1,  S = (g0 + 1)(g1 + 1).  The
+ *     "+ 1": reset() draws floor(uniform(0, g + 1)) per coordinate, so the index g, one past the grid, occurs as an episode's
+ *     first cell; the first move clips it away.
+ *   Action index to vector: j < 4: d = j >> 1, component d is +1 if (j & 1) == 0 else -1, the other component 0; j == 4 (only
+ *     with n_actions == 5): the all-zero noop.  In order: (+1,0), (-1,0), (0,+1), (0,-1)[, (0,0)].
+ *   sel(s, t), the target, the update and sarsa's carried action are those of "In-kernel tabular TD learners" above, word for
+ *     word: stream ids 15 and 16 keyed by (learner seed, global env id, t >> 2), word t & 3; (wE >> 1) < E[i] explores with
+ *     a = (uint64(wA) A) >> 32; otherwise the lowest j maximising Q[s][j]; float32 arithmetic, one rounding per operation, no
+ *     fused multiply-add.  r is the float32 reward as the launch writes it; terminated is the step's own terminated output,
+ *     the latched target flag (with autoreset disabled it stays set and y = r from then on); s' is the cell after the move,
+ *     before any autoreset; a truncation that resets drops sarsa's carry; a call's first step always selects afresh; on the
+ *     reset call of a next-step-autoreset env an action is selected from the cell in the record, written and ignored, and
+ *     nothing is updated.  Transition noise re-draws the move inside the env, from the env's own action stream: the learner
+ *     still updates Q[s][a] for the a it chose.
+ *   The learner reads none of the env's streams.  actions_out_dev is int32 [K][N][2], the action VECTORS taken: mdpp_step_n on
+ *     an identically built handle, fed those vectors, writes the same observations, rewards, terminated and truncated and
+ *     leaves the same state, streams, status words and step counter, bit for bit, in both RNG modes.
+ *   Greedy evaluation (mdpp_step_n_grid_eval): K steps of the lowest argmax of Q[s]; nothing is drawn, nothing is updated,
+ *     no parameter is read; the tables are left bit for bit as they were.
+ *   The _summary forms run the same steps, write no [K][N] array and keep the caller's five [N] arrays by the rule of
+ *     "Episode summaries" above.
+ * Served: grid handles with grid_dims == 2; make_denser on or off; reward_every_n_steps, reward scale, shift and terminal
+ * reward; max_episode_steps; the three autoreset modes; int64 or int32 observations; both RNG modes; the transition- and
+ * reward-noise keys absent, at 0 or above 0.  Refused with MDPP_EUNSUPPORTED and the reason in mdpp_last_error, from
+ * mdpp_set_grid_learner already: discrete and continuous handles ("grid learners serve grid envs only"),
+ * irrelevant_features (grid_dims == 4), image observations, episode_stats, and tables of num_envs S A 4 bytes >= 2^32 (the
+ * kernels address Q with 32-bit byte offsets).  Without a learner the launches and the Q accessors return MDPP_ESTATE
+ * ("no learner set").
+ * mdpp_set_grid_learner (re)starts the learner: alpha, gamma, epsilon are HOST pointers to float32 [N] (range-checked, NaN
+ * refused: MDPP_EINVAL, nothing changed), Q = q_init_dev (float32 [N][S][A], DEVICE, copied on `stream`) or zeros when NULL.
+ * mdpp_set_grid_learner_params: host [N] pointers, NULL keeps the current values; range-checked like
+ * mdpp_set_learner_params, an error changes nothing.  mdpp_get_grid_q / mdpp_set_grid_q: device pointers, float32 [N][S][A],
+ * ordered on `stream`.  mdpp_clear_grid_learner forgets the learner (the buffers stay for launches already queued).
+ * Kernel: k_grid_learn_rollout<PHILOX,NOISE,QLDS,EVAL,SUMMARY>, one lane per env.  Q lives in the handle entry-major: entry
+ * e = s A + j of env i at q[e N + i].  QLDS=1: each lane stages its table once per launch at q_lds[e 256 + tid] (bank = lane)
+ * and, unless EVAL, writes it back after the last step -- taken when the device grants 256 S A 4 bytes of dynamic LDS beside
+ * the kernel's static LDS (a 5 x 5 grid with 4 actions: 144 KiB); QLDS=0, or MDPP_OPT_NO_GRID_QLDS: the same indexing on the
+ * buffer.  mdpp_grid_learn_kernel_name: as mdpp_kernel_name, for the launch of mdpp_step_n_grid_learn (eval == 0) or
+ * mdpp_step_n_grid_eval, full output (summary == 0) or the _summary form; nothing is launched; empty without a learner. */
+int mdpp_set_grid_learner(mdpp_env *h, int algo, int n_actions, uint64_t seed, const float *alpha, const float *gamma,
+                          const float *epsilon, const float *q_init_dev, void *stream);
+int mdpp_clear_grid_learner(mdpp_env *h);
+int mdpp_set_grid_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream);
+int mdpp_step_n_grid_learn(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                           uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+int mdpp_step_n_grid_eval(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                          uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream);
+int mdpp_step_n_grid_learn_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                   double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+int mdpp_step_n_grid_eval_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                  double *return_sum_dev, int32_t *length_sum_dev, void *stream);
+int mdpp_get_grid_q(mdpp_env *h, float *q_out_dev, void *stream);
+int mdpp_set_grid_q(mdpp_env *h, const float *q_in_dev, void *stream);
+const char *mdpp_grid_learn_kernel_name(mdpp_env *h, int K, int eval, int summary);
+
 /* Linear policies: closed-loop CONTINUOUS rollouts.  The handle holds float32 parameters theta, one set shared by every env
  * ([D][D + 1]) or one per env ([N][D][D + 1]; per_env != 0): theta[.., r, c] for c < D is W[r][c], theta[.., r, D] is b[r]
  * (D = state_space_dim = action_space_dim).  At every step of a launch env i forms its action from o = the state in its
@@ -926,6 +988,12 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   A linear policy ES (mdpp_step_n_linear_es / _summary): likewise -- the nine pointers, seed, episodes_per_member and
  *   log_rows are those of the capture; the arrays and the candidates are read and written at replay; stream id 19 is keyed
  *   by the generation index.
+ *   A grid learner (mdpp_step_n_grid_learn / mdpp_step_n_grid_eval and their _summary forms): algo, n_actions, the seed and
+ *   the placement of the tables (QLDS, fixed at capture with the kernel options) go by value; Q is READ AND WRITTEN in the
+ *   handle's buffer at replay (mdpp_set_grid_q between replays, on the replay's stream), the alpha / gamma / epsilon arrays
+ *   are read from the handle's buffers at replay (mdpp_set_grid_learner_params: the way to change rates under a graph), and
+ *   the step counter comes through the device offset, as for the discrete learner: the learning launch replays exactly
+ *   only in capture mode, whatever the handle's RNG mode.
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

@@ -25,6 +25,8 @@ OPTIONS = {"NO_PIPE": 1 << 0, "NO_HELPER": 1 << 1, "NO_PARK": 1 << 2, "NO_CFAST"
            "NO_IMG_NEARTAB": 1 << 14, "NO_STEP1": 1 << 15, "NO_SIGMA0": 1 << 16, "NO_QUIET_SF": 1 << 17,
            "NO_LEARN_LDS": 1 << 18, "LEARN_SHORT_PIECES": 1 << 19, "NO_NLEV_LDS": 1 << 20, "NO_PM_LDS": 1 << 21,
            "NO_PM_NLEV_LDS": 1 << 22, "NO_LINEAR_LDS": 1 << 23}
+# ... of the grid learners (a table of its own: tests/test_linear_es_host.py holds OPTIONS to bits 0 - 23); set_kernel_options takes both
+GRID_OPTIONS = {"NO_GRID_QLDS": 1 << 24}
 MAX_NOISE_LEVELS = 16                              # MDPP_MAX_NOISE_LEVELS
 MAX_SCHEDULE_ENTRIES = 1 << 22                     # MDPP_MAX_SCHEDULE_ENTRIES
 ESTATE = -4               # MDPP_ESTATE
@@ -66,6 +68,9 @@ EXPORTS = [
     "mdpp_step_n_linear_search", "mdpp_step_n_linear_search_summary", "mdpp_linear_search_kernel_name",
     "mdpp_linear_es_init", "mdpp_step_n_linear_es", "mdpp_step_n_linear_es_summary", "mdpp_linear_es_kernel_name",
     "mdpp_set_linear_policy_history", "mdpp_linear_policy_history", "mdpp_linear_memory",
+    "mdpp_set_grid_learner", "mdpp_clear_grid_learner", "mdpp_set_grid_learner_params", "mdpp_step_n_grid_learn",
+    "mdpp_step_n_grid_eval", "mdpp_step_n_grid_learn_summary", "mdpp_step_n_grid_eval_summary", "mdpp_get_grid_q", "mdpp_set_grid_q",
+    "mdpp_grid_learn_kernel_name",
 ]
 
 
@@ -233,6 +238,17 @@ def load():
     L.mdpp_set_linear_policy_history.argtypes = [vp, vp, i32, i32, vp]
     L.mdpp_linear_policy_history.argtypes = [vp]
     L.mdpp_linear_memory.argtypes = [vp, vp, i32, vp]
+    L.mdpp_set_grid_learner.argtypes = [vp, i32, i32, C.c_uint64, vp, vp, vp, vp, vp]
+    L.mdpp_clear_grid_learner.argtypes = [vp]
+    L.mdpp_set_grid_learner_params.argtypes = [vp, vp, vp, vp, vp]
+    L.mdpp_step_n_grid_learn.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_step_n_grid_eval.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_step_n_grid_learn_summary.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_step_n_grid_eval_summary.argtypes = [vp, i32] + [vp] * 6
+    L.mdpp_get_grid_q.argtypes = [vp, vp, vp]
+    L.mdpp_set_grid_q.argtypes = [vp, vp, vp]
+    L.mdpp_grid_learn_kernel_name.argtypes = [vp, i32, i32, i32]
+    L.mdpp_grid_learn_kernel_name.restype = C.c_char_p
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]

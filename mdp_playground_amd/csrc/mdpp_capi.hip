@@ -59,7 +59,8 @@ static void free_all(mdpp_env *h) {
                     h->d_img_state_final, h->d_img_rec, h->d_img_ctr, h->d_line_hist, h->d_line_ws, h->d_ring64, h->d_est_cur, h->d_est_last, h->d_tick_off,
                     h->d_img_near, h->d_s1_blob, h->d_lean_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
                     h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E, h->d_sched_E, h->d_sched_alpha, h->d_sched_row, h->d_sched_ep,
-                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta, h->d_lin_mem, h->d_trace_z, h->d_trace_lambda};
+                    h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta, h->d_lin_mem, h->d_trace_z, h->d_trace_lambda,
+                    h->d_gl_q, h->d_gl_alpha, h->d_gl_gamma, h->d_gl_E};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -1946,6 +1947,161 @@ extern "C" int mdpp_current_obs(mdpp_env *h, void *obs_dev, void *stream) {
     if (h->cfg.kind == MDPP_KIND_CONTINUOUS && h->lin_ready && continuous_linear_refusal(h).empty())
         return launch_continuous_current_obs(h, (float *)obs_dev, (hipStream_t)stream);
     return launch_discrete_current_obs(h, obs_dev, (hipStream_t)stream);
+}
+
+// ---- in-kernel tabular TD learners on GRID handles (mdpp_grid_learn.hip; include/mdpp.h "Grid learners") ----
+// every element in range (NaN fails every comparison); a null array is not checked
+static bool grid_learner_params_ok(size_t N, const float *alpha, const float *gamma, const float *epsilon) {
+    for (size_t i = 0; i < N; i++) {
+        if (alpha && !(alpha[i] > 0.0f && alpha[i] <= 1.0f)) return false;
+        if (gamma && !(gamma[i] >= 0.0f && gamma[i] <= 1.0f)) return false;
+        if (epsilon && !(epsilon[i] >= 0.0f && epsilon[i] <= 1.0f)) return false;
+    }
+    return true;
+}
+
+// the given arrays into the handle's buffers on `stream` (host to device from the caller's pageable memory: the runtime has
+// read the source when the call returns; E is this call's own and needs the wait)
+static int grid_learner_send(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, hipStream_t s) {
+    const size_t N = (size_t)h->cfg.num_envs;
+    if (alpha) HIPCHK(h, hipMemcpyAsync(h->d_gl_alpha, alpha, N * 4u, hipMemcpyHostToDevice, s));
+    if (gamma) HIPCHK(h, hipMemcpyAsync(h->d_gl_gamma, gamma, N * 4u, hipMemcpyHostToDevice, s));
+    if (epsilon) {
+        std::vector<uint32_t> E(N);
+        for (size_t i = 0; i < N; i++) E[i] = (uint32_t)ceil((double)epsilon[i] * 2147483648.0);
+        HIPCHK(h, hipMemcpyAsync(h->d_gl_E, E.data(), N * 4u, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+    }
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_grid_learner(mdpp_env *h, int algo, int n_actions, uint64_t seed, const float *alpha, const float *gamma,
+                                     const float *epsilon, const float *q_init_dev, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    const std::string why = grid_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_grid_learner: " + why);
+    if (algo != MDPP_LEARN_Q_LEARNING && algo != MDPP_LEARN_SARSA) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner: algo must be q_learning or sarsa");
+    if (n_actions != 4 && n_actions != 5) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner: n_actions must be 4 or 5");
+    if (!alpha || !gamma || !epsilon) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner: null parameter array");
+    const size_t N = (size_t)h->cfg.num_envs;
+    if (!grid_learner_params_ok(N, alpha, gamma, epsilon))
+        return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner: need every alpha in (0, 1], every gamma and epsilon in [0, 1]");
+    const size_t SA = (size_t)(h->cfg.grid_shape[0] + 1) * (size_t)(h->cfg.grid_shape[1] + 1) * (size_t)n_actions;
+    // (the kernels address Q with 32-bit byte offsets)
+    if ((unsigned long long)N * SA * 4ULL >= (1ULL << 32))
+        return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_grid_learner: the Q-tables need num_envs * S * A * 4 bytes < 2^32");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->d_gl_q && h->gl_cap < SA) {                           // (hipFree waits for the launches that still use it)
+        HIPCHK(h, hipFree(h->d_gl_q));
+        h->d_gl_q = nullptr;
+        h->gl_ready = false;
+    }
+    if (!h->d_gl_q) {
+        HIPCHK(h, hipMalloc(&h->d_gl_q, N * SA * sizeof(float)));
+        h->gl_cap = SA;
+    }
+    for (void **d : {&h->d_gl_alpha, &h->d_gl_gamma, &h->d_gl_E})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
+    h->gl_A = n_actions;         // (the copy below goes by the number of actions)
+    // (on the caller's stream: behind the rollouts already queued there, ahead of the next one)
+    if (q_init_dev) {
+        int rc = launch_grid_q_copy(h, const_cast<float *>(q_init_dev), true, s);
+        if (rc) { h->gl_ready = false; return rc; }
+    } else {
+        HIPCHK(h, hipMemsetAsync(h->d_gl_q, 0, N * SA * sizeof(float), s));
+    }
+    int rc = grid_learner_send(h, alpha, gamma, epsilon, s);
+    if (rc) { h->gl_ready = false; return rc; }
+    h->gl_algo = algo; h->gl_seed = seed;
+    h->gl_ready = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_grid_learner(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->gl_ready = false;         // (the buffers stay: a launch queued earlier may still use them)
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_grid_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!h->gl_ready) return fail(h, MDPP_ESTATE, "mdpp_set_grid_learner_params: no learner set (mdpp_set_grid_learner)");
+    if (!grid_learner_params_ok((size_t)h->cfg.num_envs, alpha, gamma, epsilon))
+        return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_params: need every alpha in (0, 1], every gamma and epsilon in [0, 1]");
+    if (!alpha && !gamma && !epsilon) return MDPP_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    return grid_learner_send(h, alpha, gamma, epsilon, (hipStream_t)stream);
+}
+
+// the checks of a grid learner launch, full output (actions ... trunc) or summary (sm)
+static int step_n_grid(mdpp_env *h, const char *what, bool eval, int K, int32_t *actions, void *obs, float *reward, uint8_t *term,
+                       uint8_t *trunc, const EpisodeSummaryArgs *sm, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (K < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": K < 1");
+    if (sm ? (!sm->ret || !sm->len || !sm->episodes || !sm->return_sum || !sm->length_sum) : (!actions || !obs || !reward || !term || !trunc))
+        return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    const std::string why = grid_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
+    if (!h->gl_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_grid_learner)");
+    int rc = check_ready(h, what);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    DiscreteIO io{K, actions, obs, reward, term, trunc, nullptr, (hipStream_t)stream, nullptr};
+    io.summary = sm;
+    return launch_grid_learn(h, io, eval);
+}
+
+extern "C" int mdpp_step_n_grid_learn(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                                      uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    return step_n_grid(h, "mdpp_step_n_grid_learn", false, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, nullptr, stream);
+}
+
+extern "C" int mdpp_step_n_grid_eval(mdpp_env *h, int K, int32_t *actions_out_dev, void *obs_dev, float *reward_dev,
+                                     uint8_t *terminated_dev, uint8_t *truncated_dev, void *stream) {
+    return step_n_grid(h, "mdpp_step_n_grid_eval", true, K, actions_out_dev, obs_dev, reward_dev, terminated_dev, truncated_dev, nullptr, stream);
+}
+
+extern "C" int mdpp_step_n_grid_learn_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                              double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
+    const EpisodeSummaryArgs sm{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u};
+    return step_n_grid(h, "mdpp_step_n_grid_learn_summary", false, K, nullptr, nullptr, nullptr, nullptr, nullptr, &sm, stream);
+}
+
+extern "C" int mdpp_step_n_grid_eval_summary(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev,
+                                             double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
+    const EpisodeSummaryArgs sm{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u};
+    return step_n_grid(h, "mdpp_step_n_grid_eval_summary", true, K, nullptr, nullptr, nullptr, nullptr, nullptr, &sm, stream);
+}
+
+static int grid_q_copy(mdpp_env *h, float *q_dev, bool to_handle, void *stream, const char *what) {
+    if (!h) return MDPP_EINVAL;
+    if (!q_dev) return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    const std::string why = grid_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
+    if (!h->gl_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_grid_learner)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return launch_grid_q_copy(h, q_dev, to_handle, (hipStream_t)stream);
+}
+
+extern "C" int mdpp_get_grid_q(mdpp_env *h, float *q_out_dev, void *stream) { return grid_q_copy(h, q_out_dev, false, stream, "mdpp_get_grid_q"); }
+
+extern "C" int mdpp_set_grid_q(mdpp_env *h, const float *q_in_dev, void *stream) {
+    return grid_q_copy(h, const_cast<float *>(q_in_dev), true, stream, "mdpp_set_grid_q");
+}
+
+// (a dry run: the launcher writes the kernel's name and launches nothing)
+extern "C" const char *mdpp_grid_learn_kernel_name(mdpp_env *h, int K, int eval, int summary) {
+    if (!h) return "";
+    h->kname[0] = 0;
+    if (K < 1 || !grid_learn_refusal(h).empty() || !h->gl_ready || check_ready(h, "mdpp_grid_learn_kernel_name")) return h->kname;
+    (void)hipSetDevice(h->device);
+    const EpisodeSummaryArgs sm{};
+    DiscreteIO dry{};
+    dry.K = K; dry.name_out = h->kname;
+    if (summary) dry.summary = &sm;
+    (void)launch_grid_learn(h, dry, eval != 0);
+    return h->kname;
 }
 
 // ---- closed-loop CONTINUOUS rollouts under a linear policy per env (mdpp_continuous_linear.hip) ----

@@ -399,6 +399,14 @@ struct mdpp_env {
     int lin_hist;
     size_t lin_cap;
     void *d_lin_mem;
+    // the tabular TD learner of a GRID handle (mdpp_set_grid_learner; mdpp_grid_learn.hpp): one Q-table per env, entry-major
+    // float32 [S A][N] with S = (g0 + 1)(g1 + 1), A = gl_A (4, or 5 with the noop); alpha / gamma / E always as [N] arrays on
+    // the device; gl_cap: the entries per env the table buffer was allocated for
+    void *d_gl_q, *d_gl_alpha, *d_gl_gamma, *d_gl_E;
+    uint64_t gl_seed;
+    int32_t gl_algo, gl_A;
+    size_t gl_cap;
+    bool gl_ready;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -645,6 +653,13 @@ int launch_linear_es_init(mdpp_env *h, const mdpp_linear_es &es, hipStream_t s);
 int launch_continuous_current_obs(mdpp_env *h, float *obs, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
+// io.K steps of the grid handle's tabular learner, or (eval) of greedy evaluation of its tables (mdpp_grid_learn.hip; with
+// io.summary the summary form, mdpp_grid_summary_learn.hip; the kernel: mdpp_grid_learn.hpp): why the handle has none (empty:
+// it is served); the action vectors taken written to io.actions [K][N][2]; Q between the caller's [N][S][A] and the
+// handle's entry-major buffer
+std::string grid_learn_refusal(const mdpp_env *h);
+int launch_grid_learn(mdpp_env *h, const DiscreteIO &io, bool eval);
+int launch_grid_q_copy(mdpp_env *h, float *user_q, bool to_handle, hipStream_t s);
 // phase bits: 1 = draw + records, 2 = render (phase == 2 exactly: pipelined, the persistent grid leaves slots
 // free for the next batch's state kernel; 6 = render only on the full grid); buf: scratch set (0 / 1)
 int launch_image_obs(mdpp_env *h, int K, const int32_t *state_out, const int32_t *state_final,

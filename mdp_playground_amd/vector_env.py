@@ -97,6 +97,8 @@ class RLToyVectorEnv:
         self._learn_q_init = None             # the tensor last handed to set_learner / set_q, kept until its copy has been made
         self._learn_z_init = None             # ... to set_traces
         self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
+        self._grid_learn_A = None             # the grid learner's number of actions (set_grid_learner); None: never set
+        self._grid_q_init = None              # the tensor last handed to set_grid_learner / set_grid_q, kept until its copy has been made
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
         self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
         self._learn_sched = None              # set_learner_schedule's validated arrays while a schedule is in force
@@ -541,7 +543,10 @@ class RLToyVectorEnv:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             mptr = C.c_void_p(mask.data_ptr())
             src = getattr(self, "_obs_src", None)
-            if src is _OBS_FROM_STATE:   # (a summary launch: the observation every env shows, from its state record)
+            if src is _OBS_FROM_STATE and self.kind == "grid":   # (a grid summary launch: the cells in the state record)
+                cells = self._get_augmented_state()["curr_obs"]
+                self._obs.copy_(torch.from_numpy(cells).to(device=self.device, dtype=self._obs.dtype))
+            elif src is _OBS_FROM_STATE:   # (a summary launch: the observation every env shows, from its state record)
                 self._closed_call(self._lib.mdpp_current_obs(self._h, C.c_void_p(self._obs.data_ptr()), self._stream()), "mdpp_current_obs")
             elif src is not None:        # the rows of the envs NOT reset: their observation after the last rollout() / graph replay
                 self._obs.copy_(src)
@@ -1348,6 +1353,123 @@ class RLToyVectorEnv:
         name = self._lib.mdpp_learn_kernel_name(self._h, int(K))
         return name.decode() if name else ""
 
+    # ------------------------------------------------------------------ in-kernel tabular TD learners on grid envs
+    def _grid_learn_check_kind(self):
+        if self.kind != "grid":
+            raise NotImplementedError("grid learners serve grid envs only (this env is %s)" % self.kind)
+
+    def _grid_q_shape(self, n_actions=None):
+        g = self.mdps[0].grid_shape
+        return (self.num_envs, int(g[0]) + 1, int(g[1]) + 1, int(n_actions or self._grid_learn_A))
+
+    def _grid_q_arg(self, q, what, n_actions=None):
+        shape = self._grid_q_shape(n_actions)
+        if not (torch.is_tensor(q) and q.dtype == torch.float32 and q.device == self.device and tuple(q.shape) == shape):
+            raise ValueError(f"{what}: q must be a float32 tensor of shape {shape} on {self.device}")
+        return q.contiguous()
+
+    def _grid_param_arrays(self, alpha, gamma, epsilon):
+        """float32 [N] per parameter (a scalar is broadcast), or None for None, after policy.check_learner_params"""
+        policy_mod.check_learner_params(None, alpha, gamma, epsilon, self.num_envs)
+        out = []
+        for name, v in (("alpha", alpha), ("gamma", gamma), ("epsilon", epsilon)):
+            a = policy_mod.learner_param_array(name, v, self.num_envs)
+            out.append(a if a is not None or v is None else np.full(self.num_envs, np.float32(v), np.float32))
+        return out
+
+    def set_grid_learner(self, algo="q_learning", *, alpha=None, gamma=None, epsilon=None, seed=0, q=None, noop=False):
+        """The tabular TD learner of a GRID handle for rollout_grid_learn(): one independent agent PER GRIDWORLD, ``algo``
+        "q_learning" or "sarsa", float32 ``alpha`` in (0, 1], ``gamma`` and ``epsilon`` in [0, 1] -- each a scalar (broadcast) or a
+        1-D array of num_envs entries (env i of THIS handle learns with entry i) --, ``seed`` the 64-bit key of the learner's own
+        Philox streams, ``q`` the initial tables (float32 [N, g0 + 1, g1 + 1, A] on the device; zeros when None).  The agent's
+        actions are (+1,0), (-1,0), (0,+1), (0,-1) and, with ``noop=True``, (0,0): A = 4 or 5.  The state of cell (c0, c1) is the
+        table's row [c0, c1]; row g, one past the grid, is an episode's possible first cell (include/mdpp.h "Grid learners").
+        ``set_grid_learner(None)`` clears the learner.  Handles the kernel does not serve raise NotImplementedError with the
+        reason."""
+        if algo is None:
+            capi.check(self._lib, self._h, self._lib.mdpp_clear_grid_learner(self._h), "mdpp_clear_grid_learner")
+            return
+        if alpha is None or gamma is None or epsilon is None:
+            raise ValueError("set_grid_learner: alpha, gamma and epsilon are required")
+        if algo not in capi.LEARN_ALGOS:
+            raise ValueError(f"set_grid_learner: algo must be one of {tuple(capi.LEARN_ALGOS)}, got {algo!r}")
+        arrays = self._grid_param_arrays(alpha, gamma, epsilon)
+        self._grid_learn_check_kind()
+        A = 5 if noop else 4
+        if q is not None and len(self.mdps[0].grid_shape) == 2:
+            q = self._grid_q_arg(q, "set_grid_learner", A)
+        rc = self._lib.mdpp_set_grid_learner(self._h, capi.LEARN_ALGOS[algo], A, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                             *(capi.nptr(a) for a in arrays),
+                                             C.c_void_p(q.data_ptr()) if q is not None else None, self._stream())
+        self._closed_call(rc, "mdpp_set_grid_learner")
+        self._grid_learn_A = A
+        self._grid_q_init = q            # (kept until the copy queued on the stream has certainly been made)
+
+    def set_grid_learner_rates(self, alpha=None, gamma=None, epsilon=None):
+        """New alpha, gamma and / or epsilon for the grid learner, each a scalar (broadcast) or a per-env array as in
+        set_grid_learner; None keeps the current values.  One small copy per parameter on the current stream; the new values
+        hold from the next launch on."""
+        arrays = self._grid_param_arrays(alpha, gamma, epsilon)
+        self._grid_learn_check_kind()
+        rc = self._lib.mdpp_set_grid_learner_params(self._h, *(capi.nptr(a) for a in arrays), self._stream())
+        self._closed_call(rc, "mdpp_set_grid_learner_params")
+
+    def alloc_rollout_grid(self, K):
+        """Output buffers of rollout_grid_learn(K) / rollout_grid_eval(K): alloc_rollout(K) and the action vectors, int32 [K, N, 2]."""
+        return self.alloc_rollout(K) + (torch.empty((K, self.num_envs, 2), dtype=torch.int32, device=self.device),)
+
+    def _rollout_grid(self, stem, K, out, summary):
+        self._grid_learn_check_kind()
+        K = int(K)
+        if summary is not None:
+            if out is not None:
+                raise ValueError("a summary launch writes no [K, N] output (out must be None)")
+            return self._rollout_summary(getattr(self._lib, stem + "_summary"), stem + "_summary", K, summary)
+        if out is None:
+            out = self.alloc_rollout_grid(K)
+        return self._rollout_closed(getattr(self._lib, stem), stem, K, out)
+
+    def rollout_grid_learn(self, K, out=None, *, summary=None):
+        """K steps of "select epsilon-greedily from the gridworld's own Q, move, update that Q" in ONE kernel launch.  Returns
+        (obs, reward, terminated, truncated, actions), each with a leading K axis, ``actions`` the int32 [K, N, 2] action vectors
+        taken: rollout(actions) on an identically built env returns the same first four, bit for bit.  SARSA carries its next
+        action from step to step inside a call only.  ``summary`` (episode_summary()): the same K steps with the same effect on
+        the env and the tables, but NO [K, N] array is written -- the summary is updated and returned."""
+        return self._rollout_grid("mdpp_step_n_grid_learn", K, out, summary)
+
+    def rollout_grid_eval(self, K, out=None, *, summary=None):
+        """K steps of GREEDY evaluation of the grid learner's tables in ONE kernel launch: every env takes the lowest action that
+        maximises its own Q[s].  Nothing is drawn, nothing is updated: the tables stay bit for bit what they were.  Returns as
+        rollout_grid_learn; with ``summary`` the episode numbers instead."""
+        return self._rollout_grid("mdpp_step_n_grid_eval", K, out, summary)
+
+    def get_grid_q(self):
+        """The grid learner's tables, float32 [N, g0 + 1, g1 + 1, A]; a copy, made on the current stream."""
+        self._grid_learn_check_kind()
+        if self._grid_learn_A is None:
+            raise capi.MdppError("mdpp_get_grid_q failed (%d): no learner set (set_grid_learner)" % capi.ESTATE)
+        q = torch.empty(self._grid_q_shape(), dtype=torch.float32, device=self.device)
+        self._closed_call(self._lib.mdpp_get_grid_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_get_grid_q")
+        return q
+
+    def set_grid_q(self, q):
+        """Replace the grid learner's tables: float32 [N, g0 + 1, g1 + 1, A] on the device (copied on the current stream)."""
+        self._grid_learn_check_kind()
+        if self._grid_learn_A is None:
+            raise capi.MdppError("mdpp_set_grid_q failed (%d): no learner set (set_grid_learner)" % capi.ESTATE)
+        q = self._grid_q_arg(q, "set_grid_q")
+        self._closed_call(self._lib.mdpp_set_grid_q(self._h, C.c_void_p(q.data_ptr()), self._stream()), "mdpp_set_grid_q")
+        self._grid_q_init = q
+
+    def grid_learn_kernel_name(self, K, eval=False, summary=False):
+        """Name (with template arguments) of the kernel rollout_grid_learn(K) (``eval``: rollout_grid_eval(K); ``summary``: their
+        summary= forms) launches (mdpp_grid_learn_kernel_name; nothing is launched; QLDS=1: the Q-tables are staged in LDS);
+        empty for a handle it does not serve or one without a learner."""
+        if self.kind != "grid":
+            return ""
+        name = self._lib.mdpp_grid_learn_kernel_name(self._h, int(K), int(bool(eval)), int(bool(summary)))
+        return name.decode() if name else ""
+
     # ------------------------------------------------------------------ per-env noise levels
     _NOISE_LEVELS_ONLY = "per-env noise levels: learner and evaluation launches only; clear_noise_levels() first"
 
@@ -1440,12 +1562,12 @@ class RLToyVectorEnv:
         return name.decode() if name else ""
 
     def set_kernel_options(self, *disable):
-        """Take specialised kernels out of the dispatch (names of capi.OPTIONS, e.g. "NO_PIPE"): the
+        """Take specialised kernels out of the dispatch (names of capi.OPTIONS and capi.GRID_OPTIONS, e.g. "NO_PIPE"): the
         handle then runs on the more general kernel of the same arithmetic.  Tests / profiling only;
         results do not depend on it.  No arguments = default dispatch."""
         mask = 0
         for d in disable:
-            mask |= capi.OPTIONS[d]
+            mask |= capi.GRID_OPTIONS[d] if d in capi.GRID_OPTIONS else capi.OPTIONS[d]
         capi.check(self._lib, self._h, self._lib.mdpp_set_options(self._h, mask), "mdpp_set_options")
 
     def alloc_rollout(self, K):
