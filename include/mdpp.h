@@ -653,6 +653,57 @@ int mdpp_get_grid_q(mdpp_env *h, float *q_out_dev, void *stream);
 int mdpp_set_grid_q(mdpp_env *h, const float *q_in_dev, void *stream);
 const char *mdpp_grid_learn_kernel_name(mdpp_env *h, int K, int eval, int summary);
 
+/* Grid learner schedules and the episode log.  The reference has no such agent: this text is the definition.
+ * Schedule: a grid handle with a learner may carry one schedule -- an epsilon table (float32 in [0, 1]), an alpha table
+ * (float32 in (0, 1]) or both, each [R][M] with 1 <= M and R M <= MDPP_MAX_SCHEDULE_ENTRIES; a row index row[i] in [0, R) per
+ * env (the handle's LOCAL index i); and a counter ep[i], int32, in a buffer of the handle -- zero when the schedule is set.
+ * The epsilon table becomes thresholds on the host: T[r][e] = ceil((double)epsilon[r][e] 2^31).
+ * The kernel rules are those of "Schedules" above, word for word.  In mdpp_step_n_grid_learn, its _summary and its _log form
+ * env i starts with e = min(ep[i], M - 1), E = T[row[i]][e] if epsilon is scheduled (else E[i]), alpha = A[row[i]][e] if alpha
+ * is scheduled (else alpha[i]).  Every selection made in a step -- the action, and sarsa's a' = sel(s', t + 1) inside its
+ * target -- uses the E in force at the step's start, the update the alpha in force then.  AFTER the update of a step that is
+ * not the reset call of a next-step-autoreset env: terminated or truncated moves ep[i] by one and E and alpha are looked up
+ * again -- exactly the rule by which the summary's `episodes` moves in this kernel.  So: with autoreset disabled the counter
+ * moves at every step once a flag latches; a sarsa action carried over an episode's end was chosen under the old E; a reset
+ * call selects with the current E, writes the action, ignores it and counts nothing; past M - 1 the last entry holds.  The
+ * counter is stored when the launch ends.  gamma is never scheduled.  mdpp_step_n_grid_eval and its _summary form read no
+ * table and move no counter.  Stream ids, the twin property and the placement of Q (QLDS) are unchanged: the schedule has no
+ * LDS placement.  Behaviour of ep[i] beyond 2^31 - 1 is unspecified.
+ * mdpp_set_grid_learner_schedule takes HOST pointers: epsilon and alpha [R][M] or NULL (one at least), row [N], NULL iff
+ * R == 1.  It validates first (MDPP_EINVAL with a message: nothing changed), then forms the thresholds, copies on `stream`
+ * and zeroes the counters.  ("Nothing changed" is promised for validation failures only: an MDPP_EHIP from an allocation or a
+ * copy, after validation, may leave the handle without any schedule -- larger tables replace the old buffers first.)
+ * mdpp_clear_grid_learner_schedule drops the schedule (the scheduled parameter is again what
+ * mdpp_set_grid_learner / _params made it); so do mdpp_set_grid_learner and mdpp_clear_grid_learner.
+ * mdpp_get_grid_learner_episodes / mdpp_set_grid_learner_episodes: the counters, int32 [N] DEVICE pointers, ordered on
+ * `stream`; dev_in NULL zeroes them.  Without a learner the schedule calls and the counter accessors return MDPP_ESTATE
+ * ("no learner set"); the counter accessors also without a schedule ("no schedule set").  On a handle that is not a grid:
+ * MDPP_EUNSUPPORTED, "grid learners serve grid envs only".  While epsilon is scheduled mdpp_set_grid_learner_params with
+ * an epsilon is MDPP_ESTATE, the reason names mdpp_clear_grid_learner_schedule, and nothing is changed (a gamma given in
+ * the same call included); likewise alpha while alpha is scheduled.  gamma alone is always accepted.
+ * Log: mdpp_step_n_grid_learn_log is mdpp_step_n_grid_learn_summary with three more arrays of the caller and a capacity
+ * M >= 1 -- log_count int32 [N], log_ret float64 [M][N], log_len int32 [M][N], episode-major.  The rule is that of "The
+ * episode log" above, word for word: where the summary rule finds terminated or truncated, BEFORE ret and len are zeroed,
+ *   if (count < M) { log_ret[count][i] = ret;  log_len[count][i] = len; }      count += 1;
+ * count goes on past M; the lane loads log_count[i] where it loads its five values and stores it where it stores them (no
+ * atomics); entries the launch does not write keep what they held; a reset call writes nothing.  A null log pointer, M < 1
+ * or M * num_envs > 2^31 - 1 is MDPP_EINVAL with a message, before any device work.  With a log, the env, the tables, the
+ * five values and the schedule counters are those of the summary launch without one.  There is no log for the evaluation
+ * launches (DESIGN.md 3.24 measured that decision on discrete handles).
+ * Kernels: k_grid_learn_sched_rollout<PHILOX,NOISE,QLDS,SUMMARY> (a schedule in force, no log) and
+ * k_grid_learn_log_rollout<PHILOX,NOISE,QLDS,SCHED> (a log, with or without a schedule): the step loop of
+ * k_grid_learn_rollout with the lookup (one dword load per scheduled table at the launch's start and at each of the lane's
+ * episode ends) and the log's two stores; a launch without schedule and log runs k_grid_learn_rollout, the code it always
+ * ran.  QLDS is decided per kernel, on that kernel's own function.  mdpp_grid_learn_kernel_name keeps its signature and
+ * its names: while a schedule is in force the learning forms' names gain ",SCHED=1" after "SUMMARY=."; evaluation names do
+ * not change; a log launch reports the name of the same launch without a log. */
+int mdpp_set_grid_learner_schedule(mdpp_env *h, const float *epsilon, const float *alpha, int R, int M, const int32_t *row, void *stream);
+int mdpp_clear_grid_learner_schedule(mdpp_env *h);
+int mdpp_get_grid_learner_episodes(mdpp_env *h, int32_t *dev_out, void *stream);
+int mdpp_set_grid_learner_episodes(mdpp_env *h, const int32_t *dev_in, void *stream);   /* NULL: zeros */
+int mdpp_step_n_grid_learn_log(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev, double *return_sum_dev,
+                               int32_t *length_sum_dev, int32_t *log_count_dev, double *log_ret_dev, int32_t *log_len_dev, int M, void *stream);
+
 /* Linear policies: closed-loop CONTINUOUS rollouts.  The handle holds float32 parameters theta, one set shared by every env
  * ([D][D + 1]) or one per env ([N][D][D + 1]; per_env != 0): theta[.., r, c] for c < D is W[r][c], theta[.., r, D] is b[r]
  * (D = state_space_dim = action_space_dim).  At every step of a launch env i forms its action from o = the state in its
@@ -994,6 +1045,10 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   are read from the handle's buffers at replay (mdpp_set_grid_learner_params: the way to change rates under a graph), and
  *   the step counter comes through the device offset, as for the discrete learner: the learning launch replays exactly
  *   only in capture mode, whatever the handle's RNG mode.
+ *   A grid learner's schedule (mdpp_set_grid_learner_schedule): which tables are scheduled and M go by value; the tables, the
+ *   rows and the episode counters are read -- and the counters written -- at replay.  Its episode log
+ *   (mdpp_step_n_grid_learn_log): the three log pointers and the capacity go by value; log_count is read and written at
+ *   replay and log_ret / log_len are written, so counters and log go on from replay to replay.
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

@@ -71,6 +71,8 @@ EXPORTS = [
     "mdpp_set_grid_learner", "mdpp_clear_grid_learner", "mdpp_set_grid_learner_params", "mdpp_step_n_grid_learn",
     "mdpp_step_n_grid_eval", "mdpp_step_n_grid_learn_summary", "mdpp_step_n_grid_eval_summary", "mdpp_get_grid_q", "mdpp_set_grid_q",
     "mdpp_grid_learn_kernel_name",
+    "mdpp_set_grid_learner_schedule", "mdpp_clear_grid_learner_schedule", "mdpp_get_grid_learner_episodes", "mdpp_set_grid_learner_episodes",
+    "mdpp_step_n_grid_learn_log",
 ]
 
 
@@ -249,6 +251,11 @@ def load():
     L.mdpp_set_grid_q.argtypes = [vp, vp, vp]
     L.mdpp_grid_learn_kernel_name.argtypes = [vp, i32, i32, i32]
     L.mdpp_grid_learn_kernel_name.restype = C.c_char_p
+    L.mdpp_set_grid_learner_schedule.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    L.mdpp_clear_grid_learner_schedule.argtypes = [vp]
+    L.mdpp_get_grid_learner_episodes.argtypes = [vp, vp, vp]
+    L.mdpp_set_grid_learner_episodes.argtypes = [vp, vp, vp]
+    L.mdpp_step_n_grid_learn_log.argtypes = [vp, i32] + [vp] * 8 + [i32, vp]
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]

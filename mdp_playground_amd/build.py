@@ -40,9 +40,10 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_continuous_es.hip", "mdpp_continuous_summary_es.hip",
            "mdpp_continuous_linear_h2.hip", "mdpp_continuous_summary_linear_h2.hip", "mdpp_continuous_search_h2.hip",
            "mdpp_continuous_summary_search_h2.hip", "mdpp_continuous_es_h2.hip", "mdpp_continuous_summary_es_h2.hip",
-           "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_grid_learn.hip", "mdpp_grid_summary_learn.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
+           "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_grid_learn.hip", "mdpp_grid_summary_learn.hip",
+           "mdpp_grid_sched_learn.hip", "mdpp_grid_summary_sched_learn.hip", "mdpp_grid_episodes_learn.hip", "mdpp_grid_episodes_sched_learn.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
            "mdpp_generate.hip"]
-HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdpp_pcg64_limbs.inc", "np_ziggurat_tables.inc",
+HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdpp_pcg64_limbs.inc", "np_ziggurat_tables.inc", "mdpp_grid_learn_body.inc",
            os.path.join("..", "..", "include", "mdpp.h")]
 _CLOSED_DEPS = ["mdpp_continuous_closed.hpp", "mdpp_linear_history.hpp"]
 _LEAN_DEPS = ["mdpp_discrete_lean.hip", "mdpp_discrete_lean_e.inc"]      # (the kernel and its E role, included into its body)
@@ -54,8 +55,9 @@ INCLUDED_SOURCES = {"mdpp_discrete_lean.hip": ["mdpp_discrete_lean_e.inc"], "mdp
                     **{u: ["mdpp_discrete_trace.hpp", "mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith(("mdpp_discrete_trace", "mdpp_discrete_summary_trace"))},
                     # (... on one MDP per env: the same header's PM forms)
                     **{u: ["mdpp_discrete_trace.hpp", "mdpp_discrete_learn.hpp"] for u in SOURCES if u.startswith(("mdpp_discrete_lambda", "mdpp_discrete_summary_lambda"))},
-                    # the grid learners' two output forms: the kernel and the launcher of one form
-                    **{u: ["mdpp_grid_learn.hpp"] for u in ("mdpp_grid_learn.hip", "mdpp_grid_summary_learn.hip")},
+                    # the grid learners' two output forms and their SCHED and LOG forms: the kernels and the launcher of one form (the
+                    # step loop they share, mdpp_grid_learn_body.inc, is listed in HEADERS)
+                    **{u: ["mdpp_grid_learn.hpp"] for u in SOURCES if u.startswith("mdpp_grid_") and u.endswith("_learn.hip")},
                     # the closed-loop continuous units: the step and the history-2 act; the _summary and _h2 units include their family's .hip
                     **{f"mdpp_continuous_{pre}{fam}{suf}.hip": ([f"mdpp_continuous_{fam}.hip"] if pre or suf else []) + _CLOSED_DEPS
                        for fam in ("linear", "search", "es") for pre in ("", "summary_") for suf in ("", "_h2")}}
@@ -81,7 +83,9 @@ EXTRA_FLAGS = {s: SPILL_SAFE for s in ("mdpp_continuous.hip", "mdpp_continuous_l
 #  the six mdpp_discrete_trace*.hip / mdpp_discrete_summary_trace*.hip units likewise: profiles/learn_traces_resources.txt, tests/test_gpu_learn_traces.py;
 #  the four mdpp_discrete_lambda_pe_pm*.hip / mdpp_discrete_summary_lambda_pe_pm*.hip units -- the trace kernels on one MDP per env -- likewise:
 #  profiles/trace_seeds_resources.txt, tests/test_gpu_trace_seeds.py;
-#  mdpp_grid_learn.hip, mdpp_grid_summary_learn.hip likewise: profiles/grid_learn_resources.txt, tests/test_gpu_grid_learn.py runs every lane against a twin)
+#  mdpp_grid_learn.hip, mdpp_grid_summary_learn.hip likewise: profiles/grid_learn_resources.txt, tests/test_gpu_grid_learn.py runs every lane against a twin;
+#  the four mdpp_grid_*sched_learn.hip / mdpp_grid_episodes*_learn.hip units -- the same step loop with a schedule and / or an episode log -- likewise:
+#  profiles/grid_schedule_resources.txt, tests/test_gpu_grid_schedule.py)
 
 
 def _hipcc():

@@ -60,7 +60,8 @@ static void free_all(mdpp_env *h) {
                     h->d_img_near, h->d_s1_blob, h->d_lean_blob, h->d_imgc_boxes, h->d_hist_hi, h->d_policy_thr, h->d_learn_q, h->d_learn_carry,
                     h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E, h->d_sched_E, h->d_sched_alpha, h->d_sched_row, h->d_sched_ep,
                     h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta, h->d_lin_mem, h->d_trace_z, h->d_trace_lambda,
-                    h->d_gl_q, h->d_gl_alpha, h->d_gl_gamma, h->d_gl_E};
+                    h->d_gl_q, h->d_gl_alpha, h->d_gl_gamma, h->d_gl_E,
+                    h->d_gl_sched_E, h->d_gl_sched_alpha, h->d_gl_sched_row, h->d_gl_sched_ep};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -2015,18 +2016,24 @@ extern "C" int mdpp_set_grid_learner(mdpp_env *h, int algo, int n_actions, uint6
     if (rc) { h->gl_ready = false; return rc; }
     h->gl_algo = algo; h->gl_seed = seed;
     h->gl_ready = true;
+    h->gl_sched_on = false;      // (a new learner starts without a schedule: the next one zeroes the counters)
     return MDPP_OK;
 }
 
 extern "C" int mdpp_clear_grid_learner(mdpp_env *h) {
     if (!h) return MDPP_EINVAL;
     h->gl_ready = false;         // (the buffers stay: a launch queued earlier may still use them)
+    h->gl_sched_on = false;
     return MDPP_OK;
 }
 
 extern "C" int mdpp_set_grid_learner_params(mdpp_env *h, const float *alpha, const float *gamma, const float *epsilon, void *stream) {
     if (!h) return MDPP_EINVAL;
     if (!h->gl_ready) return fail(h, MDPP_ESTATE, "mdpp_set_grid_learner_params: no learner set (mdpp_set_grid_learner)");
+    for (const char *what : {h->gl_sched_on && epsilon && h->gl_sched_eps ? "epsilon" : nullptr, h->gl_sched_on && alpha && h->gl_sched_alpha ? "alpha" : nullptr})
+        if (what)
+            return fail(h, MDPP_ESTATE, std::string("mdpp_set_grid_learner_params: ") + what +
+                                            " follows the schedule in force (mdpp_set_grid_learner_schedule); mdpp_clear_grid_learner_schedule first");
     if (!grid_learner_params_ok((size_t)h->cfg.num_envs, alpha, gamma, epsilon))
         return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_params: need every alpha in (0, 1], every gamma and epsilon in [0, 1]");
     if (!alpha && !gamma && !epsilon) return MDPP_OK;
@@ -2035,12 +2042,19 @@ extern "C" int mdpp_set_grid_learner_params(mdpp_env *h, const float *alpha, con
 }
 
 // the checks of a grid learner launch, full output (actions ... trunc) or summary (sm)
+// (log: sm carries an episode log's three arrays and, in sm->log_cap, its capacity M as the caller gave it, checked here)
 static int step_n_grid(mdpp_env *h, const char *what, bool eval, int K, int32_t *actions, void *obs, float *reward, uint8_t *term,
-                       uint8_t *trunc, const EpisodeSummaryArgs *sm, void *stream) {
+                       uint8_t *trunc, const EpisodeSummaryArgs *sm, void *stream, bool log = false, int M = 0) {
     if (!h) return MDPP_EINVAL;
     if (K < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": K < 1");
     if (sm ? (!sm->ret || !sm->len || !sm->episodes || !sm->return_sum || !sm->length_sum) : (!actions || !obs || !reward || !term || !trunc))
         return fail(h, MDPP_EINVAL, std::string(what) + ": null buffer");
+    if (log) {
+        if (!sm->log_count || !sm->log_ret || !sm->log_len) return fail(h, MDPP_EINVAL, std::string(what) + ": null log buffer");
+        if (M < 1) return fail(h, MDPP_EINVAL, std::string(what) + ": M < 1");
+        if ((long long)M * (long long)h->cfg.num_envs > (long long)INT32_MAX)
+            return fail(h, MDPP_EINVAL, std::string(what) + ": M * num_envs > 2^31 - 1");
+    }
     const std::string why = grid_learn_refusal(h);
     if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
     if (!h->gl_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_grid_learner)");
@@ -2072,6 +2086,99 @@ extern "C" int mdpp_step_n_grid_eval_summary(mdpp_env *h, int K, double *ret_dev
                                              double *return_sum_dev, int32_t *length_sum_dev, void *stream) {
     const EpisodeSummaryArgs sm{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, nullptr, nullptr, nullptr, 0u};
     return step_n_grid(h, "mdpp_step_n_grid_eval_summary", true, K, nullptr, nullptr, nullptr, nullptr, nullptr, &sm, stream);
+}
+
+extern "C" int mdpp_step_n_grid_learn_log(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev, double *return_sum_dev,
+                                          int32_t *length_sum_dev, int32_t *log_count_dev, double *log_ret_dev, int32_t *log_len_dev, int M,
+                                          void *stream) {
+    const EpisodeSummaryArgs sm{ret_dev, len_dev, episodes_dev, return_sum_dev, length_sum_dev, log_count_dev, log_ret_dev, log_len_dev,
+                                M > 0 ? (uint32_t)M : 0u};
+    return step_n_grid(h, "mdpp_step_n_grid_learn_log", false, K, nullptr, nullptr, nullptr, nullptr, nullptr, &sm, stream, true, M);
+}
+
+// ---- per-episode epsilon / alpha schedules of the grid learner (mdpp_grid_learn.hpp: SCHED) ----
+// a grid handle with a learner, or the refusal
+static int grid_sched_ready(mdpp_env *h, const char *what) {
+    const std::string why = grid_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, std::string(what) + ": " + why);
+    if (!h->gl_ready) return fail(h, MDPP_ESTATE, std::string(what) + ": no learner set (mdpp_set_grid_learner)");
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_grid_learner_schedule(mdpp_env *h, const float *epsilon, const float *alpha, int R, int M, const int32_t *row, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (int rc = grid_sched_ready(h, "mdpp_set_grid_learner_schedule")) return rc;
+    if (!epsilon && !alpha) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_schedule: need an epsilon table, an alpha table or both");
+    if (R < 1 || M < 1 || (uint64_t)R * (uint64_t)M > (uint64_t)MDPP_MAX_SCHEDULE_ENTRIES)
+        return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_schedule: need R >= 1, M >= 1 and R M <= 2^22");
+    if (!row && R != 1) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_schedule: R > 1 needs row, the row index of every env");
+    if (row && R == 1) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_schedule: R == 1 takes no row (NULL)");
+    const size_t N = (size_t)h->cfg.num_envs, RM = (size_t)R * (size_t)M;
+    for (size_t k = 0; k < RM; k++) {                            // (NaN fails every comparison)
+        if (epsilon && !(epsilon[k] >= 0.0f && epsilon[k] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_schedule: need every epsilon in [0, 1]");
+        if (alpha && !(alpha[k] > 0.0f && alpha[k] <= 1.0f)) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_schedule: need every alpha in (0, 1]");
+    }
+    for (size_t i = 0; row && i < N; i++)
+        if (row[i] < 0 || row[i] >= R) return fail(h, MDPP_EINVAL, "mdpp_set_grid_learner_schedule: need every row index in [0, R)");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->gl_sched_cap < RM) {                                  // (hipFree waits for the launches that still read them)
+        for (void **d : {&h->d_gl_sched_E, &h->d_gl_sched_alpha})
+            if (*d) { HIPCHK(h, hipFree(*d)); *d = nullptr; }
+        h->gl_sched_cap = 0;
+        h->gl_sched_on = false;
+    }
+    for (void **d : {&h->d_gl_sched_E, &h->d_gl_sched_alpha})
+        if (!*d) HIPCHK(h, hipMalloc(d, RM * 4u));
+    h->gl_sched_cap = h->gl_sched_cap < RM ? RM : h->gl_sched_cap;
+    for (void **d : {&h->d_gl_sched_row, &h->d_gl_sched_ep})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * 4u));
+    // (host to device from the caller's pageable memory: the runtime has read the source when the call returns)
+    if (alpha) HIPCHK(h, hipMemcpyAsync(h->d_gl_sched_alpha, alpha, RM * 4u, hipMemcpyHostToDevice, s));
+    if (row) HIPCHK(h, hipMemcpyAsync(h->d_gl_sched_row, row, N * 4u, hipMemcpyHostToDevice, s));
+    else HIPCHK(h, hipMemsetAsync(h->d_gl_sched_row, 0, N * 4u, s));
+    HIPCHK(h, hipMemsetAsync(h->d_gl_sched_ep, 0, N * 4u, s));
+    if (epsilon) {
+        std::vector<uint32_t> T(RM);
+        for (size_t k = 0; k < RM; k++) T[k] = (uint32_t)ceil((double)epsilon[k] * 2147483648.0);
+        HIPCHK(h, hipMemcpyAsync(h->d_gl_sched_E, T.data(), RM * 4u, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipStreamSynchronize(s));                      // (T is this call's own: gone at return)
+    }
+    h->gl_sched_eps = epsilon != nullptr; h->gl_sched_alpha = alpha != nullptr;
+    h->gl_sched_R = R; h->gl_sched_M = M;
+    h->gl_sched_on = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_grid_learner_schedule(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    if (int rc = grid_sched_ready(h, "mdpp_clear_grid_learner_schedule")) return rc;
+    h->gl_sched_on = false;      // (the buffers stay: a launch queued earlier may still read them)
+    return MDPP_OK;
+}
+
+static int grid_sched_counters_ready(mdpp_env *h, const char *what) {
+    if (int rc = grid_sched_ready(h, what)) return rc;
+    if (!h->gl_sched_on) return fail(h, MDPP_ESTATE, std::string(what) + ": no schedule set (mdpp_set_grid_learner_schedule)");
+    HIPCHK(h, hipSetDevice(h->device));
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_get_grid_learner_episodes(mdpp_env *h, int32_t *dev_out, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (!dev_out) return fail(h, MDPP_EINVAL, "mdpp_get_grid_learner_episodes: null buffer");
+    if (int rc = grid_sched_counters_ready(h, "mdpp_get_grid_learner_episodes")) return rc;
+    HIPCHK(h, hipMemcpyAsync(dev_out, h->d_gl_sched_ep, (size_t)h->cfg.num_envs * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_set_grid_learner_episodes(mdpp_env *h, const int32_t *dev_in, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    if (int rc = grid_sched_counters_ready(h, "mdpp_set_grid_learner_episodes")) return rc;
+    const size_t bytes = (size_t)h->cfg.num_envs * 4u;
+    if (dev_in) HIPCHK(h, hipMemcpyAsync(h->d_gl_sched_ep, dev_in, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else HIPCHK(h, hipMemsetAsync(h->d_gl_sched_ep, 0, bytes, (hipStream_t)stream));
+    return MDPP_OK;
 }
 
 static int grid_q_copy(mdpp_env *h, float *q_dev, bool to_handle, void *stream, const char *what) {

@@ -407,6 +407,14 @@ struct mdpp_env {
     int32_t gl_algo, gl_A;
     size_t gl_cap;
     bool gl_ready;
+    // the grid learner's per-episode schedule (mdpp_set_grid_learner_schedule; mdpp_grid_learn.hpp SCHED): gl_sched_on: the
+    // learning launches take their SCHED form.  Device: the thresholds uint32 [R][M] and / or the alphas float32 [R][M]
+    // (gl_sched_eps / gl_sched_alpha: which table is in force), every env's row int32 [N] and episode counter int32 [N];
+    // gl_sched_cap: the entries the two table buffers were allocated for
+    bool gl_sched_on, gl_sched_eps, gl_sched_alpha;
+    int32_t gl_sched_R, gl_sched_M;
+    size_t gl_sched_cap;
+    void *d_gl_sched_E, *d_gl_sched_alpha, *d_gl_sched_row, *d_gl_sched_ep;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };
@@ -654,7 +662,8 @@ int launch_continuous_current_obs(mdpp_env *h, float *obs, hipStream_t s);
 int launch_grid_step(mdpp_env *h, const DiscreteIO &io);
 int launch_grid_reset(mdpp_env *h, const uint8_t *mask, void *obs, hipStream_t s);
 // io.K steps of the grid handle's tabular learner, or (eval) of greedy evaluation of its tables (mdpp_grid_learn.hip; with
-// io.summary the summary form, mdpp_grid_summary_learn.hip; the kernel: mdpp_grid_learn.hpp): why the handle has none (empty:
+// io.summary the summary form, mdpp_grid_summary_learn.hip; with a schedule in force or an episode log in io.summary the SCHED
+// and LOG forms, mdpp_grid_sched_learn.hip, mdpp_grid_episodes_learn.hip; the kernel: mdpp_grid_learn.hpp): why the handle has none (empty:
 // it is served); the action vectors taken written to io.actions [K][N][2]; Q between the caller's [N][S][A] and the
 // handle's entry-major buffer
 std::string grid_learn_refusal(const mdpp_env *h);

@@ -99,6 +99,8 @@ class RLToyVectorEnv:
         self._learn_algo = None               # the learner's algorithm ("double_q": two tables per env)
         self._grid_learn_A = None             # the grid learner's number of actions (set_grid_learner); None: never set
         self._grid_q_init = None              # the tensor last handed to set_grid_learner / set_grid_q, kept until its copy has been made
+        self._grid_sched = None               # set_grid_learner_schedule's validated arrays while a schedule is in force
+        self._grid_ep_init = None             # the tensor last handed to set_grid_learner_episodes, kept until its copy has been made
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
         self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
         self._learn_sched = None              # set_learner_schedule's validated arrays while a schedule is in force
@@ -1388,6 +1390,7 @@ class RLToyVectorEnv:
         reason."""
         if algo is None:
             capi.check(self._lib, self._h, self._lib.mdpp_clear_grid_learner(self._h), "mdpp_clear_grid_learner")
+            self._grid_sched = None
             return
         if alpha is None or gamma is None or epsilon is None:
             raise ValueError("set_grid_learner: alpha, gamma and epsilon are required")
@@ -1403,12 +1406,14 @@ class RLToyVectorEnv:
                                              C.c_void_p(q.data_ptr()) if q is not None else None, self._stream())
         self._closed_call(rc, "mdpp_set_grid_learner")
         self._grid_learn_A = A
+        self._grid_sched = None          # (mdpp_set_grid_learner drops the schedule and its counters)
         self._grid_q_init = q            # (kept until the copy queued on the stream has certainly been made)
 
     def set_grid_learner_rates(self, alpha=None, gamma=None, epsilon=None):
         """New alpha, gamma and / or epsilon for the grid learner, each a scalar (broadcast) or a per-env array as in
         set_grid_learner; None keeps the current values.  One small copy per parameter on the current stream; the new values
-        hold from the next launch on."""
+        hold from the next launch on.  While a schedule is in force (set_grid_learner_schedule) the parameter it schedules is
+        refused (MdppError, nothing changed; clear_grid_learner_schedule() first); gamma is always accepted."""
         arrays = self._grid_param_arrays(alpha, gamma, epsilon)
         self._grid_learn_check_kind()
         rc = self._lib.mdpp_set_grid_learner_params(self._h, *(capi.nptr(a) for a in arrays), self._stream())
@@ -1418,30 +1423,94 @@ class RLToyVectorEnv:
         """Output buffers of rollout_grid_learn(K) / rollout_grid_eval(K): alloc_rollout(K) and the action vectors, int32 [K, N, 2]."""
         return self.alloc_rollout(K) + (torch.empty((K, self.num_envs, 2), dtype=torch.int32, device=self.device),)
 
-    def _rollout_grid(self, stem, K, out, summary):
+    def _rollout_grid(self, stem, K, out, summary, log=None):
         self._grid_learn_check_kind()
         K = int(K)
+        if log is not None and (summary is None or out is not None):
+            raise ValueError("rollout_grid_learn: log goes with summary (and without out)")
         if summary is not None:
             if out is not None:
                 raise ValueError("a summary launch writes no [K, N] output (out must be None)")
+            if log is not None:
+                return self._rollout_summary(getattr(self._lib, stem + "_log"), stem + "_log", K, summary, log)
             return self._rollout_summary(getattr(self._lib, stem + "_summary"), stem + "_summary", K, summary)
         if out is None:
             out = self.alloc_rollout_grid(K)
         return self._rollout_closed(getattr(self._lib, stem), stem, K, out)
 
-    def rollout_grid_learn(self, K, out=None, *, summary=None):
+    def rollout_grid_learn(self, K, out=None, *, summary=None, log=None):
         """K steps of "select epsilon-greedily from the gridworld's own Q, move, update that Q" in ONE kernel launch.  Returns
         (obs, reward, terminated, truncated, actions), each with a leading K axis, ``actions`` the int32 [K, N, 2] action vectors
         taken: rollout(actions) on an identically built env returns the same first four, bit for bit.  SARSA carries its next
         action from step to step inside a call only.  ``summary`` (episode_summary()): the same K steps with the same effect on
-        the env and the tables, but NO [K, N] array is written -- the summary is updated and returned."""
-        return self._rollout_grid("mdpp_step_n_grid_learn", K, out, summary)
+        the env and the tables, but NO [K, N] array is written -- the summary is updated and returned.  With a schedule
+        (set_grid_learner_schedule) every env selects and updates with the epsilon / alpha of its own episode count, looked up
+        again inside the launch at each of its episode ends.  ``log`` (episode_log(M), with ``summary`` only): the same launch
+        also writes the return and length of every episode that ends into the log, at the env's own episode index
+        (DESIGN.md 3.32); ``summary`` is still what is returned."""
+        return self._rollout_grid("mdpp_step_n_grid_learn", K, out, summary, log)
 
     def rollout_grid_eval(self, K, out=None, *, summary=None):
         """K steps of GREEDY evaluation of the grid learner's tables in ONE kernel launch: every env takes the lowest action that
         maximises its own Q[s].  Nothing is drawn, nothing is updated: the tables stay bit for bit what they were.  Returns as
         rollout_grid_learn; with ``summary`` the episode numbers instead."""
         return self._rollout_grid("mdpp_step_n_grid_eval", K, out, summary)
+
+    # ---- per-episode epsilon / alpha schedules of the grid learner
+    def set_grid_learner_schedule(self, epsilon=None, alpha=None, row=None):
+        """Per-EPISODE epsilon and / or alpha for rollout_grid_learn (include/mdpp.h "Grid learner schedules and
+        the episode log").  ``epsilon`` and ``alpha`` are tables [M] or [R, M] (numpy, or a torch tensor on any device; epsilon
+        in [0, 1], alpha as float32 in (0, 1]; R M <= 2^22), ``row`` an integer array [N] in [0, R) -- the table row env i of
+        THIS handle follows; required iff R > 1.  The kernel keeps an int32 episode counter per env, zero after this call: the
+        env learns with entry min(counter, M - 1) of its row, and the counter moves, after the update, at every step that is
+        ``terminated or truncated`` and is not the reset call of a next-step-autoreset env -- the rule by which
+        summary.episodes moves.  Past M - 1 the last entry holds.  A parameter without a table stays what set_grid_learner /
+        set_grid_learner_rates made it; gamma is never scheduled.  policy.epsilon_decay makes the rows "linear", "log" and
+        "const".  rollout_grid_eval reads no table and moves no counter.  ValueError (policy.learner_schedule_arrays) before
+        any device work; MdppError without a learner; set_grid_learner drops the schedule."""
+        eps, al, rows, R, M = policy_mod.learner_schedule_arrays(epsilon, alpha, row, self.num_envs)
+        self._grid_learn_check_kind()
+        rc = self._lib.mdpp_set_grid_learner_schedule(self._h, capi.nptr(eps), capi.nptr(al), R, M, capi.nptr(rows), self._stream())
+        self._closed_call(rc, "mdpp_set_grid_learner_schedule")
+        self._grid_sched = dict(epsilon=eps, alpha=al, row=rows)
+
+    def clear_grid_learner_schedule(self):
+        """Drop the grid learner's schedule: epsilon and alpha are again what set_grid_learner / set_grid_learner_rates made
+        them.  The counters are zeroed by the next set_grid_learner_schedule."""
+        self._grid_learn_check_kind()
+        self._closed_call(self._lib.mdpp_clear_grid_learner_schedule(self._h), "mdpp_clear_grid_learner_schedule")
+        self._grid_sched = None
+
+    def grid_learner_schedule(self):
+        """The grid learner's schedule in force -- dict(epsilon=float32 [R, M] or None, alpha=likewise, row=int32 [N] or
+        None), copies -- or None."""
+        if self._grid_sched is None:
+            return None
+        return {k: None if v is None else v.copy() for k, v in self._grid_sched.items()}
+
+    def grid_learner_episodes(self):
+        """The grid schedule's per-env episode counters, int32 [N] on the device; a copy, made on the current stream."""
+        self._grid_learn_check_kind()
+        ep = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        self._closed_call(self._lib.mdpp_get_grid_learner_episodes(self._h, C.c_void_p(ep.data_ptr()), self._stream()),
+                          "mdpp_get_grid_learner_episodes")
+        return ep
+
+    def set_grid_learner_episodes(self, x=None):
+        """Replace the grid schedule's counters: an integer array [N] of values >= 0 (numpy, or a torch tensor on any device),
+        or None for zeros -- the schedule starts again.  Copied on the current stream."""
+        self._grid_learn_check_kind()
+        ep = None
+        if x is not None:
+            a = policy_mod._to_numpy(x)
+            if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or a.shape != (self.num_envs,):
+                raise ValueError(f"set_grid_learner_episodes: need an integer array of shape ({self.num_envs},), got {a.dtype} {a.shape}")
+            if a.size and (a.min() < 0 or a.max() > 2 ** 31 - 1):
+                raise ValueError("set_grid_learner_episodes: every counter must lie in [0, 2^31)")
+            ep = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        rc = self._lib.mdpp_set_grid_learner_episodes(self._h, C.c_void_p(ep.data_ptr()) if ep is not None else None, self._stream())
+        self._closed_call(rc, "mdpp_set_grid_learner_episodes")
+        self._grid_ep_init = ep          # (kept until the copy queued on the stream has certainly been made)
 
     def get_grid_q(self):
         """The grid learner's tables, float32 [N, g0 + 1, g1 + 1, A]; a copy, made on the current stream."""
@@ -1463,7 +1532,8 @@ class RLToyVectorEnv:
 
     def grid_learn_kernel_name(self, K, eval=False, summary=False):
         """Name (with template arguments) of the kernel rollout_grid_learn(K) (``eval``: rollout_grid_eval(K); ``summary``: their
-        summary= forms) launches (mdpp_grid_learn_kernel_name; nothing is launched; QLDS=1: the Q-tables are staged in LDS);
+        summary= forms) launches (mdpp_grid_learn_kernel_name; nothing is launched; QLDS=1: the Q-tables are staged in LDS;
+        ",SCHED=1" after SUMMARY= on the learning forms while a schedule is in force; a log= launch reports this name too);
         empty for a handle it does not serve or one without a learner."""
         if self.kind != "grid":
             return ""
