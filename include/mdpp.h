@@ -704,6 +704,52 @@ int mdpp_set_grid_learner_episodes(mdpp_env *h, const int32_t *dev_in, void *str
 int mdpp_step_n_grid_learn_log(mdpp_env *h, int K, double *ret_dev, int32_t *len_dev, int32_t *episodes_dev, double *return_sum_dev,
                                int32_t *length_sum_dev, int32_t *log_count_dev, double *log_ret_dev, int32_t *log_len_dev, int M, void *stream);
 
+/* Grid noise levels.  The reference has no such handle: this text is the definition.
+ * Any grid handle that mdpp_set_grid_learner serves (grid_dims == 2, no image observations, no episode_stats; a learner need
+ * not be set) may carry per-env levels of its two noise keys: env i of the handle (its LOCAL index) steps with
+ * transition_noise[i] and reward_noise[i] in place of the two creation values, in the learner and evaluation launches --
+ * mdpp_step_n_grid_learn, mdpp_step_n_grid_eval, their _summary forms, mdpp_step_n_grid_learn_log, with or without a
+ * schedule.  Levels are configuration of the handle: mdpp_set_grid_learner, mdpp_clear_grid_learner, the schedule calls,
+ * mdpp_set_grid_q and the state accessors (mdpp_get_state_* / mdpp_set_state_*, the streams, the reset-pending flags)
+ * neither carry nor disturb them.
+ *   reward_noise[i]: float64, finite, >= 0; the handle must have been created with the reward_noise key, at any value
+ *     including 0.  The env's noise term is  0.0 + reward_noise[i] * z,  z drawn exactly as without levels -- at
+ *     reward_noise[i] == 0 too.
+ *   transition_noise[i]: float64 in [0, 1] (-0.0 becomes 0.0), any number of distinct values (there is no per-level table);
+ *     the handle must have been created with transition_noise > 0, which is what gives it an action stream.
+ *     transition_noise[i] > 0: the env draws u from its env stream and re-draws the move where u < transition_noise[i],
+ *     exactly as without levels.  transition_noise[i] == 0: NO u is drawn, lane by lane (the reference's
+ *     `if self.transition_noise:`).  On numpy streams that env's env stream then moves only by its reward-noise normals and
+ *     its action stream does not move, while its neighbours' do; on Philox streams the reward-noise normal then takes the
+ *     first words of the tick's env stream.
+ *   The equivalence: env i of such a handle equals, bit for bit, env i of a handle created uniformly with transition_noise[i]
+ *     and reward_noise[i] and everything else equal, the global env id included -- for transition_noise[i] == 0 a handle
+ *     created with transition_noise = 0, which has no such key.  "Equals": the outputs, the action vectors, Q, the state
+ *     record, the words of the env, feature-space and action-space streams, the status word and the step counter.  Nothing
+ *     else of "Grid learners" and "Grid learner schedules and the episode log" changes; evaluation still draws no learner
+ *     word, and the env's noise is the lane's own.
+ * While levels are set mdpp_step and mdpp_step_n return MDPP_ESTATE ("grid noise levels: learner and evaluation launches
+ * only; clear_grid_noise_levels() first"); mdpp_reset is unaffected.  mdpp_set_noise_levels and its kin refuse a grid handle
+ * as ever.
+ * mdpp_set_grid_noise_levels takes HOST float64 [N] pointers; NULL: that key stays as it is (both NULL: MDPP_OK, nothing
+ * changes).  Everything is validated before the handle is touched: MDPP_EUNSUPPORTED for a handle the grid learner does not
+ * serve (mdpp_set_grid_learner's reasons), MDPP_ESTATE for a key the handle was not created with, MDPP_EINVAL for a value
+ * out of range or not finite; the reason is in mdpp_last_error and nothing is applied.  The levels live in two float64 [N]
+ * device buffers of the handle, allocated once and always both filled -- a key without levels holds its creation value --
+ * and overwritten in place by later calls, ordered on `stream`.  mdpp_get_grid_noise_levels: the values in force (HOST
+ * pointers, either may be NULL); while nothing is set the creation values, 0 for an absent key.
+ * mdpp_clear_grid_noise_levels: back to the creation values and to the kernels launched before (the buffers stay for
+ * launches already queued).
+ * Kernels: k_grid_learn_nlev_rollout<PHILOX,QLDS,EVAL,SUMMARY>, k_grid_learn_nlev_sched_rollout<PHILOX,QLDS,SUMMARY> and
+ * k_grid_learn_nlev_log_rollout<PHILOX,QLDS,SCHED> -- the step loop of k_grid_learn_rollout with NOISE = 1, in which the lane
+ * loads its two float64 once per launch and keeps them in registers.  A launch without levels runs the kernels, and the
+ * code, it ran before.  mdpp_grid_learn_kernel_name keeps its signature: while levels are set it reports
+ * k_grid_learn_rollout<PHILOX=.,NOISE=1,QLDS=.,EVAL=.,SUMMARY=.,NLEV=1>, with ",SCHED=1" after "NLEV=1" under a schedule; a
+ * log launch reports the name of the same launch without a log. */
+int mdpp_set_grid_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream);
+int mdpp_get_grid_noise_levels(mdpp_env *h, double *transition_noise_out, double *reward_noise_out);
+int mdpp_clear_grid_noise_levels(mdpp_env *h);
+
 /* Linear policies: closed-loop CONTINUOUS rollouts.  The handle holds float32 parameters theta, one set shared by every env
  * ([D][D + 1]) or one per env ([N][D][D + 1]; per_env != 0): theta[.., r, c] for c < D is W[r][c], theta[.., r, D] is b[r]
  * (D = state_space_dim = action_space_dim).  At every step of a launch env i forms its action from o = the state in its
@@ -1049,6 +1095,10 @@ int mdpp_graph_replay_exact(mdpp_env *h, int K);
  *   rows and the episode counters are read -- and the counters written -- at replay.  Its episode log
  *   (mdpp_step_n_grid_learn_log): the three log pointers and the capacity go by value; log_count is read and written at
  *   replay and log_ret / log_len are written, so counters and log go on from replay to replay.
+ *   Grid noise levels (mdpp_set_grid_noise_levels): "levels are set" goes by value -- a launch captured with levels replays
+ *   the NLEV kernel whatever mdpp_clear_grid_noise_levels does later --; the two float64 [N] arrays are READ from the
+ *   handle's buffers at replay, like Q and the parameter arrays (mdpp_set_grid_noise_levels between replays, on the
+ *   replay's stream: the buffers are overwritten in place, never replaced).
  *   A handle must not be destroyed, and no other HIP call that synchronises may be made from the capturing thread, while a
  *   capture is open (a garbage-collected binding object's finaliser counts). */
 int mdpp_graph_capture(mdpp_env *h, int on);

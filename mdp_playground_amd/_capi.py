@@ -73,6 +73,7 @@ EXPORTS = [
     "mdpp_grid_learn_kernel_name",
     "mdpp_set_grid_learner_schedule", "mdpp_clear_grid_learner_schedule", "mdpp_get_grid_learner_episodes", "mdpp_set_grid_learner_episodes",
     "mdpp_step_n_grid_learn_log",
+    "mdpp_set_grid_noise_levels", "mdpp_get_grid_noise_levels", "mdpp_clear_grid_noise_levels",
 ]
 
 
@@ -256,6 +257,9 @@ def load():
     L.mdpp_get_grid_learner_episodes.argtypes = [vp, vp, vp]
     L.mdpp_set_grid_learner_episodes.argtypes = [vp, vp, vp]
     L.mdpp_step_n_grid_learn_log.argtypes = [vp, i32] + [vp] * 8 + [i32, vp]
+    L.mdpp_set_grid_noise_levels.argtypes = [vp, vp, vp, vp]
+    L.mdpp_get_grid_noise_levels.argtypes = [vp, vp, vp]
+    L.mdpp_clear_grid_noise_levels.argtypes = [vp]
     L.mdpp_set_noise_levels.argtypes = [vp, vp, vp, vp]
     L.mdpp_get_noise_levels.argtypes = [vp, vp, vp]
     L.mdpp_clear_noise_levels.argtypes = [vp]

@@ -41,7 +41,9 @@ SOURCES = ["mdpp_capi.hip", "mdpp_discrete.hip", "mdpp_discrete_wide.hip", "mdpp
            "mdpp_continuous_linear_h2.hip", "mdpp_continuous_summary_linear_h2.hip", "mdpp_continuous_search_h2.hip",
            "mdpp_continuous_summary_search_h2.hip", "mdpp_continuous_es_h2.hip", "mdpp_continuous_summary_es_h2.hip",
            "mdpp_continuous_fast.hip", "mdpp_continuous_step1.hip", "mdpp_continuous_line.hip", "mdpp_image.hip", "mdpp_grid.hip", "mdpp_grid_learn.hip", "mdpp_grid_summary_learn.hip",
-           "mdpp_grid_sched_learn.hip", "mdpp_grid_summary_sched_learn.hip", "mdpp_grid_episodes_learn.hip", "mdpp_grid_episodes_sched_learn.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
+           "mdpp_grid_sched_learn.hip", "mdpp_grid_summary_sched_learn.hip", "mdpp_grid_episodes_learn.hip", "mdpp_grid_episodes_sched_learn.hip",
+           "mdpp_grid_levels_learn.hip", "mdpp_grid_summary_levels_learn.hip", "mdpp_grid_levels_sched_learn.hip", "mdpp_grid_summary_levels_sched_learn.hip",
+           "mdpp_grid_episodes_levels_learn.hip", "mdpp_grid_episodes_levels_sched_learn.hip", "mdpp_imagec.hip", "mdpp_post.hip", "mdpp_peer.hip",
            "mdpp_generate.hip"]
 HEADERS = ["mdpp_internal.hpp", "mdpp_rng.hpp", "mdpp_discrete_closed.hpp", "mdpp_pcg64_limbs.inc", "np_ziggurat_tables.inc", "mdpp_grid_learn_body.inc",
            os.path.join("..", "..", "include", "mdpp.h")]
@@ -85,7 +87,9 @@ EXTRA_FLAGS = {s: SPILL_SAFE for s in ("mdpp_continuous.hip", "mdpp_continuous_l
 #  profiles/trace_seeds_resources.txt, tests/test_gpu_trace_seeds.py;
 #  mdpp_grid_learn.hip, mdpp_grid_summary_learn.hip likewise: profiles/grid_learn_resources.txt, tests/test_gpu_grid_learn.py runs every lane against a twin;
 #  the four mdpp_grid_*sched_learn.hip / mdpp_grid_episodes*_learn.hip units -- the same step loop with a schedule and / or an episode log -- likewise:
-#  profiles/grid_schedule_resources.txt, tests/test_gpu_grid_schedule.py)
+#  profiles/grid_schedule_resources.txt, tests/test_gpu_grid_schedule.py;
+#  the six mdpp_grid_*levels*_learn.hip units -- the same six forms with per-env noise levels -- likewise:
+#  profiles/grid_noise_levels_resources.txt, tests/test_gpu_grid_noise_levels.py)
 
 
 def _hipcc():

@@ -61,7 +61,7 @@ static void free_all(mdpp_env *h) {
                     h->d_learn_alpha, h->d_learn_gamma, h->d_learn_E, h->d_sched_E, h->d_sched_alpha, h->d_sched_row, h->d_sched_ep,
                     h->d_nl_level, h->d_nl_sigma, h->d_nl_cdf, h->d_nl_T, h->d_nl_M, h->d_lin_theta, h->d_lin_mem, h->d_trace_z, h->d_trace_lambda,
                     h->d_gl_q, h->d_gl_alpha, h->d_gl_gamma, h->d_gl_E,
-                    h->d_gl_sched_E, h->d_gl_sched_alpha, h->d_gl_sched_row, h->d_gl_sched_ep};
+                    h->d_gl_sched_E, h->d_gl_sched_alpha, h->d_gl_sched_row, h->d_gl_sched_ep, h->d_gl_nl_p, h->d_gl_nl_r};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < MDPP_NUM_STREAMS; s++) {
         if (h->d_rng_s[s]) (void)hipFree(h->d_rng_s[s]);
@@ -1233,6 +1233,7 @@ static int step_common(mdpp_env *h, int K, const void *actions, void *obs, float
     int rc = check_ready(h, "mdpp_step");
     if (rc) return rc;
     if (h->nl_on) return fail(h, MDPP_ESTATE, "step: per-env noise levels: learner and evaluation launches only; clear_noise_levels() first");
+    if (h->gl_nl_on) return fail(h, MDPP_ESTATE, "step: grid noise levels: learner and evaluation launches only; clear_grid_noise_levels() first");
     if (h->line_hist_stale)
         return fail(h, MDPP_EUNSUPPORTED, "step: mdpp_set_state_continuous on a move_along_a_line handle must be followed by mdpp_set_line_history (the window of the line fit)");
     HIPCHK(h, hipSetDevice(h->device));
@@ -2209,6 +2210,61 @@ extern "C" const char *mdpp_grid_learn_kernel_name(mdpp_env *h, int K, int eval,
     if (summary) dry.summary = &sm;
     (void)launch_grid_learn(h, dry, eval != 0);
     return h->kname;
+}
+
+// ---- per-env noise levels of a GRID handle (mdpp_grid_learn.hpp: NLEV; include/mdpp.h "Grid noise levels") ----
+extern "C" int mdpp_set_grid_noise_levels(mdpp_env *h, const double *transition_noise, const double *reward_noise, void *stream) {
+    if (!h) return MDPP_EINVAL;
+    const std::string why = grid_learn_refusal(h);
+    if (!why.empty()) return fail(h, MDPP_EUNSUPPORTED, "mdpp_set_grid_noise_levels: " + why);
+    const mdpp_config &c = h->cfg;
+    if (transition_noise && !c.has_transition_noise)
+        return fail(h, MDPP_ESTATE, "mdpp_set_grid_noise_levels: transition_noise: the handle was created without the key (it needs transition_noise > 0: the action stream and the NOISE kernels)");
+    if (reward_noise && !c.has_reward_noise)
+        return fail(h, MDPP_ESTATE, "mdpp_set_grid_noise_levels: reward_noise: the handle was created without the key");
+    const size_t N = (size_t)c.num_envs;
+    for (size_t i = 0; i < N; i++) {                             // (NaN fails every comparison)
+        if (transition_noise && !(transition_noise[i] >= 0.0 && transition_noise[i] <= 1.0))
+            return fail(h, MDPP_EINVAL, "mdpp_set_grid_noise_levels: need every transition_noise in [0, 1]");
+        if (reward_noise && !(reward_noise[i] >= 0.0 && reward_noise[i] <= DBL_MAX))
+            return fail(h, MDPP_EINVAL, "mdpp_set_grid_noise_levels: need every reward_noise finite and >= 0");
+    }
+    if (!transition_noise && !reward_noise) return MDPP_OK;
+    // the values in force after this call: the creation values, what an earlier call set, what this one gives
+    std::vector<double> tn = h->gl_nl_on ? h->gl_nl_tn : std::vector<double>(N, c.has_transition_noise ? c.transition_noise : 0.0);
+    std::vector<double> rn = h->gl_nl_on ? h->gl_nl_rn : std::vector<double>(N, c.has_reward_noise ? c.reward_noise : 0.0);
+    if (transition_noise)
+        for (size_t i = 0; i < N; i++) tn[i] = transition_noise[i] == 0.0 ? 0.0 : transition_noise[i];       // (-0.0 is 0.0)
+    if (reward_noise) rn.assign(reward_noise, reward_noise + N);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    // (allocated once and overwritten in place: a launch captured into a HIP graph reads these two buffers at replay)
+    for (void **d : {&h->d_gl_nl_p, &h->d_gl_nl_r})
+        if (!*d) HIPCHK(h, hipMalloc(d, N * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->d_gl_nl_p, tn.data(), N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_gl_nl_r, rn.data(), N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));                          // (the sources are this call's own: gone at return)
+    h->gl_nl_tn.swap(tn); h->gl_nl_rn.swap(rn);
+    h->gl_nl_on = true;
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_get_grid_noise_levels(mdpp_env *h, double *transition_noise_out, double *reward_noise_out) {
+    if (!h) return MDPP_EINVAL;
+    const mdpp_config &c = h->cfg;
+    if (c.kind != MDPP_KIND_GRID) return fail(h, MDPP_EUNSUPPORTED, "mdpp_get_grid_noise_levels: grid learners serve grid envs only");
+    const size_t N = (size_t)c.num_envs;
+    for (size_t i = 0; i < N; i++) {
+        if (transition_noise_out) transition_noise_out[i] = h->gl_nl_on ? h->gl_nl_tn[i] : (c.has_transition_noise ? c.transition_noise : 0.0);
+        if (reward_noise_out) reward_noise_out[i] = h->gl_nl_on ? h->gl_nl_rn[i] : (c.has_reward_noise ? c.reward_noise : 0.0);
+    }
+    return MDPP_OK;
+}
+
+extern "C" int mdpp_clear_grid_noise_levels(mdpp_env *h) {
+    if (!h) return MDPP_EINVAL;
+    h->gl_nl_on = false;         // (the buffers stay: a launch queued earlier may still read them)
+    return MDPP_OK;
 }
 
 // ---- closed-loop CONTINUOUS rollouts under a linear policy per env (mdpp_continuous_linear.hip) ----

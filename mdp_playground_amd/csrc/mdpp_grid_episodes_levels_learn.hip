@@ -1,0 +1,10 @@
+// Grid learners with per-env noise levels (mdpp_set_grid_noise_levels; include/mdpp.h "Grid noise levels"): the instantiations of k_grid_learn_nlev_log_rollout
+// without a schedule (the summary form that also keeps an episode log).
+// The kernel and the launcher: mdpp_grid_learn.hpp.
+#include "mdpp_grid_learn.hpp"
+
+namespace mdpp {
+
+template int launch_grid_learn_form<true, false, true, true>(mdpp_env *, const DiscreteIO &, bool);
+
+} // namespace mdpp

@@ -1,8 +1,9 @@
 // Grid learners (include/mdpp.h "Grid learners"; the kernel and the launcher of one output form: mdpp_grid_learn.hpp): the
 // full-output instantiations of k_grid_learn_rollout, what a grid handle is refused for, the dispatcher between the two
 // output forms (the summary form is built in mdpp_grid_summary_learn.hip) and their SCHED and LOG forms (built in
-// mdpp_grid_sched_learn.hip, mdpp_grid_summary_sched_learn.hip, mdpp_grid_episodes_learn.hip, mdpp_grid_episodes_sched_learn.hip) and
-// the copy of Q between the caller's [N][S][A] and the handle's entry-major [S A][N].
+// mdpp_grid_sched_learn.hip, mdpp_grid_summary_sched_learn.hip, mdpp_grid_episodes_learn.hip, mdpp_grid_episodes_sched_learn.hip), the
+// same six forms under per-env noise levels (built in the six mdpp_grid_*levels*_learn.hip units) and the copy of Q between
+// the caller's [N][S][A] and the handle's entry-major [S A][N].
 #include "mdpp_grid_learn.hpp"
 
 namespace mdpp {
@@ -22,6 +23,12 @@ std::string grid_learn_refusal(const mdpp_env *h) {
 //  learner's summary form with io.summary->log_cap != 0)
 int launch_grid_learn(mdpp_env *h, const DiscreteIO &io, bool eval) {
     const bool sched = h->gl_sched_on && !eval;
+    if (h->gl_nl_on) {           // per-env noise levels: the same forms on the NLEV kernels
+        if (io.summary && io.summary->log_cap != 0u)
+            return sched ? launch_grid_learn_form<true, true, true, true>(h, io, eval) : launch_grid_learn_form<true, false, true, true>(h, io, eval);
+        if (sched) return io.summary ? launch_grid_learn_form<true, true, false, true>(h, io, eval) : launch_grid_learn_form<false, true, false, true>(h, io, eval);
+        return io.summary ? launch_grid_learn_form<true, false, false, true>(h, io, eval) : launch_grid_learn_form<false, false, false, true>(h, io, eval);
+    }
     if (io.summary && io.summary->log_cap != 0u)
         return sched ? launch_grid_learn_form<true, true, true>(h, io, eval) : launch_grid_learn_form<true, false, true>(h, io, eval);
     if (sched) return io.summary ? launch_grid_learn_form<true, true>(h, io, eval) : launch_grid_learn_form<false, true>(h, io, eval);

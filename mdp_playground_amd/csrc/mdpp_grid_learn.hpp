@@ -30,6 +30,12 @@
 // [M][N] arrays, while there is one.  Both are forms of the learner only (EVAL = 0), LOG of the summary form only.
 // The step loop is ONE text, mdpp_grid_learn_body.inc, included into three kernels: k_grid_learn_rollout (SCHED = LOG = 0: the
 // symbols and the code this kernel always had), k_grid_learn_sched_rollout and k_grid_learn_log_rollout.
+//
+// NLEV = 1 (mdpp_set_grid_noise_levels; include/mdpp.h "Grid noise levels"): the lane steps with its OWN transition_noise and
+// reward_noise, two float64 [N] arrays of the handle loaded once per launch and kept in registers, in place of GridArgs::p_noise
+// and r_noise -- a lane at p == 0 draws no u, as a handle created without the key does.  Three more kernels include the body
+// with NLEV = true and NOISE = true (levels exist only on handles with a noise key): k_grid_learn_nlev_rollout,
+// k_grid_learn_nlev_sched_rollout and k_grid_learn_nlev_log_rollout.  The three above keep their symbols and their code.
 #pragma once
 #include "mdpp_internal.hpp"
 #include "mdpp_rng.hpp"
@@ -57,12 +63,18 @@ struct GridSchedArgs {
     int32_t M;
 };
 
+// ... of the NLEV forms: every env's transition_noise and reward_noise, float64 [N] (device; both always filled)
+struct GridNoiseArgs {
+    const double *p_noise, *r_noise;
+};
+
 template <bool PHILOX, bool NOISE, bool QLDS, bool EVAL, bool SUMMARY>
 __global__ __launch_bounds__(kBlock) void k_grid_learn_rollout(GridArgs a, GridLearnArgs p, int K, void *__restrict__ obs,
                                                                float *__restrict__ reward, uint8_t *__restrict__ term,
                                                                uint8_t *__restrict__ trunc, EpisodeSummaryArgs sm) {
-    constexpr bool SCHED = false, LOG = false;
+    constexpr bool SCHED = false, LOG = false, NLEV = false;
     const GridSchedArgs sc{};       // (never read)
+    const GridNoiseArgs nl{};       // (never read)
 #include "mdpp_grid_learn_body.inc"
 }
 
@@ -71,14 +83,48 @@ template <bool PHILOX, bool NOISE, bool QLDS, bool SUMMARY>
 __global__ __launch_bounds__(kBlock) void k_grid_learn_sched_rollout(GridArgs a, GridLearnArgs p, GridSchedArgs sc, int K, void *__restrict__ obs,
                                                                      float *__restrict__ reward, uint8_t *__restrict__ term,
                                                                      uint8_t *__restrict__ trunc, EpisodeSummaryArgs sm) {
-    constexpr bool EVAL = false, SCHED = true, LOG = false;
+    constexpr bool EVAL = false, SCHED = true, LOG = false, NLEV = false;
+    const GridNoiseArgs nl{};       // (never read)
 #include "mdpp_grid_learn_body.inc"
 }
 
 // ... keeping an episode log beside the summary (LOG = 1), with or without a schedule (SCHED = 0: sc is not read)
 template <bool PHILOX, bool NOISE, bool QLDS, bool SCHED>
 __global__ __launch_bounds__(kBlock) void k_grid_learn_log_rollout(GridArgs a, GridLearnArgs p, GridSchedArgs sc, int K, EpisodeSummaryArgs sm) {
-    constexpr bool EVAL = false, SUMMARY = true, LOG = true;
+    constexpr bool EVAL = false, SUMMARY = true, LOG = true, NLEV = false;
+    const GridNoiseArgs nl{};       // (never read)
+    void *const obs = nullptr;      // (the summary form writes no [K][N] array)
+    float *const reward = nullptr;
+    uint8_t *const term = nullptr, *const trunc = nullptr;
+#include "mdpp_grid_learn_body.inc"
+}
+
+// ... with per-env noise levels (NLEV = 1; NOISE = 1: levels exist only on handles with a noise key): the learner or evaluation,
+// full output or summary
+template <bool PHILOX, bool QLDS, bool EVAL, bool SUMMARY>
+__global__ __launch_bounds__(kBlock) void k_grid_learn_nlev_rollout(GridArgs a, GridLearnArgs p, GridNoiseArgs nl, int K, void *__restrict__ obs,
+                                                                    float *__restrict__ reward, uint8_t *__restrict__ term,
+                                                                    uint8_t *__restrict__ trunc, EpisodeSummaryArgs sm) {
+    constexpr bool NOISE = true, SCHED = false, LOG = false, NLEV = true;
+    const GridSchedArgs sc{};       // (never read)
+#include "mdpp_grid_learn_body.inc"
+}
+
+// ... under a schedule too
+template <bool PHILOX, bool QLDS, bool SUMMARY>
+__global__ __launch_bounds__(kBlock) void k_grid_learn_nlev_sched_rollout(GridArgs a, GridLearnArgs p, GridSchedArgs sc, GridNoiseArgs nl, int K,
+                                                                          void *__restrict__ obs, float *__restrict__ reward,
+                                                                          uint8_t *__restrict__ term, uint8_t *__restrict__ trunc,
+                                                                          EpisodeSummaryArgs sm) {
+    constexpr bool NOISE = true, EVAL = false, SCHED = true, LOG = false, NLEV = true;
+#include "mdpp_grid_learn_body.inc"
+}
+
+// ... keeping an episode log (SCHED = 0: sc is not read)
+template <bool PHILOX, bool QLDS, bool SCHED>
+__global__ __launch_bounds__(kBlock) void k_grid_learn_nlev_log_rollout(GridArgs a, GridLearnArgs p, GridSchedArgs sc, GridNoiseArgs nl, int K,
+                                                                        EpisodeSummaryArgs sm) {
+    constexpr bool NOISE = true, EVAL = false, SUMMARY = true, LOG = true, NLEV = true;
     void *const obs = nullptr;      // (the summary form writes no [K][N] array)
     float *const reward = nullptr;
     uint8_t *const term = nullptr, *const trunc = nullptr;
@@ -86,11 +132,12 @@ __global__ __launch_bounds__(kBlock) void k_grid_learn_log_rollout(GridArgs a, G
 }
 
 // K steps of one form of the learner or (eval; SCHED = LOG = 0 only) of greedy evaluation.  SUMMARY: io.summary's five arrays
-// instead of the [K][N] ones; SCHED: the handle's schedule is in force; LOG: io.summary carries an episode log.  A dry run
-// (io.name_out) writes the kernel's name and launches nothing -- the name is the form's: k_grid_learn_rollout<...> with
-// ",SCHED=1" for the scheduled kernels, and a log launch's is that of the launch without a log.  QLDS where the device grants
-// the workgroup's tables beside the static LDS of the kernel launched and MDPP_OPT_NO_GRID_QLDS does not forbid it
-template <bool SUMMARY, bool SCHED = false, bool LOG = false>
+// instead of the [K][N] ones; SCHED: the handle's schedule is in force; LOG: io.summary carries an episode log; NLEV: the
+// handle's per-env noise levels are in force.  A dry run (io.name_out) writes the kernel's name and launches nothing -- the
+// name is the form's: k_grid_learn_rollout<...> with ",NLEV=1" for the kernels that read the levels and then ",SCHED=1" for
+// the scheduled ones, and a log launch's is that of the launch without a log.  QLDS where the device grants the workgroup's
+// tables beside the static LDS of the kernel launched and MDPP_OPT_NO_GRID_QLDS does not forbid it
+template <bool SUMMARY, bool SCHED = false, bool LOG = false, bool NLEV = false>
 int launch_grid_learn_form(mdpp_env *h, const DiscreteIO &io, bool eval) {
     static_assert(SUMMARY || !LOG, "the episode log is kept by the summary form");
     GridArgs a = h->gargs;
@@ -103,12 +150,49 @@ int launch_grid_learn_form(mdpp_env *h, const DiscreteIO &io, bool eval) {
     const bool noise = a.has_p_noise != 0 || a.has_r_noise != 0;
     const EpisodeSummaryArgs sm = SUMMARY ? *io.summary : EpisodeSummaryArgs{};
     const bool no_qlds = (a.opts & MDPP_OPT_NO_GRID_QLDS) != 0;
-    if constexpr (SCHED || LOG) {
-        if (eval) { h->err = "launch_grid_learn_form: evaluation has no SCHED or LOG form"; return MDPP_EINVAL; }
-        const GridSchedArgs sc = SCHED ? GridSchedArgs{h->gl_sched_eps ? (const uint32_t *)h->d_gl_sched_E : nullptr,
-                                                       h->gl_sched_alpha ? (const float *)h->d_gl_sched_alpha : nullptr,
-                                                       (const int32_t *)h->d_gl_sched_row, (int32_t *)h->d_gl_sched_ep, h->gl_sched_M}
-                                       : GridSchedArgs{};
+    if ((SCHED || LOG) && eval) { h->err = "launch_grid_learn_form: evaluation has no SCHED or LOG form"; return MDPP_EINVAL; }
+    const GridSchedArgs sc = SCHED ? GridSchedArgs{h->gl_sched_eps ? (const uint32_t *)h->d_gl_sched_E : nullptr,
+                                                   h->gl_sched_alpha ? (const float *)h->d_gl_sched_alpha : nullptr,
+                                                   (const int32_t *)h->d_gl_sched_row, (int32_t *)h->d_gl_sched_ep, h->gl_sched_M}
+                                   : GridSchedArgs{};
+    const char *kernel;
+    if constexpr (NLEV) {
+        if (!noise || !h->d_gl_nl_p || !h->d_gl_nl_r) { h->err = "launch_grid_learn_form: noise levels on a handle without a noise key"; return MDPP_EINVAL; }
+        const GridNoiseArgs nl{(const double *)h->d_gl_nl_p, (const double *)h->d_gl_nl_r};
+        if constexpr (SCHED || LOG) {
+            kernel = LOG ? "k_grid_learn_nlev_log_rollout" : "k_grid_learn_nlev_sched_rollout";
+            with_bools([&](auto PH) {
+                bool ql;
+                if constexpr (LOG) ql = !no_qlds && dynamic_lds_ok((const void *)k_grid_learn_nlev_log_rollout<PH(), true, SCHED>, q_bytes);
+                else ql = !no_qlds && dynamic_lds_ok((const void *)k_grid_learn_nlev_sched_rollout<PH(), true, SUMMARY>, q_bytes);
+                with_bools([&](auto QL) {
+                    if (io.name_out)
+                        snprintf(io.name_out, kNameLen, "k_grid_learn_rollout<PHILOX=%d,NOISE=1,QLDS=%d,EVAL=0,SUMMARY=%d,NLEV=1%s>", PH(), QL(),
+                                 SUMMARY ? 1 : 0, SCHED ? ",SCHED=1" : "");
+                    else if constexpr (LOG)
+                        hipLaunchKernelGGL((k_grid_learn_nlev_log_rollout<PH(), QL(), SCHED>), dim3(grid), dim3(kBlock), QL() ? q_bytes : 0, io.s,
+                                           a, p, sc, nl, io.K, sm);
+                    else
+                        hipLaunchKernelGGL((k_grid_learn_nlev_sched_rollout<PH(), QL(), SUMMARY>), dim3(grid), dim3(kBlock), QL() ? q_bytes : 0, io.s,
+                                           a, p, sc, nl, io.K, io.obs, io.reward, io.term, io.trunc, sm);
+                }, ql);
+            }, a.philox != 0);
+        } else {
+            kernel = "k_grid_learn_nlev_rollout";
+            with_bools([&](auto PH, auto EV) {
+                const bool ql = !no_qlds && dynamic_lds_ok((const void *)k_grid_learn_nlev_rollout<PH(), true, EV(), SUMMARY>, q_bytes);
+                with_bools([&](auto QL) {
+                    if (io.name_out)
+                        snprintf(io.name_out, kNameLen, "k_grid_learn_rollout<PHILOX=%d,NOISE=1,QLDS=%d,EVAL=%d,SUMMARY=%d,NLEV=1>", PH(), QL(), EV(),
+                                 SUMMARY ? 1 : 0);
+                    else
+                        hipLaunchKernelGGL((k_grid_learn_nlev_rollout<PH(), QL(), EV(), SUMMARY>), dim3(grid), dim3(kBlock), QL() ? q_bytes : 0, io.s,
+                                           a, p, nl, io.K, io.obs, io.reward, io.term, io.trunc, sm);
+                }, ql);
+            }, a.philox != 0, eval);
+        }
+    } else if constexpr (SCHED || LOG) {
+        kernel = LOG ? "k_grid_learn_log_rollout" : "k_grid_learn_sched_rollout";
         with_bools([&](auto PH, auto NZ) {
             bool ql;
             if constexpr (LOG) ql = !no_qlds && dynamic_lds_ok((const void *)k_grid_learn_log_rollout<PH(), NZ(), true, SCHED>, q_bytes);
@@ -126,6 +210,7 @@ int launch_grid_learn_form(mdpp_env *h, const DiscreteIO &io, bool eval) {
             }, ql);
         }, a.philox != 0, noise);
     } else {
+        kernel = "k_grid_learn_rollout";
         with_bools([&](auto PH, auto NZ, auto EV) {
             const bool ql = !no_qlds && dynamic_lds_ok((const void *)k_grid_learn_rollout<PH(), NZ(), true, EV(), SUMMARY>, q_bytes);
             with_bools([&](auto QL) {
@@ -137,7 +222,7 @@ int launch_grid_learn_form(mdpp_env *h, const DiscreteIO &io, bool eval) {
             }, ql);
         }, a.philox != 0, noise, eval);
     }
-    return io.name_out ? MDPP_OK : step_done(h, io.K, LOG ? "k_grid_learn_log_rollout" : SCHED ? "k_grid_learn_sched_rollout" : "k_grid_learn_rollout");
+    return io.name_out ? MDPP_OK : step_done(h, io.K, kernel);
 }
 extern template int launch_grid_learn_form<false>(mdpp_env *, const DiscreteIO &, bool);                // mdpp_grid_learn.hip
 extern template int launch_grid_learn_form<true>(mdpp_env *, const DiscreteIO &, bool);                 // mdpp_grid_summary_learn.hip
@@ -145,5 +230,11 @@ extern template int launch_grid_learn_form<false, true>(mdpp_env *, const Discre
 extern template int launch_grid_learn_form<true, true>(mdpp_env *, const DiscreteIO &, bool);           // mdpp_grid_summary_sched_learn.hip
 extern template int launch_grid_learn_form<true, false, true>(mdpp_env *, const DiscreteIO &, bool);    // mdpp_grid_episodes_learn.hip
 extern template int launch_grid_learn_form<true, true, true>(mdpp_env *, const DiscreteIO &, bool);     // mdpp_grid_episodes_sched_learn.hip
+extern template int launch_grid_learn_form<false, false, false, true>(mdpp_env *, const DiscreteIO &, bool);   // mdpp_grid_levels_learn.hip
+extern template int launch_grid_learn_form<true, false, false, true>(mdpp_env *, const DiscreteIO &, bool);    // mdpp_grid_summary_levels_learn.hip
+extern template int launch_grid_learn_form<false, true, false, true>(mdpp_env *, const DiscreteIO &, bool);    // mdpp_grid_levels_sched_learn.hip
+extern template int launch_grid_learn_form<true, true, false, true>(mdpp_env *, const DiscreteIO &, bool);     // mdpp_grid_summary_levels_sched_learn.hip
+extern template int launch_grid_learn_form<true, false, true, true>(mdpp_env *, const DiscreteIO &, bool);     // mdpp_grid_episodes_levels_learn.hip
+extern template int launch_grid_learn_form<true, true, true, true>(mdpp_env *, const DiscreteIO &, bool);      // mdpp_grid_episodes_levels_sched_learn.hip
 
 } // namespace mdpp

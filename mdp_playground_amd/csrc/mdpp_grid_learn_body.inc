@@ -1,10 +1,12 @@
 // The body of the grid learners' kernels (mdpp_grid_learn.hpp), included into each of them: K steps of one lane.  The kernel
 // that includes it has the arguments a (GridArgs), p (GridLearnArgs), sc (GridSchedArgs), K, obs, reward, term, trunc, sm
-// (EpisodeSummaryArgs) in scope and the compile-time constants PHILOX, NOISE, QLDS, EVAL, SUMMARY, SCHED, LOG.  Text included
-// into the kernel, not a function called from it: k_grid_learn_rollout (SCHED = LOG = false) compiles to the code it had
-// before the scheduled and logging kernels existed (tools/compare_code_objects.py).
+// (EpisodeSummaryArgs), nl (GridNoiseArgs) in scope and the compile-time constants PHILOX, NOISE, QLDS, EVAL, SUMMARY, SCHED, LOG,
+// NLEV.  Text included into the kernel, not a function called from it: k_grid_learn_rollout (SCHED = LOG = false) compiles to
+// the code it had before the scheduled and logging kernels existed, and the three kernels with NLEV = false to the code they
+// had before the per-env noise levels did (tools/compare_code_objects.py).
     static_assert(!EVAL || !(SCHED || LOG), "schedules and the episode log are forms of the learner");
     static_assert(SUMMARY || !LOG, "the episode log is kept by the summary form");
+    static_assert(NOISE || !NLEV, "noise levels exist only on handles with a noise key");
     const uint64_t ptick0 = tick_now(a);               // the step counter at this launch (through the device-side offset of a graph replay)
     constexpr bool ZIG = NOISE && !PHILOX;             // numpy's ziggurat tables (the Philox normal is Box-Muller)
     __shared__ uint64_t s_ki[ZIG ? 256 : 1];
@@ -15,6 +17,8 @@
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= (uint32_t)a.N) return;
     const uint32_t N = (uint32_t)a.N, A = p.A, SA = p.SA, W = p.W;
+    double lane_p = 0.0, lane_sigma = 0.0;              // NLEV: this lane's transition_noise and reward_noise (two coalesced 8-byte loads)
+    if constexpr (NLEV) { lane_p = nl.p_noise[i]; lane_sigma = nl.r_noise[i]; }
     const uint64_t genv = (uint64_t)(a.env_id_offset + (int64_t)i);     // global env id (Philox key)
     float *const q_lds = q_dyn + threadIdx.x;
     float *const qg = p.q + i;
@@ -175,9 +179,14 @@
             continue;
         }
         const int old0 = cell0, old1 = cell1;
-        if (NOISE && a.has_p_noise) {                     // the env re-draws the move from its own action stream
+        bool draw_u = NOISE && a.has_p_noise;
+        if constexpr (NLEV) draw_u = draw_u && lane_p != 0.0;   // (a lane at p == 0 draws no u: the reference's `if self.transition_noise:`)
+        if (draw_u) {                                     // the env re-draws the move from its own action stream
             const double u = PHILOX ? np_random(env_phx) : np_random(env_pcg);
-            if (u < a.p_noise) {
+            bool redraw;
+            if constexpr (NLEV) redraw = u < lane_p;
+            else redraw = u < a.p_noise;
+            if (redraw) {
                 for (int tries = 0;; tries++) {
                     const int ind = PHILOX ? np_integers(act_phx, phx_h, 0, 2) : np_integers(act_pcg, act_h, 0, 2);
                     const int val = PHILOX ? np_integers(act_phx, phx_h, 0, 3) : np_integers(act_pcg, act_h, 0, 3);
@@ -199,7 +208,10 @@
         else if (on_target) r += 1.0;
         if (a.every_n != 1 && steps % (uint32_t)a.every_n != 0) r = 0.0;
         if (NOISE && a.has_r_noise) {
-            const double nz = 0.0 + a.r_noise * (PHILOX ? np_standard_normal_lds(env_phx, zig) : np_standard_normal_lds(env_pcg, zig));
+            const double z = PHILOX ? np_standard_normal_lds(env_phx, zig) : np_standard_normal_lds(env_pcg, zig);
+            double nz;
+            if constexpr (NLEV) nz = 0.0 + lane_sigma * z;
+            else nz = 0.0 + a.r_noise * z;
             r += nz;
         }
         r *= a.scale;

@@ -1,0 +1,9 @@
+// Grid learners with per-env noise levels (mdpp_set_grid_noise_levels; include/mdpp.h "Grid noise levels"): the full-output instantiations of k_grid_learn_nlev_rollout.
+// The kernel and the launcher: mdpp_grid_learn.hpp.
+#include "mdpp_grid_learn.hpp"
+
+namespace mdpp {
+
+template int launch_grid_learn_form<false, false, false, true>(mdpp_env *, const DiscreteIO &, bool);
+
+} // namespace mdpp

@@ -415,6 +415,13 @@ struct mdpp_env {
     int32_t gl_sched_R, gl_sched_M;
     size_t gl_sched_cap;
     void *d_gl_sched_E, *d_gl_sched_alpha, *d_gl_sched_row, *d_gl_sched_ep;
+    // Per-env noise levels of a grid handle (mdpp_set_grid_noise_levels; mdpp_grid_learn.hpp NLEV): gl_nl_on: the learner and
+    // evaluation launches take their NLEV form and mdpp_step / mdpp_step_n are refused.  Device: every env's transition_noise
+    // and reward_noise, float64 [N] each, allocated once and always both filled (a key without levels holds the creation
+    // value); host: the values in force, for mdpp_get_grid_noise_levels
+    bool gl_nl_on;
+    void *d_gl_nl_p, *d_gl_nl_r;
+    std::vector<double> gl_nl_tn, gl_nl_rn;
     mdpp::ContinuousArgs cargs;
     mdpp::GridArgs gargs;
 };

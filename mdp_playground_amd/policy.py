@@ -28,7 +28,7 @@ learner_schedule_arrays validates the tables and the envs' row indices and retur
 import numpy as np
 
 __all__ = ["policy_thresholds", "epsilon_threshold", "explore_action", "check_learner_params", "learner_param_array", "LEARN_ALGOS",
-           "noise_level_array", "noise_levels_reduce", "noise_level_thresholds", "noise_level_cdfs", "MAX_NOISE_LEVELS",
+           "noise_level_array", "grid_noise_level_array", "noise_levels_reduce", "noise_level_thresholds", "noise_level_cdfs", "MAX_NOISE_LEVELS",
            "epsilon_decay", "learner_schedule_arrays", "MAX_SCHEDULE_ENTRIES", "DECAY_KINDS"]
 
 LEARN_ALGOS = ("q_learning", "sarsa", "double_q")
@@ -137,11 +137,12 @@ def check_learner_params(algo, alpha, gamma, epsilon, num_envs=None):
             raise ValueError(f"{name} must lie in [0, 1], got {v!r}")
 
 
-def noise_level_array(name, v, num_envs):
+def noise_level_array(name, v, num_envs, max_levels=MAX_NOISE_LEVELS):
     """The per-env levels of one noise key, ``name`` "transition_noise" or "reward_noise": None for None; otherwise a float64
     numpy [num_envs] -- a scalar is broadcast, an array (numpy, or a torch tensor on any device) must be 1-D with num_envs
     entries.  transition_noise lies in [0, 1] (-0.0 becomes 0.0) with at most MAX_NOISE_LEVELS distinct values, reward_noise is
-    finite and >= 0; NaN fails.  ValueError, naming the key, otherwise."""
+    finite and >= 0; NaN fails.  ValueError, naming the key, otherwise.  ``max_levels=None``: no limit on the distinct values
+    (grid_noise_level_array)."""
     if name not in ("transition_noise", "reward_noise"):
         raise ValueError(f"unknown noise key {name!r}")
     if v is None:
@@ -165,9 +166,15 @@ def noise_level_array(name, v, num_envs):
     if name == "transition_noise":
         a[a == 0.0] = 0.0
         k = len(np.unique(a))
-        if k > MAX_NOISE_LEVELS:
-            raise ValueError(f"transition_noise has {k} distinct values, at most {MAX_NOISE_LEVELS} levels are served")
+        if max_levels is not None and k > max_levels:
+            raise ValueError(f"transition_noise has {k} distinct values, at most {max_levels} levels are served")
     return a
+
+
+def grid_noise_level_array(name, v, num_envs):
+    """noise_level_array for a GRID handle (set_grid_noise_levels): the same checks and the same float64 [num_envs] result,
+    without the limit on distinct transition_noise values -- the grid kernels keep no per-level table."""
+    return noise_level_array(name, v, num_envs, max_levels=None)
 
 
 def noise_levels_reduce(transition_noise):

@@ -101,6 +101,7 @@ class RLToyVectorEnv:
         self._grid_q_init = None              # the tensor last handed to set_grid_learner / set_grid_q, kept until its copy has been made
         self._grid_sched = None               # set_grid_learner_schedule's validated arrays while a schedule is in force
         self._grid_ep_init = None             # the tensor last handed to set_grid_learner_episodes, kept until its copy has been made
+        self._grid_noise_levels_set = False   # set_grid_noise_levels is in force
         self._learn_pe = {"alpha": None, "gamma": None, "epsilon": None}
         self._learn_pm = False                # set_learner(per_env_mdp=True) is in force (the handle's flag is on)
         self._learn_sched = None              # set_learner_schedule's validated arrays while a schedule is in force
@@ -1533,12 +1534,59 @@ class RLToyVectorEnv:
     def grid_learn_kernel_name(self, K, eval=False, summary=False):
         """Name (with template arguments) of the kernel rollout_grid_learn(K) (``eval``: rollout_grid_eval(K); ``summary``: their
         summary= forms) launches (mdpp_grid_learn_kernel_name; nothing is launched; QLDS=1: the Q-tables are staged in LDS;
-        ",SCHED=1" after SUMMARY= on the learning forms while a schedule is in force; a log= launch reports this name too);
+        ",NLEV=1" after SUMMARY= while set_grid_noise_levels is in force, then ",SCHED=1" on the learning forms while a
+        schedule is in force; a log= launch reports this name too);
         empty for a handle it does not serve or one without a learner."""
         if self.kind != "grid":
             return ""
         name = self._lib.mdpp_grid_learn_kernel_name(self._h, int(K), int(bool(eval)), int(bool(summary)))
         return name.decode() if name else ""
+
+    # ---- per-env noise levels of a grid handle
+    _GRID_NOISE_LEVELS_ONLY = "grid noise levels: learner and evaluation launches only; clear_grid_noise_levels() first"
+
+    def set_grid_noise_levels(self, transition_noise=None, reward_noise=None):
+        """Per-env noise levels for rollout_grid_learn / rollout_grid_eval (their summary= and log= forms, with or without a
+        schedule; include/mdpp.h "Grid noise levels"): env i of THIS handle (its local index) steps with
+        ``transition_noise[i]`` in [0, 1] -- any number of distinct values -- and ``reward_noise[i]`` finite and >= 0, bit for
+        bit like env i of a handle created with those two values.  Each argument is None (that key stays as it is), a scalar
+        (broadcast) or a 1-D array of num_envs entries (numpy, or a torch tensor on any device; converted to float64).  The
+        handle must be one set_grid_learner serves (a learner need not be set) and must have been created with the key:
+        ``reward_noise`` present in the config (any value), ``transition_noise`` > 0.  A noise sweep then runs as ONE launch.
+        ValueError naming the key for a bad array or a key the handle lacks, before any device work; NotImplementedError with
+        the library's reason for a handle not served.  While levels are set step(), rollout() and step_graph() raise; reset()
+        is unaffected.  Levels are configuration, not state: set_grid_learner, the schedule calls, set_grid_q,
+        get_augmented_state / set_augmented_state neither carry nor disturb them."""
+        arrays = {}
+        for key, v in (("transition_noise", transition_noise), ("reward_noise", reward_noise)):
+            arrays[key] = policy_mod.grid_noise_level_array(key, v, self.num_envs)
+        self._grid_learn_check_kind()
+        for key, a in arrays.items():
+            if a is None:
+                continue
+            created = self.config.get(key)
+            if created is None or (key == "transition_noise" and not created):
+                raise ValueError("set_grid_noise_levels: %s: the handle was created without the key%s" %
+                                 (key, " (it needs transition_noise > 0)" if key == "transition_noise" else ""))
+        if all(a is None for a in arrays.values()):
+            return
+        rc = self._lib.mdpp_set_grid_noise_levels(self._h, capi.nptr(arrays["transition_noise"]), capi.nptr(arrays["reward_noise"]), self._stream())
+        self._closed_call(rc, "mdpp_set_grid_noise_levels")
+        self._grid_noise_levels_set = True
+
+    def grid_noise_levels(self):
+        """(transition_noise, reward_noise) in force on a grid handle, float64 numpy [N] each: what set_grid_noise_levels gave,
+        else the creation values (0 for a key the config does not have)."""
+        self._grid_learn_check_kind()
+        tn, rn = np.empty(self.num_envs, np.float64), np.empty(self.num_envs, np.float64)
+        capi.check(self._lib, self._h, self._lib.mdpp_get_grid_noise_levels(self._h, capi.nptr(tn), capi.nptr(rn)), "mdpp_get_grid_noise_levels")
+        return tn, rn
+
+    def clear_grid_noise_levels(self):
+        """Back to the creation values of both keys: the handle launches the kernels it launched before set_grid_noise_levels."""
+        self._grid_learn_check_kind()
+        capi.check(self._lib, self._h, self._lib.mdpp_clear_grid_noise_levels(self._h), "mdpp_clear_grid_noise_levels")
+        self._grid_noise_levels_set = False
 
     # ------------------------------------------------------------------ per-env noise levels
     _NOISE_LEVELS_ONLY = "per-env noise levels: learner and evaluation launches only; clear_noise_levels() first"
@@ -1546,6 +1594,8 @@ class RLToyVectorEnv:
     def _noise_levels_refuse(self):
         if self._noise_levels_set:
             raise capi.MdppError(self._NOISE_LEVELS_ONLY)
+        if self._grid_noise_levels_set:
+            raise capi.MdppError(self._GRID_NOISE_LEVELS_ONLY)
 
     def _drop_noise_levels_per_env_mdp(self):
         # (the library has dropped the levels and the opt-in with the learner's per-env-MDP flag)
